@@ -13,14 +13,19 @@ shift -> reposition -> Newton polytope -> done/reward for every one of the 65 53
 games included (the reference steps them too).  K steps are K//20 episodes of 20 steps (+ one shorter
 episode of K%20 steps); an episode is ONE launch of the fused rollout kernel: the state is read from
 HBM once, stays in registers for the 20 steps and is written back once.  Every episode restarts
-from the resident fresh states.  The per-step finished-game counts are reduced once per 10 episodes
-(second tiny kernel).  Launches are captured once into hipGraphs and replayed.
+from the resident fresh states.  Launches are captured once into hipGraphs of at most 100 episodes,
+each ending with the reduction of the per-step finished-game counts (second tiny kernel), and replayed.
 
-Timing.  After W untimed warm-up steps and an untimed clock warm-up as long as the measurement, the
-K-step region is REPEATED back to back until >= 0.2 s of GPU time have been timed (`repeats` on the JSON
-line; `steps` stays K).  The whole repeated region is bracketed by barrier + torch.cuda.synchronize()
-on both sides (wall clock, max over ranks -> `value`, `ms_per_step`); HIP events on the launch stream
-split it into 8 segments whose MEDIAN gives `ms_per_step_median` and `roofline.mean_launch_us`.
+Timing.  After W untimed warm-up steps and an untimed clock warm-up region of K steps, exactly K steps
+are timed once (`steps` = `timed_steps` = K): the region is bracketed by barrier +
+torch.cuda.synchronize() on both sides (wall clock, max over ranks -> `value`, `ms_per_step`); HIP
+events on the launch stream split it into at most 8 segments of whole graphs whose MEDIAN gives
+`ms_per_step_median` and `roofline.mean_launch_us`.  Choose K for the time the measurement should take.
+
+--dump-outputs DIR writes what the timed path hands its caller after its last step as DIR/<name>.npy:
+`points` (the final states of the last episode, float32 [games, 20, 3]) and `done_count` (float64
+[21]: games finished after t steps, summed over the timed episodes).  The inputs are seeded: equal
+arguments give equal inputs, so two builds can be compared output for output.
 
 N>1: `python bench.py --gpus N` starts its own ranks (python -m torch.distributed.run, one process
 per GPU, backend nccl = RCCL) before touching the GPU and relays rank 0's line; launched by
@@ -43,6 +48,8 @@ import subprocess
 import sys
 import time
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -53,12 +60,13 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured 
 # VALU issue ceiling: 256 CUs x 4 SIMDs, one wave64 VALU instruction per 2 cycles per SIMD at 2.4 GHz
 VALU_PEAK_WAVE_INSTS = 1024 * 2.4e9 / 2
 SEED = 7
-# HK_BENCH_TIME_SCALE < 1 shortens every timed region (the rocprofv3 --pmc passes of scripts/profile_round.sh, where
+# HK_BENCH_TIME_SCALE < 1 shortens every secondary section (the rocprofv3 --pmc passes of scripts/profile_round.sh, where
 # each dispatch is serialised and costs ~100 us); the driver's runs use the defaults
 _SCALE = float(os.environ.get("HK_BENCH_TIME_SCALE", "1"))
-MIN_TIMED_S = 0.2 * _SCALE  # GPU time of the headline measurement
-MIN_SECTION_S = 0.04 * _SCALE  # ... of every secondary section
+MIN_SECTION_S = 0.04 * _SCALE  # GPU time of every secondary section
 SEGMENTS = 8
+CHUNK = 100  # episodes per graph of the timed region (one counter reduction each)
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 
 
 def parse_args():
@@ -76,6 +84,8 @@ def parse_args():
                     help="skip the binned_by_live_rows section (profile passes: its launches share the headline kernel's name)")
     ap.add_argument("--no-overlap", action="store_true",
                     help="skip the two-episodes-in-flight section (profiling runs: its launches overlap in the trace)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
 
 
@@ -214,152 +224,145 @@ def main():
         return 0.5 * (seg[SEGMENTS // 2 - 1] + seg[SEGMENTS // 2]), sum(seg) / SEGMENTS, SEGMENTS * n
 
     K, W = args.steps, args.warmup
+    if K < 1:
+        raise SystemExit("--steps must be at least 1")
     n_full, rem = divmod(K, EPISODE)
     kw = dict(game_offset=game_offset, stages=stages, host_policy=A.HK_HOST_RANDOM,
               agent_policy=A.HK_AGENT_RANDOM)
     count_ws = ops.rollout_workspace(b, EPISODE, (m, d))
 
-    def episodes_deferred(n_episodes, n_steps=EPISODE):
+    def episodes_deferred(n_episodes, n_steps=EPISODE, buf=state):
         # episodes back to back, each restarting from the resident fresh states (the kernel reads `fresh`, writes
-        # `state`: no copy); the per-workgroup finished-game counts accumulate in `count_ws`
+        # `buf`: no copy); the per-workgroup finished-game counts accumulate in `count_ws`
         for _ in range(n_episodes):
-            ops.rollout(state, n_steps, SEED, defer_counts=True, workspace=count_ws, **head, **kw)
+            ops.rollout(buf, n_steps, SEED, defer_counts=True, workspace=count_ws, **head, **kw)
 
     def reduce_counts():
-        # ... and are summed into done_count once per BLOCK episodes (the reference sums its per-loop histograms
-        # the same way, jax_trainer.py:513,533-534)
+        # ... and are summed into done_count once per graph (the reference sums its per-loop histograms the same way,
+        # jax_trainer.py:513,533-534)
         ops.reduce_counts(count_ws, done_count, b, EPISODE, (m, d))
 
-    def one_region():
-        """exactly K env steps: n_full episodes of 20 steps (+ one shorter episode of K % 20 steps)"""
-        if n_full:
-            episodes_deferred(n_full)
-        if rem:
-            episodes_deferred(1, rem)
+    def region_graphs(buf):
+        """exactly K env steps into `buf` as [(graph, env steps)]: graphs of CHUNK episodes of 20 steps, then one graph of
+        the remaining episodes (+ one shorter episode of K % 20 steps); every graph ends with the counter reduction"""
+        def chunk(n_episodes, tail):
+            def run():
+                episodes_deferred(n_episodes, buf=buf)
+                if tail:
+                    episodes_deferred(1, tail, buf=buf)
+                reduce_counts()
+            return run
+        n_chunks, left = divmod(n_full, CHUNK)
+        units = [(capture(chunk(CHUNK, 0)), CHUNK * EPISODE)] * n_chunks if n_chunks else []
+        if left or rem:
+            units.append((capture(chunk(left, rem)), left * EPISODE + rem))
+        return units
 
     launches_per_region = n_full + (1 if rem else 0)
-    reduce_every = max(1, BLOCK // max(1, launches_per_region))  # regions between two counter reductions
     g_episode = capture(lambda: episodes_deferred(1))
     gather_events = []
+    # N > 1: after the region the trainer-boundary all-gather of its final states (SURVEY 8(d) config 4: an episode,
+    # then the gather).  Episodes are independent, so the gather of region i need not sit on the launch stream: regions
+    # alternate between two state buffers and hkdist.GatherPipeline runs the collective on a side stream behind an
+    # event (`value`: the timed region and its gather); the same region without any gather (`value_without_gather`)
+    # and the gather serialised on the launch stream and timed with its own events (`gather_us`) are measured next to it.
+    states = [state, torch.empty_like(state)] if distributed else [state]
+    region = [region_graphs(buf) for buf in states]
+    # HIP events split the timed region into at most SEGMENTS segments of whole graphs
+    n_seg = min(SEGMENTS, len(region[0]))
+    seg_end = [(s + 1) * len(region[0]) // n_seg for s in range(n_seg)]
+    seg_steps = [sum(st for _, st in region[0][lo:hi]) for lo, hi in zip([0] + seg_end[:-1], seg_end)]
     if distributed:
-        # One rank-local graph per region, and after EVERY region the trainer-boundary all-gather of its final states
-        # (SURVEY 8(d) config 4: an episode, then the gather).  Episodes are independent, so the gather of region i does
-        # not sit on the launch stream: the regions alternate between two state buffers and hkdist.GatherPipeline runs
-        # the collective on a side stream behind an event while region i + 1 computes (`value`); the same regions
-        # without any gather (`value_without_gather`) and with the gather serialised on the launch stream and timed with
-        # its own events (`gather_us`) are measured next to it.
-        group = 1
-        states = [state, torch.empty_like(state)]
-
-        def region_into(buf):
-            def run():
-                for n_ep, n_st in ((n_full, EPISODE), (1 if rem else 0, rem)):
-                    for _ in range(n_ep):
-                        ops.rollout(buf, n_st, SEED, defer_counts=True, workspace=count_ws, **head, **kw)
-            return run
-        g_region = [capture(region_into(buf)) for buf in states]
-        g_region_reduce = [capture(lambda buf=buf: (region_into(buf)(), reduce_counts())) for buf in states]
         direct = os.environ.get("HK_BENCH_GATHER", "rccl") == "direct"
         shard = hkdist.Shard(rank * b, b, world * b)
         pipe = hkdist.GatherPipeline(shard, depth=2, direct=direct)
 
         def boundary(buf):  # (gloo rehearsal: the states are staged through host memory)
             return buf if backend == "nccl" else buf.cpu()
-    else:
-        # ONE graph holds `group` regions + the counter reduction, so a short region (the driver's --steps 20 is a
-        # single 12-23 us launch) does not pay a graph replay of its own: the launches of a group run back to back
-        group = reduce_every
-        g_group = capture(lambda: ([one_region() for _ in range(group)], reduce_counts()))
 
-    def run_groups(count, start=0, gather="pipelined"):
-        """count x group regions (every region = exactly K env steps); N > 1: the gather of every region's final states
-        `pipelined` behind the next region, `serial` on the launch stream (timed with its own events), or `none`"""
-        out = None
-        for r in range(start, start + count):
-            if not distributed:
-                g_group.replay()
-                continue
-            p = r & 1
+    def run_region(r, gather="pipelined", ev=None):
+        """region r: exactly K env steps into state buffer r % len(states), `ev` recorded behind every segment; N > 1: then
+        the gather of its final states, `pipelined` (side stream), `serial` (launch stream, timed with its own events) or
+        `none`.  Returns the tensor of a serial gather."""
+        p = r % len(states)
+        if distributed:
             pipe.wait(tickets[p])  # the last gather that reads this buffer is done before the region overwrites it
-            (g_region_reduce[p] if (r + 1) % reduce_every == 0 else g_region[p]).replay()
-            if gather == "pipelined":
-                tickets[p] = pipe.submit(boundary(states[p]))
-            elif gather == "serial":
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                out = hkdist.all_gather_games(boundary(states[p]), shard, direct=direct, validate=False)
-                e1.record()
-                gather_events.append((e0, e1))
-        if distributed and gather == "pipelined" and count:
-            out = pipe.result()
+        for i, (g, _) in enumerate(region[p]):
+            g.replay()
+            if ev is not None and i + 1 in seg_end:
+                ev[seg_end.index(i + 1) + 1].record()
+        if not distributed or gather == "none":
+            return None
+        if gather == "pipelined":
+            tickets[p] = pipe.submit(boundary(states[p]))
+            return None
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = hkdist.all_gather_games(boundary(states[p]), shard, direct=direct, validate=False)
+        e1.record()
+        gather_events.append((e0, e1))
         return out
     tickets = [None, None]
 
-    # ---- warm-up (untimed): W steps, then a clock warm-up as long as the measurement ----------------------------
+    # ---- warm-up (untimed): W steps ------------------------------------------------------------------------------
     for _ in range(max(1, W // EPISODE)):
         g_episode.replay()
     g_reduce = capture(reduce_counts)
     g_reduce.replay()
     torch.cuda.synchronize()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(SEGMENTS + 1)]
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(n_seg + 1)]
 
     def timed_pass(gather):
-        """an untimed estimate + clock warm-up, then SEGMENTS x per_seg groups inside one barrier + synchronize bracket;
-        returns (wall seconds, median seconds per region, regions, last gathered tensor)"""
-        run_groups(2, gather=gather)
+        """an untimed region (a clock warm-up as long as the measurement), then exactly K env steps -- one region and,
+        N > 1, its gather -- inside one barrier + synchronize bracket; returns (wall seconds, median seconds per env
+        step over the segments, the gathered final states)"""
+        run_region(0, gather)
+        if distributed and gather == "pipelined":
+            pipe.result()
         torch.cuda.synchronize()
-        ev[0].record()
-        run_groups(4, gather=gather)
-        ev[1].record()
-        torch.cuda.synchronize()
-        est = max(ev[0].elapsed_time(ev[1]) / 1e3 / 4, 1e-7)  # seconds per group
-        per_seg = max(1, math.ceil(MIN_TIMED_S / SEGMENTS / est))
-        if distributed:
-            per_seg = math.ceil(per_seg / (2 * reduce_every)) * 2 * reduce_every  # (whole reduce periods, both buffers)
-        per_seg = int(max_over_ranks([per_seg])[0])  # the same on every rank
-        run_groups(SEGMENTS * per_seg, gather=gather)
         barrier()
         done_count.zero_()
         barrier()
         t0 = time.perf_counter()
         ev[0].record()
-        last = None
-        for sgm in range(SEGMENTS):
-            got = run_groups(per_seg, sgm * per_seg, gather=gather)
-            last = got if got is not None else last
-            ev[sgm + 1].record()
+        last = run_region(1, gather, ev)
+        if distributed and gather == "pipelined":
+            last = pipe.result()
         torch.cuda.synchronize()
         if distributed:
             dist.barrier()
         wall = max_over_ranks([time.perf_counter() - t0])[0]
-        seg = sorted(max_over_ranks([ev[i].elapsed_time(ev[i + 1]) / 1e3 for i in range(SEGMENTS)]))
-        median_region = 0.5 * (seg[SEGMENTS // 2 - 1] + seg[SEGMENTS // 2]) / (per_seg * group)
-        return wall, median_region, SEGMENTS * per_seg * group, last
+        seg = sorted(max_over_ranks([ev[s].elapsed_time(ev[s + 1]) / 1e3 / seg_steps[s] for s in range(n_seg)]))
+        return wall, 0.5 * (seg[(n_seg - 1) // 2] + seg[n_seg // 2]), last
 
-    # ---- the timed region: `repeats` x exactly K steps ----------------------------------------------------------
-    elapsed, median_region_s, repeats, final_states = timed_pass("pipelined")
+    # ---- the timed region: exactly K steps ----------------------------------------------------------------------
+    elapsed, median_step_s, final_states = timed_pass("pipelined")
     final_states = state if final_states is None else final_states
     assert final_states.shape[0] == world * b
-    timed_episodes = repeats * n_full
-    finished = int(done_count[EPISODE].item()) // timed_episodes if timed_episodes else 0
+    finished = int(done_count[EPISODE].item()) // n_full if n_full else 0
+    if args.dump_outputs and rank == 0:
+        # what the timed path hands its caller after its last step: the final states of the last episode and the
+        # per-step finished-game counts of the timed region (taken now: the sections below reuse both buffers)
+        dumped = {"points": final_states.cpu().numpy(), "done_count": done_count.cpu().numpy().astype(np.float64)}
     gather_us = value_without_gather = overlap_hidden = None
     if distributed:
         # the pipelined result equals the serial gather of the same buffer
-        last_buf = states[(SEGMENTS * (repeats // SEGMENTS) - 1) & 1]
-        serial = hkdist.all_gather_games(boundary(last_buf), shard, direct=direct, validate=False)
+        serial = hkdist.all_gather_games(boundary(states[1]), shard, direct=direct, validate=False)
         torch.cuda.synchronize()
         assert torch.equal(serial, final_states), "the pipelined gather differs from the serial one"
-        t_nog, _, reps_nog, _ = timed_pass("none")
-        value_without_gather = world * b * K * reps_nog / t_nog
-        run_groups(2 * reduce_every, gather="serial")
+        t_nog, _, _ = timed_pass("none")
+        value_without_gather = world * b * K / t_nog
+        for r in range(2):
+            run_region(r, "serial")
         gather_events.clear()
-        run_groups(16 * reduce_every, gather="serial")
+        for r in range(16):
+            run_region(r, "serial")
         torch.cuda.synchronize()
         gs = sorted(e0.elapsed_time(e1) * 1e3 for e0, e1 in gather_events)
         gather_us = max_over_ranks([gs[len(gs) // 2]])[0]
         # what a region costs with the gather on the launch stream (compute + gather) against what it cost pipelined
-        region_alone_us = t_nog / reps_nog * 1e6
-        pipelined_us = elapsed / repeats * 1e6
+        region_alone_us = t_nog * 1e6
+        pipelined_us = elapsed * 1e6
         hideable = min(region_alone_us, gather_us)
         overlap_hidden = max(0.0, min(1.0, (region_alone_us + gather_us - pipelined_us) / hideable)) if hideable > 0 else None
 
@@ -759,7 +762,7 @@ def main():
                    "hip_kernel_share_source": prof_src if prof.get("search_hip_kernel_share") is not None else None}
 
     if rank == 0:
-        launch_s = median_region_s / max(1, launches_per_region)  # per rollout launch (+ its share of the reduce)
+        launch_s = median_step_s * K / max(1, launches_per_region)  # per rollout launch (+ its share of the reduce)
         steps_per_launch = K / max(1, launches_per_region)
         alg_bytes = b * bytes_step * steps_per_launch
         full = b == BATCH and rem == 0
@@ -789,22 +792,21 @@ def main():
         }
         out = {
             "metric": "env-steps/sec at dim=3, max_pts=20, batch=65536; 1/2/4/8 GPUs",
-            "value": world * b * K * repeats / elapsed,
+            "value": world * b * K / elapsed,
             "unit": "env-steps/s",
             "n_gpus": world,
             "steps": K,
             "warmup": W,
-            "ms_per_step": elapsed / (K * repeats) * 1e3,
+            "ms_per_step": elapsed / K * 1e3,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
-            "repeats": repeats,
-            "timed_steps": K * repeats,
+            "timed_steps": K,
             "timed_seconds": elapsed,
-            "ms_per_step_median": median_region_s / K * 1e3,
-            "value_from_median": world * b * K / median_region_s,
+            "ms_per_step_median": median_step_s * 1e3,
+            "value_from_median": world * b / median_step_s,
             "config": {
                 "workload": f"dim={d}, max_points={m}, batch={b} games per GPU (BASELINE configs[1]), random "
                             f"host+agent policies sampled in-kernel, reposition=True, rescale=False, episodes of "
@@ -813,12 +815,12 @@ def main():
                                if args.binning else "") + f"); fused rollout: "
                             f"{EPISODE} env steps per launch",
                 "parallelism": f"{world} x independent game shards" + (
-                    f"; after EVERY {K}-step region one all-gather of the final states of all ranks "
-                    f"({os.environ.get('HK_BENCH_GATHER', 'rccl')}), pipelined behind the next region on a side "
-                    f"stream, inside the timed region" if distributed else ""),
-                "launch": f"hipGraph replays: one rollout kernel per episode, one counter reduce per "
-                          f"{reduce_every * launches_per_region} episodes, {group} region(s) per graph; the K-step "
-                          f"region repeated {repeats}x inside one barrier+synchronize bracket",
+                    f"; after the {K}-step region one all-gather of the final states of all ranks "
+                    f"({os.environ.get('HK_BENCH_GATHER', 'rccl')}) on a side stream, inside the timed region"
+                    if distributed else ""),
+                "launch": f"hipGraph replays: one rollout kernel per episode, one counter reduce per graph of at most "
+                          f"{CHUNK} episodes; the K-step region timed once inside one barrier+synchronize bracket, "
+                          f"after an untimed one",
             },
             "roofline": roofline,
             "games_finished_per_episode": finished,
@@ -846,9 +848,28 @@ def main():
             out["cpu_baseline"] = cpu_baseline()
             out["cpu_baseline_array_formulation"] = cpu_array_baseline()
         print(json.dumps(out), flush=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dumped)
     if distributed:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32 (float32 data) or float64 (the rest).  Over
+    DUMP_BYTES in all (N > 1 gathers every rank's states), `points` keeps a fixed, seeded sample of its games, and
+    their indices go to points_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64)
+              for k, v in arrays.items()}
+    pts = arrays["points"]
+    rest = sum(v.nbytes + 4096 for k, v in arrays.items() if k != "points") + 2 * 4096  # (4096: room for a .npy header)
+    if rest + pts.nbytes > DUMP_BYTES:
+        row = pts[0].nbytes + 8  # a game's states + its index
+        keep = np.sort(np.random.default_rng(SEED).choice(len(pts), (DUMP_BYTES - rest) // row, replace=False))
+        arrays["points"], arrays["points_index"] = pts[keep], keep.astype(np.float64)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def cpu_baseline(seconds: float = 12.0):

@@ -1,11 +1,13 @@
 """bench.py as the driver runs it: `python bench.py --gpus N` must start its own ranks (child processes) and print
 ONE JSON line from rank 0.  The real path (backend nccl = RCCL, one device per rank) needs >= 2 devices; on a
-one-GPU box the same flow is rehearsed with ranks sharing the device and the final gather staged through gloo."""
+one-GPU box the same flow is rehearsed with ranks sharing the device and the final gather staged through gloo.
+`--steps` is the number of timed steps: the line checks take enough of them for >= 0.1 s at ~1 us per step."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -13,11 +15,13 @@ from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
+STEPS = 200000
 
-def run_bench(n, extra_env=None, *flags):
+
+def run_bench(n, extra_env=None, *flags, steps=STEPS):
     env = dict(os.environ, **(extra_env or {}))
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "20", "--warmup", "5",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", str(steps), "--warmup", "5",
            "--no-single-step", "--no-cpu-baseline", *flags]
     proc = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert proc.returncode == 0, proc.stderr[-2000:]
@@ -26,10 +30,12 @@ def run_bench(n, extra_env=None, *flags):
     return json.loads(lines[0])
 
 
-def check_line(out, n):
-    assert out["n_gpus"] == n and out["steps"] == 20 and out["warmup"] == 5 and out["scaling"] == "weak"
+def check_line(out, n, steps=STEPS):
+    assert out["n_gpus"] == n and out["steps"] == steps and out["warmup"] == 5 and out["scaling"] == "weak"
     assert out["unit"] == "env-steps/s" and out["dtype"] == "f32" and out["value"] > 1e7
-    assert out["repeats"] >= 1 and out["timed_steps"] == 20 * out["repeats"] and out["timed_seconds"] >= 0.1
+    assert out["timed_steps"] == steps and out["timed_seconds"] >= 0.1
+    assert out["ms_per_step"] == pytest.approx(out["timed_seconds"] / steps * 1e3)
+    assert out["value"] == pytest.approx(n * 65536 / out["ms_per_step"] * 1e3)
     assert out["games_finished_per_episode"] > 60000
     r = out["roofline"]
     assert r["bound"] == "valu_issue" and (r["frac"] is None or 0 < r["frac"] <= 1)
@@ -56,3 +62,21 @@ def test_bench_two_ranks_rccl():
 
 def test_bench_two_ranks_rehearsal_on_one_device():
     check_line(run_bench(2, {"HK_BENCH_BACKEND": "gloo"}), 2)
+
+
+def test_bench_dump_outputs_are_the_timed_path_results(tmp_path):
+    """--dump-outputs: the final states of the last timed episode and the finished-game counts of the timed region
+    (two episodes), equal to the C oracle's episode from the same generated states, seed and policies"""
+    from oracle import c_oracle as CO
+    out = run_bench(1, None, "--dump-outputs", str(tmp_path), steps=40)
+    assert out["steps"] == out["timed_steps"] == 40
+    names = sorted(os.listdir(tmp_path))
+    assert names == ["done_count.npy", "points.npy"]
+    assert sum(os.path.getsize(tmp_path / f) for f in names) <= 64 << 20
+    pts, done = np.load(tmp_path / "points.npy"), np.load(tmp_path / "done_count.npy")
+    assert pts.dtype == np.float32 and pts.shape == (65536, 20, 3)
+    assert done.dtype == np.float64 and done.shape == (21,)
+    want_p, want_rec = CO.rollout(CO.generate_points(65536, 20, 3, 20, 42), 20, 7, record=False)
+    assert np.array_equal(pts, want_p)
+    assert np.array_equal(done, 2 * want_rec["done_count"].astype(np.float64))
+    assert out["games_finished_per_episode"] == int(want_rec["done_count"][-1])

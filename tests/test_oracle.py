@@ -330,24 +330,21 @@ def test_live_zeillinger_list(live_list):
 def test_native_reference_cpputil():
     """hironaka/cpp/cppUtil.cpp:58-61 getNewtonPolytope_approx compiled as-is.  It is only
     right for games with >= 2 points and no duplicates; there its compacted,
-    original-order survivor list must equal the oracle's survivors."""
+    original-order survivor list must equal the oracle's survivors.  Its outputs are recorded in
+    tests/golden/cpputil_newton_approx.npz (tests/golden/make_cpputil_golden.py); where oracle/_ref
+    is built, the library itself must still return them."""
+    fx = np.load(os.path.join(ROOT, "tests", "golden", "cpputil_newton_approx.npz"))
+    pts, out = fx["points"], fx["out"]
+    b, m, d = pts.shape
     path = os.path.join(ROOT, "oracle", "_ref", "cppUtil.so")
-    if not os.path.exists(path):
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    ref = ctypes.CDLL(path)
-    ref.getNewtonPolytope_approx.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-    ref.getNewtonPolytope_approx.restype = None
-    rng = np.random.default_rng(5)
-    b, m, d = 200, 8, 3
-    pts = np.full((b, m, d), -1, dtype=np.int64)
-    for g in range(b):
-        n = int(rng.integers(2, m + 1))
-        rows = set()
-        while len(rows) < n:
-            rows.add(tuple(rng.integers(0, 9, d).tolist()))
-        pts[g, :n] = np.array(sorted(rows, key=lambda _: rng.random()))
-    out = np.full_like(pts, -1)
-    ref.getNewtonPolytope_approx(pts.ctypes.data, b, m, d, out.ctypes.data)
+    if os.path.exists(path):
+        ref = ctypes.CDLL(path)
+        ref.getNewtonPolytope_approx.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_void_p]
+        ref.getNewtonPolytope_approx.restype = None
+        live = np.full_like(pts, -1)
+        ref.getNewtonPolytope_approx(np.ascontiguousarray(pts).ctypes.data, b, m, d, live.ctypes.data)
+        assert np.array_equal(live, out), "oracle/_ref/cppUtil.so differs from the recorded outputs"
     mine = CO.get_newton_polytope(pts.astype(np.float64), sem="jax")
     for g in range(b):
         want = [tuple(r) for r in out[g] if r[0] != -1]
