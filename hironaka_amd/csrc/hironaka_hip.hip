@@ -63,82 +63,164 @@ int launch_generic(Params& prm, int dtype, hipStream_t stream) {
   return dtype == HK_F32 ? launch_generic_t<float>(prm, stream) : launch_generic_t<double>(prm, stream);
 }
 
-// kernel selection: register-resident specialisation -> team kernel (f32, dim 2..6, <= 64 rows; also the
-// specialised shapes on HK_FLAG_FORCE_TEAM) -> generic kernel (anything else: f64, dim > 6, > 64 rows,
-// HK_FLAG_FORCE_GENERIC, and the few mode / semantics combinations fast_supported / team_supported decline)
-constexpr unsigned kHostSideFlags =
-    HK_FLAG_FORCE_ONE_LANE | HK_FLAG_FORCE_TWO_LANES | HK_FLAG_FORCE_FOUR_LANES;  // kernel selection only
+// ---- kernel selection -------------------------------------------------------------------------------------------------
+// `pick` alone decides which kernel serves a request (DESIGN.md §5 has the table).  The *_supported predicates of the
+// family headers say what a kernel CAN serve (shapes, alignment, semantics, mode, records); pick adds the testing flags
+// and the measured crossovers, and everything that launches or sizes a launch asks it.
+enum class Kernel { None, Quad, QuadRoll, QuadRollFused, QuadGen, QuadZeil, Duo, Fast, Team, Generic };
 
-// hk_step on four lanes per game (hk_quad_kernel.h): where it is ahead of the two-lane kernel
-static bool use_quad(const Params& prm, int dtype) {
-  if (prm.flags & HK_FLAG_FORCE_FOUR_LANES) {
-    Params probe = prm;
-    probe.flags &= ~kHostSideFlags;
-    return quad_supported(probe, dtype);
-  }
-  if (!quad_supported(prm, dtype)) return false;
-  return quad_default(prm, device_simds());
+constexpr unsigned kForceFlags = HK_FLAG_FORCE_GENERIC | HK_FLAG_FORCE_TEAM | HK_FLAG_FORCE_ONE_LANE |
+                                 HK_FLAG_FORCE_TWO_LANES | HK_FLAG_FORCE_FOUR_LANES;
+// read by pick only: cleared before a launcher sees the request (the compiled rollout configurations compare flags)
+constexpr unsigned kHostSideFlags = HK_FLAG_FORCE_ONE_LANE | HK_FLAG_FORCE_TWO_LANES | HK_FLAG_FORCE_FOUR_LANES;
+
+inline int64_t workgroups(int batch, int games_per_block) { return ((int64_t)batch + games_per_block - 1) / games_per_block; }
+
+// a generated / multi-episode rollout the fused kernel declines runs as hk_generate_points into `out` + one plain
+// rollout per episode from there
+Params plain_rollout(Params prm) {
+  prm.max_value = 0;
+  prm.episodes = 1;
+  if (!prm.in) prm.in = prm.out;
+  return prm;
 }
-// hk_generate_points on four lanes per game (hk_quadgen_kernel.h): everywhere it applies
-static bool use_quadgen(const Params& prm, int dtype) {
-  Params probe = prm;
-  probe.flags &= ~(unsigned)HK_FLAG_FORCE_FOUR_LANES;
-  return quadgen_supported(probe, dtype);
+
+// hk_zeillinger on the register-resident / team kernels: a step launch without stages and without a state output, whose
+// only product is class_out (both variants: the semantics code travels in the flags)
+Params zeillinger_step(Params prm) {
+  prm.mode = kModeStep;
+  prm.pad = -1.0;
+  return prm;
 }
-// plain rollouts on four lanes per game (hk_quadroll_kernel.h): forced, or where it is the default
-static bool use_duo(const Params& prm) { return !(prm.flags & HK_FLAG_FORCE_ONE_LANE) && duo_wanted(prm); }
-static bool use_quadroll(const Params& prm, int dtype) {
-  Params probe = prm;
-  probe.flags &= ~(unsigned)HK_FLAG_FORCE_FOUR_LANES;
-  if (!quadroll_supported(probe, dtype)) return false;
-  if (prm.flags & HK_FLAG_FORCE_FOUR_LANES) return true;
-  // the small records without observations ride on the two-lane plain rollout too (hk_duo_kernel.h: flush_records):
-  // where that is the faster plain kernel it takes them (28.8 -> ~23 us at (20,3) x 65 536)
-  const bool small_only = !prm.obs_out && (prm.r_host_class_out || prm.r_axis_out || prm.r_done_out || prm.r_reward_out);
-  const bool duo_takes = small_only && fast_supported(prm, dtype) && use_duo(prm);
-  return quadroll_default(prm, device_simds(), duo_takes);
+
+// The testing flags (HK_FLAG_FORCE_*) choose among the kernels that can serve a request, never change its result.
+// Precedence:
+//   GENERIC   the generic kernel, for every request;
+//   TEAM      the team kernel where it applies, else the generic kernel;
+//   then, on requests a kernel with a per-shape specialisation can serve:
+//   steps     FOUR_LANES: the four-lane kernel wherever it applies (over ONE_LANE / TWO_LANES); else ONE_LANE or TWO_LANES
+//             keep it out; then ONE_LANE: one lane per game (over TWO_LANES), TWO_LANES: two lanes wherever they apply;
+//   rollouts  ONE_LANE or TWO_LANES keep every four-lane kernel out (over FOUR_LANES), then as steps; FOUR_LANES: the
+//             four-lane kernel wherever it applies, the fused one without its residency rule;
+//   generator ONE_LANE or TWO_LANES keep the four-lane kernel out; FOUR_LANES changes nothing;
+//   hk_zeillinger: TEAM, ONE_LANE or TWO_LANES keep the four-lane kernel out; FOUR_LANES changes nothing.
+// Kernel::None: no kernel serves the request.
+Kernel pick(const Params& prm, int dtype) {
+  const unsigned f = prm.flags;
+  const bool generic = f & HK_FLAG_FORCE_GENERIC;
+  const bool shaped = !(f & (HK_FLAG_FORCE_GENERIC | HK_FLAG_FORCE_TEAM));  // the kernels with per-shape specialisations
+  const bool lanes = f & (HK_FLAG_FORCE_ONE_LANE | HK_FLAG_FORCE_TWO_LANES);
+  const bool four = f & HK_FLAG_FORCE_FOUR_LANES;
+  const int64_t quad_waves = workgroups(prm.batch, kQuadGames);
+  // measured (scripts/probe_duo.py): two lanes per game are ahead while the one-lane kernel (64 games per wave) leaves
+  // SIMDs short of a second wave -- up to 1.5 waves per SIMD, 98 304 games on the 1024 SIMDs of an MI355X -- and at any
+  // size for the shapes whose one-lane kernel runs one wave per SIMD
+  const auto duo_preferred = [&] {
+    return (int64_t)prm.batch * 2 <= (int64_t)3 * kWave * device_simds() || prm.m * prm.d > 64;
+  };
+
+  if (prm.mode == kModeZeillinger) {
+    if (generic) return Kernel::Generic;
+    // four lanes per game (the rollout kernel's prologue + its balanced pair loop) wherever that kernel exists: the JAX
+    // variant over contiguous 16-B aligned records ((20,3) x 65 536: 21.4 us on one lane per game, (20,4): 37.4)
+    if (shaped && !lanes && quadzeil_supported(prm, dtype)) return Kernel::QuadZeil;
+    const Params step = zeillinger_step(prm);
+    if (shaped && fast_supported(step, dtype)) return Kernel::Fast;
+    return team_supported(step, dtype) ? Kernel::Team : Kernel::Generic;
+  }
+
+  if (prm.mode == kModeRollout && (prm.max_value > 0 || prm.episodes > 1)) {
+    // generated initial states and / or several episodes as ONE launch (hk_quadroll_kernel.h: GEN, EPI)
+    if (shaped && !lanes) {
+      if (prm.max_value > 0) {
+        if (quadroll_gen_supported(prm, dtype)) return Kernel::QuadRollFused;
+      } else if (quadroll_episodes_supported(prm, dtype)) {
+        // episodes from the states in memory: where the waves of the launch are resident all at once (four per SIMD), a
+        // wave that starts its next episode early fills what the launch boundary left idle -- (20,3) x 65 536: 16.5 -
+        // 17.0 us per episode against 20.8 one launch each; beyond (131 072 games: 37 against 30 us; (50,4) x 262 144:
+        // 205 against 172 us, scripts/probe_persistent.py) the per-episode launches of the default kernels stay ahead
+        if (four || (prm.m <= 32 && quad_waves <= (int64_t)4 * device_simds())) return Kernel::QuadRollFused;
+      }
+    }
+    return pick(plain_rollout(prm), dtype);
+  }
+
+  // hk_step on four lanes per game: everywhere it applies (scripts/probe_crossover.py: ahead of the one-lane kernel
+  // from 32 768 to 524 288 games on (10,3), (20,3), (20,4) -- e.g. (20,3): 6.0 vs 11.3 us at 32 768, 44.9 vs 52.7 us at
+  // 524 288 -- and of the team kernel on (50,4): 94 vs 113 us at 262 144)
+  if (shaped && (four || !lanes) && quad_supported(prm, dtype)) return Kernel::Quad;
+  // hk_generate_points on four lanes per game: everywhere it applies
+  if (shaped && !lanes && quadgen_supported(prm, dtype)) return Kernel::QuadGen;
+  if (shaped && !lanes && quadroll_supported(prm, dtype)) {
+    // plain rollouts on four lanes per game: the shapes without a two-lane kernel ((50,4): hk::team_kernel's rollouts
+    // before) ... and, on the small shapes, batches of up to two of its waves per SIMD (32 768 games on an MI355X):
+    // measured (scripts/probe_rollout_families.py, (20,3)): 14.0 / 15.0 / 17.4 us per 20-step episode at 4 096 / 16 384 /
+    // 32 768 games against 16.9 / 18.3 / 18.8 on two lanes per game, 24.5 against 22.2 at 65 536
+    if (four || prm.m > 32) return Kernel::QuadRoll;
+    // Zeillinger's host: the two-lane kernel is ahead at every size it serves (scripts/probe_zeillinger.py, (20,3):
+    // 40.9 against 44.3 us at 32 768 games, 37.4 against 38.5 at 8 192, 44.2 against 57.0 at 65 536)
+    if (prm.host_policy != HK_HOST_ZEILLINGER) {
+      // Recording rollouts: at every size (scripts/probe_records.py, (20,3), per 20-step episode incl. the counter
+      // reduce: 39.8 against 48.6 us with the small records and 69.5 against 82.1 us with the observations at 65 536
+      // games, 90.6 / 240 against 114 / 279 us at 262 144) -- except that the small records without observations ride
+      // on the two-lane plain rollout too (hk_duo_kernel.h: flush_records): where that is the faster plain kernel it
+      // takes them (28.8 -> ~23 us at (20,3) x 65 536)
+      if (prm.obs_out) return Kernel::QuadRoll;
+      if (small_records(prm) && !(duo_supported(prm, dtype) && duo_preferred())) return Kernel::QuadRoll;
+      // short rollouts (measured at (20,3) x 65 536, scripts/probe_short_rollouts.py: 1 / 2 / 4 / 6 steps 8.2 / 10.0 /
+      // 12.3 / 14.4 us against the two-lane kernel's 9.6 / 11.5 / 13.6 / 15.0; level at 8 steps): the wave's shorter
+      // chain counts while the wide first steps are most of the launch
+      const int64_t simds = device_simds();
+      if (prm.steps <= 6 && quad_waves <= 4 * simds) return Kernel::QuadRoll;
+      if (quad_waves <= 2 * simds) return Kernel::QuadRoll;
+    }
+  }
+  // (the step's observation features, and the agent's move as an argmax of its logits, come from the four-lane kernel only)
+  if (prm.feat_out || ((prm.stages & HK_STAGE_SHIFT) && prm.axis_dtype == HK_AXIS_MASKED_LOGITS)) return Kernel::None;
+  if (shaped && fast_supported(prm, dtype)) {
+    const bool two = !(f & HK_FLAG_FORCE_ONE_LANE) && duo_supported(prm, dtype) &&
+                     ((f & HK_FLAG_FORCE_TWO_LANES) || duo_preferred());
+    return two ? Kernel::Duo : Kernel::Fast;
+  }
+  // the team kernel: f32, dim 2..6, <= 64 rows; the generic kernel: anything else (f64, dim > 6, > 64 rows, and the few
+  // mode / semantics combinations fast_supported / team_supported decline)
+  return !generic && team_supported(prm, dtype) ? Kernel::Team : Kernel::Generic;
 }
-int launch(Params& prm, int dtype, hipStream_t stream) {
-  if (prm.batch == 0) return HK_OK;
-  if (use_quad(prm, dtype)) {
-    prm.flags &= ~kHostSideFlags;
-    return launch_quad(prm, stream);
-  }
-  if (use_quadroll(prm, dtype)) {
-    prm.flags &= ~kHostSideFlags;  // (the compiled rollout configurations compare flags)
-    return launch_quadroll(prm, stream);
-  }
-  if (use_quadgen(prm, dtype)) {
-    prm.flags &= ~kHostSideFlags;
-    return launch_quadgen(prm, stream);
-  }
-  // (the agent's move as an argmax of its logits is decoded by the four-lane kernel only)
-  if ((prm.stages & HK_STAGE_SHIFT) && prm.axis_dtype == HK_AXIS_MASKED_LOGITS) return HK_ERR_UNSUPPORTED;
-  if (fast_supported(prm, dtype)) {
-    const bool duo = use_duo(prm);
-    prm.flags &= ~kHostSideFlags;  // (the compiled rollout configurations compare flags)
-    return duo ? launch_duo(prm, stream) : launch_fast(prm, stream);
-  }
+
+int run(Kernel k, Params prm, int dtype, hipStream_t stream) {
   prm.flags &= ~kHostSideFlags;
-  if (team_supported(prm, dtype)) {
-    const int st = launch_team(prm, stream);
-    if (st != HK_ERR_UNSUPPORTED) return st;
+  switch (k) {
+    case Kernel::Quad: return launch_quad(prm, stream);
+    case Kernel::QuadRoll: return launch_quadroll(prm, stream);
+    case Kernel::QuadRollFused: return launch_quadroll_gen(prm, stream);
+    case Kernel::QuadGen: return launch_quadgen(prm, stream);
+    case Kernel::QuadZeil: return launch_quadzeil(prm, stream);
+    case Kernel::Duo: return launch_duo(prm, stream);
+    case Kernel::Fast: return launch_fast(prm, stream);
+    case Kernel::Team: return launch_team(prm, stream);
+    case Kernel::Generic: return launch_generic(prm, dtype, stream);
+    case Kernel::None: break;
   }
-  return launch_generic(prm, dtype, stream);
+  return HK_ERR_UNSUPPORTED;
 }
 
-// number of workgroups `launch` will use for this request (0: not launchable)
+int launch(const Params& prm, int dtype, hipStream_t stream) {
+  if (prm.batch == 0) return HK_OK;
+  return run(pick(prm, dtype), prm, dtype, stream);
+}
+
+// workgroups of the launch that serves this rollout request (0: not launchable)
 int64_t planned_grid(Params prm, int dtype) {
   if (prm.batch == 0) return 0;
-  if (use_quadroll(prm, dtype)) return quadroll_grid(prm);
-  if (fast_supported(prm, dtype)) {
-    const int gpb = use_duo(prm) ? kDuoGames : fast_games_per_block(prm);
-    return ((int64_t)prm.batch + gpb - 1) / gpb;
+  switch (pick(prm, dtype)) {
+    case Kernel::QuadRoll:
+    case Kernel::QuadRollFused: return quadroll_grid(prm);
+    case Kernel::Duo: return workgroups(prm.batch, kDuoGames);
+    case Kernel::Fast: return workgroups(prm.batch, kWave);
+    case Kernel::Team: return workgroups(prm.batch, kTeamGames);
+    case Kernel::Generic: return plan_generic(prm, dtype) == HK_OK ? workgroups(prm.batch, prm.games_per_block) : 0;
+    default: return 0;
   }
-  if (team_supported(prm, dtype) && plan_team(prm) == HK_OK)
-    return ((int64_t)prm.batch + prm.games_per_block - 1) / prm.games_per_block;
-  if (plan_generic(prm, dtype) != HK_OK) return 0;
-  return ((int64_t)prm.batch + prm.games_per_block - 1) / prm.games_per_block;
 }
 
 // row length of the finished-game workspace for a geometry: an upper bound of the grids of all the kernel
@@ -147,12 +229,9 @@ int64_t count_slots(Params prm, int dtype) {
   if (prm.batch == 0) return 0;
   int64_t slots = planned_grid(prm, dtype);
   if (dtype == HK_F32 && prm.d >= 2 && prm.d <= 6 && prm.m <= kTeam * kTeamSlots)
-    slots = std::max<int64_t>(slots, ((int64_t)prm.batch + kTeamGames - 1) / kTeamGames);
-  if (has_fast_path(prm.m, prm.d, dtype))
-    slots = std::max<int64_t>(slots, ((int64_t)prm.batch + kDuoGames - 1) / kDuoGames);
-  Params gen = prm;
-  if (plan_generic(gen, dtype) == HK_OK)
-    slots = std::max<int64_t>(slots, ((int64_t)prm.batch + gen.games_per_block - 1) / gen.games_per_block);
+    slots = std::max<int64_t>(slots, workgroups(prm.batch, kTeamGames));
+  if (has_fast_path(prm.m, prm.d, dtype)) slots = std::max<int64_t>(slots, workgroups(prm.batch, kDuoGames));
+  if (plan_generic(prm, dtype) == HK_OK) slots = std::max<int64_t>(slots, workgroups(prm.batch, prm.games_per_block));
   return slots;
 }
 
@@ -286,9 +365,7 @@ int hk_step_features(const hk_step_desc* desc, void* features_out, int scale_obs
   if (desc->dtype != HK_F32 || !(prm.stages & HK_STAGE_SHIFT)) return HK_ERR_UNSUPPORTED;
   prm.feat_out = (float*)features_out;
   prm.feat_scale = scale_observation ? 1 : 0;
-  if (!use_quad(prm, desc->dtype)) return HK_ERR_UNSUPPORTED;
-  prm.flags &= ~kHostSideFlags;
-  return launch_quad(prm, (hipStream_t)stream);
+  return launch(prm, desc->dtype, (hipStream_t)stream);
 }
 
 int hk_shift(const void* points_in, void* points_out, const void* coords, int coords_kind,
@@ -412,9 +489,10 @@ int hk_generate_points_binned(void* points_out, int32_t* game_ids_out, int32_t* 
   prm.m = max_points;
   prm.d = dim;
   prm.stages = stages;
-  prm.flags = flags & ~(unsigned)HK_FLAG_FORCE_FOUR_LANES;
+  prm.flags = flags;
   prm.mode = kModeGenerate;
-  if (!quadgen_supported(prm, dtype)) return HK_ERR_UNSUPPORTED;  // (what the four-lane generator serves)
+  if (pick(prm, dtype) != Kernel::QuadGen) return HK_ERR_UNSUPPORTED;  // (the four-lane generator bins the games)
+  prm.flags &= ~kHostSideFlags;
   return launch_quadbin(prm, nullptr, game_ids_out, num_points_out, (hipStream_t)stream);
 }
 
@@ -490,31 +568,9 @@ static int params_from_rollout(const hk_rollout_desc* r, Params& prm) {
   return HK_OK;
 }
 
-// rollouts with generated initial states and / or several episodes as ONE launch (hk_quadroll_kernel.h: GEN)
-static bool use_quadroll_gen(const Params& prm, int dtype) {
-  Params probe = prm;
-  probe.flags &= ~(unsigned)HK_FLAG_FORCE_FOUR_LANES;
-  if (prm.max_value <= 0) {
-    // episodes from the states in memory: where the waves of the launch are resident all at once (four per SIMD), a wave
-    // that starts its next episode early fills what the launch boundary left idle -- (20,3) x 65 536: 16.5 - 17.0 us per
-    // episode against 20.8 one launch each; beyond (131 072 games: 37 against 30 us; (50,4) x 262 144: 205 against
-    // 172 us, scripts/probe_persistent.py) the per-episode launches of the default kernels stay ahead
-    if (prm.flags & HK_FLAG_FORCE_FOUR_LANES) return quadroll_episodes_supported(probe, dtype);
-    const int64_t waves = ((int64_t)prm.batch + kQuadGames - 1) / kQuadGames;
-    return prm.m <= 32 && waves <= (int64_t)4 * device_simds() && quadroll_episodes_supported(probe, dtype);
-  }
-  return quadroll_gen_supported(probe, dtype);
-}
-
-// the geometry of the launch(es) that will serve a rollout request (a request the fused kernel declines is served by
-// hk_generate_points + a rollout per episode: the plain request's kernels)
-static Params rollout_geometry(Params prm, int dtype) {
-  if (!use_quadroll_gen(prm, dtype)) {
-    prm.max_value = 0;
-    prm.episodes = 1;
-    if (!prm.in) prm.in = prm.out;
-  }
-  return prm;  // (the fused kernel's grid is quadroll_grid: within count_slots' bound whatever planned_grid picks)
+// the geometry of the launch(es) that will serve a rollout request
+static Params rollout_geometry(const Params& prm, int dtype) {
+  return pick(prm, dtype) == Kernel::QuadRollFused ? prm : plain_rollout(prm);
 }
 
 uint64_t hk_rollout_workspace_bytes(const hk_rollout_desc* r) {
@@ -537,12 +593,12 @@ int hk_rollout(const hk_rollout_desc* r, void* stream) {
   const int st = params_from_rollout(r, prm);
   if (st != HK_OK) return st;
   if (prm.batch == 0) return HK_OK;
-  const bool fused = use_quadroll_gen(prm, r->dtype);
+  const bool fused = pick(prm, r->dtype) == Kernel::QuadRollFused;
   const bool gen = prm.max_value > 0;
   // what the fused kernel declines runs as hk_generate_points + a rollout per episode: the state then needs a buffer
   // (and a generated batch re-ordered by ids exists inside the fused kernel only)
   if (gen && !fused && (!r->points || r->game_ids)) return HK_ERR_UNSUPPORTED;
-  const Params geo = rollout_geometry(prm, r->dtype);
+  const Params geo = fused ? prm : plain_rollout(prm);
   if (planned_grid(geo, r->dtype) == 0) return HK_ERR_UNSUPPORTED;
   const int64_t slots = count_slots(geo, r->dtype);
   const bool defer = (r->flags & HK_FLAG_DEFER_COUNTS) != 0;
@@ -553,23 +609,16 @@ int hk_rollout(const hk_rollout_desc* r, void* stream) {
   prm.count_stride = (uint32_t)slots;
   int ls = HK_OK;
   if (fused) {
-    prm.flags &= ~kHostSideFlags;  // (the compiled rollout configurations compare flags)
-    ls = launch_quadroll_gen(prm, (hipStream_t)stream);
+    ls = run(Kernel::QuadRollFused, prm, r->dtype, (hipStream_t)stream);
   } else {
-    const int episodes = prm.episodes;
-    for (int e = 0; e < episodes && ls == HK_OK; ++e) {
-      Params p = prm;
-      p.max_value = 0;
-      p.episodes = 1;
+    Params p = plain_rollout(prm);  // (with the workspace of the counts)
+    for (int e = 0; e < prm.episodes && ls == HK_OK; ++e) {
       p.seed = prm.seed + (uint64_t)e;
       if (gen) {
         ls = hk_generate_points(r->points, r->batch, r->max_points, r->dim, r->dtype, r->gen_max_value,
                                 r->gen_seed + (uint64_t)e, r->game_offset, r->gen_stages, r->padding_value,
-                                r->flags & (HK_SEM_MASK | HK_FLAG_FORCE_GENERIC | HK_FLAG_FORCE_TEAM | HK_FLAG_FORCE_ONE_LANE |
-                                            HK_FLAG_FORCE_TWO_LANES | HK_FLAG_FORCE_FOUR_LANES),
-                                stream);
+                                r->flags & (HK_SEM_MASK | kForceFlags), stream);
         if (ls != HK_OK) break;
-        p.in = r->points;
       }
       ls = launch(p, r->dtype, (hipStream_t)stream);
     }
@@ -769,28 +818,8 @@ int hk_zeillinger(const void* points, int64_t stride, int32_t* class_out, int ba
   prm.m = max_points;
   prm.d = dim;
   prm.mode = kModeZeillinger;
-  // on the register-resident / team kernels: a step launch without stages and without a state output, whose
-  // only product is class_out (both variants: the semantics code travels in the flags)
-  if (!(flags & HK_FLAG_FORCE_GENERIC)) {
-    Params fast = prm;
-    fast.mode = kModeStep;
-    fast.pad = -1.0;
-    // four lanes per game (hk_quadroll_kernel.h: the rollout kernel's prologue + its balanced pair loop) wherever that
-    // kernel exists: the JAX variant over contiguous 16-B aligned records ((20,3) x 65 536: 21.4 us on one lane per
-    // game, (20,4): 37.4)
-    if (dtype == HK_F32 && (flags & HK_SEM_MASK) == HK_SEM_JAX &&
-        !(flags & (HK_FLAG_FORCE_TEAM | HK_FLAG_FORCE_ONE_LANE | HK_FLAG_FORCE_TWO_LANES)) &&
-        stride == (int64_t)max_points * dim && aligned(points, 16)) {
-      const int qs = launch_quadzeil(prm, (hipStream_t)stream);
-      if (qs != HK_ERR_UNSUPPORTED) return qs;
-    }
-    if (fast_supported(fast, dtype)) return launch_fast(fast, (hipStream_t)stream);
-    if (team_supported(fast, dtype)) {
-      const int ts = launch_team(fast, (hipStream_t)stream);
-      if (ts != HK_ERR_UNSUPPORTED) return ts;
-    }
-  }
-  return launch_generic(prm, dtype, (hipStream_t)stream);
+  const Kernel k = pick(prm, dtype);
+  return run(k, (k == Kernel::Fast || k == Kernel::Team) ? zeillinger_step(prm) : prm, dtype, (hipStream_t)stream);
 }
 
 int hk_get_features(const void* points_in, int64_t in_stride, void* features_out,

@@ -95,6 +95,19 @@ struct Params {
   int32_t episodes;  // >= 1
 };
 
+// ---- request properties the host side reads (kernel selection, and each launcher's choice of instantiation) ----------
+// sorted + compacted output: the list semantics' Newton stage, or HK_FLAG_COMPACT_SORTED
+inline bool sorted_output(const Params& prm) {
+  return (prm.stages & HK_STAGE_NEWTON) &&
+         ((prm.flags & HK_SEM_MASK) == HK_SEM_LIST || (prm.flags & HK_FLAG_COMPACT_SORTED));
+}
+// the per-step rollout records other than the observations
+inline bool small_records(const Params& prm) {
+  return prm.r_host_class_out || prm.r_axis_out || prm.r_done_out || prm.r_reward_out;
+}
+inline bool any_records(const Params& prm) { return prm.obs_out || small_records(prm); }
+inline bool small_records_only(const Params& prm) { return !prm.obs_out && small_records(prm); }
+
 // hipGetLastError() is sticky per host thread and other users of the runtime in this process
 // (torch) leave benign errors behind: clear it right before a launch, read it right after.
 inline void launch_prepare() { (void)hipGetLastError(); }

@@ -1027,8 +1027,6 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------
-// steps and rollouts on a shape with a register-resident specialisation, when the batch leaves SIMDs
-// short of a second wave under the one-lane kernel
 // SIMDs of the current device (4 per CU); queried once per device
 inline int device_simds() {
   static int cached[16] = {0};
@@ -1043,23 +1041,16 @@ inline int device_simds() {
   return cached[dev];
 }
 
-inline bool duo_wanted(const Params& prm) {
+// steps and rollouts the two-lane kernel serves: those of a register-resident specialisation (fast_supported) of up to
+// 32 rows, without class / feature outputs
+inline bool duo_supported(const Params& prm, int dtype) {
   if ((prm.mode != kModeRollout && prm.mode != kModeStep) || prm.m > 32) return false;
   if (prm.mode == kModeStep && (prm.class_out || (prm.stages & kStageFeatureSorts))) return false;
-  const bool any_records = prm.obs_out || prm.r_host_class_out || prm.r_axis_out || prm.r_done_out || prm.r_reward_out;
   // Zeillinger's host: plain rollouts (duo_kernel<..., ZEIL>); with records the one-lane kernel
-  if (prm.mode == kModeRollout && prm.host_policy == HK_HOST_ZEILLINGER && any_records) return false;
-  if ((prm.stages & HK_STAGE_NEWTON) &&
-      ((prm.flags & HK_SEM_MASK) == HK_SEM_LIST || (prm.flags & HK_FLAG_COMPACT_SORTED))) {
-    // sorted + compacted output: plain rollouts only (they sort once, at the end)
-    const bool records = prm.obs_out || prm.r_host_class_out || prm.r_axis_out || prm.r_done_out || prm.r_reward_out;
-    if (prm.mode != kModeRollout || records) return false;
-  }
-  if (prm.flags & HK_FLAG_FORCE_TWO_LANES) return true;
-  // measured (scripts/probe_duo.py): ahead while the one-lane kernel (64 games per wave) leaves SIMDs short of
-  // a second wave -- up to 1.5 waves per SIMD, 98 304 games on the 1024 SIMDs of an MI355X -- and at any size
-  // for the shapes whose one-lane kernel runs one wave per SIMD
-  return (int64_t)prm.batch * 2 <= (int64_t)3 * kWave * device_simds() || prm.m * prm.d > 64;
+  if (prm.mode == kModeRollout && prm.host_policy == HK_HOST_ZEILLINGER && any_records(prm)) return false;
+  // sorted + compacted output: plain rollouts only (they sort once, at the end)
+  if (sorted_output(prm) && (prm.mode != kModeRollout || any_records(prm))) return false;
+  return fast_supported(prm, dtype);
 }
 
 template <int M, int D>
@@ -1069,7 +1060,7 @@ int launch_duo_t(Params prm, hipStream_t stream) {
   launch_prepare();
   // (the small records alone ride on the plain rollout kernels: ACTS)
   const bool records = prm.obs_out != nullptr;
-  const bool acts = !records && (prm.r_host_class_out || prm.r_axis_out || prm.r_done_out || prm.r_reward_out);
+  const bool acts = small_records_only(prm);
   const int hot = (prm.mode == kModeRollout && !records) ? fast_hot_config(prm) : kHotNone;
   if (prm.mode == kModeRollout && records)
     hipLaunchKernelGGL((duo_kernel<M, D, kModeRolloutRec>), dim3(grid), dim3(kWave), 0, stream, (const float*)prm.in,

@@ -377,7 +377,7 @@ __global__ __launch_bounds__(kWave, ((MODE == kModeRolloutRec || M * D > 64) ? 1
   constexpr bool kRoll = MODE == kModeRollout || kRec;
   constexpr bool kStep = MODE == kModeStep || MODE == kModeStepAux;  // Aux: features / Zeillinger's class
   const int lane = threadIdx.x;
-  // games per wave: 64 (fewer only through the tuning hook of fast_games_per_block())
+  // games per wave: 64 (launch_fast_t)
   const int gpb = gpb0;
   const int64_t g0 = (int64_t)blockIdx.x * gpb;
   const int64_t left = (int64_t)batch0 - g0;
@@ -781,14 +781,6 @@ bool fast_aligned_t(const Params& prm) {
   return true;
 }
 
-// One lane per game means one INSTRUCTION STREAM per 64 games; a wave's stream is latency-bound on its
-// own (~7.7 cycles per instruction measured, whether or not it shares its SIMD), so 65 536 games = 1024
-// waves leave the 1024 SIMDs half idle and the same kernels run ~2x more games per second at >= 262 144
-// games.  Putting fewer games in a wave (idle lanes, more waves) does not buy that back: measured at
-// 65 536 games, 64/32/16 games per wave give 50.4/50.7/84.8 us per 20-step rollout and 11.6/12.3/18.5 us
-// per hk_step, so a wave always takes 64 games.
-inline int fast_games_per_block(const Params&) { return kWave; }
-
 inline int fast_hot_config(const Params& prm) {
   if (prm.stages != (HK_STAGE_SHIFT | HK_STAGE_REPOSITION | HK_STAGE_NEWTON) || prm.host_policy != HK_HOST_RANDOM)
     return kHotNone;
@@ -821,21 +813,24 @@ HK_FAST_SPECS(HK_X)
 #undef HK_X
 #endif
 
+// One lane per game means one INSTRUCTION STREAM per 64 games; a wave's stream is latency-bound on its
+// own (~7.7 cycles per instruction measured, whether or not it shares its SIMD), so 65 536 games = 1024
+// waves leave the 1024 SIMDs half idle and the same kernels run ~2x more games per second at >= 262 144
+// games.  Putting fewer games in a wave (idle lanes, more waves) does not buy that back: measured at
+// 65 536 games, 64/32/16 games per wave give 50.4/50.7/84.8 us per 20-step rollout and 11.6/12.3/18.5 us
+// per hk_step, so a wave always takes 64 games.
 template <int M, int D>
 int launch_fast_t(Params prm, hipStream_t stream) {
-  prm.games_per_block = fast_games_per_block(prm);
-  const unsigned grid = (unsigned)(((int64_t)prm.batch + prm.games_per_block - 1) / prm.games_per_block);
+  prm.games_per_block = kWave;
+  const unsigned grid = (unsigned)(((int64_t)prm.batch + kWave - 1) / kWave);
   launch_prepare();
-  const bool sorted_out = (prm.stages & HK_STAGE_NEWTON) &&
-                          ((prm.flags & HK_SEM_MASK) == HK_SEM_LIST || (prm.flags & HK_FLAG_COMPACT_SORTED));
-  if (prm.mode == kModeStep && (prm.class_out || (prm.stages & kStageFeatureSorts) || sorted_out))
+  if (prm.mode == kModeStep && (prm.class_out || (prm.stages & kStageFeatureSorts) || sorted_output(prm)))
     hipLaunchKernelGGL((fast_kernel<M, D, kModeStepAux>), dim3(grid), dim3(kWave), 0, stream, (const float*)prm.in,
                        prm.in_stride, prm.batch, prm.games_per_block, prm);
   else if (prm.mode == kModeStep)
     hipLaunchKernelGGL((fast_kernel<M, D, kModeStep>), dim3(grid), dim3(kWave), 0, stream, (const float*)prm.in,
                        prm.in_stride, prm.batch, prm.games_per_block, prm);
-  else if (prm.mode == kModeRollout && (prm.obs_out || prm.r_host_class_out || prm.r_axis_out ||
-                                        prm.r_done_out || prm.r_reward_out))
+  else if (prm.mode == kModeRollout && any_records(prm))
     hipLaunchKernelGGL((fast_kernel<M, D, kModeRolloutRec>), dim3(grid), dim3(kWave), 0, stream, (const float*)prm.in,
                        prm.in_stride, prm.batch, prm.games_per_block, prm);
   else if (prm.mode == kModeRollout)
@@ -846,17 +841,14 @@ int launch_fast_t(Params prm, hipStream_t stream) {
   return launch_status();
 }
 
-// does this request run on a register-resident specialisation? (else: generic kernel)
+// can a register-resident specialisation serve this request?
 inline bool fast_supported(const Params& prm, int dtype) {
   if (dtype != HK_F32) return false;
   // sorted + compacted output (list semantics): not from the generator, and not under Zeillinger's host,
   // whose tie-breaks follow the physical row order
-  const bool sorted_out = (prm.stages & HK_STAGE_NEWTON) &&
-                          ((prm.flags & HK_SEM_MASK) == HK_SEM_LIST || (prm.flags & HK_FLAG_COMPACT_SORTED));
-  if (sorted_out && (prm.mode == kModeGenerate ||
-                     (prm.mode == kModeRollout && prm.host_policy == HK_HOST_ZEILLINGER)))
+  if (sorted_output(prm) && (prm.mode == kModeGenerate ||
+                             (prm.mode == kModeRollout && prm.host_policy == HK_HOST_ZEILLINGER)))
     return false;
-  if (prm.flags & (HK_FLAG_FORCE_GENERIC | HK_FLAG_FORCE_TEAM)) return false;
   if ((prm.stages & kStageFeatureSorts) && prm.mode != kModeStep) return false;
   if (prm.mode == kModeZeillinger) return false;
 #define HK_X(M_, D_) if (prm.m == M_ && prm.d == D_) return fast_aligned_t<M_, D_>(prm);

@@ -1707,21 +1707,12 @@ inline bool quad_supported(const Params& prm, int dtype) {
   if (dtype != HK_F32 || prm.mode != kModeStep) return false;
   if (prm.class_out) return false;
   if (prm.coords_kind == HK_COORDS_IN_RECORD) return false;
-  if (prm.flags & (HK_FLAG_FORCE_GENERIC | HK_FLAG_FORCE_TEAM | HK_FLAG_FORCE_ONE_LANE | HK_FLAG_FORCE_TWO_LANES))
-    return false;
-  const bool sorted = (prm.stages & HK_STAGE_NEWTON) &&
-                      ((prm.flags & HK_SEM_MASK) == HK_SEM_LIST || (prm.flags & HK_FLAG_COMPACT_SORTED));
-  if (sorted && prm.m * prm.d > 128) return false;  // (the large games' sorted output stays with the team kernel)
+  if (sorted_output(prm) && prm.m * prm.d > 128) return false;  // (the large games' sorted output stays with the team kernel)
 #define HK_X(M_, D_) if (prm.m == M_ && prm.d == D_) return quad_ok_t<M_, D_>(prm);
   HK_QUAD_SPECS(HK_X)
 #undef HK_X
   return false;
 }
-
-// where the four-lane kernel is the default choice: everywhere it applies (scripts/probe_crossover.py: ahead of the
-// one-lane kernel from 32 768 to 524 288 games on (10,3), (20,3), (20,4) -- e.g. (20,3): 6.0 vs 11.3 us at 32 768,
-// 44.9 vs 52.7 us at 524 288 -- and of the team kernel on (50,4): 94 vs 113 us at 262 144)
-inline bool quad_default(const Params&, int) { return true; }
 
 #ifndef HK_SPEC_TU
 #define HK_X(M_, D_) extern template int launch_quad_t<M_, D_>(Params, hipStream_t);

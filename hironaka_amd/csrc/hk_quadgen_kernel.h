@@ -189,8 +189,6 @@ int launch_quadgen_t(Params prm, hipStream_t stream) {
 // fill equal to the padding value (the other kernels' exactness guard sends anything else down the generic routines)
 inline bool quadgen_supported(const Params& prm, int dtype) {
   if (dtype != HK_F32 || prm.mode != kModeGenerate) return false;
-  if (prm.flags & (HK_FLAG_FORCE_GENERIC | HK_FLAG_FORCE_TEAM | HK_FLAG_FORCE_ONE_LANE | HK_FLAG_FORCE_TWO_LANES))
-    return false;
   if ((prm.flags & HK_SEM_MASK) == HK_SEM_LIST || (prm.flags & HK_FLAG_COMPACT_SORTED)) return false;
   if ((prm.flags & HK_SEM_MASK) == HK_SEM_JAX && (prm.stages & HK_STAGE_NEWTON) && (float)prm.pad != -1.0f) return false;
   if (!((float)prm.pad < 0.0f)) return false;  // (a removed row must read as padding)

@@ -877,25 +877,15 @@ __global__ __launch_bounds__(kWave * WPB, (QuadRollGeom<M, D>::kWavesPerSimd)) v
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
-inline bool quadroll_sorted_output(const Params& prm) {
-  return (prm.stages & HK_STAGE_NEWTON) &&
-         ((prm.flags & HK_SEM_MASK) == HK_SEM_LIST || (prm.flags & HK_FLAG_COMPACT_SORTED));
-}
-
 // rollouts of float32, contiguous, W-aligned records
 inline bool quadroll_request_ok(const Params& prm) {
   if (prm.mode != kModeRollout || prm.m > 255) return false;
   // Zeillinger's host: plain rollouts (quadroll_kernel<..., ZEIL>)
-  if (prm.host_policy == HK_HOST_ZEILLINGER &&
-      (prm.obs_out || prm.r_host_class_out || prm.r_axis_out || prm.r_done_out || prm.r_reward_out))
-    return false;
+  if (prm.host_policy == HK_HOST_ZEILLINGER && any_records(prm)) return false;
   // sorted + compacted output (list semantics): plain rollouts only -- ranked once, at the publish --, not under
   // Zeillinger's host, whose tie-breaks follow the physical row order
-  if (quadroll_sorted_output(prm) &&
-      (prm.max_value > 0 || prm.episodes > 1 || prm.host_policy == HK_HOST_ZEILLINGER || prm.obs_out ||
-       prm.r_host_class_out || prm.r_axis_out || prm.r_done_out || prm.r_reward_out))
-    return false;
-  if (prm.flags & (HK_FLAG_FORCE_GENERIC | HK_FLAG_FORCE_TEAM | HK_FLAG_FORCE_ONE_LANE | HK_FLAG_FORCE_TWO_LANES))
+  if (sorted_output(prm) &&
+      (prm.max_value > 0 || prm.episodes > 1 || prm.host_policy == HK_HOST_ZEILLINGER || any_records(prm)))
     return false;
   return true;
 }
@@ -909,7 +899,7 @@ int launch_quadroll_t(Params prm, hipStream_t stream) {
   prm.pad_f32 = (float)prm.pad;
   launch_prepare();
   const int hot = fast_hot_config(prm);
-  if (prm.obs_out || prm.r_host_class_out || prm.r_axis_out || prm.r_done_out || prm.r_reward_out) {
+  if (any_records(prm)) {
     if (prm.obs_out && reinterpret_cast<uintptr_t>(prm.obs_out) % (QuadGeom<M, D>::W * 4)) return HK_ERR_ALIGN;
     if (hot == kHotJax)
       hipLaunchKernelGGL((quadroll_kernel<M, D, kHotJax, WPB, true>), dim3(grid), dim3(kWave * WPB), 0, stream,
@@ -928,7 +918,7 @@ int launch_quadroll_t(Params prm, hipStream_t stream) {
   else if (hot == kHotTorch)
     hipLaunchKernelGGL((quadroll_kernel<M, D, kHotTorch, WPB>), dim3(grid), dim3(kWave * WPB), 0, stream,
                        (const float*)prm.in, prm.in_stride, prm.batch, prm);
-  else if (quadroll_sorted_output(prm))
+  else if (sorted_output(prm))
     hipLaunchKernelGGL((quadroll_kernel<M, D, kHotList, WPB>), dim3(grid), dim3(kWave * WPB), 0, stream,
                        (const float*)prm.in, prm.in_stride, prm.batch, prm);
   else
@@ -957,6 +947,16 @@ int launch_quadzeil_t(Params prm, hipStream_t stream) {
   hipLaunchKernelGGL((quadroll_kernel<M, D, kHotNone, WPB, false, true>), dim3(grid), dim3(kWave * WPB), 0, stream,
                      (const float*)prm.in, prm.in_stride, prm.batch, prm);
   return launch_status();
+}
+
+// hk_zeillinger requests it serves: the JAX variant over contiguous 16-B aligned float32 records
+inline bool quadzeil_supported(const Params& prm, int dtype) {
+  if (dtype != HK_F32 || prm.mode != kModeZeillinger || (prm.flags & HK_SEM_MASK) != HK_SEM_JAX) return false;
+  if (prm.in_stride != (int64_t)prm.m * prm.d || reinterpret_cast<uintptr_t>(prm.in) % 16) return false;
+#define HK_X(M_, D_) if (prm.m == M_ && prm.d == D_) return true;
+  HK_QUAD_SPECS(HK_X)
+#undef HK_X
+  return false;
 }
 
 inline bool quadroll_supported(const Params& prm, int dtype) {
@@ -1015,14 +1015,14 @@ int launch_quadroll_gen_t(Params prm, hipStream_t stream) {
 // episodes back to back from the states in memory: plain rollouts the four-lane kernel serves, not Zeillinger's host
 inline bool quadroll_episodes_supported(const Params& prm, int dtype) {
   if (prm.max_value > 0 || prm.episodes <= 1 || !prm.in || !prm.out) return false;
-  if (prm.obs_out || prm.r_host_class_out || prm.r_axis_out || prm.r_done_out || prm.r_reward_out) return false;
+  if (any_records(prm)) return false;
   if (prm.host_policy == HK_HOST_ZEILLINGER) return false;
   return quadroll_supported(prm, dtype);
 }
 
 inline bool quadroll_gen_supported(const Params& prm, int dtype) {
   if (dtype != HK_F32 || prm.max_value <= 0 || !quadroll_request_ok(prm)) return false;
-  if (prm.obs_out || prm.r_host_class_out || prm.r_axis_out || prm.r_done_out || prm.r_reward_out) return false;
+  if (any_records(prm)) return false;
   if (prm.host_policy == HK_HOST_ZEILLINGER && prm.m <= 32) return false;
   const float pad = (float)prm.pad;
   if (!(pad < 0.0f) || ((prm.flags & HK_SEM_MASK) == HK_SEM_JAX && pad != -1.0f)) return false;
@@ -1031,28 +1031,6 @@ inline bool quadroll_gen_supported(const Params& prm, int dtype) {
   HK_QUAD_SPECS(HK_X)
 #undef HK_X
   return false;
-}
-
-// where this kernel is the default: the shapes without a two-lane kernel ((50,4): hk::team_kernel's rollouts before)
-// ... and, on the small shapes, batches of up to two of its waves per SIMD (32 768 games on an MI355X): measured
-// (scripts/probe_rollout_families.py, (20,3)): 14.0 / 15.0 / 17.4 us per 20-step episode at 4 096 / 16 384 / 32 768 games against
-// 16.9 / 18.3 / 18.8 on two lanes per game, 24.5 against 22.2 at 65 536
-// Recording rollouts: at every size (scripts/probe_records.py, (20,3), per 20-step episode incl. the counter reduce:
-// 39.8 against 48.6 us with the small records and 69.5 against 82.1 us with the observations at 65 536 games, 90.6 / 240
-// against 114 / 279 us at 262 144).
-inline bool quadroll_default(const Params& prm, int simds, bool small_records_elsewhere = false) {
-  if (prm.m > 32) return true;
-  // Zeillinger's host: the two-lane kernel is ahead at every size it serves (scripts/probe_zeillinger.py, (20,3):
-  // 40.9 against 44.3 us at 32 768 games, 37.4 against 38.5 at 8 192, 44.2 against 57.0 at 65 536)
-  if (prm.host_policy == HK_HOST_ZEILLINGER) return false;
-  if (prm.obs_out) return true;
-  if ((prm.r_host_class_out || prm.r_axis_out || prm.r_done_out || prm.r_reward_out) && !small_records_elsewhere) return true;
-  const int64_t waves = ((int64_t)prm.batch + kQuadGames - 1) / kQuadGames;
-  // short rollouts (measured at (20,3) x 65 536, scripts/probe_short_rollouts.py: 1 / 2 / 4 / 6 steps 8.2 / 10.0 / 12.3 /
-  // 14.4 us against the two-lane kernel's 9.6 / 11.5 / 13.6 / 15.0; level at 8 steps): the wave's shorter chain
-  // counts while the wide first steps are most of the launch
-  if (prm.steps <= 6 && waves <= (int64_t)4 * simds) return true;
-  return waves <= (int64_t)2 * simds;
 }
 
 // workgroups of a launch (the finished-game workspace has one slot per workgroup and step)

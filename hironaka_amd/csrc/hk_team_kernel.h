@@ -689,32 +689,26 @@ __global__ __launch_bounds__(kWave, (D <= 4 ? 3 : 2)) void team_kernel(const Par
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-// HK_FLAG_FORCE_TEAM puts the shapes that have a register-resident specialisation on this kernel too
-inline bool team_supported(const Params& prm, int dtype) {
-  if (dtype != HK_F32) return false;
-  // sorted + compacted output (list semantics): single steps only
-  if ((prm.stages & HK_STAGE_NEWTON) && prm.mode != kModeStep &&
-      ((prm.flags & HK_SEM_MASK) == HK_SEM_LIST || (prm.flags & HK_FLAG_COMPACT_SORTED)))
-    return false;
-  if (prm.flags & HK_FLAG_FORCE_GENERIC) return false;
-  if ((prm.stages & kStageFeatureSorts) && prm.mode != kModeStep) return false;
-  if (prm.mode == kModeZeillinger) return false;
-  if (prm.d < 2 || prm.d > 6 || prm.m > kTeam * kTeamSlots) return false;
-  return true;
-}
-
 // LDS geometry: 16 regions of `stride` floats (>= the rows rounded up to a multiple of 4, stride / row
 // width odd so that the 16 teams' broadcast reads fall on different banks) + D floats per game of
 // slow-path scratch
-inline int plan_team(Params& prm) {
-  const int w = prm.d == 4 ? 4 : (prm.d == 2 ? 2 : 1);
-  int stride = ((prm.m + kTeam - 1) / kTeam) * kTeam * prm.d;
+inline int team_lds_stride(int m, int d) {
+  const int w = d == 4 ? 4 : (d == 2 ? 2 : 1);
+  int stride = ((m + kTeam - 1) / kTeam) * kTeam * d;
   stride = (stride + w - 1) / w * w;
   if (((stride / w) & 1) == 0) stride += w;
-  if ((int64_t)(stride + prm.d) * 4 * kTeamGames > kMaxLdsBytes) return HK_ERR_UNSUPPORTED;
-  prm.lds_stride = stride;
-  prm.games_per_block = kTeamGames;
-  return HK_OK;
+  return stride;
+}
+
+// float32, dim 2..6, <= 64 rows: also the shapes that have a register-resident specialisation
+inline bool team_supported(const Params& prm, int dtype) {
+  if (dtype != HK_F32) return false;
+  // sorted + compacted output (list semantics): single steps only
+  if (sorted_output(prm) && prm.mode != kModeStep) return false;
+  if ((prm.stages & kStageFeatureSorts) && prm.mode != kModeStep) return false;
+  if (prm.mode == kModeZeillinger) return false;
+  if (prm.d < 2 || prm.d > 6 || prm.m > kTeam * kTeamSlots) return false;
+  return (int64_t)(team_lds_stride(prm.m, prm.d) + prm.d) * 4 * kTeamGames <= kMaxLdsBytes;
 }
 
 template <int D, int MODE, bool ZEIL = false>
@@ -728,9 +722,7 @@ int launch_team_t(const Params& prm, hipStream_t stream) {
 
 template <int D>
 int launch_team_d(const Params& prm, hipStream_t stream) {
-  const bool sorted_out = (prm.stages & HK_STAGE_NEWTON) &&
-                          ((prm.flags & HK_SEM_MASK) == HK_SEM_LIST || (prm.flags & HK_FLAG_COMPACT_SORTED));
-  if (prm.mode == kModeStep && (prm.class_out || (prm.stages & kStageFeatureSorts) || sorted_out))
+  if (prm.mode == kModeStep && (prm.class_out || (prm.stages & kStageFeatureSorts) || sorted_output(prm)))
     return launch_team_t<D, kModeStepAux>(prm, stream);
   if (prm.mode == kModeStep) return launch_team_t<D, kModeStep>(prm, stream);
   if (prm.mode == kModeRollout && prm.host_policy == HK_HOST_ZEILLINGER)
@@ -747,9 +739,9 @@ extern template int launch_team_d<4>(const Params&, hipStream_t);
 extern template int launch_team_d<5>(const Params&, hipStream_t);
 extern template int launch_team_d<6>(const Params&, hipStream_t);
 
-inline int launch_team(Params& prm, hipStream_t stream) {
-  const int st = plan_team(prm);
-  if (st != HK_OK) return st;
+inline int launch_team(Params prm, hipStream_t stream) {
+  prm.lds_stride = team_lds_stride(prm.m, prm.d);
+  prm.games_per_block = kTeamGames;
   switch (prm.d) {
     case 2: return launch_team_d<2>(prm, stream);
     case 3: return launch_team_d<3>(prm, stream);

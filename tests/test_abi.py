@@ -94,6 +94,17 @@ def test_rollout_and_search_validation_without_gpu():
     r.points = ctypes.addressof(buf)
     need = L.hk_rollout_workspace_bytes(ctypes.byref(r))
     assert need == 4 * 6 * 4   # (steps + 1) rows of counters, one slot per 16 games: the finest kernel variant's grid
+    # the same bound on (50,4), a team-kernel shape, dim 7 and float64, with forced families and generated initial states
+    for (m, d, dt, b, fl, gen), slots in (((50, 4, A.HK_F32, 65536, 0, 0), 4096), ((50, 4, A.HK_F32, 65536, 0, 20), 4096),
+                                          ((7, 3, A.HK_F32, 98304, 0, 0), 6144),
+                                          ((7, 3, A.HK_F32, 98304, A.HK_FLAG_FORCE_GENERIC, 0), 6144),
+                                          ((20, 3, A.HK_F32, 98304, A.HK_FLAG_FORCE_ONE_LANE, 0), 6144),
+                                          ((20, 3, A.HK_F64, 32768, 0, 0), 512), ((9, 7, A.HK_F32, 32768, 0, 0), 512)):
+        q = A.hk_rollout_desc()
+        q.batch, q.max_points, q.dim, q.dtype, q.steps, q.flags = b, m, d, dt, 5, fl
+        q.points = None if gen else ctypes.addressof(buf)
+        q.gen_max_value, q.padding_value = gen, -1.0
+        assert L.hk_rollout_workspace_bytes(ctypes.byref(q)) == 6 * slots * 4, (m, d, dt, b, fl, gen)
     r.flags = A.HK_FLAG_DEFER_COUNTS
     assert L.hk_rollout(ctypes.byref(r), None) == A.HK_ERR_NULL          # deferred counts need the workspace
     t = A.hk_search_tree()
