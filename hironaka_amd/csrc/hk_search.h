@@ -20,6 +20,12 @@ namespace hk {
 
 constexpr int kSearchMaxActions = 32;
 
+// max / min / argmax of the decision arithmetic with the NaN rule of numpy / JAX (and so of the oracle and of
+// mctx): a NaN operand makes the result NaN, and the first NaN wins an argmax.  fmax / fmin / `s > best` drop it.
+__device__ inline double nan_max(double x, double y) { return (x > y || x != x) ? x : y; }
+__device__ inline double nan_min(double x, double y) { return (x < y || x != x) ? x : y; }
+__device__ inline bool argmax_beats(double s, double best) { return s > best || (s != s && best == best); }
+
 struct SearchTree {
   int32_t* node_visits;
   float* raw_values;
@@ -52,7 +58,7 @@ __device__ inline void search_completed_q(const SearchTree& t, int64_t b, int n,
       visits[a] = t.children_visits[e0 + a];
       cq[a] = (double)t.children_rewards[e0 + a] +
               (double)t.children_discounts[e0 + a] * (double)t.children_values[e0 + a];
-      mx = fmax(mx, logit[a]);
+      mx = nan_max(mx, logit[a]);
     }
   double den = 0.0;
 #pragma unroll
@@ -66,7 +72,7 @@ __device__ inline void search_completed_q(const SearchTree& t, int64_t b, int n,
 #pragma unroll
   for (int a = 0; a < AMAX; ++a)
     if (a < A) {
-      p[a] = fmax(1.1754943508222875e-38, p[a] / den);
+      p[a] = nan_max(1.1754943508222875e-38, p[a] / den);
       if (visits[a] > 0) sum_probs += p[a];
       sum_visits += (double)visits[a];
       maxvisit = visits[a] > maxvisit ? visits[a] : maxvisit;
@@ -82,18 +88,18 @@ __device__ inline void search_completed_q(const SearchTree& t, int64_t b, int n,
   for (int a = 0; a < AMAX; ++a)
     if (a < A) {
       if (!(visits[a] > 0)) cq[a] = value;
-      lo = fmin(lo, cq[a]);
-      hi = fmax(hi, cq[a]);
+      lo = nan_min(lo, cq[a]);
+      hi = nan_max(hi, cq[a]);
     }
   const double scale = (50.0 + (double)maxvisit) * 0.1;
-  const double span = fmax(hi - lo, 1e-8);
+  const double span = nan_max(hi - lo, 1e-8);
 #pragma unroll
   for (int a = 0; a < AMAX; ++a)
     if (a < A) cq[a] = scale * ((cq[a] - lo) / span);
 }
 
-// Gumbel + logits + completed Q of the root actions whose visit count equals `considered_visit`
-// (sequential halving), -inf for the others; first maximum
+// Gumbel + logits + completed Q of the root actions, plus a penalty of -inf for those whose visit count is not
+// `considered_visit` (sequential halving); invalid actions -inf; first maximum
 template <int AMAX>
 __device__ inline int search_root_argmax(const SearchTree& t, int64_t b, const double (&cq)[AMAX], const float* gumbel,
                                          const uint8_t* invalid, int considered_visit) {
@@ -102,16 +108,16 @@ __device__ inline int search_root_argmax(const SearchTree& t, int64_t b, const d
   double mx = -INFINITY;
 #pragma unroll
   for (int a = 0; a < AMAX; ++a)
-    if (a < A) mx = fmax(mx, (double)t.children_prior_logits[e0 + a]);
+    if (a < A) mx = nan_max(mx, (double)t.children_prior_logits[e0 + a]);
   int best = 0;
   double best_s = -INFINITY;
 #pragma unroll
   for (int a = 0; a < AMAX; ++a)
     if (a < A) {
-      double s = fmax(-1e9, (double)gumbel[b * A + a] + ((double)t.children_prior_logits[e0 + a] - mx) + cq[a]);
-      if (t.children_visits[e0 + a] != considered_visit) s = -INFINITY;
+      double s = nan_max(-1e9, (double)gumbel[b * A + a] + ((double)t.children_prior_logits[e0 + a] - mx) + cq[a]) +
+                 (t.children_visits[e0 + a] == considered_visit ? 0.0 : -INFINITY);
       if (invalid && invalid[b * A + a]) s = -INFINITY;
-      if (s > best_s) {
+      if (argmax_beats(s, best_s)) {
         best_s = s;
         best = a;
       }
@@ -129,13 +135,13 @@ __device__ inline double grp_get(double v, int src) { return __shfl(v, src, AMAX
 template <int AMAX>
 __device__ inline double grp_max(double v) {
 #pragma unroll
-  for (int off = AMAX / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, AMAX));
+  for (int off = AMAX / 2; off > 0; off >>= 1) v = nan_max(v, __shfl_xor(v, off, AMAX));
   return v;
 }
 template <int AMAX>
 __device__ inline double grp_min(double v) {
 #pragma unroll
-  for (int off = AMAX / 2; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, AMAX));
+  for (int off = AMAX / 2; off > 0; off >>= 1) v = nan_min(v, __shfl_xor(v, off, AMAX));
   return v;
 }
 template <int AMAX>
@@ -160,12 +166,12 @@ __device__ inline double grp_seq_sum(double v, int A) {  // v_0 + v_1 + ... in t
   return s;
 }
 template <int AMAX>
-__device__ inline int grp_first_argmax(double v, int A) {  // the one-lane loop: `if (s > best_s)` over a = 0 .. A-1
+__device__ inline int grp_first_argmax(double v, int A) {  // the one-lane loop over a = 0 .. A-1
   int best = 0;
   double best_s = -INFINITY;
   for (int k = 0; k < A; ++k) {
     const double sk = grp_get<AMAX>(v, k);
-    if (sk > best_s) {
+    if (argmax_beats(sk, best_s)) {
       best_s = sk;
       best = k;
     }
@@ -188,7 +194,7 @@ __device__ inline double lane_completed_q(const SearchTree& t, int64_t b, int n,
   const double mx = grp_max<AMAX>(logit);
   double p = on ? exp(logit - mx) : 0.0;
   const double den = grp_seq_sum<AMAX>(p, A);
-  p = on ? fmax(1.1754943508222875e-38, p / den) : 0.0;
+  p = on ? nan_max(1.1754943508222875e-38, p / den) : 0.0;
   const double sum_probs = grp_seq_sum<AMAX>(visits > 0 ? p : 0.0, A);
   const double sum_visits = (double)grp_isum<AMAX>(visits);
   const int maxvisit = grp_imax<AMAX>(visits);
@@ -197,7 +203,7 @@ __device__ inline double lane_completed_q(const SearchTree& t, int64_t b, int n,
   if (!(visits > 0)) cq = value;
   const double lo = grp_min<AMAX>(on ? cq : INFINITY), hi = grp_max<AMAX>(on ? cq : -INFINITY);
   const double scale = (50.0 + (double)maxvisit) * 0.1;
-  const double span = fmax(hi - lo, 1e-8);
+  const double span = nan_max(hi - lo, 1e-8);
   logit_out = logit;
   visits_out = visits;
   mx_out = mx;
@@ -225,8 +231,7 @@ __device__ inline void search_descend(const SearchTree& t, int64_t b, int a, con
   const int considered_visit = table[(int64_t)num_considered * num_simulations + sim_index];
   double s = -INFINITY;
   if (on) {
-    s = fmax(-1e9, (double)gumbel[b * A + a] + (logit - mx) + cq);
-    if (visits != considered_visit) s = -INFINITY;
+    s = nan_max(-1e9, (double)gumbel[b * A + a] + (logit - mx) + cq) + (visits == considered_visit ? 0.0 : -INFINITY);
     if (bad) s = -INFINITY;
   }
   int node = 0;
@@ -326,7 +331,7 @@ __global__ __launch_bounds__(64) void search_policy_kernel(SearchTree t, const f
   for (int a = 0; a < AMAX; ++a)
     if (a < A) {
       cq[a] += (double)t.children_prior_logits[e0 + a];
-      mx = fmax(mx, cq[a]);
+      mx = nan_max(mx, cq[a]);
     }
   if (invalid) {
 #pragma unroll
@@ -335,7 +340,7 @@ __global__ __launch_bounds__(64) void search_policy_kernel(SearchTree t, const f
     mx = -INFINITY;
 #pragma unroll
     for (int a = 0; a < AMAX; ++a)
-      if (a < A) mx = fmax(mx, cq[a]);
+      if (a < A) mx = nan_max(mx, cq[a]);
   }
   double den = 0.0;
 #pragma unroll

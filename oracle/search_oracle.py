@@ -176,6 +176,20 @@ class PolicyOutput(NamedTuple):
     search_tree: Tree
 
 
+def instantiate_tree_from_root(root_prior_logits, root_value, root_embedding, num_simulations: int,
+                               invalid_actions=None) -> Tree:
+    """a tree of num_simulations + 1 nodes holding only the root (its logits masked like mctx's)"""
+    b, a = root_prior_logits.shape
+    tree = new_tree(b, num_simulations + 1, a, root_embedding.shape[1], root_embedding.dtype)
+    tree.children_prior_logits[:, ROOT] = mask_invalid_actions(np.asarray(root_prior_logits, np.float32),
+                                                              invalid_actions)
+    tree.raw_values[:, ROOT] = root_value
+    tree.node_values[:, ROOT] = root_value
+    tree.node_visits[:, ROOT] = 1
+    tree.embeddings[:, ROOT] = root_embedding
+    return tree
+
+
 def gumbel_muzero_policy(params, root_prior_logits, root_value, root_embedding, recurrent_fn: Callable,
                          num_simulations: int, gumbel: np.ndarray, invalid_actions=None, max_depth=None,
                          max_num_considered_actions: int = 16, rng_key=None) -> PolicyOutput:
@@ -183,62 +197,77 @@ def gumbel_muzero_policy(params, root_prior_logits, root_value, root_embedding, 
     given the same numbers).  recurrent_fn(params, key, action [B] int, embedding [B, E]) ->
     ((reward, discount, prior_logits, value), next_embedding), all numpy; key = the per-simulation value
     hironaka_amd.search.simulation_key derives from an int `rng_key` (None otherwise)."""
-    b, a = root_prior_logits.shape
-    n = num_simulations + 1
+    b = root_prior_logits.shape[0]
     max_depth = num_simulations if max_depth is None else max_depth
-    logits0 = mask_invalid_actions(np.asarray(root_prior_logits, np.float32), invalid_actions)
-    tree = new_tree(b, n, a, root_embedding.shape[1], root_embedding.dtype)
+    tree = instantiate_tree_from_root(root_prior_logits, root_value, root_embedding, num_simulations, invalid_actions)
     bi = np.arange(b)
-    tree.children_prior_logits[:, ROOT] = logits0
-    tree.raw_values[:, ROOT] = root_value
-    tree.node_values[:, ROOT] = root_value
-    tree.node_visits[:, ROOT] = 1
-    tree.embeddings[:, ROOT] = root_embedding
     table = get_table_of_considered_visits(max_num_considered_actions, num_simulations)
     for sim in range(num_simulations):
-        # -- simulate: walk down until an unvisited edge (or the depth limit)
-        node = np.zeros(b, np.int64)
-        action = root_action_selection(tree, gumbel, invalid_actions, table, max_num_considered_actions, bi)
-        nxt = tree.children_index[bi, node, action].astype(np.int64)
-        depth = np.zeros(b, np.int64)
-        going = (nxt != UNVISITED) & (depth + 1 < max_depth)
-        while going.any():
-            node = np.where(going, nxt, node)
-            depth = depth + going
-            act_in = interior_action_selection(tree, node)
-            action = np.where(going, act_in, action)
-            nxt2 = tree.children_index[bi, node, action].astype(np.int64)
-            nxt = np.where(going, nxt2, nxt)
-            going = going & (nxt != UNVISITED) & (depth + 1 < max_depth)
-        # -- expand
-        new_node = np.where(nxt == UNVISITED, sim + 1, nxt)
+        node, action, new_node = simulate(tree, gumbel, invalid_actions, table, max_num_considered_actions, max_depth,
+                                          sim + 1)
         key = None if rng_key is None else (int(rng_key) + 1000003 * (sim + 1)) % (1 << 63)
         (reward, discount, prior_logits, value), emb = recurrent_fn(params, key, action, tree.embeddings[bi, node])
-        tree.children_prior_logits[bi, new_node] = np.asarray(prior_logits, np.float32)
-        tree.raw_values[bi, new_node] = value
-        tree.node_values[bi, new_node] = value
-        tree.node_visits[bi, new_node] += 1
         tree.embeddings[bi, new_node] = emb
-        tree.children_index[bi, node, action] = new_node
-        tree.children_rewards[bi, node, action] = reward
-        tree.children_discounts[bi, node, action] = discount
-        tree.parents[bi, new_node] = node
-        tree.action_from_parent[bi, new_node] = action
+        expand(tree, node, action, new_node, prior_logits, value, reward, discount)
         backward(tree, new_node)
-    # -- the improved policy at the root
+    action, weights = final_policy(tree, gumbel, invalid_actions)
+    return PolicyOutput(action, weights, tree)
+
+
+def simulate(tree: Tree, gumbel, invalid, table, max_considered: int, max_depth: int, next_free: int):
+    """one simulation's descent (hk_search_select): walk down from the root until an unvisited edge or the depth
+    limit -> (parent [B], action [B], node [B]): the edge to expand and the node the expansion writes (the existing
+    child at the depth limit, else `next_free`)"""
+    b = tree.node_visits.shape[0]
+    bi = np.arange(b)
+    node = np.zeros(b, np.int64)
+    action = root_action_selection(tree, gumbel, invalid, table, max_considered, bi)
+    nxt = tree.children_index[bi, node, action].astype(np.int64)
+    depth = np.zeros(b, np.int64)
+    going = (nxt != UNVISITED) & (depth + 1 < max_depth)
+    while going.any():
+        node = np.where(going, nxt, node)
+        depth = depth + going
+        act_in = interior_action_selection(tree, node)
+        action = np.where(going, act_in, action)
+        nxt2 = tree.children_index[bi, node, action].astype(np.int64)
+        nxt = np.where(going, nxt2, nxt)
+        going = going & (nxt != UNVISITED) & (depth + 1 < max_depth)
+    new_node = np.where(nxt == UNVISITED, next_free, nxt)
+    return node, action, new_node
+
+
+def expand(tree: Tree, node, action, new_node, prior_logits, value, reward, discount) -> None:
+    """the new node's statistics and its edge (the first half of hk_search_backup; embeddings are the caller's)"""
+    bi = np.arange(tree.node_visits.shape[0])
+    tree.children_prior_logits[bi, new_node] = np.asarray(prior_logits, np.float32)
+    tree.raw_values[bi, new_node] = value
+    tree.node_values[bi, new_node] = value
+    tree.node_visits[bi, new_node] += 1
+    tree.children_index[bi, node, action] = new_node
+    tree.children_rewards[bi, node, action] = reward
+    tree.children_discounts[bi, node, action] = discount
+    tree.parents[bi, new_node] = node
+    tree.action_from_parent[bi, new_node] = action
+
+
+def final_policy(tree: Tree, gumbel, invalid):
+    """the improved policy at the root after the last simulation (hk_search_policy) -> (action [B] int32,
+    action_weights [B, A] f32): the Gumbel argmax among the most visited actions, softmax(logits + completed Q)"""
+    b = tree.node_visits.shape[0]
     visits = tree.children_visits[:, ROOT]
     cq = completed_qvalues(tree, np.zeros(b, np.int64))
     considered_visit = visits.max(axis=-1)
     s = score_considered(considered_visit, gumbel, tree.children_prior_logits[:, ROOT], cq, visits)
-    if invalid_actions is not None:
-        s = np.where(invalid_actions.astype(bool), -np.inf, s)
+    if invalid is not None:
+        s = np.where(invalid.astype(bool), -np.inf, s)
     action = s.argmax(axis=-1)
     search_logits = tree.children_prior_logits[:, ROOT].astype(np.float64) + cq
-    if invalid_actions is not None:
+    if invalid is not None:
         search_logits = search_logits - search_logits.max(axis=-1, keepdims=True)
-        search_logits = np.where(invalid_actions.astype(bool), F32_MIN, search_logits)
+        search_logits = np.where(invalid.astype(bool), F32_MIN, search_logits)
     weights = _softmax64(search_logits).astype(np.float32)
-    return PolicyOutput(action.astype(np.int32), weights, tree)
+    return action.astype(np.int32), weights
 
 
 # ---- expansion glue (hironaka_amd/csrc/hk_search.h: expand_* / masked_argmax / mask_logits kernels) -------------------

@@ -43,7 +43,7 @@ def _as_numpy_recurrent(recurrent_fn):
 
 @pytest.mark.parametrize("role,spec,num_simulations,max_considered,max_depth",
                          [("host", (20, 3), 32, 16, 20), ("host", (10, 3), 9, 2, 3), ("agent", (20, 3), 16, 3, 16),
-                          ("host", (8, 4), 24, 4, 24)])
+                          ("host", (8, 4), 24, 4, 24), ("host", (12, 5), 12, 8, 12)])
 def test_search_matches_oracle(role, spec, num_simulations, max_considered, max_depth):
     m, d = spec
     b = 96
