@@ -5,7 +5,7 @@ descriptors with host pointers) can import it without a GPU.
 """
 import ctypes as C
 
-HK_ABI_VERSION = 4
+HK_ABI_VERSION = 5
 
 # status codes
 HK_OK = 0
@@ -47,6 +47,13 @@ HK_FLAG_FORCE_FOUR_LANES = 1024
 # fused policies
 HK_HOST_RANDOM, HK_HOST_ALL_COORD, HK_HOST_ZEILLINGER = 0, 1, 2
 HK_AGENT_RANDOM, HK_AGENT_RANDOM_LEGAL, HK_AGENT_CHOOSE_FIRST, HK_AGENT_CHOOSE_LAST = 0, 1, 2, 3
+
+# hk_search_depth status bits
+HK_SEARCH_DEPTH_LIMIT = 1
+HK_SEARCH_NODE_LIMIT = 2
+HK_SEARCH_STACK_LIMIT = 4
+HK_SEARCH_INEXACT = 8
+HK_SEARCH_ROOT_ENDED = 16
 
 SEMANTICS = {"jax": HK_SEM_JAX, "torch": HK_SEM_TORCH, "list": HK_SEM_LIST}
 
@@ -171,6 +178,8 @@ PROTOTYPES = {
     "hk_search_expand_gather_agent": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "hk_search_expand_scatter_agent": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "hk_search_mask_logits": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp]),
+    "hk_search_depth_workspace_bytes": (C.c_uint64, [_i, _i, _i, _i, _i]),
+    "hk_search_depth": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _u64, _i, _vp, _u64, _vp, _vp, _vp, _vp]),
 }
 
 STATUS_TEXT = {

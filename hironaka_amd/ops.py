@@ -632,3 +632,55 @@ def generate_points_binned(batch: int, max_points: int, dim: int, max_value: int
 
 def has_fast_path(max_points: int, dim: int, dtype=torch.float32) -> bool:
     return bool(lib().hk_has_fast_path(max_points, dim, _TORCH2HK.get(dtype, -1)))
+
+
+SEARCH_HOSTS = {"zeillinger": A.HK_HOST_ZEILLINGER, "all_coord": A.HK_HOST_ALL_COORD}
+_SEARCH_WORKSPACE_BYTES = 4 << 30  # per launch; a larger batch runs as several launches
+
+
+def search_depth(points: torch.Tensor, host: str, *, max_depth: int, max_nodes: int,
+                 stack_nodes: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Exhaustive worst-case game length under a fixed host, one tree per root (hironaka/util/search.py:9-32,
+    hk_search_depth).  points: [B, m, d] float32/float64 roots in list semantics, used as given (rows with
+    coordinate 0 >= 0 are points; padding rows may sit anywhere).  host: "zeillinger" or "all_coord".
+    Returns (depth int32[B], nodes int64[B], status int32[B]); status 0 = finished and exact, else an OR of
+    HK_SEARCH_* bits (the numbers are then bounds, see include/hironaka_hip.h)."""
+    _require_device(points, "points")
+    if points.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"points must be float32 or float64. Got {points.dtype}.")
+    if points.dim() != 3:
+        raise ValueError(f"points must be [B, max_points, dim]. Got shape {tuple(points.shape)}.")
+    if host not in SEARCH_HOSTS:
+        raise ValueError(f"host must be one of {sorted(SEARCH_HOSTS)}. Got {host!r}.")
+    if not (0 <= max_depth < 2 ** 31 and 1 <= max_nodes < 2 ** 63 and 1 <= stack_nodes < 2 ** 31):
+        raise ValueError(f"need 0 <= max_depth < 2^31, 1 <= max_nodes < 2^63, 1 <= stack_nodes < 2^31. Got "
+                         f"{max_depth}, {max_nodes}, {stack_nodes}.")
+    pts = points.contiguous()
+    b, m, d = pts.shape
+    limit = 2.0 ** 24 if pts.dtype == torch.float32 else 2.0 ** 53
+    avail = (pts[:, :, 0] >= 0).unsqueeze(2).expand_as(pts)
+    vals = pts[avail]
+    if vals.numel() and not bool(((vals >= 0) & (vals < limit) & (vals == torch.floor(vals))).all()):
+        raise ValueError(f"the points of a root (rows with coordinate 0 >= 0) must be integers in [0, {int(limit)}) "
+                         f"for {pts.dtype}")
+    dt = _TORCH2HK[pts.dtype]
+    L = lib()
+    per_root = L.hk_search_depth_workspace_bytes(1, m, d, dt, stack_nodes)
+    if per_root == 0:
+        check(L.hk_search_depth(None, 1, m, d, dt, SEARCH_HOSTS[host], max_depth, max_nodes, stack_nodes, None, 0,
+                                None, None, None, None), "hk_search_depth")
+    depth = torch.empty(b, dtype=torch.int32, device=pts.device)
+    nodes = torch.empty(b, dtype=torch.int64, device=pts.device)
+    status = torch.empty(b, dtype=torch.int32, device=pts.device)
+    chunk = max(1, min(b, _SEARCH_WORKSPACE_BYTES // max(per_root, 1)))
+    with torch.cuda.device(pts.device):
+        ws = torch.empty(per_root * chunk if b else 0, dtype=torch.uint8, device=pts.device)
+        for lo in range(0, b, chunk):
+            n = min(chunk, b - lo)
+            check(L.hk_search_depth(pts[lo].data_ptr(), n, m, d, dt, SEARCH_HOSTS[host], max_depth, max_nodes,
+                                    stack_nodes, ws.data_ptr(), ws.numel(), depth[lo].data_ptr(),
+                                    nodes[lo].data_ptr(), status[lo].data_ptr(), _stream(pts)), "hk_search_depth")
+        if b == 0:
+            check(L.hk_search_depth(pts.data_ptr(), 0, m, d, dt, SEARCH_HOSTS[host], max_depth, max_nodes,
+                                    stack_nodes, None, 0, None, None, None, _stream(pts)), "hk_search_depth")
+    return depth, nodes, status

@@ -48,6 +48,7 @@
  *   hk_search_expand_gather_agent / _expand_scatter_agent / _mask_logits
  *                            jax/recurrent_fn.py:105-121 (agent-role tree) and the agent's
  *                            action mask jax/util.py:287-305
+ *   hk_search_depth          hironaka/util/search.py:9-32 search_depth (one tree per root, a batch of roots)
  */
 #ifndef HIRONAKA_HIP_H
 #define HIRONAKA_HIP_H
@@ -58,7 +59,7 @@
 extern "C" {
 #endif
 
-#define HK_ABI_VERSION 4 /* 2: + HK_AXIS_MASKED_LOGITS, hk_step_features, hk_rollout_values, hk_search_expand_* / _masked_argmax / _mask_logits; 3: + hk_rollout_desc.game_ids (and the policy stream of dim <= 8 became four steps per Philox block with 16-bit draws: seeds are not comparable with ABI 2); 4: + hk_rollout_desc.gen_max_value / gen_stages / gen_seed / episodes (initial states drawn inside the launch, `points` may be NULL), - HK_FLAG_FORCE_POOL */
+#define HK_ABI_VERSION 5 /* 2: + HK_AXIS_MASKED_LOGITS, hk_step_features, hk_rollout_values, hk_search_expand_* / _masked_argmax / _mask_logits; 3: + hk_rollout_desc.game_ids (and the policy stream of dim <= 8 became four steps per Philox block with 16-bit draws: seeds are not comparable with ABI 2); 4: + hk_rollout_desc.gen_max_value / gen_stages / gen_seed / episodes (initial states drawn inside the launch, `points` may be NULL), - HK_FLAG_FORCE_POOL; 5: + hk_search_depth, hk_search_depth_workspace_bytes, HK_SEARCH_* status bits */
 
 /* ---- status codes -------------------------------------------------------------------- */
 #define HK_OK 0
@@ -414,6 +415,33 @@ int hk_get_features_torch(const void* points_in, int64_t in_stride, void* featur
 /* ---- host action codec ------------------------------------------------------------------ */
 int hk_decode_host_class(const int32_t* class_in, void* mask_out, int mask_dtype, int batch,
                          int dim, void* stream);
+
+/* ---- exhaustive worst-case game length under a fixed host (ABI 5; hironaka/util/search.py:9-32 search_depth) --
+ * Per root: every agent choice is enumerated depth first.  A state is one game in list semantics (ListPoints:
+ * shift, then Newton sorted + compacted, no reposition, no rescale).  The root is used as given: rows with
+ * coordinate 0 >= 0 are its points, padding rows may sit anywhere, and no Newton pass or sort precedes the first
+ * move.  At a node the host picks a subset I (HK_HOST_ZEILLINGER: host.py:54-95 on rows in row order;
+ * HK_HOST_ALL_COORD: host.py:48-51); the node gets one child per axis a in I: x_a <- sum_{k in I} x_k, then
+ * Newton.  A child with fewer than 2 points is a finished game and is not visited.  Per root:
+ *   depth_out  1 + the largest depth of a visited node (the root has depth 0): the reference's max_depth + 1
+ *   nodes_out  visited nodes, root included (the reference's host.select_coord calls); identical states reached
+ *              by different paths count separately, as in the reference
+ *   status_out 0 = the search finished and both numbers are exact, else an OR of the bits below.
+ * Roots must hold integers below 2^24 (float32) / 2^53 (float64); nothing here checks that.
+ * `workspace` holds each root's LIFO stack of `stack_nodes` entries (hk_search_depth_workspace_bytes).
+ * dim 2..6, max_points 1..64, HK_F32 / HK_F64; anything else is HK_ERR_UNSUPPORTED / HK_ERR_SHAPE before any
+ * launch.  max_depth >= 0, max_nodes >= 1, stack_nodes >= 1.  Every loop is bounded by these three.         */
+#define HK_SEARCH_DEPTH_LIMIT 1 /* a node at depth max_depth was visited; its children were not generated. depth
+                                   and nodes are exact for the tree truncated there                        */
+#define HK_SEARCH_NODE_LIMIT 2  /* stopped once nodes reached max_nodes with nodes left: lower bounds        */
+#define HK_SEARCH_STACK_LIMIT 4 /* a child did not fit the root's stack: lower bounds                      */
+#define HK_SEARCH_INEXACT 8     /* a generated coordinate reached 2^24 (float32) / 2^53 (float64), where
+                                   integers stop being exact; the root stopped there: lower bounds          */
+#define HK_SEARCH_ROOT_ENDED 16 /* the root has fewer than 2 points: depth = nodes = 0 (the reference asserts) */
+uint64_t hk_search_depth_workspace_bytes(int batch, int max_points, int dim, int dtype, int stack_nodes);
+int hk_search_depth(const void* points, int batch, int max_points, int dim, int dtype, int host, int max_depth,
+                    uint64_t max_nodes, int stack_nodes, void* workspace, uint64_t workspace_bytes,
+                    int32_t* depth_out, uint64_t* nodes_out, int32_t* status_out, void* stream);
 
 #ifdef __cplusplus
 }
