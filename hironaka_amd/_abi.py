@@ -5,7 +5,7 @@ descriptors with host pointers) can import it without a GPU.
 """
 import ctypes as C
 
-HK_ABI_VERSION = 5
+HK_ABI_VERSION = 6
 
 # status codes
 HK_OK = 0
@@ -46,6 +46,7 @@ HK_FLAG_FORCE_FOUR_LANES = 1024
 
 # fused policies
 HK_HOST_RANDOM, HK_HOST_ALL_COORD, HK_HOST_ZEILLINGER = 0, 1, 2
+HK_HOST_ZEILLINGER_LEX, HK_HOST_WEAK_SPIVAKOVSKY, HK_HOST_MIN_HITTING = 3, 4, 5  # hk_host_select / hk_search_depth
 HK_AGENT_RANDOM, HK_AGENT_RANDOM_LEGAL, HK_AGENT_CHOOSE_FIRST, HK_AGENT_CHOOSE_LAST = 0, 1, 2, 3
 
 # hk_search_depth status bits
@@ -193,8 +194,17 @@ STATUS_TEXT = {
 }
 
 
-def bind(lib: C.CDLL, prototypes=PROTOTYPES) -> None:
-    """Attach restype/argtypes; raises AttributeError for a symbol the library lacks."""
+# the entry points of include/hironaka_hip_hosts.h: the device library's only (no hko_ counterpart in the oracle)
+DEVICE_PROTOTYPES = {
+    "hk_host_select": (C.c_int, [_vp, _i64, _vp, _i, _i, _i, _i, _i, _vp]),
+}
+
+
+def bind(lib: C.CDLL, prototypes=None) -> None:
+    """Attach restype/argtypes (default: PROTOTYPES and DEVICE_PROTOTYPES); raises AttributeError for a symbol the
+    library lacks."""
+    if prototypes is None:
+        prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES}
     for name, (res, args) in prototypes.items():
         fn = getattr(lib, name)
         fn.restype = res

@@ -18,22 +18,22 @@
 namespace hk {
 
 // cooperative, coalesced HBM -> LDS copy of `ngames` records of `n` elements
-// (rolled loop, n is a run-time value: batched by hand so that kSlabBatch independent requests per lane
+// (rolled loop, n is a run-time value: batched by hand so that BATCH independent requests per lane
 // are in flight before the first dependent access -- one per iteration would expose a full HBM latency)
 constexpr int kSlabBatch = 8;
 
-template <typename T, bool TO_LDS>
+template <typename T, bool TO_LDS, int BATCH = kSlabBatch>
 __device__ inline void copy_slab(T* lds, T* glob, int64_t gstride, int n, int S, int64_t g0, int ngames,
                                  int lane) {
   int g = lane / n, e = lane % n;
   const int dg = kWave / n, de = kWave % n;
   const int total = ngames * n;
-  for (int c0 = lane; c0 < total; c0 += kWave * kSlabBatch) {
-    T v[kSlabBatch];
-    int lo[kSlabBatch];
-    int64_t go[kSlabBatch];
+  for (int c0 = lane; c0 < total; c0 += kWave * BATCH) {
+    T v[BATCH];
+    int lo[BATCH];
+    int64_t go[BATCH];
 #pragma unroll
-    for (int u = 0; u < kSlabBatch; ++u) {
+    for (int u = 0; u < BATCH; ++u) {
       lo[u] = g * S + e;
       go[u] = (g0 + g) * gstride + e;
       g += dg;
@@ -47,17 +47,17 @@ __device__ inline void copy_slab(T* lds, T* glob, int64_t gstride, int n, int S,
     // the whole batch is in flight before the opaque use below; a load left inside its `if` is sunk
     // next to its store by the compiler and waited for there, one round trip per element
 #pragma unroll
-    for (int u = 1; u < kSlabBatch; ++u)
+    for (int u = 1; u < BATCH; ++u)
       if (c0 + u * kWave >= total) {
         lo[u] = lo[0];
         go[u] = go[0];
       }
 #pragma unroll
-    for (int u = 0; u < kSlabBatch; ++u) v[u] = TO_LDS ? glob[go[u]] : lds[lo[u]];
+    for (int u = 0; u < BATCH; ++u) v[u] = TO_LDS ? glob[go[u]] : lds[lo[u]];
 #pragma unroll
-    for (int u = 0; u < kSlabBatch; ++u) asm volatile("" : "+v"(v[u]));
+    for (int u = 0; u < BATCH; ++u) asm volatile("" : "+v"(v[u]));
 #pragma unroll
-    for (int u = 0; u < kSlabBatch; ++u)
+    for (int u = 0; u < BATCH; ++u)
       if (c0 + u * kWave < total) {
         if (TO_LDS) lds[lo[u]] = v[u];
         else glob[go[u]] = v[u];

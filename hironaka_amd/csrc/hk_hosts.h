@@ -1,0 +1,149 @@
+// The deterministic hosts of hironaka/host.py beyond Zeillinger, on one game in list semantics (ListPoints): a row is
+// a point when p[i*d] >= 0 (the availability test of zeillinger_list_game: a NaN coordinate 0 is a hole), rows are
+// read in row order and holes may sit anywhere.  Each routine returns the class id (encode_mask) of the host's subset,
+// or -1 for "no subset".  Runtime m and d; d <= 6 for the hitting-set hosts (their support bitmap has 2^d bits).
+//
+//   zeillinger_lex_list_game  ZeillingerLex      host.py:116-127  (Zeillinger's key, ties broken lexicographically)
+//   weak_spivakovsky_game     WeakSpivakovsky    host.py:357-378  (a minimal hitting set, first in combinations order)
+//   min_hitting_game          WeakSpivakovskyMinHitting  host.py:381-427  (a minimal hitting set, smallest integer)
+//
+// -1 cases: fewer than 2 points (every host here; the reference returns []), and for the hitting-set hosts a zero row,
+// whose empty support no subset meets.  WeakSpivakovsky also gives -1 when the union U of the supports has fewer than
+// 2 coordinates.  The reference misbehaves on these inputs: WeakSpivakovsky appends no subset for that game, and
+// WeakSpivakovskyMinHitting decodes its sentinel 65536 (coordinate 16) for a zero row.  No Newton-reduced state with
+// >= 2 points has a zero row or |U| < 2.  WeakSpivakovskyMinHitting is well defined at |U| = 1 (the lone coordinate and
+// the smallest other one) and returns that.
+#pragma once
+
+#include "hk_game_generic.h"
+
+namespace hk {
+
+// ZeillingerLex._get_coord (host.py:116-127) over Zeillinger._select_coord's pairs (host.py:70-89): pairs i<j of the
+// points in row order, v = P_i - P_j, key (L, S) as in zeillinger_list_game.  Every pair whose key equals the smallest
+// one contributes r = [first argmin v, first argmax v] ([0, 1] if they coincide); the host takes the lexicographically
+// smallest r (the orientation P_i - P_j matters, not just the unordered pair).  One pass: a strictly smaller key
+// restarts the candidate, an equal key keeps the smaller r.  r is compared as r[0] * 8 + r[1].
+template <typename T>
+__device__ inline int zeillinger_lex_list_game(const T* p, int m, int d) {
+  T bestL = (T)0;
+  int bestS = 0, bestR = -1;
+  for (int i = 0; i < m; ++i) {
+    if (!(p[i * d] >= (T)0)) continue;
+    for (int j = i + 1; j < m; ++j) {
+      if (!(p[j * d] >= (T)0)) continue;
+      T mx = p[i * d] - p[j * d], mn = mx;
+      int lo = 0, hi = 0;
+      for (int k = 1; k < d; ++k) {
+        const T v = p[i * d + k] - p[j * d + k];
+        if (v < mn) { mn = v; lo = k; }
+        if (v > mx) { mx = v; hi = k; }
+      }
+      int cnt = 0;
+      for (int k = 0; k < d; ++k) {
+        const T v = p[i * d + k] - p[j * d + k];
+        cnt += (v == mx) + (v == mn);
+      }
+      const T L = mx - mn;
+      const int r = lo == hi ? 1 : lo * 8 + hi;  // [0, 1] when argmin == argmax
+      if (bestR < 0 || L < bestL || (L == bestL && cnt < bestS)) {
+        bestL = L;
+        bestS = cnt;
+        bestR = r;
+      } else if (L == bestL && cnt == bestS && r < bestR) {
+        bestR = r;
+      }
+    }
+  }
+  if (bestR < 0) return -1;
+  return encode_mask((1u << (bestR >> 3)) | (1u << (bestR & 7)));
+}
+
+// Which supports occur: bit s of the result is set when some point's set of nonzero coordinates is s (x != 0: NaN
+// counts as nonzero and -0.0 as zero, as np.nonzero does).  d <= 6.  `npts` receives the number of points.
+template <typename T>
+__device__ inline uint64_t support_bitmap(const T* p, int m, int d, int& npts) {
+  uint64_t occ = 0;
+  int n = 0;
+  for (int i = 0; i < m; ++i) {
+    if (!(p[i * d] >= (T)0)) continue;
+    uint32_t s = 0;
+    for (int k = 0; k < d; ++k) s |= (p[i * d + k] != (T)0) ? (1u << k) : 0u;
+    occ |= 1ull << s;
+    ++n;
+  }
+  npts = n;
+  return occ;
+}
+
+// bit s set for every s that is a subset of x (x < 64): the supports a candidate with complement x misses
+__device__ inline uint64_t subsets_of(uint32_t x) {
+  uint64_t b = 1;  // {empty set}
+  for (int k = 0; k < 6; ++k)
+    if ((x >> k) & 1u) b |= b << (1u << k);
+  return b;
+}
+
+// c meets every occurring support: no support lies inside the complement of c
+__device__ inline bool hits_all(uint64_t occ, uint32_t c, uint32_t full) { return (occ & subsets_of(full & ~c)) == 0; }
+
+// WeakSpivakovsky._select_coord (host.py:357-378): U = the union of the supports; candidates are the c within U with
+// |c| >= 2 that meet every support.  combinations(U, i) runs over sorted coordinate tuples in lexicographic order, so
+// the host takes the smallest |c|, then the lexicographically first tuple: for equal sizes, the largest bit-reversed c.
+template <typename T>
+__device__ inline int weak_spivakovsky_game(const T* p, int m, int d) {
+  int npts;
+  const uint64_t occ = support_bitmap(p, m, d, npts);
+  if (npts < 2) return -1;
+  const uint32_t full = (1u << d) - 1u;
+  uint32_t U = 0;
+  for (uint32_t s = 0; s <= full; ++s) U |= ((occ >> s) & 1ull) ? s : 0u;
+  int best = -1, bestPc = 0;
+  uint32_t bestRev = 0;
+  for (uint32_t c = 3; c <= full; ++c) {
+    if ((c & ~U) != 0) continue;
+    const int pc = __popc(c);
+    if (pc < 2 || !hits_all(occ, c, full)) continue;
+    const uint32_t rev = __brev(c);  // the order among equal sizes only: the shift by 32 - d is common to all
+    if (best < 0 || pc < bestPc || (pc == bestPc && rev > bestRev)) {
+      best = (int)c;
+      bestPc = pc;
+      bestRev = rev;
+    }
+  }
+  return best < 0 ? -1 : encode_mask((uint32_t)best);
+}
+
+// WeakSpivakovskyMinHitting._select_coord (host.py:381-427): candidates are all c with |c| >= 2 that meet every
+// support; subset_route orders them by (|c|, c).  The reference's masks have 16 bits: a bit >= d meets no support, so
+// the first hit lies within the d coordinates.
+template <typename T>
+__device__ inline int min_hitting_game(const T* p, int m, int d) {
+  int npts;
+  const uint64_t occ = support_bitmap(p, m, d, npts);
+  if (npts < 2) return -1;
+  const uint32_t full = (1u << d) - 1u;
+  int best = -1, bestPc = 0;
+  for (uint32_t c = 3; c <= full; ++c) {
+    const int pc = __popc(c);
+    if (pc < 2 || (best >= 0 && pc >= bestPc) || !hits_all(occ, c, full)) continue;
+    best = (int)c;  // ascending c: the first hit of a size is the smallest of that size
+    bestPc = pc;
+  }
+  return best < 0 ? -1 : encode_mask((uint32_t)best);
+}
+
+// the class id a host picks on one game in list semantics; host is one of HK_HOST_ALL_COORD .. HK_HOST_MIN_HITTING
+template <typename T>
+__device__ inline int host_list_game(const T* p, int m, int d, int host) {
+  switch (host) {
+    case HK_HOST_ALL_COORD: return encode_mask((1u << d) - 1u);
+    case HK_HOST_ZEILLINGER: return zeillinger_list_game(p, m, d);
+    case HK_HOST_ZEILLINGER_LEX: return zeillinger_lex_list_game(p, m, d);
+    case HK_HOST_WEAK_SPIVAKOVSKY: return weak_spivakovsky_game(p, m, d);
+    case HK_HOST_MIN_HITTING: return min_hitting_game(p, m, d);
+  }
+  return -1;
+}
+
+}  // namespace hk

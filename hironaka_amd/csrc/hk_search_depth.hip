@@ -1,4 +1,4 @@
-// C ABI of hk_search_depth (include/hironaka_hip.h, ABI 5): argument validation and launch of
+// C ABI of hk_search_depth (include/hironaka_hip.h, ABI 5; the hosts of ABI 6): argument validation and launch of
 // hk::search_depth_kernel.  No allocation, no synchronisation; every status is decided before the launch.
 #include "hk_search_depth_kernel.h"
 
@@ -23,14 +23,26 @@ uint64_t stack_bytes(int batch, int m, int d, int dtype, int stack_nodes) {
   return per_root * (uint64_t)batch;
 }
 
-template <typename T>
+template <typename T, int HOST>
 int launch_search_depth(SearchDepthArgs a, int batch, hipStream_t stream) {
   const int per_lane = a.lds_stride * (int)sizeof(T);
   a.lanes = kSearchDepthLdsBytes / per_lane < kWave ? kSearchDepthLdsBytes / per_lane : kWave;
   const size_t lds = (size_t)a.lanes * per_lane;
   launch_prepare();
-  hipLaunchKernelGGL(search_depth_kernel<T>, dim3((unsigned)batch), dim3(kWave), lds, stream, a);
+  hipLaunchKernelGGL((search_depth_kernel<T, HOST>), dim3((unsigned)batch), dim3(kWave), lds, stream, a);
   return launch_status();
+}
+
+template <typename T>
+int launch_search_depth(const SearchDepthArgs& a, int batch, hipStream_t stream) {
+  switch (a.host) {
+    case HK_HOST_ALL_COORD: return launch_search_depth<T, HK_HOST_ALL_COORD>(a, batch, stream);
+    case HK_HOST_ZEILLINGER: return launch_search_depth<T, HK_HOST_ZEILLINGER>(a, batch, stream);
+    case HK_HOST_ZEILLINGER_LEX: return launch_search_depth<T, HK_HOST_ZEILLINGER_LEX>(a, batch, stream);
+    case HK_HOST_WEAK_SPIVAKOVSKY: return launch_search_depth<T, HK_HOST_WEAK_SPIVAKOVSKY>(a, batch, stream);
+    case HK_HOST_MIN_HITTING: return launch_search_depth<T, HK_HOST_MIN_HITTING>(a, batch, stream);
+  }
+  return HK_ERR_UNSUPPORTED;
 }
 
 }  // namespace
@@ -47,7 +59,7 @@ int hk_search_depth(const void* points, int batch, int max_points, int dim, int 
                     uint64_t* nodes_out, int32_t* status_out, void* stream) {
   const int st = search_spec(batch, max_points, dim, dtype, stack_nodes);
   if (st != HK_OK) return st;
-  if (host != HK_HOST_ZEILLINGER && host != HK_HOST_ALL_COORD) return HK_ERR_UNSUPPORTED;
+  if (host < HK_HOST_ALL_COORD || host > HK_HOST_MIN_HITTING) return HK_ERR_UNSUPPORTED;
   if (max_depth < 0 || max_nodes < 1) return HK_ERR_SHAPE;
   if (batch == 0) return HK_OK;
   if (!points || !workspace || !depth_out || !nodes_out || !status_out) return HK_ERR_NULL;

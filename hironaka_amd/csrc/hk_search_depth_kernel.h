@@ -3,8 +3,8 @@
 // One workgroup of one wave per root; the root's pending nodes live on a LIFO stack in the caller's workspace (an
 // entry = the max_points*dim coordinates, plus an int32 depth in a parallel array).  Every iteration pops up to
 // `lanes` nodes from the top, one per lane, and expands them in LDS with the list-semantics routines of
-// hk_game_generic.h: the host's subset I (Zeillinger or all coordinates), then per axis a in I a copy of the parent,
-// shift x_a <- sum_{k in I} x_k, Newton, sort-compact.  Children with >= 2 points are pushed back, in axis-then-lane
+// hk_game_generic.h: the host's subset I (hk_hosts.h: Zeillinger, all coordinates, ZeillingerLex or a weak
+// Spivakovsky host), then per axis a in I a copy of the parent, shift x_a <- sum_{k in I} x_k, Newton, sort-compact.  Children with >= 2 points are pushed back, in axis-then-lane
 // order, at positions a wave prefix sum hands out.  Depth max and node count are independent of the traversal order;
 // the stack's peak size is not.
 //
@@ -12,7 +12,7 @@
 // at the stack's capacity.  No communication between workgroups.
 #pragma once
 
-#include "hk_game_generic.h"
+#include "hk_hosts.h"
 
 namespace hk {
 
@@ -33,7 +33,8 @@ struct SearchDepthArgs {
 // private slices start in different banks
 inline int search_depth_lds_stride(int m, int d) { return (2 * m * d + 2 * d) | 1; }
 
-template <typename T>
+// HOST: the host code, one instantiation per host (a.host is not read)
+template <typename T, int HOST>
 __global__ void __launch_bounds__(kWave) search_depth_kernel(SearchDepthArgs a) {
   extern __shared__ unsigned char hk_sd_lds[];
   __shared__ int slot_lane[kWave];
@@ -89,11 +90,15 @@ __global__ void __launch_bounds__(kWave) search_depth_kernel(SearchDepthArgs a) 
     const bool expand = active && !capped;
     uint32_t subset = 0;
     if (expand) {
-      if (a.host == HK_HOST_ZEILLINGER) {
+      if (HOST == HK_HOST_ZEILLINGER) {
         const int cls = zeillinger_list_game(par, m, d);  // >= 0: a visited node holds >= 2 points
         subset = decode_class(cls < 0 ? 0 : cls, d);
-      } else {
+      } else if (HOST == HK_HOST_ALL_COORD) {
         subset = (1u << d) - 1u;
+      } else {
+        // -1 (a zero row, or |U| < 2 for WeakSpivakovsky) only at a root that is not Newton-reduced: no children
+        const int cls = host_list_game(par, m, d, HOST);
+        subset = cls < 0 ? 0u : decode_class(cls, d);
       }
       for (int j = 0; j < d; ++j) c[j] = ((subset >> j) & 1u) ? (T)1 : (T)0;
     }

@@ -1,5 +1,6 @@
 """Fixed hosts for the gym / game surfaces, vectorised over a batch of games -- the counterparts of
-``hironaka/host.py`` (`Host.select_coord`, `RandomHost`, `AllCoordHost`, `Zeillinger`).
+``hironaka/host.py`` (`Host.select_coord`, `RandomHost`, `AllCoordHost`, `Zeillinger`, `ZeillingerLex`,
+`WeakSpivakovsky`, `WeakSpivakovskyMinHitting`).
 
 ``select_coord(points)`` takes the padded state ``[B, m, d]`` (device tensor or a container with a
 ``.points`` attribute) and returns the chosen coordinate subsets as a multi-binary mask ``[B, d]``
@@ -73,6 +74,46 @@ class Zeillinger(Host):
         cls = ops.zeillinger(points, sem="list")
         mask = ops.decode_host_class(cls.clamp(min=0), d, torch.int32)
         return mask * (cls >= 0).unsqueeze(1).to(torch.int32)
+
+
+MAX_HOST_DIM = 6  # hk_host_select: the hitting-set hosts keep one bit per possible support
+
+
+def _hk_host(points: torch.Tensor, host: str) -> torch.Tensor:
+    """select_coord of a host of hk_host_select (list semantics): the decoded mask, empty where the class is -1"""
+    d = points.shape[2]
+    if d > MAX_HOST_DIM:
+        raise ValueError(f"{host} runs on the GPU for dimensions up to {MAX_HOST_DIM} (hk_host_select). Got {d}.")
+    cls = ops.host_select(points, host)
+    mask = ops.decode_host_class(cls.clamp(min=0), d, torch.int32)
+    return mask * (cls >= 0).unsqueeze(1).to(torch.int32)
+
+
+class ZeillingerLex(Zeillinger):
+    """host.py:116-127 -- Zeillinger's key (L, S); among the pairs of the smallest key, the lexicographically
+    smallest [argmin, argmax] of P_i - P_j (hk_host_select)."""
+
+    def _select_coord(self, points: torch.Tensor) -> torch.Tensor:
+        return _hk_host(points, "zeillinger_lex")
+
+
+class WeakSpivakovsky(Host):
+    """host.py:357-378 -- a minimal hitting set of the points' supports (sets of nonzero coordinates), the first in
+    lexicographic order of its sorted coordinates (hk_host_select)."""
+
+    def _select_coord(self, points: torch.Tensor) -> torch.Tensor:
+        return _hk_host(points, "weak_spivakovsky")
+
+
+class WeakSpivakovskyMinHitting(Host):
+    """host.py:381-427 -- a minimal hitting set of the points' supports, the smallest as an integer
+    (hk_host_select).  ``dim`` (the width of the reference's subset table) is accepted and ignored."""
+
+    def __init__(self, dim=16):
+        self.dim = dim
+
+    def _select_coord(self, points: torch.Tensor) -> torch.Tensor:
+        return _hk_host(points, "weak_spivakovsky_min_hitting")
 
 
 class PolicyHost(Host):

@@ -300,6 +300,35 @@ def zeillinger(points: torch.Tensor, sem: str = "jax", spec=None, force_generic:
     return out
 
 
+HOSTS = {"all_coord": A.HK_HOST_ALL_COORD, "zeillinger": A.HK_HOST_ZEILLINGER,
+         "zeillinger_lex": A.HK_HOST_ZEILLINGER_LEX, "weak_spivakovsky": A.HK_HOST_WEAK_SPIVAKOVSKY,
+         "weak_spivakovsky_min_hitting": A.HK_HOST_MIN_HITTING}
+
+
+def host_select(points: torch.Tensor, host: str, spec=None) -> torch.Tensor:
+    """The class id a deterministic host of hironaka/host.py picks per game, in list semantics (hk_host_select):
+    "all_coord", "zeillinger" (== zeillinger(sem="list")), "zeillinger_lex", "weak_spivakovsky",
+    "weak_spivakovsky_min_hitting".  -1 = no subset (fewer than 2 points; a zero row or fewer than 2 nonzero
+    coordinates in all for the hitting-set hosts, see include/hironaka_hip_hosts.h).  dim 2..6, up to 64 points.
+    points: [B, m, d], or [B, stride] records with spec=(m, d)."""
+    if host not in HOSTS:
+        raise ValueError(f"host must be one of {sorted(HOSTS)}. Got {host!r}.")
+    pts, _ = _state(points)
+    if pts.dim() == 3:
+        b, m, d = pts.shape
+        stride = m * d
+    elif pts.dim() == 2 and spec is not None:
+        b, stride = pts.shape
+        m, d = spec
+    else:
+        raise ValueError("points must be [B, m, d], or [B, stride] together with spec=(m, d)")
+    out = torch.empty(b, dtype=torch.int32, device=pts.device)
+    with torch.cuda.device(pts.device):
+        check(lib().hk_host_select(pts.data_ptr(), stride, out.data_ptr(), b, m, d, _TORCH2HK[pts.dtype], HOSTS[host],
+                                   _stream(pts)), "hk_host_select")
+    return out
+
+
 def get_features(points: torch.Tensor, scale_observation: bool = True, padding_value: float = -1.0,
                  spec=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """order_and_rescale (jax/util.py:186-197): [B, m*d] rows sorted descending, last coordinate
@@ -634,7 +663,9 @@ def has_fast_path(max_points: int, dim: int, dtype=torch.float32) -> bool:
     return bool(lib().hk_has_fast_path(max_points, dim, _TORCH2HK.get(dtype, -1)))
 
 
-SEARCH_HOSTS = {"zeillinger": A.HK_HOST_ZEILLINGER, "all_coord": A.HK_HOST_ALL_COORD}
+SEARCH_HOSTS = {"zeillinger": A.HK_HOST_ZEILLINGER, "all_coord": A.HK_HOST_ALL_COORD,
+                "zeillinger_lex": A.HK_HOST_ZEILLINGER_LEX, "weak_spivakovsky": A.HK_HOST_WEAK_SPIVAKOVSKY,
+                "weak_spivakovsky_min_hitting": A.HK_HOST_MIN_HITTING}
 _SEARCH_WORKSPACE_BYTES = 4 << 30  # per launch; a larger batch runs as several launches
 
 
@@ -642,7 +673,7 @@ def search_depth(points: torch.Tensor, host: str, *, max_depth: int, max_nodes: 
                  stack_nodes: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Exhaustive worst-case game length under a fixed host, one tree per root (hironaka/util/search.py:9-32,
     hk_search_depth).  points: [B, m, d] float32/float64 roots in list semantics, used as given (rows with
-    coordinate 0 >= 0 are points; padding rows may sit anywhere).  host: "zeillinger" or "all_coord".
+    coordinate 0 >= 0 are points; padding rows may sit anywhere).  host: a key of SEARCH_HOSTS.
     Returns (depth int32[B], nodes int64[B], status int32[B]); status 0 = finished and exact, else an OR of
     HK_SEARCH_* bits (the numbers are then bounds, see include/hironaka_hip.h)."""
     _require_device(points, "points")

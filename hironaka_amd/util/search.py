@@ -11,7 +11,7 @@ import torch
 
 from .. import _abi as A
 from .. import ops
-from ..host import AllCoordHost, Zeillinger
+from ..host import AllCoordHost, WeakSpivakovsky, WeakSpivakovskyMinHitting, Zeillinger, ZeillingerLex
 
 DEFAULT_MAX_DEPTH = 1 << 20
 DEFAULT_MAX_NODES = 1 << 24
@@ -29,14 +29,18 @@ class SearchDepthResult(NamedTuple):
     status: torch.Tensor  # int32 [B]: 0 = exact, else an OR of A.HK_SEARCH_* bits
 
 
+_SEARCH_HOSTS = {Zeillinger: "zeillinger", AllCoordHost: "all_coord", ZeillingerLex: "zeillinger_lex",
+                 WeakSpivakovsky: "weak_spivakovsky", WeakSpivakovskyMinHitting: "weak_spivakovsky_min_hitting"}
+
+
 def _host_name(host) -> str:
     # exact types: a subclass may override select_coord, which the kernel would not see
-    if type(host) is Zeillinger:
-        return "zeillinger"
-    if type(host) is AllCoordHost:
-        return "all_coord"
-    raise TypeError("search_depth runs the host inside the GPU search: supported hosts are "
-                    f"hironaka_amd.host.Zeillinger and hironaka_amd.host.AllCoordHost. Got {type(host).__name__}.")
+    name = _SEARCH_HOSTS.get(type(host))
+    if name is None:
+        raise TypeError("search_depth runs the host inside the GPU search: supported hosts are "
+                        "hironaka_amd.host.Zeillinger and hironaka_amd.host.AllCoordHost, plus ZeillingerLex, "
+                        f"WeakSpivakovsky and WeakSpivakovskyMinHitting. Got {type(host).__name__}.")
+    return name
 
 
 def _roots(points, dtype: Optional[torch.dtype]) -> torch.Tensor:

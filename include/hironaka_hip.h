@@ -49,6 +49,9 @@
  *                            jax/recurrent_fn.py:105-121 (agent-role tree) and the agent's
  *                            action mask jax/util.py:287-305
  *   hk_search_depth          hironaka/util/search.py:9-32 search_depth (one tree per root, a batch of roots)
+ *   hk_host_select           (hironaka_hip_hosts.h) host.py:48-51 AllCoordHost, host.py:54-95 Zeillinger, host.py:116-127 ZeillingerLex,
+ *                            host.py:357-378 WeakSpivakovsky, host.py:381-427 WeakSpivakovskyMinHitting
+ *                            (select_coord on ListPoints)
  */
 #ifndef HIRONAKA_HIP_H
 #define HIRONAKA_HIP_H
@@ -59,7 +62,7 @@
 extern "C" {
 #endif
 
-#define HK_ABI_VERSION 5 /* 2: + HK_AXIS_MASKED_LOGITS, hk_step_features, hk_rollout_values, hk_search_expand_* / _masked_argmax / _mask_logits; 3: + hk_rollout_desc.game_ids (and the policy stream of dim <= 8 became four steps per Philox block with 16-bit draws: seeds are not comparable with ABI 2); 4: + hk_rollout_desc.gen_max_value / gen_stages / gen_seed / episodes (initial states drawn inside the launch, `points` may be NULL), - HK_FLAG_FORCE_POOL; 5: + hk_search_depth, hk_search_depth_workspace_bytes, HK_SEARCH_* status bits */
+#define HK_ABI_VERSION 6 /* 2: + HK_AXIS_MASKED_LOGITS, hk_step_features, hk_rollout_values, hk_search_expand_* / _masked_argmax / _mask_logits; 3: + hk_rollout_desc.game_ids (and the policy stream of dim <= 8 became four steps per Philox block with 16-bit draws: seeds are not comparable with ABI 2); 4: + hk_rollout_desc.gen_max_value / gen_stages / gen_seed / episodes (initial states drawn inside the launch, `points` may be NULL), - HK_FLAG_FORCE_POOL; 5: + hk_search_depth, hk_search_depth_workspace_bytes, HK_SEARCH_* status bits; 6: + hk_host_select (declared in hironaka_hip_hosts.h), HK_HOST_ZEILLINGER_LEX / _WEAK_SPIVAKOVSKY / _MIN_HITTING (hk_search_depth accepts them too) */
 
 /* ---- status codes -------------------------------------------------------------------- */
 #define HK_OK 0
@@ -126,6 +129,11 @@ extern "C" {
 #define HK_HOST_RANDOM 0    /* players.py:28-39   uniform class id                          */
 #define HK_HOST_ALL_COORD 1 /* players.py:42-52   all coordinates                          */
 #define HK_HOST_ZEILLINGER 2 /* players.py:84-109                                           */
+/* ABI 6: deterministic hosts of hironaka/host.py served by hk_host_select and hk_search_depth only (hk_rollout
+ * returns HK_ERR_UNSUPPORTED for them: jax/players.py has no counterpart)                                  */
+#define HK_HOST_ZEILLINGER_LEX 3   /* host.py:116-127  ZeillingerLex                                   */
+#define HK_HOST_WEAK_SPIVAKOVSKY 4 /* host.py:357-378  WeakSpivakovsky                                 */
+#define HK_HOST_MIN_HITTING 5      /* host.py:381-427  WeakSpivakovskyMinHitting                       */
 #define HK_AGENT_RANDOM 0       /* players.py:142-153 uniform over all `dim` axes (JAX)    */
 #define HK_AGENT_RANDOM_LEGAL 1 /* trainer/player_modules/modules.py:48-52, agent.py:85-90 */
 #define HK_AGENT_CHOOSE_FIRST 2 /* players.py:156-183                                      */
@@ -421,7 +429,9 @@ int hk_decode_host_class(const int32_t* class_in, void* mask_out, int mask_dtype
  * shift, then Newton sorted + compacted, no reposition, no rescale).  The root is used as given: rows with
  * coordinate 0 >= 0 are its points, padding rows may sit anywhere, and no Newton pass or sort precedes the first
  * move.  At a node the host picks a subset I (HK_HOST_ZEILLINGER: host.py:54-95 on rows in row order;
- * HK_HOST_ALL_COORD: host.py:48-51); the node gets one child per axis a in I: x_a <- sum_{k in I} x_k, then
+ * HK_HOST_ALL_COORD: host.py:48-51; ABI 6: HK_HOST_ZEILLINGER_LEX, HK_HOST_WEAK_SPIVAKOVSKY, HK_HOST_MIN_HITTING as in
+ * hk_host_select -- a node where the host returns -1, only possible at a root that is not Newton-reduced, gets no
+ * children); the node gets one child per axis a in I: x_a <- sum_{k in I} x_k, then
  * Newton.  A child with fewer than 2 points is a finished game and is not visited.  Per root:
  *   depth_out  1 + the largest depth of a visited node (the root has depth 0): the reference's max_depth + 1
  *   nodes_out  visited nodes, root included (the reference's host.select_coord calls); identical states reached
@@ -446,4 +456,8 @@ int hk_search_depth(const void* points, int batch, int max_points, int dim, int 
 #ifdef __cplusplus
 }
 #endif
+
+/* ABI 6: hk_host_select, an entry point with no CPU-oracle counterpart */
+#include "hironaka_hip_hosts.h"
+
 #endif /* HIRONAKA_HIP_H */
