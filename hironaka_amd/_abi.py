@@ -49,7 +49,7 @@ HK_HOST_RANDOM, HK_HOST_ALL_COORD, HK_HOST_ZEILLINGER = 0, 1, 2
 HK_HOST_ZEILLINGER_LEX, HK_HOST_WEAK_SPIVAKOVSKY, HK_HOST_MIN_HITTING = 3, 4, 5  # hk_host_select / hk_search_depth
 HK_AGENT_RANDOM, HK_AGENT_RANDOM_LEGAL, HK_AGENT_CHOOSE_FIRST, HK_AGENT_CHOOSE_LAST = 0, 1, 2, 3
 
-# hk_search_depth status bits
+# hk_search_depth / hk_search_game_tree status bits
 HK_SEARCH_DEPTH_LIMIT = 1
 HK_SEARCH_NODE_LIMIT = 2
 HK_SEARCH_STACK_LIMIT = 4
@@ -181,6 +181,9 @@ PROTOTYPES = {
     "hk_search_mask_logits": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp]),
     "hk_search_depth_workspace_bytes": (C.c_uint64, [_i, _i, _i, _i, _i]),
     "hk_search_depth": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _u64, _i, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "hk_search_game_tree_workspace_bytes": (C.c_uint64, [_i, _i, _i, _i, _i, _i]),
+    "hk_search_game_tree": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp]),
 }
 
 STATUS_TEXT = {

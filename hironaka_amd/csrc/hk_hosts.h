@@ -59,6 +59,44 @@ __device__ inline int zeillinger_lex_list_game(const T* p, int m, int d) {
   return encode_mask((1u << (bestR >> 3)) | (1u << (bestR & 7)));
 }
 
+// The ordered lists of Zeillinger (LEX false, host.py:90-95) and ZeillingerLex (LEX true, host.py:116-127), for
+// hk_search_game_tree, whose children follow the list's order: the chosen r = [first argmin v, first argmax v] packed as
+// r[0] * 8 + r[1] ([0, 1] = 1 when they coincide), -1 for fewer than 2 points.  The pair is chosen exactly as in
+// zeillinger_list_game / zeillinger_lex_list_game, which return the unordered class id and are left as they are.
+template <typename T, bool LEX>
+__device__ inline int zeillinger_list_pair(const T* p, int m, int d) {
+  T bestL = (T)0;
+  int bestS = 0, bestR = -1;
+  for (int i = 0; i < m; ++i) {
+    if (!(p[i * d] >= (T)0)) continue;
+    for (int j = i + 1; j < m; ++j) {
+      if (!(p[j * d] >= (T)0)) continue;
+      T mx = p[i * d] - p[j * d], mn = mx;
+      int lo = 0, hi = 0;
+      for (int k = 1; k < d; ++k) {
+        const T v = p[i * d + k] - p[j * d + k];
+        if (v < mn) { mn = v; lo = k; }
+        if (v > mx) { mx = v; hi = k; }
+      }
+      int cnt = 0;
+      for (int k = 0; k < d; ++k) {
+        const T v = p[i * d + k] - p[j * d + k];
+        cnt += (v == mx) + (v == mn);
+      }
+      const T L = mx - mn;
+      const int r = lo == hi ? 1 : lo * 8 + hi;
+      if (bestR < 0 || L < bestL || (L == bestL && cnt < bestS)) {
+        bestL = L;
+        bestS = cnt;
+        bestR = r;
+      } else if (LEX && L == bestL && cnt == bestS && r < bestR) {
+        bestR = r;
+      }
+    }
+  }
+  return bestR;
+}
+
 // Which supports occur: bit s of the result is set when some point's set of nonzero coordinates is s (x != 0: NaN
 // counts as nonzero and -0.0 as zero, as np.nonzero does).  d <= 6.  `npts` receives the number of points.
 template <typename T>

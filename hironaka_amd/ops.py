@@ -669,6 +669,18 @@ SEARCH_HOSTS = {"zeillinger": A.HK_HOST_ZEILLINGER, "all_coord": A.HK_HOST_ALL_C
 _SEARCH_WORKSPACE_BYTES = 4 << 30  # per launch; a larger batch runs as several launches
 
 
+def _search_roots(points: torch.Tensor) -> torch.Tensor:
+    """the roots of hk_search_depth / hk_search_game_tree, contiguous; their points must be exact integers"""
+    pts = points.contiguous()
+    limit = 2.0 ** 24 if pts.dtype == torch.float32 else 2.0 ** 53
+    avail = (pts[:, :, 0] >= 0).unsqueeze(2).expand_as(pts)
+    vals = pts[avail]
+    if vals.numel() and not bool(((vals >= 0) & (vals < limit) & (vals == torch.floor(vals))).all()):
+        raise ValueError(f"the points of a root (rows with coordinate 0 >= 0) must be integers in [0, {int(limit)}) "
+                         f"for {pts.dtype}")
+    return pts
+
+
 def search_depth(points: torch.Tensor, host: str, *, max_depth: int, max_nodes: int,
                  stack_nodes: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Exhaustive worst-case game length under a fixed host, one tree per root (hironaka/util/search.py:9-32,
@@ -686,14 +698,8 @@ def search_depth(points: torch.Tensor, host: str, *, max_depth: int, max_nodes: 
     if not (0 <= max_depth < 2 ** 31 and 1 <= max_nodes < 2 ** 63 and 1 <= stack_nodes < 2 ** 31):
         raise ValueError(f"need 0 <= max_depth < 2^31, 1 <= max_nodes < 2^63, 1 <= stack_nodes < 2^31. Got "
                          f"{max_depth}, {max_nodes}, {stack_nodes}.")
-    pts = points.contiguous()
+    pts = _search_roots(points)
     b, m, d = pts.shape
-    limit = 2.0 ** 24 if pts.dtype == torch.float32 else 2.0 ** 53
-    avail = (pts[:, :, 0] >= 0).unsqueeze(2).expand_as(pts)
-    vals = pts[avail]
-    if vals.numel() and not bool(((vals >= 0) & (vals < limit) & (vals == torch.floor(vals))).all()):
-        raise ValueError(f"the points of a root (rows with coordinate 0 >= 0) must be integers in [0, {int(limit)}) "
-                         f"for {pts.dtype}")
     dt = _TORCH2HK[pts.dtype]
     L = lib()
     per_root = L.hk_search_depth_workspace_bytes(1, m, d, dt, stack_nodes)
@@ -715,3 +721,51 @@ def search_depth(points: torch.Tensor, host: str, *, max_depth: int, max_nodes: 
             check(L.hk_search_depth(pts.data_ptr(), 0, m, d, dt, SEARCH_HOSTS[host], max_depth, max_nodes,
                                     stack_nodes, None, 0, None, None, None, _stream(pts)), "hk_search_depth")
     return depth, nodes, status
+
+
+def search_game_tree(points: torch.Tensor, host: str, *, expand_limit: Optional[int], max_depth: int, max_nodes: int,
+                     stack_nodes: int, states: bool = True) -> Tuple[torch.Tensor, ...]:
+    """The game tree under a fixed host, every node kept in the reference's preorder (hironaka/util/search.py:35-50
+    search_tree, hk_search_game_tree).  points: [B, m, d] float32/float64 roots as for search_depth.  host: a key of
+    SEARCH_HOSTS.  expand_limit: None for the whole tree, else L >= 0: only nodes numbered <= L are expanded (the
+    reference's max_size - tree.size()).  Returns (parent, child_index, axis, depth, num_points, host_class) int32
+    [B, max_nodes], states [B, max_nodes, m, d] of the roots' dtype (None unless ``states``), count int32 [B] and
+    status int32 [B].  Slots from count on hold -1.  A status other than 0 / HK_SEARCH_ROOT_ENDED /
+    HK_SEARCH_DEPTH_LIMIT leaves only count and status meaningful (include/hironaka_hip.h)."""
+    _require_device(points, "points")
+    if points.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"points must be float32 or float64. Got {points.dtype}.")
+    if points.dim() != 3:
+        raise ValueError(f"points must be [B, max_points, dim]. Got shape {tuple(points.shape)}.")
+    if host not in SEARCH_HOSTS:
+        raise ValueError(f"host must be one of {sorted(SEARCH_HOSTS)}. Got {host!r}.")
+    if expand_limit is not None and not 0 <= expand_limit < 2 ** 63:
+        raise ValueError(f"expand_limit must be None or in [0, 2^63). Got {expand_limit}.")
+    if not (0 <= max_depth < 2 ** 31 and 1 <= max_nodes < 2 ** 31 and 1 <= stack_nodes < 2 ** 31):
+        raise ValueError(f"need 0 <= max_depth < 2^31, 1 <= max_nodes < 2^31, 1 <= stack_nodes < 2^31. Got "
+                         f"{max_depth}, {max_nodes}, {stack_nodes}.")
+    pts = _search_roots(points)
+    b, m, d = pts.shape
+    dt = _TORCH2HK[pts.dtype]
+    lim = -1 if expand_limit is None else int(expand_limit)
+    L = lib()
+    per_root = L.hk_search_game_tree_workspace_bytes(1, m, d, dt, max_nodes, stack_nodes)
+    if per_root == 0:
+        check(L.hk_search_game_tree(None, 1, m, d, dt, SEARCH_HOSTS[host], lim, max_depth, max_nodes, stack_nodes,
+                                    None, 0, *([None] * 9), None), "hk_search_game_tree")
+    dev = pts.device
+    ints = [torch.full((b, max_nodes), -1, dtype=torch.int32, device=dev) for _ in range(6)]
+    st = torch.full((b, max_nodes, m, d), -1, dtype=pts.dtype, device=dev) if states else None
+    count = torch.zeros(b, dtype=torch.int32, device=dev)
+    status = torch.zeros(b, dtype=torch.int32, device=dev)
+    chunk = max(1, min(b, _SEARCH_WORKSPACE_BYTES // max(per_root, 1)))
+    with torch.cuda.device(dev):
+        ws = torch.empty(per_root * chunk if b else 0, dtype=torch.uint8, device=dev)
+        for lo in range(0, b, chunk):
+            n = min(chunk, b - lo)
+            outs = [t[lo].data_ptr() for t in ints] + [st[lo].data_ptr() if states else None]
+            check(L.hk_search_game_tree(pts[lo].data_ptr(), n, m, d, dt, SEARCH_HOSTS[host], lim, max_depth,
+                                        max_nodes, stack_nodes, ws.data_ptr(), ws.numel(), *outs,
+                                        count[lo].data_ptr(), status[lo].data_ptr(), _stream(pts)),
+                  "hk_search_game_tree")
+    return (*ints, st, count, status)

@@ -1,4 +1,6 @@
 """Tools that study a host strategy itself -- the counterpart of ``hironaka/util`` (search.py)."""
-from .search import SearchDepthResult, search_depth, search_depths
+from .search import (SearchDepthResult, SearchTreeResult, TreeNodeData, search_depth, search_depths, search_tree,
+                     search_trees)
 
-__all__ = ["SearchDepthResult", "search_depth", "search_depths"]
+__all__ = ["SearchDepthResult", "SearchTreeResult", "TreeNodeData", "search_depth", "search_depths", "search_tree",
+           "search_trees"]

@@ -2,8 +2,11 @@
 make the game last?  Every agent choice is enumerated depth first, on the GPU (hk_search_depth): one tree per root,
 any number of roots per call.
 
-The reference's ``search_tree`` / ``search_tree_morin`` (treelib output) and the JAX ``search_tree_fix_host`` are
-not built here.
+``search_tree`` (hironaka/util/search.py:35-50): the same game tree with every node kept, in the reference's node
+order, built on the GPU (hk_search_game_tree) and handed to any tree object with ``size()`` and ``create_node``
+(treelib's ``Tree`` among them).  ``search_trees`` returns the trees of a batch of roots as tensors.
+
+The reference's ``search_tree_morin`` and the JAX ``search_tree_fix_host`` are not built here.
 """
 from typing import NamedTuple, Optional
 
@@ -17,6 +20,8 @@ DEFAULT_MAX_DEPTH = 1 << 20
 DEFAULT_MAX_NODES = 1 << 24
 DEFAULT_STACK_NODES = 1 << 16  # per root, for one root (the 5552-deep reference tree peaks at a few hundred)
 DEFAULT_BATCH_STACK_NODES = 1 << 12  # per root of a batch; ops.search_depth splits a batch to bound the workspace
+DEFAULT_TREE_NODES = 1 << 21  # search_tree: one root; the 5552-deep reference tree has 1 128 897 nodes
+DEFAULT_BATCH_TREE_NODES = 1 << 14  # search_trees: per root of a batch
 
 _LIMITS = ((A.HK_SEARCH_DEPTH_LIMIT, "max_depth"), (A.HK_SEARCH_NODE_LIMIT, "max_nodes"),
            (A.HK_SEARCH_STACK_LIMIT, "stack_nodes"),
@@ -92,3 +97,88 @@ def search_depth(points, host, debug=False, *, max_depth: Optional[int] = None,
         raise RuntimeError(f"search_depth did not finish exactly (status {status}): limited by {', '.join(hit)}; "
                            f"depth >= {int(res.depth[0])}, nodes >= {int(res.nodes[0])}")
     return int(res.depth[0])
+
+
+class SearchTreeResult(NamedTuple):
+    parent: torch.Tensor       # int32 [B, max_nodes]: the parent's id, -1 for the root; ids are preorder
+    child_index: torch.Tensor  # int32 [B, max_nodes]: the position in the parent's host list, -1 for the root
+    axis: torch.Tensor         # int32 [B, max_nodes]: the agent's axis that made the node, -1 for the root
+    depth: torch.Tensor        # int32 [B, max_nodes]: the root has depth 0
+    num_points: torch.Tensor   # int32 [B, max_nodes]
+    host_class: torch.Tensor   # int32 [B, max_nodes]: an expanded node's host subset (class id), else -1
+    states: Optional[torch.Tensor]  # [B, max_nodes, m, d]: list semantics, padding -1; None unless states=True
+    count: torch.Tensor        # int32 [B]: the nodes; slots from count on hold -1
+    status: torch.Tensor       # int32 [B]: 0, or an OR of A.HK_SEARCH_* bits
+
+
+def search_trees(points, host, *, max_size: Optional[int] = None, max_depth: int = DEFAULT_MAX_DEPTH,
+                 max_nodes: int = DEFAULT_BATCH_TREE_NODES, stack_nodes: int = DEFAULT_BATCH_STACK_NODES,
+                 states: bool = True, dtype: Optional[torch.dtype] = None) -> SearchTreeResult:
+    """The reference's ``search_tree`` for a batch of roots [B, m, d] (tensor, HipPoints or nested lists), as padded
+    tensors.  ``max_size`` counts as in the reference with the root alone in the tree (tree.size() == 1): nodes
+    numbered <= max_size - 1 are expanded; None expands the whole tree.  A root with ``max_size`` < 1 is refused
+    here (the reference adds nothing).  Nothing is raised for a non-zero status: read ``status``."""
+    if max_size is not None and max_size < 1:
+        raise ValueError(f"max_size must be None or >= 1 (the root is in the tree). Got {max_size}.")
+    res = ops.search_game_tree(_roots(points, dtype), _host_name(host),
+                               expand_limit=None if max_size is None else max_size - 1, max_depth=max_depth,
+                               max_nodes=max_nodes, stack_nodes=stack_nodes, states=states)
+    return SearchTreeResult(*res)
+
+
+class TreeNodeData:
+    """The ``data`` of a node made by ``search_tree``: a light stand-in for the reference's ListPoints of one game.
+    ``points`` is the nested list [[[x, ...], ...]] of a batch of one, ``str()`` prints it as ListPoints does."""
+    __slots__ = ("points",)
+    batch_size = 1
+
+    def __init__(self, points):
+        self.points = points
+
+    @property
+    def ended(self) -> bool:
+        return len(self.points[0]) <= 1
+
+    def __repr__(self) -> str:
+        return str(self.points)
+
+
+def _node_points(state) -> list:
+    # the rows with coordinate 0 >= 0, as Python ints (the states are exact integers)
+    return [[[int(x) for x in row] for row in state if row[0] >= 0]]
+
+
+def search_tree(points, tree, curr_node, host, max_size=100, *, max_depth: Optional[int] = None,
+                max_nodes: Optional[int] = None, stack_nodes: Optional[int] = None):
+    """The reference's ``search_tree(points, tree, curr_node, host, max_size=100)``: builds the game tree under
+    ``host`` below ``curr_node``, which the caller has already created in ``tree``, and adds its nodes with
+    ``tree.create_node(node_id, node_id, parent=..., data=...)`` in the reference's order, node_id = tree.size().
+    ``tree`` is any object with ``size()`` and ``create_node`` (a treelib Tree works).  Returns ``tree``, or None
+    when the root has fewer than 2 points or ``tree.size() > max_size`` (nothing is added then).  ``max_size``
+    None builds the whole tree.  ``points``: a HipPoints of batch 1, a [m, d] or [1, m, d] tensor, or nested lists.
+    The tree is built on the GPU first and handed over afterwards; RuntimeError names the limit when it did not
+    fit (``max_nodes``, ``stack_nodes``) or left the exact integer range.  A node's ``data`` is a TreeNodeData."""
+    name = _host_name(host)
+    roots = _roots(points, None)
+    if roots.shape[0] != 1:
+        raise ValueError(f"search_tree searches one root; got a batch of {roots.shape[0]}: use search_trees")
+    s0 = tree.size()
+    if max_size is not None and s0 > max_size:
+        return None
+    res = ops.search_game_tree(roots, name, expand_limit=None if max_size is None else max_size - s0,
+                               max_depth=DEFAULT_MAX_DEPTH if max_depth is None else max_depth,
+                               max_nodes=DEFAULT_TREE_NODES if max_nodes is None else max_nodes,
+                               stack_nodes=DEFAULT_STACK_NODES if stack_nodes is None else stack_nodes)
+    parent, _, _, _, _, _, st, count, status = res
+    status, count = int(status[0]), int(count[0])
+    if status & A.HK_SEARCH_ROOT_ENDED:
+        return None
+    hit = [name for bit, name in _LIMITS if status & bit and bit != A.HK_SEARCH_DEPTH_LIMIT]
+    if hit:
+        raise RuntimeError(f"search_tree did not finish exactly (status {status}): limited by {', '.join(hit)}")
+    par = parent[0, :count].tolist()
+    states = st[0, :count].cpu().numpy()
+    ident = [curr_node] + [s0 + j - 1 for j in range(1, count)]
+    for j in range(1, count):
+        tree.create_node(ident[j], ident[j], parent=ident[par[j]], data=TreeNodeData(_node_points(states[j])))
+    return tree

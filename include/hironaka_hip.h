@@ -49,6 +49,7 @@
  *                            jax/recurrent_fn.py:105-121 (agent-role tree) and the agent's
  *                            action mask jax/util.py:287-305
  *   hk_search_depth          hironaka/util/search.py:9-32 search_depth (one tree per root, a batch of roots)
+ *   hk_search_game_tree      hironaka/util/search.py:35-50 search_tree (the nodes themselves, in preorder)
  *   hk_host_select           (hironaka_hip_hosts.h) host.py:48-51 AllCoordHost, host.py:54-95 Zeillinger, host.py:116-127 ZeillingerLex,
  *                            host.py:357-378 WeakSpivakovsky, host.py:381-427 WeakSpivakovskyMinHitting
  *                            (select_coord on ListPoints)
@@ -452,6 +453,40 @@ uint64_t hk_search_depth_workspace_bytes(int batch, int max_points, int dim, int
 int hk_search_depth(const void* points, int batch, int max_points, int dim, int dtype, int host, int max_depth,
                     uint64_t max_nodes, int stack_nodes, void* workspace, uint64_t workspace_bytes,
                     int32_t* depth_out, uint64_t* nodes_out, int32_t* status_out, void* stream);
+
+/* ---- the game tree under a fixed host (an addition within ABI 6; hironaka/util/search.py:35-50 search_tree) ----
+ * Per root: the tree of hk_search_depth with every node kept, in the reference's node order.  Unlike hk_search_depth,
+ * every child is a node, ended or not; a node is expanded when it holds >= 2 points (and depth < max_depth).  A
+ * node's children follow its host's list: [argmin v, argmax v] of the chosen pair for HK_HOST_ZEILLINGER /
+ * HK_HOST_ZEILLINGER_LEX (often descending), ascending axes for the other hosts.  Ids are preorder, node 0 = the
+ * root.  expand_limit L >= 0 reproduces search_tree's max_size with L = max_size - tree.size() at the call: node j
+ * is expanded only when j <= L, and the tree holds nodes 0 .. L+1, then the children after the path child of each
+ * ancestor of node L+1 (the deepest first), numbered L+2, ...  L < 0: the whole tree.  Per root, slots 0 .. count-1
+ * of each [batch, max_nodes] output (later slots are not written):
+ *   parent_out       the parent's id, -1 for the root
+ *   child_index_out  the position in the parent's host list, -1 for the root
+ *   axis_out         the agent's axis that made the node, -1 for the root
+ *   depth_out        the root has depth 0
+ *   num_points_out   the node's points
+ *   host_class_out   the class id of an expanded node's host subset (hk_step's coords), -1 for every other node
+ *   states_out       [batch, max_nodes, max_points, dim] the node's state (list semantics: shift, then Newton sorted
+ *                    + compacted, padding -1; the root as given), not written when NULL
+ *   count_out        the nodes
+ *   status_out       0, or HK_SEARCH_ROOT_ENDED (count 1), HK_SEARCH_DEPTH_LIMIT (the tree cut at max_depth, exact),
+ *                    or HK_SEARCH_NODE_LIMIT / _STACK_LIMIT / _INEXACT, after which only count_out (the nodes
+ *                    recorded so far) and status_out are written.
+ * max_nodes bounds the nodes recorded per root, which with L >= 0 may exceed count by the nodes beyond L that the
+ * traversal expanded before it could tell.  stack_nodes bounds the pending nodes.  The workspace
+ * (hk_search_game_tree_workspace_bytes) holds each root's records and stack.  Roots, dims, dtypes and host codes
+ * as hk_search_depth; max_depth >= 0, max_nodes >= 1, stack_nodes >= 1; states_out may be NULL.  Every status for
+ * bad arguments is decided before any launch.  A consumer of ABI 6 detects this entry point by its symbol.    */
+uint64_t hk_search_game_tree_workspace_bytes(int batch, int max_points, int dim, int dtype, int max_nodes,
+                                             int stack_nodes);
+int hk_search_game_tree(const void* points, int batch, int max_points, int dim, int dtype, int host,
+                        int64_t expand_limit, int max_depth, int max_nodes, int stack_nodes, void* workspace,
+                        uint64_t workspace_bytes, int32_t* parent_out, int32_t* child_index_out, int32_t* axis_out,
+                        int32_t* depth_out, int32_t* num_points_out, int32_t* host_class_out, void* states_out,
+                        int32_t* count_out, int32_t* status_out, void* stream);
 
 #ifdef __cplusplus
 }
