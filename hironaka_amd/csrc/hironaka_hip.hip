@@ -15,9 +15,6 @@ using namespace hk;
 
 namespace {
 
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-inline size_t elem_size(int dtype) { return dtype == HK_F64 ? 8 : 4; }
-
 int check_spec(int batch, int m, int d, int dtype) {
   if (batch < 0 || m < 1 || d < 1 || d > kMaxDim) return HK_ERR_SHAPE;
   if ((int64_t)m * d > (1 << 20)) return HK_ERR_SHAPE;

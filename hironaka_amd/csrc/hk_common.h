@@ -113,6 +113,12 @@ inline bool small_records_only(const Params& prm) { return !prm.obs_out && small
 inline void launch_prepare() { (void)hipGetLastError(); }
 inline int launch_status() { return hipGetLastError() == hipSuccess ? HK_OK : HK_ERR_LAUNCH; }
 
+// ---- argument checks of the C ABI entry points ---------------------------------------------------------------------
+inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+inline size_t elem_size(int dtype) { return dtype == HK_F64 ? 8 : 4; }
+// a * b, 0 when that overflows 64 bits (workspace sizes: 0 means "too large")
+inline uint64_t checked_mul(uint64_t a, uint64_t b) { return b > 0 && a > UINT64_MAX / b ? 0 : a * b; }
+
 // ---- Philox4x32-10 ------------------------------------------------------------------------
 struct U4 {
   uint32_t x, y, z, w;

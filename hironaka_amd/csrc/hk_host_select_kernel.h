@@ -36,7 +36,7 @@ __global__ void __launch_bounds__(kWave) host_select_kernel(HostSelectArgs a) {
   copy_slab<T, true, kHostSelectBatch>(lds, const_cast<T*>(static_cast<const T*>(a.points)), a.stride, a.m * a.d,
                                        a.lds_stride, g0, ngames, lane);
   __syncthreads();
-  if (lane < ngames) a.class_out[g0 + lane] = host_list_game<T>(lds + (size_t)lane * a.lds_stride, a.m, a.d, HOST);
+  if (lane < ngames) a.class_out[g0 + lane] = host_class_game<T, HOST>(lds + (size_t)lane * a.lds_stride, a.m, a.d);
 }
 
 }  // namespace hk

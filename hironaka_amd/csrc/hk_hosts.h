@@ -3,9 +3,12 @@
 // read in row order and holes may sit anywhere.  Each routine returns the class id (encode_mask) of the host's subset,
 // or -1 for "no subset".  Runtime m and d; d <= 6 for the hitting-set hosts (their support bitmap has 2^d bits).
 //
+//   zeillinger_list_pair      Zeillinger / ZeillingerLex as ordered pairs (hk_search_game_tree's child order)
 //   zeillinger_lex_list_game  ZeillingerLex      host.py:116-127  (Zeillinger's key, ties broken lexicographically)
 //   weak_spivakovsky_game     WeakSpivakovsky    host.py:357-378  (a minimal hitting set, first in combinations order)
 //   min_hitting_game          WeakSpivakovskyMinHitting  host.py:381-427  (a minimal hitting set, smallest integer)
+//
+//   host_class_game<T, HOST>  any fixed host, chosen at compile time (zeillinger_list_game for Zeillinger)
 //
 // -1 cases: fewer than 2 points (every host here; the reference returns []), and for the hitting-set hosts a zero row,
 // whose empty support no subset meets.  WeakSpivakovsky also gives -1 when the union U of the supports has fewer than
@@ -15,17 +18,21 @@
 // the smallest other one) and returns that.
 #pragma once
 
+#include <type_traits>
+
 #include "hk_game_generic.h"
 
 namespace hk {
 
-// ZeillingerLex._get_coord (host.py:116-127) over Zeillinger._select_coord's pairs (host.py:70-89): pairs i<j of the
-// points in row order, v = P_i - P_j, key (L, S) as in zeillinger_list_game.  Every pair whose key equals the smallest
-// one contributes r = [first argmin v, first argmax v] ([0, 1] if they coincide); the host takes the lexicographically
-// smallest r (the orientation P_i - P_j matters, not just the unordered pair).  One pass: a strictly smaller key
-// restarts the candidate, an equal key keeps the smaller r.  r is compared as r[0] * 8 + r[1].
-template <typename T>
-__device__ inline int zeillinger_lex_list_game(const T* p, int m, int d) {
+// The ordered lists of Zeillinger (LEX false, host.py:90-95) and ZeillingerLex (LEX true, host.py:116-127) over
+// Zeillinger._select_coord's pairs (host.py:70-89): pairs i<j of the points in row order, v = P_i - P_j, key (L, S) as
+// in zeillinger_list_game.  Each pair has r = [first argmin v, first argmax v] ([0, 1] if they coincide), packed as
+// r[0] * 8 + r[1].  Zeillinger takes the first pair of the smallest key; ZeillingerLex takes, among the pairs of the
+// smallest key, the lexicographically smallest r (the orientation P_i - P_j matters, not just the unordered pair).  One
+// pass: a strictly smaller key restarts the candidate, an equal key keeps the smaller r.  Returns r, -1 for fewer than
+// 2 points.  For LEX false the pair is chosen exactly as in zeillinger_list_game, which the rollout kernels use.
+template <typename T, bool LEX>
+__device__ inline int zeillinger_list_pair(const T* p, int m, int d) {
   T bestL = (T)0;
   int bestS = 0, bestR = -1;
   for (int i = 0; i < m; ++i) {
@@ -50,51 +57,19 @@ __device__ inline int zeillinger_lex_list_game(const T* p, int m, int d) {
         bestL = L;
         bestS = cnt;
         bestR = r;
-      } else if (L == bestL && cnt == bestS && r < bestR) {
-        bestR = r;
-      }
-    }
-  }
-  if (bestR < 0) return -1;
-  return encode_mask((1u << (bestR >> 3)) | (1u << (bestR & 7)));
-}
-
-// The ordered lists of Zeillinger (LEX false, host.py:90-95) and ZeillingerLex (LEX true, host.py:116-127), for
-// hk_search_game_tree, whose children follow the list's order: the chosen r = [first argmin v, first argmax v] packed as
-// r[0] * 8 + r[1] ([0, 1] = 1 when they coincide), -1 for fewer than 2 points.  The pair is chosen exactly as in
-// zeillinger_list_game / zeillinger_lex_list_game, which return the unordered class id and are left as they are.
-template <typename T, bool LEX>
-__device__ inline int zeillinger_list_pair(const T* p, int m, int d) {
-  T bestL = (T)0;
-  int bestS = 0, bestR = -1;
-  for (int i = 0; i < m; ++i) {
-    if (!(p[i * d] >= (T)0)) continue;
-    for (int j = i + 1; j < m; ++j) {
-      if (!(p[j * d] >= (T)0)) continue;
-      T mx = p[i * d] - p[j * d], mn = mx;
-      int lo = 0, hi = 0;
-      for (int k = 1; k < d; ++k) {
-        const T v = p[i * d + k] - p[j * d + k];
-        if (v < mn) { mn = v; lo = k; }
-        if (v > mx) { mx = v; hi = k; }
-      }
-      int cnt = 0;
-      for (int k = 0; k < d; ++k) {
-        const T v = p[i * d + k] - p[j * d + k];
-        cnt += (v == mx) + (v == mn);
-      }
-      const T L = mx - mn;
-      const int r = lo == hi ? 1 : lo * 8 + hi;
-      if (bestR < 0 || L < bestL || (L == bestL && cnt < bestS)) {
-        bestL = L;
-        bestS = cnt;
-        bestR = r;
       } else if (LEX && L == bestL && cnt == bestS && r < bestR) {
         bestR = r;
       }
     }
   }
   return bestR;
+}
+
+// ZeillingerLex._get_coord (host.py:116-127): the class id of the pair zeillinger_list_pair<T, true> picks
+template <typename T>
+__device__ inline int zeillinger_lex_list_game(const T* p, int m, int d) {
+  const int r = zeillinger_list_pair<T, true>(p, m, d);
+  return r < 0 ? -1 : encode_mask((1u << (r >> 3)) | (1u << (r & 7)));
 }
 
 // Which supports occur: bit s of the result is set when some point's set of nonzero coordinates is s (x != 0: NaN
@@ -171,17 +146,39 @@ __device__ inline int min_hitting_game(const T* p, int m, int d) {
   return best < 0 ? -1 : encode_mask((uint32_t)best);
 }
 
-// the class id a host picks on one game in list semantics; host is one of HK_HOST_ALL_COORD .. HK_HOST_MIN_HITTING
-template <typename T>
-__device__ inline int host_list_game(const T* p, int m, int d, int host) {
-  switch (host) {
-    case HK_HOST_ALL_COORD: return encode_mask((1u << d) - 1u);
-    case HK_HOST_ZEILLINGER: return zeillinger_list_game(p, m, d);
-    case HK_HOST_ZEILLINGER_LEX: return zeillinger_lex_list_game(p, m, d);
-    case HK_HOST_WEAK_SPIVAKOVSKY: return weak_spivakovsky_game(p, m, d);
-    case HK_HOST_MIN_HITTING: return min_hitting_game(p, m, d);
-  }
-  return -1;
+// the class id a fixed host (HOST: HK_HOST_ALL_COORD .. HK_HOST_MIN_HITTING) picks on one game in list semantics
+template <typename T, int HOST>
+__device__ inline int host_class_game(const T* p, int m, int d) {
+  if (HOST == HK_HOST_ALL_COORD) return encode_mask((1u << d) - 1u);
+  if (HOST == HK_HOST_ZEILLINGER) return zeillinger_list_game(p, m, d);
+  if (HOST == HK_HOST_ZEILLINGER_LEX) return zeillinger_lex_list_game(p, m, d);
+  if (HOST == HK_HOST_WEAK_SPIVAKOVSKY) return weak_spivakovsky_game(p, m, d);
+  return min_hitting_game(p, m, d);
+}
+
+// ---- host side of the fixed-host operators (hk_host_select, hk_search_depth, hk_search_game_tree) -------------------
+// Shapes they accept: the hitting-set hosts keep one bit per possible support (2^6 bits), and hk_search_game_tree
+// packs a node's host list 3 bits per axis into one word.
+constexpr int kFixedHostMaxPoints = 64;
+constexpr int kFixedHostMaxDim = 6;
+
+inline bool fixed_host(int host) { return host >= HK_HOST_ALL_COORD && host <= HK_HOST_MIN_HITTING; }
+
+// f(T(), std::integral_constant<int, HOST>()) for the element type of dtype (HK_F32 -> float, else double) and a fixed
+// host; HK_ERR_UNSUPPORTED for any other host
+template <typename F>
+int with_fixed_host(int dtype, int host, F&& f) {
+  auto on = [&](auto t) -> int {
+    switch (host) {
+      case HK_HOST_ALL_COORD: return f(t, std::integral_constant<int, HK_HOST_ALL_COORD>());
+      case HK_HOST_ZEILLINGER: return f(t, std::integral_constant<int, HK_HOST_ZEILLINGER>());
+      case HK_HOST_ZEILLINGER_LEX: return f(t, std::integral_constant<int, HK_HOST_ZEILLINGER_LEX>());
+      case HK_HOST_WEAK_SPIVAKOVSKY: return f(t, std::integral_constant<int, HK_HOST_WEAK_SPIVAKOVSKY>());
+      case HK_HOST_MIN_HITTING: return f(t, std::integral_constant<int, HK_HOST_MIN_HITTING>());
+    }
+    return HK_ERR_UNSUPPORTED;
+  };
+  return dtype == HK_F32 ? on(float()) : on(double());
 }
 
 }  // namespace hk

@@ -12,11 +12,9 @@
 // at the stack's capacity.  No communication between workgroups.
 #pragma once
 
-#include "hk_hosts.h"
+#include "hk_search_wave.h"
 
 namespace hk {
-
-constexpr int kSearchDepthLdsBytes = 64 * 1024;  // per workgroup: two or more roots share a CU
 
 struct SearchDepthArgs {
   const void* points;  // [batch, m, d] roots, used as given
@@ -28,10 +26,6 @@ struct SearchDepthArgs {
   unsigned long long max_nodes;
   int m, d, host, max_depth, stack_nodes, lanes, lds_stride;
 };
-
-// LDS words per lane: parent, child, the shift coefficients c and sort_compact's row scratch; odd, so that the lanes'
-// private slices start in different banks
-inline int search_depth_lds_stride(int m, int d) { return (2 * m * d + 2 * d) | 1; }
 
 // HOST: the host code, one instantiation per host (a.host is not read)
 template <typename T, int HOST>
@@ -46,8 +40,6 @@ __global__ void __launch_bounds__(kWave) search_depth_kernel(SearchDepthArgs a) 
   const T* src = static_cast<const T*>(a.points) + root * (size_t)n;
   T* stk = static_cast<T*>(a.stack) + root * (size_t)a.stack_nodes * (size_t)n;
   int32_t* sdep = a.stack_depth + root * (size_t)a.stack_nodes;
-  const T limit = sizeof(T) == 4 ? (T)16777216.0 : (T)9007199254740992.0;  // 2^24 / 2^53: integers stay exact below
-  const unsigned flags = HK_SEM_LIST | HK_FLAG_COMPACT_SORTED;
 
   if (num_points(src, m, d) < 2) {
     if (lane == 0) {
@@ -61,10 +53,7 @@ __global__ void __launch_bounds__(kWave) search_depth_kernel(SearchDepthArgs a) 
   if (lane == 0) sdep[0] = 0;
   __syncthreads();
 
-  T* par = lds + (size_t)lane * a.lds_stride;
-  T* chd = par + n;
-  T* c = chd + n;
-  T* row = c + d;
+  const LaneSlice<T> sl(lds, lane, a.lds_stride, m, d);
   int top = 1;  // wave-uniform from here on
   unsigned long long nodes = 0;
   int status = 0;
@@ -74,7 +63,8 @@ __global__ void __launch_bounds__(kWave) search_depth_kernel(SearchDepthArgs a) 
     if ((unsigned long long)k > a.max_nodes - nodes) k = (int)(a.max_nodes - nodes);
     const int base = top - k;
     __syncthreads();  // the previous iteration's reads of the parent slices are done
-    // pop: the k top entries are contiguous, copied by the whole wave
+    // pop: the k top entries are contiguous, copied by the whole wave.  This loop and the push are written out rather
+    // than wave_copy_states: through the helper the 2 048-root batch of scripts/probe_search_depth.py ran 1.6 % slower.
     for (int e = lane; e < k * n; e += kWave) {
       const int s = e / n;
       lds[(size_t)s * a.lds_stride + (e - s * n)] = stk[(size_t)base * n + e];
@@ -90,30 +80,18 @@ __global__ void __launch_bounds__(kWave) search_depth_kernel(SearchDepthArgs a) 
     const bool expand = active && !capped;
     uint32_t subset = 0;
     if (expand) {
-      if (HOST == HK_HOST_ZEILLINGER) {
-        const int cls = zeillinger_list_game(par, m, d);  // >= 0: a visited node holds >= 2 points
-        subset = decode_class(cls < 0 ? 0 : cls, d);
-      } else if (HOST == HK_HOST_ALL_COORD) {
-        subset = (1u << d) - 1u;
-      } else {
-        // -1 (a zero row, or |U| < 2 for WeakSpivakovsky) only at a root that is not Newton-reduced: no children
-        const int cls = host_list_game(par, m, d, HOST);
-        subset = cls < 0 ? 0u : decode_class(cls, d);
-      }
-      for (int j = 0; j < d; ++j) c[j] = ((subset >> j) & 1u) ? (T)1 : (T)0;
+      // -1 (a zero row, or |U| < 2 for WeakSpivakovsky) only at a root that is not Newton-reduced: no children.  Never
+      // for Zeillinger, whose -1 needs fewer than 2 points, which no visited node holds.  All coordinates skips the
+      // class round trip: its decode loop costs the float64 instance an occupancy level.
+      const int cls = host_class_game<T, HOST>(sl.par, m, d);
+      subset = HOST == HK_HOST_ALL_COORD ? (1u << d) - 1u : cls < 0 ? 0u : decode_class(cls, d);
+      for (int j = 0; j < d; ++j) sl.c[j] = ((subset >> j) & 1u) ? (T)1 : (T)0;
     }
     bool stop = false;
     for (int j = 0; j < d; ++j) {
       bool live = expand && ((subset >> j) & 1u);
       bool inexact = false;
-      if (live) {
-        for (int e = 0; e < n; ++e) chd[e] = par[e];
-        shift_game(chd, m, d, c, j, (T)-1, flags);
-        for (int i = 0; i < m; ++i) inexact |= chd[i * d + j] >= limit;
-        newton_game(chd, m, d, (T)-1, flags);
-        sort_compact_game(chd, m, d, (T)-1, row);
-        live = num_points(chd, m, d) >= 2;
-      }
+      if (live) live = expand_child(sl, m, d, j, inexact) >= 2;
       if (__ballot(inexact)) {
         status |= HK_SEARCH_INEXACT;
         stop = true;
@@ -128,7 +106,7 @@ __global__ void __launch_bounds__(kWave) search_depth_kernel(SearchDepthArgs a) 
         break;
       }
       if (live) {
-        const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+        const int rank = lane_rank(b);
         slot_lane[rank] = lane;
         sdep[top + rank] = dep + 1;
       }

@@ -25,11 +25,9 @@
 // renumbering runs over recorded batches or up a parent chain of strictly decreasing record indices.
 #pragma once
 
-#include "hk_hosts.h"
+#include "hk_search_wave.h"
 
 namespace hk {
-
-constexpr int kSearchTreeLdsBytes = 64 * 1024;  // dynamic LDS per workgroup, as hk_search_depth
 
 struct SearchTreeArgs {
   const void* points;  // [batch, m, d] roots, used as given
@@ -54,10 +52,6 @@ inline uint64_t search_tree_int_words(int max_nodes, int stack_nodes) {
   return 10ull * (uint64_t)max_nodes + 1ull + (uint64_t)stack_nodes;
 }
 
-// LDS words per lane: parent, child, the shift coefficients c and sort_compact's row scratch (odd: lanes start in
-// different banks)
-inline int search_tree_lds_stride(int m, int d) { return (2 * m * d + 2 * d) | 1; }
-
 // The host's list for one game, in the reference's order.  Zeillinger and ZeillingerLex return [argmin v, argmax v]
 // of the chosen pair (host.py:90-95, :116-127), or [0, 1] when they coincide: `order` packs the axes 3 bits each.  The
 // other hosts' lists are ascending.  Returns the class id of the set, -1 for no list (nc = 0).
@@ -72,24 +66,12 @@ __device__ inline int host_order_game(const T* p, int m, int d, uint32_t& order,
     nc = 2;
     return encode_mask((1u << (r >> 3)) | (1u << (r & 7)));
   }
-  const int cls = HOST == HK_HOST_ALL_COORD ? encode_mask((1u << d) - 1u) : host_list_game(p, m, d, HOST);
+  const int cls = host_class_game<T, HOST>(p, m, d);
   if (cls < 0) return -1;
   const uint32_t sub = decode_class(cls, d);
   for (int j = 0; j < d; ++j)
     if ((sub >> j) & 1u) order |= (uint32_t)j << (3 * nc++);
   return cls;
-}
-
-// exclusive prefix over the lanes of a per-lane count in 0..6, and the wave's total
-__device__ inline int lane_prefix(int v, int& total) {
-  int pre = 0;
-  total = 0;
-  for (int j = 0; j < 6; ++j) {
-    const unsigned long long b = __ballot(v > j);
-    pre += (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-    total += (int)__popcll(b);
-  }
-  return pre;
 }
 
 // HOST: the host code, one instantiation per host
@@ -119,8 +101,6 @@ __global__ void __launch_bounds__(kWave) search_tree_kernel(SearchTreeArgs a) {
   int32_t* bstart = rid + M;   // M + 1: batch b holds the records [bstart[b], bstart[b+1])
   int32_t* stk = bstart + M + 1;
   const size_t out0 = root * (size_t)M;
-  const T limit = sizeof(T) == 4 ? (T)16777216.0 : (T)9007199254740992.0;  // 2^24 / 2^53: integers stay exact below
-  const unsigned flags = HK_SEM_LIST | HK_FLAG_COMPACT_SORTED;
   const long long L = a.expand_limit < 0 ? LLONG_MAX - 1 : a.expand_limit;
 
   // the root: record 0, batch 0
@@ -135,20 +115,15 @@ __global__ void __launch_bounds__(kWave) search_tree_kernel(SearchTreeArgs a) {
   int top = np0 >= 2 && a.max_depth > 0 ? 1 : 0;  // wave-uniform from here on
   int nrec = 1, nb = 1;
 
-  T* par = lds + (size_t)lane * a.lds_stride;
-  T* chd = par + n;
-  T* c = chd + n;
-  T* row = c + d;
+  const LaneSlice<T> sl(lds, lane, a.lds_stride, m, d);
   for (long long it = 0; top > 0 && it <= L; ++it) {
     int k = top < a.lanes ? top : a.lanes;
     if ((long long)k > L + 1 - it) k = (int)(L + 1 - it);
     __syncthreads();  // the previous iteration's reads of slot_* and the parent slices are done
     if (lane < k) slot_rec[lane] = stk[top - 1 - lane];  // lane 0: the smallest pending preorder number
     __syncthreads();
-    for (int e = lane; e < k * n; e += kWave) {
-      const int s = e / n;
-      lds[(size_t)s * a.lds_stride + (e - s * n)] = rst[(size_t)slot_rec[s] * n + (e - s * n)];
-    }
+    wave_copy_states(k, n, lane, [&](int s) { return lds + (size_t)s * a.lds_stride; },
+                     [&](int s) { return rst + (size_t)slot_rec[s] * n; });
     const bool active = lane < k;
     const int me = active ? slot_rec[lane] : -1;
     const int dep = active ? rdep[me] : 0;
@@ -156,7 +131,7 @@ __global__ void __launch_bounds__(kWave) search_tree_kernel(SearchTreeArgs a) {
     __syncthreads();
     uint32_t order = 0;
     int nc = 0, cls = -1;
-    if (active) cls = host_order_game<T, HOST>(par, m, d, order, nc);
+    if (active) cls = host_order_game<T, HOST>(sl.par, m, d, order, nc);
     int tot;
     const int rbase = nrec + lane_prefix(nc, tot);  // this lane's first child record
     if (tot > M - nrec) {
@@ -167,7 +142,7 @@ __global__ void __launch_bounds__(kWave) search_tree_kernel(SearchTreeArgs a) {
       rcls[me] = cls;
       rfirst[me] = nc ? rbase : -1;
       const uint32_t sub = cls < 0 ? 0u : decode_class(cls, d);
-      for (int j = 0; j < d; ++j) c[j] = ((sub >> j) & 1u) ? (T)1 : (T)0;
+      for (int j = 0; j < d; ++j) sl.c[j] = ((sub >> j) & 1u) ? (T)1 : (T)0;
     }
     uint32_t push = 0;  // bit j: the lane's j-th child may be expanded
     bool stop = false;
@@ -176,12 +151,7 @@ __global__ void __launch_bounds__(kWave) search_tree_kernel(SearchTreeArgs a) {
       bool inexact = false;
       if (live) {
         const int ax = (int)((order >> (3 * j)) & 7u);
-        for (int e = 0; e < n; ++e) chd[e] = par[e];
-        shift_game(chd, m, d, c, ax, (T)-1, flags);
-        for (int i = 0; i < m; ++i) inexact |= chd[i * d + ax] >= limit;
-        newton_game(chd, m, d, (T)-1, flags);
-        sort_compact_game(chd, m, d, (T)-1, row);
-        const int np = num_points(chd, m, d);
+        const int np = expand_child(sl, m, d, ax, inexact);
         const int r = rbase + j;
         rpar[r] = me, rchd[r] = j, rax[r] = ax, rdep[r] = dep + 1, rnp[r] = np, rcls[r] = -1, rfirst[r] = -1,
         rsize[r] = 1;
@@ -196,15 +166,13 @@ __global__ void __launch_bounds__(kWave) search_tree_kernel(SearchTreeArgs a) {
       const int cnt = (int)__popcll(b);
       if (cnt == 0) break;  // j >= nc on every lane
       if (live) {
-        const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+        const int rank = lane_rank(b);
         slot_lane[rank] = lane;
         slot_dst[rank] = rbase + j;
       }
       __syncthreads();
-      for (int e = lane; e < cnt * n; e += kWave) {
-        const int s = e / n;
-        rst[(size_t)slot_dst[s] * n + (e - s * n)] = lds[(size_t)slot_lane[s] * a.lds_stride + n + (e - s * n)];
-      }
+      wave_copy_states(cnt, n, lane, [&](int s) { return rst + (size_t)slot_dst[s] * n; },
+                       [&](int s) { return lds + (size_t)slot_lane[s] * a.lds_stride + n; });
       __syncthreads();
     }
     if (stop) break;
@@ -304,7 +272,7 @@ __global__ void __launch_bounds__(kWave) search_tree_kernel(SearchTreeArgs a) {
       slot_dst[lane] = id;
       __syncthreads();
       const int cn = nrec - cb < kWave ? nrec - cb : kWave;
-      for (int e = lane; e < cn * n; e += kWave) {
+      for (int e = lane; e < cn * n; e += kWave) {  // wave_copy_states, but only the records that have an id
         const int s = e / n;
         if (slot_dst[s] >= 0) sout[(out0 + (size_t)slot_dst[s]) * n + (e - s * n)] = rst[(size_t)(cb + s) * n + (e - s * n)];
       }

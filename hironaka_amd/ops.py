@@ -681,13 +681,9 @@ def _search_roots(points: torch.Tensor) -> torch.Tensor:
     return pts
 
 
-def search_depth(points: torch.Tensor, host: str, *, max_depth: int, max_nodes: int,
-                 stack_nodes: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """Exhaustive worst-case game length under a fixed host, one tree per root (hironaka/util/search.py:9-32,
-    hk_search_depth).  points: [B, m, d] float32/float64 roots in list semantics, used as given (rows with
-    coordinate 0 >= 0 are points; padding rows may sit anywhere).  host: a key of SEARCH_HOSTS.
-    Returns (depth int32[B], nodes int64[B], status int32[B]); status 0 = finished and exact, else an OR of
-    HK_SEARCH_* bits (the numbers are then bounds, see include/hironaka_hip.h)."""
+def _search_checks(points: torch.Tensor, host: str, max_depth: int, max_nodes: int, stack_nodes: int, node_bits: int,
+                   expand_limit: Optional[int] = None) -> torch.Tensor:
+    """the argument checks of search_depth / search_game_tree (max_nodes < 2^node_bits); returns the roots"""
     _require_device(points, "points")
     if points.dtype not in (torch.float32, torch.float64):
         raise TypeError(f"points must be float32 or float64. Got {points.dtype}.")
@@ -695,31 +691,48 @@ def search_depth(points: torch.Tensor, host: str, *, max_depth: int, max_nodes: 
         raise ValueError(f"points must be [B, max_points, dim]. Got shape {tuple(points.shape)}.")
     if host not in SEARCH_HOSTS:
         raise ValueError(f"host must be one of {sorted(SEARCH_HOSTS)}. Got {host!r}.")
-    if not (0 <= max_depth < 2 ** 31 and 1 <= max_nodes < 2 ** 63 and 1 <= stack_nodes < 2 ** 31):
-        raise ValueError(f"need 0 <= max_depth < 2^31, 1 <= max_nodes < 2^63, 1 <= stack_nodes < 2^31. Got "
+    if expand_limit is not None and not 0 <= expand_limit < 2 ** 63:
+        raise ValueError(f"expand_limit must be None or in [0, 2^63). Got {expand_limit}.")
+    if not (0 <= max_depth < 2 ** 31 and 1 <= max_nodes < 2 ** node_bits and 1 <= stack_nodes < 2 ** 31):
+        raise ValueError(f"need 0 <= max_depth < 2^31, 1 <= max_nodes < 2^{node_bits}, 1 <= stack_nodes < 2^31. Got "
                          f"{max_depth}, {max_nodes}, {stack_nodes}.")
-    pts = _search_roots(points)
+    return _search_roots(points)
+
+
+def _search_launch(fn, name: str, pts: torch.Tensor, host: str, params: tuple, per_root: int, outs: list) -> list:
+    """fn(points, batch, m, d, dtype, host, *params, workspace, workspace_bytes, *outs, stream) over the roots, in
+    chunks that share one workspace of at most _SEARCH_WORKSPACE_BYTES.  per_root == 0: the C entry refuses the
+    arguments; one call with batch 1 and no buffers raises its status.  outs: (shape, dtype, fill or None) of each
+    output, batch first, or None for an output not wanted; they are made once the arguments pass, and returned."""
     b, m, d = pts.shape
-    dt = _TORCH2HK[pts.dtype]
-    L = lib()
-    per_root = L.hk_search_depth_workspace_bytes(1, m, d, dt, stack_nodes)
+    head = (m, d, _TORCH2HK[pts.dtype], SEARCH_HOSTS[host], *params)
     if per_root == 0:
-        check(L.hk_search_depth(None, 1, m, d, dt, SEARCH_HOSTS[host], max_depth, max_nodes, stack_nodes, None, 0,
-                                None, None, None, None), "hk_search_depth")
-    depth = torch.empty(b, dtype=torch.int32, device=pts.device)
-    nodes = torch.empty(b, dtype=torch.int64, device=pts.device)
-    status = torch.empty(b, dtype=torch.int32, device=pts.device)
+        check(fn(None, 1, *head, None, 0, *([None] * len(outs)), None), name)
+    outs = [None if o is None else torch.empty(o[0], dtype=o[1], device=pts.device) if o[2] is None else
+            torch.full(o[0], o[2], dtype=o[1], device=pts.device) for o in outs]
     chunk = max(1, min(b, _SEARCH_WORKSPACE_BYTES // max(per_root, 1)))
     with torch.cuda.device(pts.device):
         ws = torch.empty(per_root * chunk if b else 0, dtype=torch.uint8, device=pts.device)
         for lo in range(0, b, chunk):
-            n = min(chunk, b - lo)
-            check(L.hk_search_depth(pts[lo].data_ptr(), n, m, d, dt, SEARCH_HOSTS[host], max_depth, max_nodes,
-                                    stack_nodes, ws.data_ptr(), ws.numel(), depth[lo].data_ptr(),
-                                    nodes[lo].data_ptr(), status[lo].data_ptr(), _stream(pts)), "hk_search_depth")
-        if b == 0:
-            check(L.hk_search_depth(pts.data_ptr(), 0, m, d, dt, SEARCH_HOSTS[host], max_depth, max_nodes,
-                                    stack_nodes, None, 0, None, None, None, _stream(pts)), "hk_search_depth")
+            ptrs = [None if t is None else t[lo].data_ptr() for t in outs]
+            check(fn(pts[lo].data_ptr(), min(chunk, b - lo), *head, ws.data_ptr(), ws.numel(), *ptrs, _stream(pts)),
+                  name)
+    return outs
+
+
+def search_depth(points: torch.Tensor, host: str, *, max_depth: int, max_nodes: int,
+                 stack_nodes: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Exhaustive worst-case game length under a fixed host, one tree per root (hironaka/util/search.py:9-32,
+    hk_search_depth).  points: [B, m, d] float32/float64 roots in list semantics, used as given (rows with
+    coordinate 0 >= 0 are points; padding rows may sit anywhere).  host: a key of SEARCH_HOSTS.
+    Returns (depth int32[B], nodes int64[B], status int32[B]); status 0 = finished and exact, else an OR of
+    HK_SEARCH_* bits (the numbers are then bounds, see include/hironaka_hip.h)."""
+    pts = _search_checks(points, host, max_depth, max_nodes, stack_nodes, 63)
+    b, m, d = pts.shape
+    per_root = lib().hk_search_depth_workspace_bytes(1, m, d, _TORCH2HK[pts.dtype], stack_nodes)
+    outs = [((b,), torch.int32, None), ((b,), torch.int64, None), ((b,), torch.int32, None)]
+    depth, nodes, status = _search_launch(lib().hk_search_depth, "hk_search_depth", pts, host,
+                                          (max_depth, max_nodes, stack_nodes), per_root, outs)
     return depth, nodes, status
 
 
@@ -732,40 +745,11 @@ def search_game_tree(points: torch.Tensor, host: str, *, expand_limit: Optional[
     [B, max_nodes], states [B, max_nodes, m, d] of the roots' dtype (None unless ``states``), count int32 [B] and
     status int32 [B].  Slots from count on hold -1.  A status other than 0 / HK_SEARCH_ROOT_ENDED /
     HK_SEARCH_DEPTH_LIMIT leaves only count and status meaningful (include/hironaka_hip.h)."""
-    _require_device(points, "points")
-    if points.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"points must be float32 or float64. Got {points.dtype}.")
-    if points.dim() != 3:
-        raise ValueError(f"points must be [B, max_points, dim]. Got shape {tuple(points.shape)}.")
-    if host not in SEARCH_HOSTS:
-        raise ValueError(f"host must be one of {sorted(SEARCH_HOSTS)}. Got {host!r}.")
-    if expand_limit is not None and not 0 <= expand_limit < 2 ** 63:
-        raise ValueError(f"expand_limit must be None or in [0, 2^63). Got {expand_limit}.")
-    if not (0 <= max_depth < 2 ** 31 and 1 <= max_nodes < 2 ** 31 and 1 <= stack_nodes < 2 ** 31):
-        raise ValueError(f"need 0 <= max_depth < 2^31, 1 <= max_nodes < 2^31, 1 <= stack_nodes < 2^31. Got "
-                         f"{max_depth}, {max_nodes}, {stack_nodes}.")
-    pts = _search_roots(points)
+    pts = _search_checks(points, host, max_depth, max_nodes, stack_nodes, 31, expand_limit)
     b, m, d = pts.shape
-    dt = _TORCH2HK[pts.dtype]
     lim = -1 if expand_limit is None else int(expand_limit)
-    L = lib()
-    per_root = L.hk_search_game_tree_workspace_bytes(1, m, d, dt, max_nodes, stack_nodes)
-    if per_root == 0:
-        check(L.hk_search_game_tree(None, 1, m, d, dt, SEARCH_HOSTS[host], lim, max_depth, max_nodes, stack_nodes,
-                                    None, 0, *([None] * 9), None), "hk_search_game_tree")
-    dev = pts.device
-    ints = [torch.full((b, max_nodes), -1, dtype=torch.int32, device=dev) for _ in range(6)]
-    st = torch.full((b, max_nodes, m, d), -1, dtype=pts.dtype, device=dev) if states else None
-    count = torch.zeros(b, dtype=torch.int32, device=dev)
-    status = torch.zeros(b, dtype=torch.int32, device=dev)
-    chunk = max(1, min(b, _SEARCH_WORKSPACE_BYTES // max(per_root, 1)))
-    with torch.cuda.device(dev):
-        ws = torch.empty(per_root * chunk if b else 0, dtype=torch.uint8, device=dev)
-        for lo in range(0, b, chunk):
-            n = min(chunk, b - lo)
-            outs = [t[lo].data_ptr() for t in ints] + [st[lo].data_ptr() if states else None]
-            check(L.hk_search_game_tree(pts[lo].data_ptr(), n, m, d, dt, SEARCH_HOSTS[host], lim, max_depth,
-                                        max_nodes, stack_nodes, ws.data_ptr(), ws.numel(), *outs,
-                                        count[lo].data_ptr(), status[lo].data_ptr(), _stream(pts)),
-                  "hk_search_game_tree")
-    return (*ints, st, count, status)
+    per_root = lib().hk_search_game_tree_workspace_bytes(1, m, d, _TORCH2HK[pts.dtype], max_nodes, stack_nodes)
+    outs = ([((b, max_nodes), torch.int32, -1)] * 6 + [((b, max_nodes, m, d), pts.dtype, -1) if states else None] +
+            [((b,), torch.int32, 0)] * 2)
+    return tuple(_search_launch(lib().hk_search_game_tree, "hk_search_game_tree", pts, host,
+                                (lim, max_depth, max_nodes, stack_nodes), per_root, outs))

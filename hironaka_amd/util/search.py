@@ -66,6 +66,20 @@ def _roots(points, dtype: Optional[torch.dtype]) -> torch.Tensor:
     return t
 
 
+def _one_root(points, fn: str, why: str = "") -> torch.Tensor:
+    # the root of search_depth / search_tree, a batch of one; fn + "s" takes a batch
+    roots = _roots(points, None)
+    if roots.shape[0] != 1:
+        raise ValueError(f"{fn} searches one root{why}; got a batch of {roots.shape[0]}: use {fn}s")
+    return roots
+
+
+def _limit_message(fn: str, status: int, ignore: int = 0) -> Optional[str]:
+    # the limits a status names, None when there are none
+    hit = [name for bit, name in _LIMITS if status & bit & ~ignore]
+    return f"{fn} did not finish exactly (status {status}): limited by {', '.join(hit)}" if hit else None
+
+
 def search_depths(points, host, *, max_depth: int = DEFAULT_MAX_DEPTH, max_nodes: int = DEFAULT_MAX_NODES,
                   stack_nodes: int = DEFAULT_BATCH_STACK_NODES, dtype: Optional[torch.dtype] = None) -> SearchDepthResult:
     """``search_depth`` for a batch of roots [B, m, d] (tensor, HipPoints or nested lists); the reference asserts a
@@ -82,20 +96,16 @@ def search_depth(points, host, debug=False, *, max_depth: Optional[int] = None,
     ``host``.  ``points``: a HipPoints of batch 1, a [m, d] or [1, m, d] tensor, or nested lists.  Raises
     RuntimeError naming the limit when the search did not finish exactly, ValueError for a root with fewer than
     2 points (the reference asserts).  ``debug`` is accepted for the reference's signature and prints nothing."""
-    roots = _roots(points, None)
-    if roots.shape[0] != 1:
-        raise ValueError(f"search_depth searches one root (the reference asserts batch_size == 1); got a batch of "
-                         f"{roots.shape[0]}: use search_depths")
+    roots = _one_root(points, "search_depth", " (the reference asserts batch_size == 1)")
     res = search_depths(roots, host, max_depth=DEFAULT_MAX_DEPTH if max_depth is None else max_depth,
                         max_nodes=DEFAULT_MAX_NODES if max_nodes is None else max_nodes,
                         stack_nodes=DEFAULT_STACK_NODES if stack_nodes is None else stack_nodes)
     status = int(res.status[0])
     if status & A.HK_SEARCH_ROOT_ENDED:
         raise ValueError("the root has fewer than 2 points: the game has already ended")
-    hit = [name for bit, name in _LIMITS if status & bit]
-    if hit:
-        raise RuntimeError(f"search_depth did not finish exactly (status {status}): limited by {', '.join(hit)}; "
-                           f"depth >= {int(res.depth[0])}, nodes >= {int(res.nodes[0])}")
+    msg = _limit_message("search_depth", status)
+    if msg:
+        raise RuntimeError(f"{msg}; depth >= {int(res.depth[0])}, nodes >= {int(res.nodes[0])}")
     return int(res.depth[0])
 
 
@@ -159,9 +169,7 @@ def search_tree(points, tree, curr_node, host, max_size=100, *, max_depth: Optio
     The tree is built on the GPU first and handed over afterwards; RuntimeError names the limit when it did not
     fit (``max_nodes``, ``stack_nodes``) or left the exact integer range.  A node's ``data`` is a TreeNodeData."""
     name = _host_name(host)
-    roots = _roots(points, None)
-    if roots.shape[0] != 1:
-        raise ValueError(f"search_tree searches one root; got a batch of {roots.shape[0]}: use search_trees")
+    roots = _one_root(points, "search_tree")
     s0 = tree.size()
     if max_size is not None and s0 > max_size:
         return None
@@ -173,9 +181,9 @@ def search_tree(points, tree, curr_node, host, max_size=100, *, max_depth: Optio
     status, count = int(status[0]), int(count[0])
     if status & A.HK_SEARCH_ROOT_ENDED:
         return None
-    hit = [name for bit, name in _LIMITS if status & bit and bit != A.HK_SEARCH_DEPTH_LIMIT]
-    if hit:
-        raise RuntimeError(f"search_tree did not finish exactly (status {status}): limited by {', '.join(hit)}")
+    msg = _limit_message("search_tree", status, ignore=A.HK_SEARCH_DEPTH_LIMIT)
+    if msg:
+        raise RuntimeError(msg)
     par = parent[0, :count].tolist()
     states = st[0, :count].cpu().numpy()
     ident = [curr_node] + [s0 + j - 1 for j in range(1, count)]
