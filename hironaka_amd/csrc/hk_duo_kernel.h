@@ -25,7 +25,7 @@ namespace hk {
 constexpr int kDuoGames = kWave / 2;
 
 // the partner lane's value: DPP quad_perm [1, 0, 3, 2]
-__device__ __forceinline__ int duo_other_i(int v) { return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true); }
+__device__ __forceinline__ int duo_other_i(int v) { return qperm_i<0xB1>(v); }
 __device__ __forceinline__ float duo_other(float v) { return __int_as_float(duo_other_i(__float_as_int(v))); }
 
 template <int M, int D>
@@ -167,7 +167,7 @@ __device__ __forceinline__ uint32_t duo_scatter(const float (&q)[CH * D], float*
     }
     return true;
   });
-  return alive | (uint32_t)duo_other_i((int)alive);
+  return lanes_or<2>(alive);
 }
 
 // one pass over the lane's HALF of the game's image (rows h * ceil(M / 2) ...): bitmask of the fully available rows of
@@ -198,82 +198,10 @@ __device__ __forceinline__ void duo_scan_half(const float* mine, float fill, int
     mask |= (ge && valid) ? (1u << r) : 0u;
   }
   mask <<= i0;
-  live = mask | (uint32_t)duo_other_i((int)mask);
+  live = lanes_or<2>(mask);
 }
 
 // ---- the stages on NB slots per lane ----------------------------------------------------------------------
-template <int CH, int D, int NB, bool BIN = false>
-__device__ __forceinline__ void d_reposition(float (&q)[CH * D], unsigned flags) {
-  const bool jax_sem = (flags & HK_SEM_MASK) == HK_SEM_JAX;
-  if constexpr (BIN) {
-    // Rollouts with in-kernel 0/1 subsets: every coordinate is >= +0 or the +inf of a hole (guarded at entry; sums,
-    // differences against the column minimum and quotients keep it so, and x - x is +0), so the float order is the
-    // unsigned order of the bit patterns: v_min_u32 with the partner's value as a DPP operand -- the float minimum of
-    // values of unknown origin costs a canonicalising v_max x, x per operand (5 instructions per column at one slot
-    // per lane, now 1).  A column without live rows subtracts 0; a minimum of 0 subtracts itself (JAX and torch
-    // semantics agree there).
-    uint32_t mb[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) mb[k] = __float_as_uint(q[k]);
-#pragma unroll
-    for (int r = 1; r < NB; ++r)
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        const uint32_t w = __float_as_uint(q[r * D + k]);
-        mb[k] = w < mb[k] ? w : mb[k];
-      }
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      const uint32_t o = (uint32_t)duo_other_i((int)mb[k]);
-      mb[k] = o < mb[k] ? o : mb[k];
-      // (a column without live rows -- an empty game -- subtracts the largest finite float: +inf stays +inf, one
-      // v_min_u32 where the test for +inf took a compare and a select)
-      const float sub = __uint_as_float(mb[k] < 0x7F7FFFFFu ? mb[k] : 0x7F7FFFFFu);
-#pragma unroll
-      for (int r = 0; r < NB; ++r) q[r * D + k] = q[r * D + k] - sub;
-    }
-    return;
-  }
-  float mn[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) mn[k] = INFINITY;
-#pragma unroll
-  for (int r = 0; r < NB; ++r)
-#pragma unroll
-    for (int k = 0; k < D; ++k) mn[k] = hk_fmin(mn[k], q[r * D + k]);
-  float sub[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    mn[k] = hk_fmin(mn[k], duo_other(mn[k]));
-    sub[k] = (mn[k] < INFINITY && (!jax_sem || mn[k] > 0.0f)) ? mn[k] : 0.0f;  // see b_reposition
-  }
-#pragma unroll
-  for (int r = 0; r < NB; ++r)
-#pragma unroll
-    for (int k = 0; k < D; ++k) q[r * D + k] = q[r * D + k] - sub[k];
-}
-
-template <int CH, int D, int NB>
-__device__ __forceinline__ void d_rescale(float (&q)[CH * D], unsigned flags) {
-  const bool jax_sem = (flags & HK_SEM_MASK) == HK_SEM_JAX;
-  float mx = -1.0f;
-#pragma unroll
-  for (int r = 0; r < NB; ++r) {
-    const bool live = q[r * D] < INFINITY;
-#pragma unroll
-    for (int k = 0; k < D; ++k) mx = hk_fmax(mx, live ? q[r * D + k] : -1.0f);
-  }
-  mx = hk_fmax(mx, duo_other(mx));
-  const bool skip = jax_sem ? (mx <= 1e-8f) : (mx < 0.0f);
-  const float div = (skip || mx == 0.0f) ? 1.0f : mx;
-#pragma unroll
-  for (int r = 0; r < NB; ++r) {
-    const bool live = q[r * D] < INFINITY;
-#pragma unroll
-    for (int k = 0; k < D; ++k) q[r * D + k] = live ? q[r * D + k] / div : INFINITY;
-  }
-}
-
 // _jax_ops.py:15-73 across the pair.  Own rows i < j as in b_newton (rank 2i+h < 2j+h).  Cross pairs (mine a,
 // partner's b) with a <= b: my rank 2a+h, the partner's 2b+1-h, so my row is the earlier one unless a == b and
 // h == 1.  With t = max_k(mine - other), u = min_k(mine - other):
@@ -337,18 +265,19 @@ __device__ __forceinline__ int d_stages(float (&q)[CH * D], const float (&c)[D],
     if constexpr (BIN) b_shift_mask<CH, D, NB>(q, cmask, axis, np, flags);
     else b_shift<CH, D, NB>(q, c, axis, np, flags);
   }
-  if (stages & HK_STAGE_REPOSITION) d_reposition<CH, D, NB, BIN>(q, flags);
+  if (stages & HK_STAGE_REPOSITION) reposition<2, CH, D, NB, BIN>(q, flags);
   if (stages & HK_STAGE_NEWTON) d_newton<CH, D, NB>(q, h);
-  if (stages & HK_STAGE_RESCALE) d_rescale<CH, D, NB>(q, flags);
-  int n = 0;
-#pragma unroll
-  for (int r = 0; r < NB; ++r) n += (q[r * D] < INFINITY) ? 1 : 0;
-  return n + duo_other_i(n);
+  if (stages & HK_STAGE_RESCALE) rescale<2, CH, D, NB>(q, flags);
+  return live_rows<2, CH, D, NB>(q);
 }
+
+struct DuoLadder {  // slots per lane: 1..6, 8, 10, ...
+  static constexpr int next_bucket(int nb) { return nb < 6 ? nb + 1 : nb + 2; }
+};
 
 template <int CH, int D, int NB, bool BIN = false>
 struct DuoStagesFor {
-  static constexpr int kNext = (NB < 6) ? NB + 1 : NB + 2;
+  static constexpr int kNext = DuoLadder::next_bucket(NB);
   static __device__ __forceinline__ int run(float (&q)[CH * D], int smax, const float (&c)[D], int axis, int np,
                                             int h, unsigned flags, unsigned stages, uint32_t cmask = 0) {
     if constexpr (NB >= CH) {
@@ -397,18 +326,6 @@ __device__ __forceinline__ void duo_scatter_ranked(const float (&q)[CH * D], flo
     return true;
   });
 }
-
-// The buckets of slots per lane (1..6, 8, 10, ...) from the top down: f(NB, LO) for every bucket NB with the next
-// smaller one LO (0 below the first)
-template <int NB>
-struct DuoLevels {
-  static constexpr int kLo = (NB <= 6) ? NB - 1 : NB - 2;
-  template <typename F>
-  static __device__ __forceinline__ void run(F&& f) {
-    f(std::integral_constant<int, NB>{}, std::integral_constant<int, kLo>{});
-    if constexpr (kLo >= 1) DuoLevels<kLo>::run(f);
-  }
-};
 
 // The policy stream of a pair: Philox block b (steps 4b .. 4b + 3, hk_common.h policy_words) is computed by the lane
 // with (b & 1) == h only -- one Philox per lane per EIGHT steps -- and its word reaches the partner through DPP.
@@ -824,7 +741,7 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
     // the action byte of step t, requested one step ahead: the LDS round trip (it opened every step: ds_read, wait)
     // runs behind the previous step's arithmetic
     uint32_t a_next = ZEIL ? 0u : pol[(int)(step0 + (uint32_t)t - (pol_b0 << 2)) * kDuoGames + gi];
-    DuoLevels<CH>::run([&](auto nbc, auto loc) {
+    Levels<DuoLadder, CH>::run([&](auto nbc, auto loc) {
       constexpr int NB = decltype(nbc)::value, LO = decltype(loc)::value;
 #ifndef HK_NO_SETPRIO
       // The launch ends with its slowest waves -- the ones that start in a wide bucket or run many steps -- and the two
@@ -1002,7 +919,7 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
   if (kEndSort && end_sort) {
     int rank[CH];
     duo_ranks_first<CH, D>(q, smax, rank);
-    if (rescale_pending) d_rescale<CH, D, CH>(q, flags);
+    if (rescale_pending) rescale<2, CH, D, CH>(q, flags);
     duo_scatter_ranked<CH, D>(q, mine, rank, smax);
   } else {
     duo_scatter<M, CH, D>(q, mine, gmask, smax, h);

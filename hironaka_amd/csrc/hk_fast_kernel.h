@@ -602,7 +602,7 @@ __global__ __launch_bounds__(kWave, ((MODE == kModeRolloutRec || M * D > 64) ? 1
         const uint32_t wend_abs = (pol_b0 + (uint32_t)kFastPreBlocks) << 2;  // last step (exclusive) the window covers
         tw = (wend_abs - step0 < (uint32_t)nsteps) ? (int)(wend_abs - step0) : nsteps;
       }
-      RowLevels<G::C>::run([&](auto nbc, auto loc) {
+      Levels<RowLadder, G::C>::run([&](auto nbc, auto loc) {
         constexpr int NB = decltype(nbc)::value, LO = decltype(loc)::value;
         while (t < tw && (nmax > LO || LO == 0) && !stop) {  // (a wave of empty games has nmax 0: the last loop's)
           int axis, cls;
@@ -744,7 +744,7 @@ __global__ __launch_bounds__(kWave, ((MODE == kModeRolloutRec || M * D > 64) ? 1
   } else if (kEndSort && end_sort) {
     int rank[G::C];
     feature_ranks<G::C, D, kKeyFirst>(q, nmax, rank);
-    if (rescale_pending) c_rescale<G::C, D>(q, nmax, flags);
+    if (rescale_pending) rescale_upto<1, G::C, D>(q, nmax, flags);
     scatter_ranked<G::C, D>(q, mine, rank, nmax);
   } else {
     scatter_rows<M, G::C, D>(q, mine, gmask, nmax);

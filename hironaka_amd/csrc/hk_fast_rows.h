@@ -39,6 +39,61 @@ __device__ inline int mask_pop(unsigned long long m) { return __popcll(m); }
 __device__ inline int mask_first(uint32_t m) { return __ffs(m) - 1; }
 __device__ inline int mask_first(unsigned long long m) { return __ffsll(m) - 1; }
 
+// ---- the L lanes of one game (L = 1, 2 or 4 neighbouring lanes) ---------------------------------------------------
+// qperm: another lane's value inside the quad (DPP quad_perm CTRL; 0xB1 = [1,0,3,2] is the partner in a pair).  The
+// reductions over a game's lanes exchange 0xB1, then (four lanes) 0x4E = [2,3,0,1]; on one lane they are the identity.
+template <int CTRL>
+__device__ __forceinline__ int qperm_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
+template <int CTRL>
+__device__ __forceinline__ float qperm(float v) { return __int_as_float(qperm_i<CTRL>(__float_as_int(v))); }
+
+template <int L>
+__device__ __forceinline__ float lanes_min(float v) {
+  static_assert(L == 1 || L == 2 || L == 4, "one, two or four lanes per game");
+  if constexpr (L >= 2) v = hk_fmin(v, qperm<0xB1>(v));
+  if constexpr (L == 4) v = hk_fmin(v, qperm<0x4E>(v));
+  return v;
+}
+template <int L>
+__device__ __forceinline__ float lanes_max(float v) {
+  static_assert(L == 1 || L == 2 || L == 4, "one, two or four lanes per game");
+  if constexpr (L >= 2) v = hk_fmax(v, qperm<0xB1>(v));
+  if constexpr (L == 4) v = hk_fmax(v, qperm<0x4E>(v));
+  return v;
+}
+template <int L>
+__device__ __forceinline__ uint32_t lanes_umin(uint32_t v) {
+  static_assert(L == 1 || L == 2 || L == 4, "one, two or four lanes per game");
+  uint32_t o;
+  if constexpr (L >= 2) {
+    o = (uint32_t)qperm_i<0xB1>((int)v);
+    v = o < v ? o : v;
+  }
+  if constexpr (L == 4) {
+    o = (uint32_t)qperm_i<0x4E>((int)v);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+template <int L>
+__device__ __forceinline__ uint32_t lanes_or(uint32_t v) {
+  static_assert(L == 1 || L == 2 || L == 4, "one, two or four lanes per game");
+  if constexpr (L >= 2) v |= (uint32_t)qperm_i<0xB1>((int)v);
+  if constexpr (L == 4) v |= (uint32_t)qperm_i<0x4E>((int)v);
+  return v;
+}
+template <int L>
+__device__ __forceinline__ uint64_t lanes_or64(uint64_t v) {
+  return ((uint64_t)lanes_or<L>((uint32_t)(v >> 32)) << 32) | lanes_or<L>((uint32_t)v);
+}
+template <int L>
+__device__ __forceinline__ int lanes_sum(int v) {
+  static_assert(L == 1 || L == 2 || L == 4, "one, two or four lanes per game");
+  if constexpr (L >= 2) v += qperm_i<0xB1>(v);
+  if constexpr (L == 4) v += qperm_i<0x4E>(v);
+  return v;
+}
+
 // rows of the set bits of `mask`, ascending, into q[0..n); q[n..nmax) := +inf
 // (SB: compile-time bound of the rows touched -- the staircase of rollout loops knows it per level)
 template <int M, int C, int D, int SB = C>
@@ -80,16 +135,142 @@ __device__ __forceinline__ MaskT<M> scatter_rows(const float (&q)[C * D], float*
   return alive;
 }
 
-template <int C, int D>
-__device__ __forceinline__ int count_live(const float (&q)[C * D], int nmax) {
+// the game's live rows: slots [0, NB) below +inf, over its L lanes
+template <int L, int C, int D, int NB>
+__device__ __forceinline__ int live_rows(const float (&q)[C * D]) {
   int n = 0;
-  unrolled_while<0, C>([&](auto rc) {
-    constexpr int r = decltype(rc)::value;
-    if (r >= nmax) return false;
-    n += (q[r * D] < INFINITY) ? 1 : 0;
+#pragma unroll
+  for (int r = 0; r < NB; ++r) n += (q[r * D] < INFINITY) ? 1 : 0;
+  return lanes_sum<L>(n);
+}
+
+// ---- reposition and rescale over the game's L lanes, in two forms: on NB slots per lane as straight-line code (the
+// bucketed bodies), and (*_upto) on the slots [0, n) of a run-time n <= C, leaving early with a scalar branch ----------
+// _jax_ops.py:114-123 / _torch_ops.py:113-133 (padding rows are not in q)
+// BIN: rollouts with in-kernel 0/1 subsets.  Every coordinate is >= +0 or the +inf of a hole (guarded at entry; sums,
+// differences against the column minimum and quotients keep it so, and x - x is +0), so the float order is the unsigned
+// order of the bit patterns: v_min_u32 / v_min3_u32, with another lane's value as a DPP operand -- the float minimum of
+// values of unknown origin costs a canonicalising v_max x, x per operand (5 instructions per column at one slot per lane
+// of two, now 1).  A minimum of 0 subtracts itself (JAX and torch semantics agree there).
+template <int L, int C, int D, int NB, bool BIN = false>
+__device__ __forceinline__ void reposition(float (&q)[C * D], unsigned flags) {
+  const bool jax_sem = (flags & HK_SEM_MASK) == HK_SEM_JAX;
+  if constexpr (BIN) {
+    uint32_t mb[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) mb[k] = __float_as_uint(q[k]);
+#pragma unroll
+    for (int r = 1; r < NB; ++r)
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        const uint32_t w = __float_as_uint(q[r * D + k]);
+        mb[k] = w < mb[k] ? w : mb[k];
+      }
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      mb[k] = lanes_umin<L>(mb[k]);
+      // (a column without live rows -- an empty game -- subtracts the largest finite float: +inf stays +inf, one
+      // v_min_u32 where the test for +inf took a compare and a select)
+      const float sub = __uint_as_float(mb[k] < 0x7F7FFFFFu ? mb[k] : 0x7F7FFFFFu);
+#pragma unroll
+      for (int r = 0; r < NB; ++r) q[r * D + k] = q[r * D + k] - sub;
+    }
+    return;
+  }
+  float mn[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) mn[k] = INFINITY;
+#pragma unroll
+  for (int r = 0; r < NB; ++r)
+#pragma unroll
+    for (int k = 0; k < D; ++k) mn[k] = hk_fmin(mn[k], q[r * D + k]);
+  float sub[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    mn[k] = lanes_min<L>(mn[k]);
+    sub[k] = (mn[k] < INFINITY && (!jax_sem || mn[k] > 0.0f)) ? mn[k] : 0.0f;  // see reposition_upto
+  }
+#pragma unroll
+  for (int r = 0; r < NB; ++r)
+#pragma unroll
+    for (int k = 0; k < D; ++k) q[r * D + k] = q[r * D + k] - sub[k];
+}
+
+template <int L, int C, int D>
+__device__ __forceinline__ void reposition_upto(float (&q)[C * D], int n, unsigned flags) {
+  const bool jax_sem = (flags & HK_SEM_MASK) == HK_SEM_JAX;
+  float mn[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) mn[k] = INFINITY;
+  unrolled_while<0, C>([&](auto sc) {
+    constexpr int s = decltype(sc)::value;
+    if (s >= n) return false;
+#pragma unroll
+    for (int k = 0; k < D; ++k) mn[k] = hk_fmin(mn[k], q[s * D + k]);
     return true;
   });
-  return n;
+  float sub[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    mn[k] = lanes_min<L>(mn[k]);
+    // JAX leaves a column whose minimum is <= 0 untouched: subtract 0
+    sub[k] = (mn[k] < INFINITY && (!jax_sem || mn[k] > 0.0f)) ? mn[k] : 0.0f;
+  }
+  unrolled_while<0, C>([&](auto sc) {
+    constexpr int s = decltype(sc)::value;
+    if (s >= n) return false;
+#pragma unroll
+    for (int k = 0; k < D; ++k) q[s * D + k] = q[s * D + k] - sub[k];  // inf - sub = inf: holes stay
+    return true;
+  });
+}
+
+// _jax_ops.py:93-111 / _torch_ops.py:136-146 (the maximum over a game that has a live row is attained on a live row; a
+// game without one is all padding and does not change).  The four-lane bodies have a form of their own (qd_rescale).
+template <int L, int C, int D, int NB>
+__device__ __forceinline__ void rescale(float (&q)[C * D], unsigned flags) {
+  const bool jax_sem = (flags & HK_SEM_MASK) == HK_SEM_JAX;
+  float mx = -1.0f;
+#pragma unroll
+  for (int r = 0; r < NB; ++r) {
+    const bool live = q[r * D] < INFINITY;
+#pragma unroll
+    for (int k = 0; k < D; ++k) mx = hk_fmax(mx, live ? q[r * D + k] : -1.0f);
+  }
+  mx = lanes_max<L>(mx);
+  const bool skip = jax_sem ? (mx <= 1e-8f) : (mx < 0.0f);
+  const float div = (skip || mx == 0.0f) ? 1.0f : mx;
+#pragma unroll
+  for (int r = 0; r < NB; ++r) {
+    const bool live = q[r * D] < INFINITY;
+#pragma unroll
+    for (int k = 0; k < D; ++k) q[r * D + k] = live ? q[r * D + k] / div : INFINITY;
+  }
+}
+
+template <int L, int C, int D>
+__device__ __forceinline__ void rescale_upto(float (&q)[C * D], int n, unsigned flags) {
+  const bool jax_sem = (flags & HK_SEM_MASK) == HK_SEM_JAX;
+  float mx = -1.0f;
+  unrolled_while<0, C>([&](auto sc) {
+    constexpr int s = decltype(sc)::value;
+    if (s >= n) return false;
+    const bool live = q[s * D] < INFINITY;
+#pragma unroll
+    for (int k = 0; k < D; ++k) mx = hk_fmax(mx, live ? q[s * D + k] : -1.0f);
+    return true;
+  });
+  mx = lanes_max<L>(mx);
+  const bool skip = jax_sem ? (mx <= 1e-8f) : (mx < 0.0f);
+  const float div = (skip || mx == 0.0f) ? 1.0f : mx;
+  unrolled_while<0, C>([&](auto sc) {
+    constexpr int s = decltype(sc)::value;
+    if (s >= n) return false;
+    const bool live = q[s * D] < INFINITY;
+#pragma unroll
+    for (int k = 0; k < D; ++k) q[s * D + k] = live ? q[s * D + k] / div : INFINITY;
+    return true;
+  });
 }
 
 // _jax_ops.py:76-90 / _torch_ops.py:46-110
@@ -121,33 +302,6 @@ __device__ __forceinline__ void c_shift(float (&q)[C * D], int nmax, const float
   });
 }
 
-// _jax_ops.py:114-123 / _torch_ops.py:113-133 (padding rows are not in q)
-template <int C, int D>
-__device__ __forceinline__ void c_reposition(float (&q)[C * D], int nmax, unsigned flags) {
-  const bool jax_sem = (flags & HK_SEM_MASK) == HK_SEM_JAX;
-  float mn[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) mn[k] = INFINITY;
-  unrolled_while<0, C>([&](auto rc) {
-    constexpr int r = decltype(rc)::value;
-    if (r >= nmax) return false;
-#pragma unroll
-    for (int k = 0; k < D; ++k) mn[k] = hk_fmin(mn[k], q[r * D + k]);
-    return true;
-  });
-  float sub[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k)  // JAX leaves a column whose minimum is <= 0 untouched: subtract 0
-    sub[k] = (mn[k] < INFINITY && (!jax_sem || mn[k] > 0.0f)) ? mn[k] : 0.0f;
-  unrolled_while<0, C>([&](auto rc) {
-    constexpr int r = decltype(rc)::value;
-    if (r >= nmax) return false;
-#pragma unroll
-    for (int k = 0; k < D; ++k) q[r * D + k] = q[r * D + k] - sub[k];  // inf - sub = inf: holes stay
-    return true;
-  });
-}
-
 // t = max_k(a - b), u = min_k(a - b).  The differences are results of a subtraction (canonical), so plain fmaxf /
 // fminf chains become v_max3_f32 / v_min3_f32 (one instruction per three values) without the canonicalising
 // v_max x, x that values of unknown origin get; hk_fmax / hk_fmin (v_med3) stay for those.
@@ -163,63 +317,6 @@ __device__ __forceinline__ void diff_extrema(const float* a, const float* b, flo
     t = __builtin_fmaxf(t, dk[k]);
     u = __builtin_fminf(u, dk[k]);
   }
-}
-
-// _jax_ops.py:15-73: removed rows become holes.  Pair i<j:  t = max_k(q_i-q_j), u = min_k(q_i-q_j);
-// j removed iff t <= 0 (ties go to the lower index), i removed iff u >= 0 and t > 0.
-template <int C, int D>
-__device__ __forceinline__ void c_newton(float (&q)[C * D], int nmax) {
-  float acc[C];
-#pragma unroll
-  for (int r = 0; r < C; ++r) acc[r] = INFINITY;
-  unrolled_while<0, C - 1>([&](auto ic) {
-    constexpr int i = decltype(ic)::value;
-    if (i + 1 >= nmax) return false;
-    unrolled_while<i + 1, C>([&](auto jc) {
-      constexpr int j = decltype(jc)::value;
-      if (j >= nmax) return false;
-      float t, u;
-      diff_extrema<D>(&q[i * D], &q[j * D], t, u);
-      acc[j] = hk_fmin(acc[j], t);
-      acc[i] = hk_fmin(acc[i], (t > 0.0f) ? -u : 1.0f);
-      return true;
-    });
-    return true;
-  });
-  unrolled_while<0, C>([&](auto rc) {
-    constexpr int r = decltype(rc)::value;
-    if (r >= nmax) return false;
-    const bool removed = acc[r] <= 0.0f;
-#pragma unroll
-    for (int k = 0; k < D; ++k) q[r * D + k] = removed ? INFINITY : q[r * D + k];
-    return true;
-  });
-}
-
-// _jax_ops.py:93-111 / _torch_ops.py:136-146 on the live rows (the maximum over a game that has a
-// live row is attained on a live row; a game without one is all padding and does not change)
-template <int C, int D>
-__device__ __forceinline__ void c_rescale(float (&q)[C * D], int nmax, unsigned flags) {
-  const bool jax_sem = (flags & HK_SEM_MASK) == HK_SEM_JAX;
-  float mx = -1.0f;
-  unrolled_while<0, C>([&](auto rc) {
-    constexpr int r = decltype(rc)::value;
-    if (r >= nmax) return false;
-    const bool live = q[r * D] < INFINITY;
-#pragma unroll
-    for (int k = 0; k < D; ++k) mx = hk_fmax(mx, live ? q[r * D + k] : -1.0f);
-    return true;
-  });
-  const bool skip = jax_sem ? (mx <= 1e-8f) : (mx < 0.0f);
-  const float div = (skip || mx == 0.0f) ? 1.0f : mx;
-  unrolled_while<0, C>([&](auto rc) {
-    constexpr int r = decltype(rc)::value;
-    if (r >= nmax) return false;
-    const bool live = q[r * D] < INFINITY;
-#pragma unroll
-    for (int k = 0; k < D; ++k) q[r * D + k] = live ? q[r * D + k] / div : INFINITY;
-    return true;
-  });
 }
 
 // ---- straight-line bodies ------------------------------------------------------------------------------
@@ -278,48 +375,6 @@ __device__ __forceinline__ void b_shift_mask(float (&q)[C * D], uint32_t cmask, 
   }
 }
 
-template <int C, int D, int NB, bool BIN = false>
-__device__ __forceinline__ void b_reposition(float (&q)[C * D], unsigned flags) {
-  const bool jax_sem = (flags & HK_SEM_MASK) == HK_SEM_JAX;
-  if constexpr (BIN) {
-    // rollouts with in-kernel 0/1 subsets: coordinates are >= +0 or the +inf of a hole, so the float order is the
-    // unsigned order of the bit patterns (v_min_u32 / v_min3_u32, no canonicalising v_max x, x; see d_reposition)
-    uint32_t mb[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) mb[k] = __float_as_uint(q[k]);
-#pragma unroll
-    for (int r = 1; r < NB; ++r)
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        const uint32_t w = __float_as_uint(q[r * D + k]);
-        mb[k] = w < mb[k] ? w : mb[k];
-      }
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      // (no live row in the column: subtract the largest finite float -- +inf stays +inf; see hk_duo_kernel.h)
-      const float sub = __uint_as_float(mb[k] < 0x7F7FFFFFu ? mb[k] : 0x7F7FFFFFu);
-#pragma unroll
-      for (int r = 0; r < NB; ++r) q[r * D + k] = q[r * D + k] - sub;
-    }
-    return;
-  }
-  float mn[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) mn[k] = INFINITY;
-#pragma unroll
-  for (int r = 0; r < NB; ++r)
-#pragma unroll
-    for (int k = 0; k < D; ++k) mn[k] = hk_fmin(mn[k], q[r * D + k]);
-  float sub[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k)  // JAX leaves a column whose minimum is <= 0 untouched: subtract 0
-    sub[k] = (mn[k] < INFINITY && (!jax_sem || mn[k] > 0.0f)) ? mn[k] : 0.0f;
-#pragma unroll
-  for (int r = 0; r < NB; ++r)
-#pragma unroll
-    for (int k = 0; k < D; ++k) q[r * D + k] = q[r * D + k] - sub[k];  // inf - sub = inf: holes stay
-}
-
 template <int C, int D, int NB>
 __device__ __forceinline__ void b_newton(float (&q)[C * D]) {
   if constexpr (NB < 2) return;  // (one row: nothing to compare)
@@ -348,26 +403,6 @@ __device__ __forceinline__ void b_newton(float (&q)[C * D]) {
   }
 }
 
-template <int C, int D, int NB>
-__device__ __forceinline__ void b_rescale(float (&q)[C * D], unsigned flags) {
-  const bool jax_sem = (flags & HK_SEM_MASK) == HK_SEM_JAX;
-  float mx = -1.0f;
-#pragma unroll
-  for (int r = 0; r < NB; ++r) {
-    const bool live = q[r * D] < INFINITY;
-#pragma unroll
-    for (int k = 0; k < D; ++k) mx = hk_fmax(mx, live ? q[r * D + k] : -1.0f);
-  }
-  const bool skip = jax_sem ? (mx <= 1e-8f) : (mx < 0.0f);
-  const float div = (skip || mx == 0.0f) ? 1.0f : mx;
-#pragma unroll
-  for (int r = 0; r < NB; ++r) {
-    const bool live = q[r * D] < INFINITY;
-#pragma unroll
-    for (int k = 0; k < D; ++k) q[r * D + k] = live ? q[r * D + k] / div : INFINITY;
-  }
-}
-
 // one transition on rows [0, NB); returns the number of live rows.  BIN: the subset is the 0/1 mask `cmask`
 template <int C, int D, int NB, bool BIN = false>
 __device__ __forceinline__ int b_stages(float (&q)[C * D], const float (&c)[D], int axis, int np, unsigned flags,
@@ -376,46 +411,57 @@ __device__ __forceinline__ int b_stages(float (&q)[C * D], const float (&c)[D], 
     if constexpr (BIN) b_shift_mask<C, D, NB>(q, cmask, axis, np, flags);
     else b_shift<C, D, NB>(q, c, axis, np, flags);
   }
-  if (stages & HK_STAGE_REPOSITION) b_reposition<C, D, NB, BIN>(q, flags);
+  if (stages & HK_STAGE_REPOSITION) reposition<1, C, D, NB, BIN>(q, flags);
   if (stages & HK_STAGE_NEWTON) b_newton<C, D, NB>(q);
-  if (stages & HK_STAGE_RESCALE) b_rescale<C, D, NB>(q, flags);
-  int n = 0;
-#pragma unroll
-  for (int r = 0; r < NB; ++r) n += (q[r * D] < INFINITY) ? 1 : 0;
-  return n;
+  if (stages & HK_STAGE_RESCALE) rescale<1, C, D, NB>(q, flags);
+  return live_rows<1, C, D, NB>(q);
 }
 
-// the smallest body that covers nmax
-template <int C, int D, int NB, bool BIN = false>
+// ---- ladders of bucketed bodies: LADDER::next_bucket(nb) is the bucket after nb (the first is 1) ----------------------
+struct RowLadder {  // one lane per game: 1..8, 10, 12, ...
+  static constexpr int next_bucket(int nb) { return nb < 8 ? nb + 1 : nb + 2; }
+};
+
+// the smallest body that covers n rows: f(NB) for the first bucket NB >= n, C (the top) at most
+template <typename LADDER, int C, int NB = 1>
 struct StagesFor {
-  static constexpr int kNext = (NB < 8) ? NB + 1 : NB + 2;
-  static __device__ __forceinline__ int run(float (&q)[C * D], int nmax, const float (&c)[D], int axis, int np,
-                                            unsigned flags, unsigned stages, uint32_t cmask = 0) {
+  template <typename F>
+  static __device__ __forceinline__ int run(int n, F&& f) {
     if constexpr (NB >= C) {
-      return b_stages<C, D, C, BIN>(q, c, axis, np, flags, stages, cmask);
+      return f(std::integral_constant<int, C>{});
     } else {
-      if (nmax <= NB) return b_stages<C, D, NB, BIN>(q, c, axis, np, flags, stages, cmask);
-      return StagesFor<C, D, kNext, BIN>::run(q, nmax, c, axis, np, flags, stages, cmask);
+      if (n <= NB) return f(std::integral_constant<int, NB>{});
+      return StagesFor<LADDER, C, LADDER::next_bucket(NB)>::run(n, f);
     }
   }
 };
 
-// The buckets of rows (1..8, 10, 12, ...) from the top down: f(NB, LO) for every bucket NB with the next smaller one
-// LO (0 below the first) -- the staircase of rollout loops (hk_fast_kernel.h, hk_duo_kernel.h)
-template <int NB>
-struct RowLevels {
-  static constexpr int kLo = (NB <= 8) ? NB - 1 : NB - 2;
+// The buckets from NB (the top) down: f(NB, LO) for every bucket with the next smaller one LO (0 below the first) --
+// the staircase of rollout loops (hk_fast_kernel.h, hk_duo_kernel.h, hk_quadroll_kernel.h)
+template <typename LADDER, int NB>
+struct Levels {
+  static constexpr int prev_bucket(int nb) {
+    int p = 0, b = 1;
+    while (b < nb) {
+      p = b;
+      b = LADDER::next_bucket(b);
+    }
+    return p;
+  }
+  static constexpr int kLo = prev_bucket(NB);
   template <typename F>
   static __device__ __forceinline__ void run(F&& f) {
     f(std::integral_constant<int, NB>{}, std::integral_constant<int, kLo>{});
-    if constexpr (kLo >= 1) RowLevels<kLo>::run(f);
+    if constexpr (kLo >= 1) Levels<LADDER, kLo>::run(f);
   }
 };
 
 template <int C, int D, bool BIN = false>
 __device__ __forceinline__ int run_stages(float (&q)[C * D], int nmax, const float (&c)[D], int axis, int np,
                                           unsigned flags, unsigned stages, uint32_t cmask = 0) {
-  return StagesFor<C, D, 1, BIN>::run(q, nmax, c, axis, np, flags, stages, cmask);
+  return StagesFor<RowLadder, C>::run(nmax, [&](auto nb) {
+    return b_stages<C, D, decltype(nb)::value, BIN>(q, c, axis, np, flags, stages, cmask);
+  });
 }
 
 // ---- observation features (jax/util.py:186-197): rows in descending order, LAST coordinate primary ------

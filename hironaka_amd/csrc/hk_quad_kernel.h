@@ -30,28 +30,7 @@ constexpr int kQuad = 4;
 constexpr int kQuadGames = kWave / kQuad;
 
 // DPP quad_perm controls: the value of the lane 1 up / 2 up / 3 up (= 1 down) inside the quad
-constexpr int kQuadUp1 = 0x39, kQuadUp2 = 0x4E, kQuadUp3 = 0x93, kQuadSwap1 = 0xB1;
-template <int CTRL>
-__device__ __forceinline__ int qperm_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
-template <int CTRL>
-__device__ __forceinline__ float qperm(float v) { return __int_as_float(qperm_i<CTRL>(__float_as_int(v))); }
-
-__device__ __forceinline__ float q_min(float v) {
-  v = hk_fmin(v, qperm<kQuadSwap1>(v));
-  return hk_fmin(v, qperm<kQuadUp2>(v));
-}
-__device__ __forceinline__ float q_max(float v) {
-  v = hk_fmax(v, qperm<kQuadSwap1>(v));
-  return hk_fmax(v, qperm<kQuadUp2>(v));
-}
-__device__ __forceinline__ uint32_t q_or(uint32_t v) {
-  v |= (uint32_t)qperm_i<kQuadSwap1>((int)v);
-  return v | (uint32_t)qperm_i<kQuadUp2>((int)v);
-}
-__device__ __forceinline__ int q_sum(int v) {
-  v += qperm_i<kQuadSwap1>(v);
-  return v + qperm_i<kQuadUp2>(v);
-}
+constexpr int kQuadUp1 = 0x39, kQuadUp2 = 0x4E, kQuadUp3 = 0x93;
 
 template <int M, int D>
 struct QuadGeom {
@@ -181,29 +160,7 @@ __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// ---- the stages on NB slots per lane --------------------------------------------------------------------------------
-template <int R, int D, int NB>
-__device__ __forceinline__ void qd_reposition(float (&q)[R * D], unsigned flags) {
-  const bool jax_sem = (flags & HK_SEM_MASK) == HK_SEM_JAX;
-  float mn[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) mn[k] = INFINITY;
-#pragma unroll
-  for (int r = 0; r < NB; ++r)
-#pragma unroll
-    for (int k = 0; k < D; ++k) mn[k] = hk_fmin(mn[k], q[r * D + k]);
-  float sub[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    mn[k] = q_min(mn[k]);
-    sub[k] = (mn[k] < INFINITY && (!jax_sem || mn[k] > 0.0f)) ? mn[k] : 0.0f;  // see b_reposition
-  }
-#pragma unroll
-  for (int r = 0; r < NB; ++r)
-#pragma unroll
-    for (int k = 0; k < D; ++k) q[r * D + k] = q[r * D + k] - sub[k];
-}
-
+// ---- the stages on NB slots per lane (reposition: hk_fast_rows.h) ---------------------------------------------------
 template <int R, int D, int NB>
 __device__ __forceinline__ void qd_rescale(float (&q)[R * D], unsigned flags) {
   const bool jax_sem = (flags & HK_SEM_MASK) == HK_SEM_JAX;
@@ -214,7 +171,7 @@ __device__ __forceinline__ void qd_rescale(float (&q)[R * D], unsigned flags) {
 #pragma unroll
     for (int k = 0; k < D; ++k) mx = hk_fmax(mx, live ? q[r * D + k] : -1.0f);
   }
-  mx = q_max(mx);
+  mx = lanes_max<kQuad>(mx);
   const bool skip = jax_sem ? (mx <= 1e-8f) : (mx < 0.0f);
   const float div = (skip || mx == 0.0f) ? 1.0f : mx;
 #pragma unroll
@@ -228,22 +185,6 @@ __device__ __forceinline__ void qd_rescale(float (&q)[R * D], unsigned flags) {
   }
 }
 
-// t = max_k(a - b), u = min_k(a - b).  The differences are results of a subtraction (canonical), so the plain
-// fmaxf / fminf chains become v_max3_f32 / v_min3_f32 without the canonicalising v_max x, x that loaded values get.
-template <int D>
-__device__ __forceinline__ void qd_extrema(const float* a, const float* b, float& t, float& u) {
-  float dk[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) dk[k] = a[k] - b[k];
-  t = dk[0];
-  u = dk[0];
-#pragma unroll
-  for (int k = 1; k < D; ++k) {
-    t = __builtin_fmaxf(t, dk[k]);
-    u = __builtin_fminf(u, dk[k]);
-  }
-}
-
 // One pair (mine, other) with t = max_k(mine - other), u = min_k(mine - other) (see d_newton in hk_duo_kernel.h):
 //   mine earlier:  other removed iff t <= 0;            mine removed iff u >= 0 and t > 0
 //   other earlier: other removed iff t <= 0 and u < 0;  mine removed iff u >= 0
@@ -252,7 +193,7 @@ __device__ __forceinline__ void qd_extrema(const float* a, const float* b, float
 template <int D, int ORDER, bool ACC_FIRST = false, bool OTH_FIRST = false>
 __device__ __forceinline__ void qd_pair(const float* mine, const float* other, float& acc, float& oth, bool late) {
   float t, u;
-  qd_extrema<D>(mine, other, t, u);
+  diff_extrema<D>(mine, other, t, u);
   float vo, va;
   if (ORDER > 0) {
     vo = t;
@@ -282,7 +223,7 @@ __device__ __forceinline__ void qd_newton(float (&q)[R * D], int j) {
 #pragma unroll
     for (int b = a + 1; b < NB; ++b) {
       float t, u;
-      qd_extrema<D>(&q[a * D], &q[b * D], t, u);
+      diff_extrema<D>(&q[a * D], &q[b * D], t, u);
       const float va = (t > 0.0f) ? -u : 1.0f;
       acc[b] = (a == 0) ? t : hk_fmin(acc[b], t);
       acc[a] = (a == 0 && b == 1) ? va : hk_fmin(acc[a], va);
@@ -359,7 +300,7 @@ struct QuadLdsPairs {
 #pragma unroll
       for (int s = 0; s < CSEG; ++s) {
         float t, u;
-        qd_extrema<D>(pj, &q[s * D], t, u);
+        diff_extrema<D>(pj, &q[s * D], t, u);
         const bool below = (s < CSEG - 1) || (r0 + j < row);  // my row 4s + j lies below row j
         jdead |= below && (u >= 0.0f);
         acc[s] = hk_fmin(acc[s], (below && u < 0.0f) ? t : 1.0f);
@@ -397,8 +338,8 @@ __device__ __forceinline__ void qd_newton_lds(float (&q)[R * D], float* cmine, i
   for (int s = 0; s < NB; ++s) acc[s] = INFINITY;
   uint32_t jmask[2] = {0u, 0u};
   QuadLdsPairs<CW, R, D, NB, 1>::run(q, acc, jmask, cmine, j, rows_end);
-  jmask[0] = q_or(jmask[0]);
-  jmask[1] = q_or(jmask[1]);
+  jmask[0] = lanes_or<kQuad>(jmask[0]);
+  jmask[1] = lanes_or<kQuad>(jmask[1]);
 #pragma unroll
   for (int s = 0; s < NB; ++s) {
     const int i = kQuad * s + j;
@@ -431,7 +372,7 @@ __device__ __forceinline__ void qd_newton_two_level(float (&q)[R * D], float* cm
 #pragma unroll
     for (int b = a + 1; b < NB; ++b) {
       float t, u;
-      qd_extrema<D>(&q[a * D], &q[b * D], t, u);
+      diff_extrema<D>(&q[a * D], &q[b * D], t, u);
       acc[b] = hk_fmin(acc[b], t);
       acc[a] = hk_fmin(acc[a], (t > 0.0f) ? -u : 1.0f);
     }
@@ -440,7 +381,7 @@ __device__ __forceinline__ void qd_newton_two_level(float (&q)[R * D], float* cm
   uint32_t lm = 0;  // my slots that are live and survived level 1
 #pragma unroll
   for (int s = 0; s < NB; ++s) lm |= (q[s * D] < INFINITY && acc[s] > 0.0f) ? (1u << s) : 0u;
-  const int np1 = q_sum(__popc(lm));
+  const int np1 = lanes_sum<kQuad>(__popc(lm));
   int s1 = NB;  // slots per lane at level 2: the wave-uniform maximum of ceil(np1 / 4)
 #pragma nounroll
   while (s1 > 1 && !__any(np1 > kQuad * (s1 - 1))) --s1;
@@ -817,7 +758,7 @@ __device__ __forceinline__ void qg_newton_on_packed(float (&q)[R * D], uint32_t 
   uint32_t lm = 0;
 #pragma unroll
   for (int s = 0; s < NB; ++s) lm |= (w[s] != kPackHole) ? (1u << s) : 0u;
-  const int np1 = q_sum(__popc(lm));
+  const int np1 = lanes_sum<kQuad>(__popc(lm));
   int s1 = NB;  // slots per lane at level 1: the wave-uniform maximum of ceil(np1 / 4)
 #pragma nounroll
   while (s1 > 1 && !__any(np1 > kQuad * (s1 - 1))) --s1;
@@ -905,7 +846,7 @@ __device__ __forceinline__ int qd_stages(float (&q)[R * D], const float (&c)[D],
                                          unsigned flags, unsigned stages, float* cmine, int slots_end, bool sorted,
                                          int (&rank)[R], uint8_t* tsc = nullptr) {
   if (stages & HK_STAGE_SHIFT) b_shift<R, D, NB>(q, c, axis, np, flags);
-  if (stages & HK_STAGE_REPOSITION) qd_reposition<R, D, NB>(q, flags);
+  if (stages & HK_STAGE_REPOSITION) reposition<kQuad, R, D, NB>(q, flags);
   if (stages & HK_STAGE_NEWTON) {
     if constexpr (NB > kQuadDppSlots) {
       // many slots per lane (states no Newton pass has thinned): integral rows of small coordinates -- what a generator's
@@ -934,10 +875,7 @@ __device__ __forceinline__ int qd_stages(float (&q)[R * D], const float (&c)[D],
     if (stages & kStageFeatureSorts)
       qd_ranks_lds<M, CW, R, D, NB>(q, cmine, j, slots_end, (stages & kStageFeatureSort0) != 0, rank);
   }
-  int n = 0;
-#pragma unroll
-  for (int r = 0; r < NB; ++r) n += (q[r * D] < INFINITY) ? 1 : 0;
-  return q_sum(n);
+  return live_rows<kQuad, R, D, NB>(q);
 }
 
 template <int M, int D, int NB, bool AUX = true>
@@ -1185,11 +1123,11 @@ __global__ __launch_bounds__(kWave * WPB, (quad_waves_per_simd<M, D, HOT>())) vo
   MaskM gmask;
   int below;  // live rows of the game below my first row
   if constexpr (M <= 32) {
-    gmask = q_or(lmask << i0);
+    gmask = lanes_or<kQuad>(lmask << i0);
     below = __popc(gmask & ((1u << i0) - 1u));
   } else {
     const unsigned long long mm = (unsigned long long)lmask << i0;
-    gmask = ((unsigned long long)q_or((uint32_t)(mm >> 32)) << 32) | q_or((uint32_t)mm);
+    gmask = ((unsigned long long)lanes_or<kQuad>((uint32_t)(mm >> 32)) << 32) | lanes_or<kQuad>((uint32_t)mm);
     below = __popcll(gmask & ((1ull << i0) - 1ull));
   }
   int np = mask_pop(gmask);

@@ -84,7 +84,7 @@ __global__ __launch_bounds__((kWave * QuadBinGeom<M, D>::kWaves)) void quadbin_k
 #pragma unroll
     for (int s = 0; s < R; ++s)
       if ((kQuad * s + kQuad <= M) || kQuad * s + j < M) n += (mine[(kQuad * s + j) * D] >= 0.0f) ? 1 : 0;
-    np = q_sum(n);
+    np = lanes_sum<kQuad>(n);
 #pragma unroll
     for (int i = 0; i < BG::kPay; ++i) {
       const int c = kQuad * i + j;

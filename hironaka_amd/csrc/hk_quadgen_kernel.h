@@ -113,7 +113,7 @@ __device__ __forceinline__ int qg_stages(float (&q)[RD], int j, unsigned flags, 
   if constexpr (R > kQuadDppSlots && D <= 4) {
     if (packed) qg_newton_packed<M, D, R>(q, reinterpret_cast<uint32_t*>(cmine), j, lane);
   }
-  if (stages & HK_STAGE_REPOSITION) qd_reposition<R, D, R>(q, flags);
+  if (stages & HK_STAGE_REPOSITION) reposition<kQuad, R, D, R>(q, flags);
   if ((stages & HK_STAGE_NEWTON) && !packed) {
     if constexpr (R > kQuadDppSlots) {
       if constexpr (TWO && QuadGenGeom<M, D>::kTwoLevel) qd_newton_two_level<M, G::CW, R, D, R>(q, cmine, tsc, j, M);
@@ -126,7 +126,7 @@ __device__ __forceinline__ int qg_stages(float (&q)[RD], int j, unsigned flags, 
   int n = 0;
 #pragma unroll
   for (int r = 0; r < R; ++r) n += (q[r * D] < INFINITY) ? 1 : 0;
-  return q_sum(n);
+  return lanes_sum<kQuad>(n);
 }
 
 template <int M, int D, int WPB>

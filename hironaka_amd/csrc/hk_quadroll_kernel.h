@@ -53,62 +53,14 @@ struct QuadRollGeom {
   static constexpr int kWavesPerSimd = kBig ? 3 : 4;
   static_assert(D <= 5, "an action travels as a byte: subset mask (D bits) | axis << 5");
   static_assert(kActs >= kQuadGames * D * 4, "the slow path's subset scratch lies over the action window");
-  // the bucket below nb on the ladder 1..6, 8, 10, 13, 16, ... (QuadGeom::next_bucket), the top bucket being R
-  static constexpr int prev_bucket(int nb) {
-    int p = 0, b = 1;
-    while (b < nb) {
-      p = b;
-      b = Q::next_bucket(b);
-    }
-    return p;
-  }
 };
-
-// f(NB, LO) for every bucket NB from R down, LO the next smaller one (0 below the first)
-template <int M, int D, int NB>
-struct QuadLevels {
-  static constexpr int kLo = QuadRollGeom<M, D>::prev_bucket(NB);
-  template <typename F>
-  static __device__ __forceinline__ void run(F&& f) {
-    f(std::integral_constant<int, NB>{}, std::integral_constant<int, kLo>{});
-    if constexpr (kLo >= 1) QuadLevels<M, D, kLo>::run(f);
-  }
-};
-
-// reposition when every coordinate is >= +0 or the +inf of a hole (in-kernel 0/1 subsets; see d_reposition): unsigned
-// minima of the bit patterns, the quad's through two DPP exchanges
-template <int R, int D, int NB>
-__device__ __forceinline__ void qr_reposition_bin(float (&q)[R * D]) {
-  uint32_t mb[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) mb[k] = __float_as_uint(q[k]);
-#pragma unroll
-  for (int r = 1; r < NB; ++r)
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      const uint32_t w = __float_as_uint(q[r * D + k]);
-      mb[k] = w < mb[k] ? w : mb[k];
-    }
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    uint32_t o = (uint32_t)qperm_i<kQuadSwap1>((int)mb[k]);
-    mb[k] = o < mb[k] ? o : mb[k];
-    o = (uint32_t)qperm_i<kQuadUp2>((int)mb[k]);
-    mb[k] = o < mb[k] ? o : mb[k];
-    // (a column without live rows -- an empty game -- subtracts the largest finite float: +inf stays +inf, one
-    // v_min_u32 where the test for +inf took a compare and a select)
-    const float sub = __uint_as_float(mb[k] < 0x7F7FFFFFu ? mb[k] : 0x7F7FFFFFu);
-#pragma unroll
-    for (int r = 0; r < NB; ++r) q[r * D + k] = q[r * D + k] - sub;
-  }
-}
 
 // one transition on slots [0, NB) of the four lanes with the policy's 0/1 subset `cmask`; returns the GAME's live rows
 template <int M, int CW, int R, int D, int NB>
 __device__ __forceinline__ int qr_stages(float (&q)[R * D], uint32_t cmask, int axis, int np, int j, unsigned flags,
                                          unsigned stages, float* cmine, int smax) {
   if (stages & HK_STAGE_SHIFT) b_shift_mask<R, D, NB>(q, cmask, axis, np, flags);
-  if (stages & HK_STAGE_REPOSITION) qr_reposition_bin<R, D, NB>(q);
+  if (stages & HK_STAGE_REPOSITION) reposition<kQuad, R, D, NB, true>(q, flags);
   if (stages & HK_STAGE_NEWTON) {
     if constexpr (NB > kQuadDppSlots) {
       const int slots_end = kQuad * smax < M ? kQuad * smax : M;
@@ -118,10 +70,7 @@ __device__ __forceinline__ int qr_stages(float (&q)[R * D], uint32_t cmask, int 
     }
   }
   if (stages & HK_STAGE_RESCALE) qd_rescale<R, D, NB>(q, flags);
-  int n = 0;
-#pragma unroll
-  for (int r = 0; r < NB; ++r) n += (q[r * D] < INFINITY) ? 1 : 0;
-  return q_sum(n);
+  return live_rows<kQuad, R, D, NB>(q);
 }
 
 // the decoded actions of blocks [wb0, wb0 + nb) of the wave's 16 games: lane l serves game l & 15, blocks (l >> 4) + 4 i.
@@ -549,11 +498,11 @@ __global__ __launch_bounds__(kWave * WPB, (QuadRollGeom<M, D>::kWavesPerSimd)) v
   MaskM gmask;
   int below;  // live rows of the game below my first row
   if constexpr (M <= 32) {
-    gmask = q_or(lmask << i0);
+    gmask = lanes_or<kQuad>(lmask << i0);
     below = __popc(gmask & ((1u << i0) - 1u));
   } else {
     const unsigned long long mm = (unsigned long long)lmask << i0;
-    gmask = ((unsigned long long)q_or((uint32_t)(mm >> 32)) << 32) | q_or((uint32_t)mm);
+    gmask = ((unsigned long long)lanes_or<kQuad>((uint32_t)(mm >> 32)) << 32) | lanes_or<kQuad>((uint32_t)mm);
     below = __popcll(gmask & ((1ull << i0) - 1ull));
   }
   np = mask_pop(gmask);
@@ -769,7 +718,7 @@ __global__ __launch_bounds__(kWave * WPB, (QuadRollGeom<M, D>::kWavesPerSimd)) v
     const uint8_t* arow = act + gi;
     // the action byte of step t, requested one step ahead (the LDS round trip opened every step: hk_duo_kernel.h)
     uint32_t a_next = ZEIL ? 0u : arow[(int)(step0 + (uint32_t)t - wstep0) * kQuadGames];
-    QuadLevels<M, D, R>::run([&](auto nbc, auto loc) {
+    Levels<QuadGeom<M, D>, R>::run([&](auto nbc, auto loc) {
       constexpr int NB = decltype(nbc)::value, LO = decltype(loc)::value;
       // (no s_setprio by bucket here: with three or four waves per SIMD it starves the others -- measured 24.4 -> 26.5 us
       // at (20,3) x 65 536, 192 -> 202 us at (50,4) x 262 144; hk_duo_kernel.h, two waves per SIMD, gains 3 % from it)

@@ -35,28 +35,7 @@ constexpr int kTeam = 4;
 constexpr int kTeamGames = kWave / kTeam;
 constexpr int kTeamSlots = 16;  // register slots per lane: 4 * 16 = 64 rows
 
-// ---- exchanges inside a quad: DPP quad_perm [1,0,3,2] and [2,3,0,1] ------------------------------------
-template <int CTRL>
-__device__ __forceinline__ int quad_perm_i(int v) {
-  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
-}
-constexpr int kQuadXor1 = 0xB1, kQuadXor2 = 0x4E;
-
-__device__ __forceinline__ float quad_min(float v) {
-  v = hk_fmin(v, __int_as_float(quad_perm_i<kQuadXor1>(__float_as_int(v))));
-  return hk_fmin(v, __int_as_float(quad_perm_i<kQuadXor2>(__float_as_int(v))));
-}
-__device__ __forceinline__ float quad_max(float v) {
-  v = hk_fmax(v, __int_as_float(quad_perm_i<kQuadXor1>(__float_as_int(v))));
-  return hk_fmax(v, __int_as_float(quad_perm_i<kQuadXor2>(__float_as_int(v))));
-}
-__device__ __forceinline__ uint32_t quad_or(uint32_t v) {
-  v |= (uint32_t)quad_perm_i<kQuadXor1>((int)v);
-  return v | (uint32_t)quad_perm_i<kQuadXor2>((int)v);
-}
-__device__ __forceinline__ Mask64 quad_or64(Mask64 v) {
-  return ((Mask64)quad_or((uint32_t)(v >> 32)) << 32) | quad_or((uint32_t)v);
-}
+constexpr int kQuadXor1 = 0xB1, kQuadXor2 = 0x4E;  // DPP quad_perm [1,0,3,2] and [2,3,0,1]
 
 // ---- rows <-> registers --------------------------------------------------------------------------------
 template <int S_, int W>
@@ -106,61 +85,6 @@ __device__ __forceinline__ void team_mirror(const float (&q)[C * D], float* mine
 #pragma unroll
     for (int k = 0; k < D; ++k) v[k] = q[s * D + k];
     row_store<D>(mine + (kTeam * s + tl) * D, v);
-    return true;
-  });
-}
-
-// _jax_ops.py:114-123 / _torch_ops.py:113-133
-template <int D, int C>
-__device__ __forceinline__ void team_reposition(float (&q)[C * D], int smax, unsigned flags) {
-  const bool jax_sem = (flags & HK_SEM_MASK) == HK_SEM_JAX;
-  float mn[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) mn[k] = INFINITY;
-  unrolled_while<0, C>([&](auto sc) {
-    constexpr int s = decltype(sc)::value;
-    if (s >= smax) return false;
-#pragma unroll
-    for (int k = 0; k < D; ++k) mn[k] = hk_fmin(mn[k], q[s * D + k]);
-    return true;
-  });
-  float sub[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    mn[k] = quad_min(mn[k]);
-    sub[k] = (mn[k] < INFINITY && (!jax_sem || mn[k] > 0.0f)) ? mn[k] : 0.0f;
-  }
-  unrolled_while<0, C>([&](auto sc) {
-    constexpr int s = decltype(sc)::value;
-    if (s >= smax) return false;
-#pragma unroll
-    for (int k = 0; k < D; ++k) q[s * D + k] = q[s * D + k] - sub[k];  // inf - sub = inf: holes stay
-    return true;
-  });
-}
-
-// _jax_ops.py:93-111 / _torch_ops.py:136-146
-template <int D, int C>
-__device__ __forceinline__ void team_rescale(float (&q)[C * D], int smax, unsigned flags) {
-  const bool jax_sem = (flags & HK_SEM_MASK) == HK_SEM_JAX;
-  float mx = -1.0f;
-  unrolled_while<0, C>([&](auto sc) {
-    constexpr int s = decltype(sc)::value;
-    if (s >= smax) return false;
-    const bool live = q[s * D] < INFINITY;
-#pragma unroll
-    for (int k = 0; k < D; ++k) mx = hk_fmax(mx, live ? q[s * D + k] : -1.0f);
-    return true;
-  });
-  mx = quad_max(mx);
-  const bool skip = jax_sem ? (mx <= 1e-8f) : (mx < 0.0f);
-  const float div = (skip || mx == 0.0f) ? 1.0f : mx;
-  unrolled_while<0, C>([&](auto sc) {
-    constexpr int s = decltype(sc)::value;
-    if (s >= smax) return false;
-    const bool live = q[s * D] < INFINITY;
-#pragma unroll
-    for (int k = 0; k < D; ++k) q[s * D + k] = live ? q[s * D + k] / div : INFINITY;
     return true;
   });
 }
@@ -223,8 +147,8 @@ __device__ __forceinline__ Mask64 team_newton(float (&q)[C * D], const uint32_t 
   for (int s = 0; s < C; ++s) acc[s] = INFINITY;
   uint32_t jmask[2] = {0u, 0u};
   TeamPairs<D, C, 1>::run(q, acc, jmask, mine, tl, nmax);
-  jmask[0] = quad_or(jmask[0]);
-  jmask[1] = quad_or(jmask[1]);
+  jmask[0] = lanes_or<kTeam>(jmask[0]);
+  jmask[1] = lanes_or<kTeam>(jmask[1]);
   const Mask64 jm = ((Mask64)jmask[1] << 32) | jmask[0];
   Mask64 dead = 0;
   unrolled_while<0, C>([&](auto sc) {
@@ -237,7 +161,7 @@ __device__ __forceinline__ Mask64 team_newton(float (&q)[C * D], const uint32_t 
     for (int k = 0; k < D; ++k) q[s * D + k] = removed ? INFINITY : q[s * D + k];
     return true;
   });
-  return quad_or64(dead);
+  return lanes_or64<kTeam>(dead);
 }
 
 // pad everywhere, then the live rows at their original slots
@@ -314,12 +238,12 @@ __device__ __forceinline__ int team_zeillinger(const float (&q)[C * D], const fl
   // the team's best: exchange with the lane 1 away, then 2 away
 #define HK_TEAM_MERGE(CTRL)                                                                              \
   {                                                                                                      \
-    const float oL = __int_as_float(quad_perm_i<CTRL>(__float_as_int(bestL)));                           \
-    const float oS = __int_as_float(quad_perm_i<CTRL>(__float_as_int(bestS)));                           \
-    const int oP = quad_perm_i<CTRL>(bestP);                                                             \
+    const float oL = __int_as_float(qperm_i<CTRL>(__float_as_int(bestL)));                           \
+    const float oS = __int_as_float(qperm_i<CTRL>(__float_as_int(bestS)));                           \
+    const int oP = qperm_i<CTRL>(bestP);                                                             \
     const bool take = oL < bestL || (oL == bestL && (oS < bestS || (oS == bestS && oP < bestP)));        \
     _Pragma("unroll") for (int k = 0; k < D; ++k) {                                                      \
-      const float ov = __int_as_float(quad_perm_i<CTRL>(__float_as_int(bd[k])));                         \
+      const float ov = __int_as_float(qperm_i<CTRL>(__float_as_int(bd[k])));                         \
       bd[k] = take ? ov : bd[k];                                                                         \
     }                                                                                                    \
     bestL = take ? oL : bestL;                                                                           \
@@ -478,8 +402,8 @@ __global__ __launch_bounds__(kWave, (D <= 4 ? 3 : 2)) void team_kernel(const Par
       ok &= (ge | fl);
       part |= ge ? ((Mask64)1 << i) : (Mask64)0;
     }
-  Mask64 gmask = quad_or64(part);
-  ok = quad_or(ok ? 0u : 1u) == 0u;
+  Mask64 gmask = lanes_or64<kTeam>(part);
+  ok = lanes_or<kTeam>(ok ? 0u : 1u) == 0u;
   int np = __popcll(gmask);
   int nmax = wave_max(np, m);
   int smax = (nmax + kTeam - 1) / kTeam;
@@ -601,7 +525,7 @@ __global__ __launch_bounds__(kWave, (D <= 4 ? 3 : 2)) void team_kernel(const Par
     const bool prev_done = np < 2;
 
     if (stages & HK_STAGE_SHIFT) c_shift<C, D>(q, smax, c, axis, np, flags);
-    if (stages & HK_STAGE_REPOSITION) team_reposition<D, C>(q, smax, flags);
+    if (stages & HK_STAGE_REPOSITION) reposition_upto<kTeam, C, D>(q, smax, flags);
     if (stages & HK_STAGE_NEWTON) {
       team_mirror<D, C>(q, mine, tl, smax);
       __syncthreads();
@@ -628,7 +552,7 @@ __global__ __launch_bounds__(kWave, (D <= 4 ? 3 : 2)) void team_kernel(const Par
         team_gather<D, C>(q, orig, mine, gmask, tl, sprev, true);
       }
     }
-    if (stages & HK_STAGE_RESCALE) team_rescale<D, C>(q, smax, flags);
+    if (stages & HK_STAGE_RESCALE) rescale_upto<kTeam, C, D>(q, smax, flags);
 
     const bool done = np < 2;
     if (done && length < 0) length = t + 1;
