@@ -358,7 +358,9 @@ int hk_step_features(const hk_step_desc* desc, void* features_out, int scale_obs
   if (st != HK_OK) return st;
   if (prm.batch == 0) return HK_OK;
   if (!features_out) return HK_ERR_NULL;
-  if (!aligned(features_out, 16)) return HK_ERR_ALIGN;
+  // (element alignment here; what the four-lane kernel's W-wide feature stores need is quad_supported's to say: a pointer
+  // it cannot store to leaves pick without a kernel, HK_ERR_UNSUPPORTED like every other request it declines)
+  if (!aligned(features_out, sizeof(float))) return HK_ERR_ALIGN;
   if (desc->dtype != HK_F32 || !(prm.stages & HK_STAGE_SHIFT)) return HK_ERR_UNSUPPORTED;
   prm.feat_out = (float*)features_out;
   prm.feat_scale = scale_observation ? 1 : 0;

@@ -1632,13 +1632,16 @@ int launch_quad_t(Params prm, hipStream_t stream) {
 #endif
 
 // hk_step requests this kernel serves: plain steps (no class / feature outputs), JAX or torch semantics (the sorted
-// output of the list semantics stays with the other kernels), float32, contiguous W-aligned records
+// output of the list semantics stays with the other kernels), float32, contiguous W-aligned records; the slabs stored
+// beside the state (a step's features, a rollout's observations) go out in the same W-wide chunks
 template <int M, int D>
 bool quad_ok_t(const Params& prm) {
   using G = QuadGeom<M, D>;
   const size_t vec_bytes = G::W * 4;
   return prm.in_stride == G::N && prm.out_stride == G::N && reinterpret_cast<uintptr_t>(prm.in) % vec_bytes == 0 &&
-         reinterpret_cast<uintptr_t>(prm.out) % vec_bytes == 0;
+         reinterpret_cast<uintptr_t>(prm.out) % vec_bytes == 0 &&
+         reinterpret_cast<uintptr_t>(prm.feat_out) % vec_bytes == 0 &&
+         reinterpret_cast<uintptr_t>(prm.obs_out) % vec_bytes == 0;
 }
 
 inline bool quad_supported(const Params& prm, int dtype) {

@@ -848,8 +848,7 @@ int launch_quadroll_t(Params prm, hipStream_t stream) {
   prm.pad_f32 = (float)prm.pad;
   launch_prepare();
   const int hot = fast_hot_config(prm);
-  if (any_records(prm)) {
-    if (prm.obs_out && reinterpret_cast<uintptr_t>(prm.obs_out) % (QuadGeom<M, D>::W * 4)) return HK_ERR_ALIGN;
+  if (any_records(prm)) {  // (quadroll_supported has checked obs_out: W-aligned like the state)
     if (hot == kHotJax)
       hipLaunchKernelGGL((quadroll_kernel<M, D, kHotJax, WPB, true>), dim3(grid), dim3(kWave * WPB), 0, stream,
                          (const float*)prm.in, prm.in_stride, prm.batch, prm);

@@ -257,3 +257,18 @@ def test_fused_expansion_equals_generic_path(role, use_graph):
         x, y = a.simulate(key, role), b.simulate(key, role)
         for u, v in zip(x, y):
             assert torch.equal(torch.nan_to_num(u, neginf=-1e30), torch.nan_to_num(v, neginf=-1e30))
+
+
+@pytest.mark.parametrize("role", ["host", "agent"])
+def test_fused_expansion_equals_generic_path_on_odd_batches(role):
+    """the same at (10,3) with 33 games: every odd slot of the [N, 33, 30] node tables starts 8 bytes off a 16-byte
+    boundary, which is what that shape's four-lane kernel stores to -- HostExpander's step writes the new node's points
+    and features there (in one launch, or through its hk_step + hk_get_features fallback), bit for bit as the generic path"""
+    over = dict(max_num_points=10, dimension=3, eval_batch_size=33, num_evaluations=12)
+    a = make_trainer(fused_expand=True, **over)
+    b = make_trainer(fused_expand=False, **over)
+    assert a.fused_expand and not b.fused_expand and a.spec == (10, 3) and a.eval_batch_size == 33
+    for key in (3, 4):
+        x, y = a.simulate(key, role), b.simulate(key, role)
+        for u, v in zip(x, y):
+            assert torch.equal(torch.nan_to_num(u, neginf=-1e30), torch.nan_to_num(v, neginf=-1e30))

@@ -13,6 +13,7 @@ from oracle import c_oracle as CO
 from oracle import np_oracle as NO
 
 from conftest import ROOT
+import layout_cases as LC
 
 
 def f32(x):
@@ -501,3 +502,41 @@ def test_torch_cpu_array_formulation_equals_numpy():
     want_p, want_rec = NO.rollout(fresh, 12, 7)
     got_p, got_counts = TO.rollout(fresh, 12, 7)
     assert np.array_equal(got_p, want_p) and np.array_equal(got_counts, want_rec["done_count"])
+
+
+@pytest.mark.parametrize("shape", LC.SHAPES, ids=LC.shape_id)
+def test_c_oracle_does_not_depend_on_the_record_layout(shape):
+    """What tests/test_gpu_layouts.py rests on: the C oracle gives the same result, on every output, for the
+    contiguous batch with class-id coords, with the classes' masks, and for [B, m*d + d] agent observations with the
+    mask in the record's tail (HK_COORDS_IN_RECORD); the strided operators (Zeillinger's host, the features, the
+    counts) read the records as they read the contiguous batch."""
+    m, d, dtype = shape
+    L = CO.lib()
+    for b in (1, 193):
+        p = LC.states(m, d, b, dtype)
+        cls, ax, mask = LC.actions(m, d, b)
+        rec = LC.records(p, mask)
+        for name, cfg in LC.STEP_CONFIGS.items():
+            want = LC.expected_step(m, d, b, dtype, name)
+            kw = dict(stages=cfg[4], flags=LC.config_flags(name), reward_sign=-1.0)
+            for got in (CO.step(p, mask, ax, **kw), CO.step(p, mask.astype(np.uint8), ax.astype(np.int64), **kw),
+                        CO.step(rec, None, ax, coords_kind=A.HK_COORDS_IN_RECORD, max_points=m, dim=d, **kw)):
+                for k in ("points", "done", "prev_done", "reward", "num_points"):
+                    assert np.array_equal(got[k], want[k]), (shape, b, name, k)
+        junk = LC.records(p, np.full((b, d), 7.0))  # a tail that is no mask: the strided operators must not look at it
+        code, stride, n = CO._hk_dtype(p), m * d + d, m * d
+        for sem in ("jax", "list"):
+            out = np.empty(b, dtype=np.int32)
+            CO._check(L.hko_zeillinger(junk.ctypes.data, stride, out.ctypes.data, b, m, d, code, A.SEMANTICS[sem]))
+            assert np.array_equal(out, CO.zeillinger(p, sem)), (shape, b, sem)
+        for scale in (0, 1):
+            feat = np.full((b, n + 3), 5.0, dtype=dtype)
+            CO._check(L.hko_get_features(junk.ctypes.data, stride, feat.ctypes.data, n + 3, b, m, d, code, scale, -1.0))
+            assert np.array_equal(feat[:, :n], CO.get_features(p, bool(scale))) and (feat[:, n:] == 5.0).all()
+        feat = np.full((b, n + 3), 5.0, dtype=dtype)
+        CO._check(L.hko_get_features_torch(junk.ctypes.data, stride, feat.ctypes.data, n + 3, b, m, d, code, -1.0))
+        assert np.array_equal(feat[:, :n].reshape(b, m, d), CO.get_features_torch(p)) and (feat[:, n:] == 5.0).all()
+        done, npts = np.empty(b, dtype=np.uint8), np.empty(b, dtype=np.int32)
+        CO._check(L.hko_get_dones(junk.ctypes.data, stride, done.ctypes.data, b, m, d, code))
+        CO._check(L.hko_get_num_points(junk.ctypes.data, stride, npts.ctypes.data, b, m, d, code))
+        assert np.array_equal(done.astype(bool), CO.get_dones(p)) and np.array_equal(npts, CO.get_num_points(p))
