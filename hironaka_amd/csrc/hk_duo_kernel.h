@@ -33,6 +33,12 @@ struct DuoGeom {
   using G = FastGeom<M, D>;
   static constexpr int CH = (G::C + 1) / 2;                       // slots per lane
   static constexpr int QH = (kDuoGames * G::Q + kWave - 1) / kWave;  // slab chunks per lane
+  // plain rollouts deal their rows level by level in straight line, publish only the rows that changed and store the final
+  // state write-through (duo_kernel)
+  // where the rows take up to 30 registers: at (20,4) -- 40 -- the headline instantiation sits at the 168 VGPRs of three
+  // waves per SIMD, and each change costs it the third wave (169 with the partial publish, 185 with the level deal, 169
+  // with the write-through final stores' descriptor): it keeps the slot-by-slot deal, the refill and non-temporal stores
+  static constexpr bool kLean = CH * D <= 30;
 };
 
 // ---- slab I/O for 32 games per wave (see hk_fast_kernel.h: all requests in flight before the first use) --
@@ -77,14 +83,24 @@ __device__ __forceinline__ void duo_slab_commit(DuoSlabRegs<M, D>& r, float* lds
   }
 }
 
+// How a slab's chunks leave for memory.  Plain and non-temporal stores keep their lines, dirty, in the XCD's L2.
+// Write-through stores (sc1) cost a plain store each, drain while the launch's other waves still play and leave nothing
+// to write back; the line is dropped from the writer's L2, so the next reader is served from the Infinity Cache.
+// Measured on the headline: the kernel is 4 % shorter than with non-temporal stores, the gap to
+// the next dispatch the same; plain stores and `sc1 nt` lost.
+constexpr int kStorePlain = 0, kStoreNT = 1, kStoreWT = 2;
+
 // kBatch: image chunks read per round (everything at once for the final store; fewer inside the recording loop,
 // whose register budget the rows own)
-template <int M, int D, bool CONTIG, int kBatch, bool NT = false>
+// (write-through: 16-byte chunks of contiguous records, through a buffer descriptor over the wave's own slab -- its
+// range check bounds every store once more; other chunk widths and strided records stay non-temporal)
+template <int M, int D, bool CONTIG, int kBatch, int ST = kStorePlain>
 __device__ __forceinline__ void duo_store_slab_impl(const float* lds, float* base, int64_t out_stride, int ngames,
                                                     int lane) {
   using G = FastGeom<M, D>;
   using V = typename VecOf<G::W>::type;
   constexpr int QH = DuoGeom<M, D>::QH;
+  constexpr bool kWT = ST == kStoreWT && CONTIG && G::W == 4;
   const int total = ngames * G::Q;
 #pragma unroll
   for (int i0 = 0; i0 < QH; i0 += kBatch) {
@@ -97,44 +113,60 @@ __device__ __forceinline__ void duo_store_slab_impl(const float* lds, float* bas
     }
 #pragma unroll
     for (int u = 0; u < kBatch; ++u) asm volatile("" : "+v"(v[u]));
+    if constexpr (kWT) {
+      typedef unsigned int vu4 __attribute__((ext_vector_type(4)));
+      // (the descriptor from wave-uniform values: the slab's base as two scalar halves, its bytes)
+      const uint64_t b = (uint64_t)base;
+      const uint32_t blo = __builtin_amdgcn_readfirstlane((uint32_t)b), bhi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
+      const int bytes = __builtin_amdgcn_readfirstlane(total * G::W * (int)sizeof(float));
+      const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)bhi << 32) | blo), 0, bytes, 0x00020000);
 #pragma unroll
-    for (int u = 0; u < kBatch; ++u) {
-      const int q = lane + (i0 + u) * kWave;
-      if (i0 + u < QH && q < total) {
-        V* dst = reinterpret_cast<V*>(base + slab_chunk_global<M, D, CONTIG>(q, out_stride));
-        if constexpr (NT) __builtin_nontemporal_store(v[u], dst);
-        else *dst = v[u];
+      for (int u = 0; u < kBatch; ++u) {
+        const int q = lane + (i0 + u) * kWave;
+        if (i0 + u < QH && q < total)
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(vu4, v[u]), rsrc, q * G::W * (int)sizeof(float), 0,
+                                                 16);  // aux: sc1
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int q = lane + (i0 + u) * kWave;
+        if (i0 + u < QH && q < total) {
+          V* dst = reinterpret_cast<V*>(base + slab_chunk_global<M, D, CONTIG>(q, out_stride));
+          if constexpr (ST != kStorePlain) __builtin_nontemporal_store(v[u], dst);
+          else *dst = v[u];
+        }
       }
     }
   }
 }
 
-// NT: non-temporal stores -- a rollout's final state is written once and not read again by the launch: kept out of the
-// XCD's L2 it leaves the NEXT episode's initial states there (an episode restart re-reads them)
-template <int M, int D, int kBatch = DuoGeom<M, D>::QH, bool NT = false>
+template <int M, int D, int kBatch = DuoGeom<M, D>::QH, int ST = kStorePlain>
 __device__ inline void duo_store_slab(const float* lds, float* out, int64_t out_stride, int64_t g0, int ngames,
                                       int lane) {
   float* base = out + g0 * out_stride;
-  if (out_stride == FastGeom<M, D>::N) duo_store_slab_impl<M, D, true, kBatch, NT>(lds, base, out_stride, ngames, lane);
-  else duo_store_slab_impl<M, D, false, kBatch, NT>(lds, base, out_stride, ngames, lane);
+  if (out_stride == FastGeom<M, D>::N) duo_store_slab_impl<M, D, true, kBatch, ST>(lds, base, out_stride, ngames, lane);
+  else duo_store_slab_impl<M, D, false, kBatch, ST>(lds, base, out_stride, ngames, lane);
 }
+
+struct DuoLadder {  // slots per lane: 1..6, 8, 10, ...
+  static constexpr int next_bucket(int nb) { return nb < 6 ? nb + 1 : nb + 2; }
+};
 
 // ---- image <-> registers ----------------------------------------------------------------------------------
 // the set bits of `mask` in ascending order are the game's live rows; lane h takes the ranks h, h + 2, ...
-// (SB: compile-time bound of the slots touched -- the staircase of rollout loops below knows it per level)
+// slot by slot, with an early exit at the first slot past smax (SB: compile-time bound of the slots touched); a slot
+// past the lane's last row becomes a hole
 template <int M, int CH, int D, int SB = CH>
-__device__ __forceinline__ void duo_gather(float (&q)[CH * D], const float* mine, uint32_t mask, int smax, int h) {
+__device__ __forceinline__ void duo_gather_slots(float (&q)[CH * D], const float* mine, uint32_t mask, int smax, int h) {
+  mask = h ? (mask & (mask - 1)) : mask;  // (the second lane drops the first bit once: one bit scan per slot)
   unrolled_while<0, SB>([&](auto sc) {
     constexpr int s = decltype(sc)::value;
     if (s >= smax) return false;
-    const bool has0 = mask != 0;
-    const int b0 = has0 ? mask_first(mask) : 0;
+    const bool has = mask != 0;
+    const float* row = mine + (has ? mask_first(mask) : 0) * D;
     mask &= mask - 1;
-    const bool has1 = mask != 0;
-    const int b1 = has1 ? mask_first(mask) : 0;
     mask &= mask - 1;
-    const bool has = h ? has1 : has0;
-    const float* row = mine + (h ? b1 : b0) * D;
 #pragma unroll
     for (int k = 0; k < D; ++k) {
       const float v = row[k];
@@ -144,30 +176,101 @@ __device__ __forceinline__ void duo_gather(float (&q)[CH * D], const float* mine
   });
 }
 
-// the lane's live rows back to their slots; returns the mask of the GAME's slots still alive
-template <int M, int CH, int D, int SB = CH>
-__device__ __forceinline__ uint32_t duo_scatter(const float (&q)[CH * D], float* mine, uint32_t mask, int smax, int h) {
+// One level of the deal, straight line on NB slots per lane: the lane's own ranks first (the second lane drops the
+// mask's first bit once; a slot then costs one bit scan and two clears), then every read of the image back to back and
+// one wait.  A slot past the lane's last row reads `hole`, a row of +inf in LDS: it becomes a hole without a select.
+// Slots [NB, SB) are set to holes here, by every level of a dispatch alike: levels that wrote different sets of slots
+// were merged by the compiler into stores at a run-time index, which put the rows into scratch memory.
+template <int CH, int D, int NB, int SB = NB>
+__device__ __forceinline__ void duo_gather_level(float (&q)[CH * D], const float* mine, const float* hole, uint32_t mask,
+                                                 int h) {
+  mask = h ? (mask & (mask - 1)) : mask;
+  const float* row[NB];
+#pragma unroll
+  for (int s = 0; s < NB; ++s) {
+    row[s] = mask != 0 ? mine + mask_first(mask) * D : hole;
+    mask &= mask - 1;
+    mask &= mask - 1;
+  }
+#pragma unroll
+  for (int s = 0; s < NB; ++s)
+#pragma unroll
+    for (int k = 0; k < D; ++k) q[s * D + k] = row[s][k];
+#pragma unroll
+  for (int e = NB * D; e < SB * D; ++e) q[e] = INFINITY;
+}
+
+// slots [0, smax) from the image.  LEVELS: the body is the smallest DuoLadder level that covers smax (wave-uniform), SB
+// at most, and every slot up to SB is written; else slot by slot.
+template <int M, int CH, int D, bool LEVELS, int SB = CH>
+__device__ __forceinline__ void duo_gather(float (&q)[CH * D], const float* mine, const float* hole, uint32_t mask,
+                                           int smax, int h) {
+  if constexpr (LEVELS) {
+    StagesFor<DuoLadder, SB>::run(smax, [&](auto nb) {
+      duo_gather_level<CH, D, decltype(nb)::value, SB>(q, mine, hole, mask, h);
+      return 0;
+    });
+  } else {
+    duo_gather_slots<M, CH, D, SB>(q, mine, mask, smax, h);
+  }
+}
+
+// the lane's live rows back to their slots, straight line on NB slots; returns the lane's part of the mask of the
+// game's slots still alive
+template <int CH, int D, int NB>
+__device__ __forceinline__ uint32_t duo_scatter_level(const float (&q)[CH * D], float* mine, uint32_t mask, int h) {
+  mask = h ? (mask & (mask - 1)) : mask;
   uint32_t alive = 0;
-  unrolled_while<0, SB>([&](auto sc) {
-    constexpr int s = decltype(sc)::value;
-    if (s >= smax) return false;
-    const bool has0 = mask != 0;
-    const int b0 = has0 ? mask_first(mask) : 0;
-    mask &= mask - 1;
-    const bool has1 = mask != 0;
-    const int b1 = has1 ? mask_first(mask) : 0;
-    mask &= mask - 1;
-    const bool has = h ? has1 : has0;
-    const int slot = h ? b1 : b0;
-    if (has && q[s * D] < INFINITY) {
+#pragma unroll
+  for (int s = 0; s < NB; ++s) {
+    if (mask != 0 && q[s * D] < INFINITY) {
+      const int slot = mask_first(mask);
       alive |= 1u << slot;
       float* row = mine + slot * D;
 #pragma unroll
       for (int k = 0; k < D; ++k) row[k] = q[s * D + k];
     }
+    mask &= mask - 1;
+    mask &= mask - 1;
+  }
+  return alive;
+}
+
+// the lane's live rows back to their slots; returns the mask of the GAME's slots still alive
+// (slot by slot with an early exit: where the width is not known at compile time -- the publish, the recording loop --
+// few slots are in use, and levels that read different sets of slots end up reading the rows from scratch memory)
+template <int M, int CH, int D, int SB = CH>
+__device__ __forceinline__ uint32_t duo_scatter(const float (&q)[CH * D], float* mine, uint32_t mask, int smax, int h) {
+  mask = h ? (mask & (mask - 1)) : mask;
+  uint32_t alive = 0;
+  unrolled_while<0, SB>([&](auto sc) {
+    constexpr int s = decltype(sc)::value;
+    if (s >= smax) return false;
+    if (mask != 0 && q[s * D] < INFINITY) {
+      const int slot = mask_first(mask);
+      alive |= 1u << slot;
+      float* row = mine + slot * D;
+#pragma unroll
+      for (int k = 0; k < D; ++k) row[k] = q[s * D + k];
+    }
+    mask &= mask - 1;
+    mask &= mask - 1;
     return true;
   });
   return lanes_or<2>(alive);
+}
+
+// `dead`: rows of the game's image to overwrite with the padding row; the pair shares them by rank
+template <int D>
+__device__ __forceinline__ void duo_pad_rows(float* mine, uint32_t dead, float pad, int h) {
+  dead = h ? (dead & (dead - 1)) : dead;
+  while (dead != 0) {
+    float* row = mine + mask_first(dead) * D;
+#pragma unroll
+    for (int k = 0; k < D; ++k) row[k] = pad;
+    dead &= dead - 1;
+    dead &= dead - 1;
+  }
 }
 
 // one pass over the lane's HALF of the game's image (rows h * ceil(M / 2) ...): bitmask of the fully available rows of
@@ -270,10 +373,6 @@ __device__ __forceinline__ int d_stages(float (&q)[CH * D], const float (&c)[D],
   if (stages & HK_STAGE_RESCALE) rescale<2, CH, D, NB>(q, flags);
   return live_rows<2, CH, D, NB>(q);
 }
-
-struct DuoLadder {  // slots per lane: 1..6, 8, 10, ...
-  static constexpr int next_bucket(int nb) { return nb < 6 ? nb + 1 : nb + 2; }
-};
 
 template <int CH, int D, int NB, bool BIN = false>
 struct DuoStagesFor {
@@ -500,11 +599,16 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
   static_assert(!ZEIL || (MODE == kModeRollout && HOT == kHotNone && !ACTS), "Zeillinger's host: plain rollouts");
   constexpr bool kRec = MODE == kModeRolloutRec;
   constexpr bool kRoll = MODE == kModeRollout || kRec;
+  // Plain rollouts of the lean shapes (DuoGeom::kLean) deal their rows level by level (duo_gather_level) and publish only
+  // the rows that changed.  Not Zeillinger's host for the publish: it parks rows by rank in the image between two deals.
+  constexpr bool kPartialPublish = MODE == kModeRollout && !ZEIL && DuoGeom<M, D>::kLean;
+  constexpr bool kLevelDeal = MODE == kModeRollout && DuoGeom<M, D>::kLean;
   using G = FastGeom<M, D>;
   constexpr int CH = DuoGeom<M, D>::CH;
   static_assert(M <= 32, "the live mask of a game travels as 32 bits");
   __shared__ __align__(16) float lds[kDuoGames * G::S];
   __shared__ float cbuf[kDuoGames * D];  // slow path only
+  __shared__ float hole_row[D];          // +inf: what the deal reads for a slot without a row (duo_gather_level)
   // plain rollouts: the policy words of a window of steps (duo_policy_fill)
   // (one row more than the window: the step loop requests the NEXT step's byte while it works on this one)
   __shared__ __align__(16) uint8_t pol[(MODE == kModeRollout) ? (4 * kDuoPreBlocks + 1) * kDuoGames : 16];
@@ -569,6 +673,7 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
   const bool fetch_actions = !kRoll && (stages & HK_STAGE_SHIFT) && active;
   if (fetch_actions) fast_fetch_actions<D>(prm, g, M, raw);
   duo_slab_commit<M, D>(slab, lds, ngames, lane);
+  if (kLevelDeal && lane < D) hole_row[lane] = INFINITY;
   if (fetch_actions) fast_decode_actions<D>(prm, raw, c, axis_in);
   __syncthreads();
 #ifdef HK_DUO_PROBE
@@ -645,15 +750,20 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
   }
 
   // ---- the pair's rows ----------------------------------------------------------------------------------
+  // plain rollouts publish only what changed (see the end of the kernel): the rows that are live now are parked in the
+  // slow path's buffer, which this path does not use otherwise -- not a register held across the loop
+  if (kPartialPublish && h == 0) reinterpret_cast<uint32_t*>(cbuf)[gi] = gmask;
   int smax = (nmax + 1) >> 1;
 #ifdef HK_DUO_PROBE
   probe_t1 = wall_clock64();
   probe_smax = smax;
 #endif
   float q[CH * D];
+  if constexpr (!kLevelDeal) {  // (the level deal writes every slot)
 #pragma unroll
-  for (int e = 0; e < CH * D; ++e) q[e] = INFINITY;
-  duo_gather<M, CH, D>(q, mine, gmask, smax, h);
+    for (int e = 0; e < CH * D; ++e) q[e] = INFINITY;
+  }
+  duo_gather<M, CH, D, kLevelDeal>(q, mine, hole_row, gmask, smax, h);
 #ifdef HK_DUO_PROBE
   {
     float sink = 0.0f;
@@ -805,12 +915,20 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
           // re-deal the rows when the widest game of the wave fits fewer slots per lane
           if (t + 1 < nsteps && !__any(active && ((np + 1) >> 1) >= smax)) {
             __syncthreads();
-            gmask = duo_scatter<M, CH, D, NB>(q, mine, gmask, smax, h);
-            __syncthreads();
-            const int sprev = smax;
-            nmax = wave_max(active ? np : 0, 2 * smax - 2);
-            smax = (nmax + 1) >> 1;
-            duo_gather<M, CH, D, NB>(q, mine, gmask, sprev, h);  // slots [smax, sprev) become holes again
+            if constexpr (kLevelDeal) {  // (LO < smax <= NB: this level's straight-line deal, no dispatch)
+              gmask = lanes_or<2>(duo_scatter_level<CH, D, NB>(q, mine, gmask, h));
+              __syncthreads();
+              nmax = wave_max(active ? np : 0, 2 * smax - 2);
+              smax = (nmax + 1) >> 1;
+              duo_gather_level<CH, D, NB>(q, mine, hole_row, gmask, h);  // slots [smax, NB) become holes again
+            } else {
+              gmask = duo_scatter<M, CH, D, NB>(q, mine, gmask, smax, h);
+              __syncthreads();
+              const int sprev = smax;
+              nmax = wave_max(active ? np : 0, 2 * smax - 2);
+              smax = (nmax + 1) >> 1;
+              duo_gather_slots<M, CH, D, NB>(q, mine, gmask, sprev, h);  // slots [smax, sprev) become holes again
+            }
           }
         }
 #ifdef HK_DUO_PROBE  // per-step stamps: the clock and the slots per lane after the step
@@ -907,25 +1025,37 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
       const int sprev = smax;
       nmax = wave_max(active ? np : 0, 2 * smax - 2);
       smax = (nmax + 1) >> 1;
-      duo_gather<M, CH, D>(q, mine, gmask, sprev, h);  // slots [smax, sprev) become holes again
+      duo_gather_slots<M, CH, D>(q, mine, gmask, sprev, h);  // slots [smax, sprev) become holes again
     }
   }
   if (kRoll && leader && prm.game_length_out) prm.game_length_out[g] = length;
 
-  // ---- publish: pad everywhere, live rows back in their slots --------------------------------------------------
+  // ---- publish ---------------------------------------------------------------------------------------------------
   __syncthreads();
-  if (h == 0) fill_image<M, D>(mine, pad);
-  __syncthreads();
-  if (kEndSort && end_sort) {
-    int rank[CH];
-    duo_ranks_first<CH, D>(q, smax, rank);
-    if (rescale_pending) rescale<2, CH, D, CH>(q, flags);
-    duo_scatter_ranked<CH, D>(q, mine, rank, smax);
+  if (kPartialPublish && !end_sort) {
+    // Rows keep their slots, and on this path every row of the loaded image was live or exactly the padding row
+    // (duo_scan_half, `exact`: fill == pad); the re-deals wrote live slots only.  So the image already holds the padding
+    // wherever a row was never live: the live rows go back to their slots, and the rows that were live at the start and
+    // are not any more take the padding -- no refill of the whole image, one barrier less.
+    const uint32_t alive = duo_scatter<M, CH, D>(q, mine, gmask, smax, h);
+    duo_pad_rows<D>(mine, reinterpret_cast<const uint32_t*>(cbuf)[gi] & ~alive, pad, h);
   } else {
-    duo_scatter<M, CH, D>(q, mine, gmask, smax, h);
+    // pad everywhere, live rows back in their slots (list semantics: in their rank's)
+    if (h == 0) fill_image<M, D>(mine, pad);
+    __syncthreads();
+    if (kEndSort && end_sort) {
+      int rank[CH];
+      duo_ranks_first<CH, D>(q, smax, rank);
+      if (rescale_pending) rescale<2, CH, D, CH>(q, flags);
+      duo_scatter_ranked<CH, D>(q, mine, rank, smax);
+    } else {
+      duo_scatter<M, CH, D>(q, mine, gmask, smax, h);
+    }
   }
   __syncthreads();
-  duo_store_slab<M, D, DuoGeom<M, D>::QH, (MODE == kModeRollout)>(lds, (float*)prm.out, prm.out_stride, g0, ngames, lane);
+  // (plain rollouts: write-through for the lean shapes; at (20,4) the descriptor's registers cost the third wave: nt)
+  constexpr int kFinalStore = MODE != kModeRollout ? kStorePlain : DuoGeom<M, D>::kLean ? kStoreWT : kStoreNT;
+  duo_store_slab<M, D, DuoGeom<M, D>::QH, kFinalStore>(lds, (float*)prm.out, prm.out_stride, g0, ngames, lane);
 #ifdef HK_DUO_PROBE
   if (kRoll && lane == 0 && prm.game_length_out && ngames >= 8) {
     int32_t* w = prm.game_length_out + g0;
