@@ -28,6 +28,10 @@ constexpr int kDuoGames = kWave / 2;
 __device__ __forceinline__ int duo_other_i(int v) { return qperm_i<0xB1>(v); }
 __device__ __forceinline__ float duo_other(float v) { return __int_as_float(duo_other_i(__float_as_int(v))); }
 
+// the wave's lanes with `p` as a scalar mask (a bool in, the compare's own mask out: __any / __ballot take an int and
+// put a select and a second compare in front of the branch)
+__device__ __forceinline__ uint64_t duo_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+
 template <int M, int D>
 struct DuoGeom {
   using G = FastGeom<M, D>;
@@ -360,12 +364,44 @@ __device__ __forceinline__ void d_newton(float (&q)[CH * D], int h) {
   }
 }
 
+// b_shift_mask without compares, for the one-slot level (a step on one slot per lane is a single dependent chain: nothing
+// fills the wait states between a compare and the select that reads it; at two slots per lane the hot (10,3) rollout
+// paid 19 registers and a wave per SIMD for it, so the wider levels keep the selects).  The subset's bits and the axis become
+// words of all ones / zero (v_bfe_i32); a coordinate joins the sum through AND -- zero gives +0.0 as the select did,
+// +inf stays +inf -- and the sum replaces the axis' coordinate through a bit-field insert.
+template <int CH, int D, int NB>
+__device__ __forceinline__ void d_shift_words(float (&q)[CH * D], uint32_t cmask, int axis, int np, unsigned flags) {
+  bool apply = true;
+  if (flags & HK_FLAG_AXIS_NOOP_IF_INVALID) apply = axis >= 0 && ((cmask >> axis) & 1u);
+  if ((flags & HK_FLAG_IGNORE_ENDED) && np < 2) apply = false;
+  const uint32_t onehot = apply ? 1u << (axis & 31) : 0u;  // (an axis past the dimension selects nothing, as k == axis did)
+  uint32_t isax[D], in[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    isax[k] = (uint32_t)((int32_t)(onehot << (31 - k)) >> 31);
+    in[k] = (uint32_t)((int32_t)(cmask << (31 - k)) >> 31);
+    asm volatile("" : "+v"(isax[k]), "+v"(in[k]));  // (left in sight, the words are turned back into compares and selects)
+  }
+#pragma unroll
+  for (int r = 0; r < NB; ++r) {
+    float s = __uint_as_float(__float_as_uint(q[r * D]) & in[0]);
+#pragma unroll
+    for (int k = 1; k < D; ++k) s = s + __uint_as_float(__float_as_uint(q[r * D + k]) & in[k]);  // order 0..D-1
+#pragma unroll
+    for (int k = 0; k < D; ++k)
+      q[r * D + k] = __uint_as_float((__float_as_uint(s) & isax[k]) | (__float_as_uint(q[r * D + k]) & ~isax[k]));
+  }
+}
+
 // one transition on slots [0, NB) of both lanes; returns the GAME's number of live rows
-template <int CH, int D, int NB, bool BIN = false>
+// (WORDS: the shift of a 0/1 subset as d_shift_words)
+template <int CH, int D, int NB, bool BIN = false, bool WORDS = false>
 __device__ __forceinline__ int d_stages(float (&q)[CH * D], const float (&c)[D], int axis, int np, int h,
                                         unsigned flags, unsigned stages, uint32_t cmask = 0) {
+  static_assert(!WORDS || BIN, "the subset as bits");
   if (stages & HK_STAGE_SHIFT) {
-    if constexpr (BIN) b_shift_mask<CH, D, NB>(q, cmask, axis, np, flags);
+    if constexpr (WORDS) d_shift_words<CH, D, NB>(q, cmask, axis, np, flags);
+    else if constexpr (BIN) b_shift_mask<CH, D, NB>(q, cmask, axis, np, flags);
     else b_shift<CH, D, NB>(q, c, axis, np, flags);
   }
   if (stages & HK_STAGE_REPOSITION) reposition<2, CH, D, NB, BIN>(q, flags);
@@ -833,11 +869,23 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
     // per-step dispatch over the buckets, and only the slots the bucket covers are loop-carried registers (a single
     // loop over all buckets moves the whole row array at every back edge: 16 v_mov_b64 per step at (20,3)). -------
     static_assert(CH <= 6 || CH % 2 == 0, "bucket ladder: 1..6, then even numbers");
+    // The wave's votes are scalar: a ballot, ANDed with the mask of the lanes that speak for a game (both lanes of a
+    // pair: `amask`; its first lane: `lmask`), and a branch on the AND's own condition code.
+    uint64_t amask = duo_ballot(active), lmask = duo_ballot(leader);
+    asm volatile("" : "+s"(amask), "+s"(lmask));
+    // A finished game stays finished, so its first finished step is the number of steps it was NOT finished after: a
+    // counter on the pair's first lane (the only one read), one add per step on the not-done mask the step has anyway.
+    // Games finished at entry start at -1, so that they read 0; a game never finished has counted every step.
+    int open_steps = (np < 2) ? -1 : 0;
+    auto length_at = [&](int tt) { return open_steps == tt ? -1 : open_steps + 1; };  // after tt steps (wave-uniform)
     int t = 0;
-    bool stop = false;
+    bool stop = false;  // (set under a scalar branch only)
     while (t < nsteps && !stop) {  // one pass per window of policy words (episodes of up to 24 steps: one pass)
     if (!ZEIL && (uint32_t)((step0 + (uint32_t)t) >> 2) - pol_b0 >= (uint32_t)kDuoPreBlocks) {
-      if constexpr (want_small) flush_records(__builtin_amdgcn_readfirstlane(t));
+      if constexpr (want_small) {
+        length = length_at(t);
+        flush_records(__builtin_amdgcn_readfirstlane(t));
+      }
       __syncthreads();
       pol_b0 = (step0 + (uint32_t)t) >> 2;
       const uint32_t nb = pol_last - pol_b0 + 1u;
@@ -853,91 +901,118 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
     uint32_t a_next = ZEIL ? 0u : pol[(int)(step0 + (uint32_t)t - (pol_b0 << 2)) * kDuoGames + gi];
     Levels<DuoLadder, CH>::run([&](auto nbc, auto loc) {
       constexpr int NB = decltype(nbc)::value, LO = decltype(loc)::value;
+      if (!((smax > LO || LO == 0) && t < tw && !stop)) return;  // (a wave of empty games has smax 0: the last loop's)
 #ifndef HK_NO_SETPRIO
       // The launch ends with its slowest waves -- the ones that start in a wide bucket or run many steps -- and the two
       // waves of a SIMD share its issue slots by priority, then age: a wave in a wide bucket outranks its neighbour
       // (who is ahead anyway), and so does one that is still running late in the episode.
-      if ((smax > LO || LO == 0) && t < tw && !stop) {
-        if (t >= 10) __builtin_amdgcn_s_setprio(3);
-        else if constexpr (NB >= 6) __builtin_amdgcn_s_setprio(3);
-        else if constexpr (NB >= 4) __builtin_amdgcn_s_setprio(2);
-        else if constexpr (NB >= 2) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
-      }
+      if (t >= 10) __builtin_amdgcn_s_setprio(3);
+      else if constexpr (NB >= 6) __builtin_amdgcn_s_setprio(3);
+      else if constexpr (NB >= 4) __builtin_amdgcn_s_setprio(2);
+      else if constexpr (NB >= 2) __builtin_amdgcn_s_setprio(1);
+      else __builtin_amdgcn_s_setprio(0);
 #endif
-      while (t < tw && (smax > LO || LO == 0) && !stop) {  // (a wave of empty games has smax 0: the last loop's)
-#ifndef HK_NO_SETPRIO
-        if constexpr (NB == 1) {
-          if (t == 10) __builtin_amdgcn_s_setprio(3);
-        }
-#endif
-        uint32_t mask;
-        int axis;
-        if constexpr (ZEIL) {
-          // (a game with fewer than two rows has no pair: class 0 -- a wave of finished games skips the test)
-          static_assert(NB <= kDuoZeilDpp || 2 * NB <= M, "the rolled pair loop parks ranks 0 .. 2 NB - 1 in the game's M rows");
-          const int zc = __any(active && np >= 2) ? duo_zeillinger<CH, D, NB>(q, h, mine, smax) : 0;
-          uint32_t ra, rb;
-          int cls;
-          duo_policy_words(gg, step0 + (uint32_t)t, seed, dcache, h, ra, rb);
-          policy_from_words<D>(ra, rb, host_policy, agent_policy, cls, axis, mask, zc);
-        } else {
-          const uint32_t a = a_next;
-          a_next = pol[(int)(step0 + (uint32_t)t + 1u - (pol_b0 << 2)) * kDuoGames + gi];  // (past the window: not used)
-          mask = a & 31u;
-          axis = (int)(a >> 5);
-        }
-        const unsigned st = (end_sort && t + 1 == nsteps) ? (stages & ~(unsigned)HK_STAGE_RESCALE) : stages;
-        rescale_pending = end_sort && t + 1 == nsteps && (stages & HK_STAGE_RESCALE);
-        np = d_stages<CH, D, NB, true>(q, c, axis, np, h, flags, st, mask);
-#ifdef HK_DUO_PROBE
-        if (lane == 0 && t == 0) probe_buf[20] = (int32_t)wall_clock64();  // step 0: the stages are done
-#endif
-        if (!active) np = 2;
-        const bool done = np < 2;
-        if (done && length < 0) length = t + 1;
-        // (the finished-game counts: ballots over the games' first finished steps after the loop -- a finished game
-        // stays finished --, not an atomic per step in here)
-        if constexpr (NB == 1) {
-          // Fixed point: a game that is down to ONE point sitting at the origin (or to none) does not change any
-          // more -- whatever the subset and the axis: the shift adds zeros, reposition / rescale find nothing to move,
-          // the Newton stage has nothing to compare.  Once every game of the wave is there (a game reaches it one
-          // step after it ends when reposition is on; the mean game lasts 5 steps, the longest of 32 about 13), the
-          // rest of the episode changes nothing.
-          if (t + 1 < nsteps && !__any(active && !done)) {
-            bool still = true;  // (one slot per lane: it holds the game's point, a hole, or nothing)
-#pragma unroll
-            for (int k = 0; k < D; ++k) still &= (q[k] == 0.0f);
-            still |= !(q[0] < INFINITY);
-            if (!__any(active && !still)) stop = true;
+      // steps [t, tend) at this level: ONE exit test per step; the rare ways out -- the wave's widest game fits the next
+      // level down, every game sits at its fixed point -- pull the loop's end in from inside their own branch
+      auto play = [&](int tend) {
+        while (t < tend) {
+          uint32_t mask;
+          int axis;
+          if constexpr (ZEIL) {
+            // (a game with fewer than two rows has no pair: class 0 -- a wave of finished games skips the test)
+            static_assert(NB <= kDuoZeilDpp || 2 * NB <= M, "the rolled pair loop parks ranks 0 .. 2 NB - 1 in the game's M rows");
+            const int zc = (duo_ballot(np >= 2) & amask) != 0 ? duo_zeillinger<CH, D, NB>(q, h, mine, smax) : 0;
+            uint32_t ra, rb;
+            int cls;
+            duo_policy_words(gg, step0 + (uint32_t)t, seed, dcache, h, ra, rb);
+            policy_from_words<D>(ra, rb, host_policy, agent_policy, cls, axis, mask, zc);
+          } else {
+            const uint32_t a = a_next;
+            a_next = pol[(int)(step0 + (uint32_t)t + 1u - (pol_b0 << 2)) * kDuoGames + gi];  // (past the window: not used)
+            mask = a & 31u;
+            axis = (int)(a >> 5);
           }
-        } else {
-          // re-deal the rows when the widest game of the wave fits fewer slots per lane
-          if (t + 1 < nsteps && !__any(active && ((np + 1) >> 1) >= smax)) {
-            __syncthreads();
-            if constexpr (kLevelDeal) {  // (LO < smax <= NB: this level's straight-line deal, no dispatch)
-              gmask = lanes_or<2>(duo_scatter_level<CH, D, NB>(q, mine, gmask, h));
-              __syncthreads();
-              nmax = wave_max(active ? np : 0, 2 * smax - 2);
-              smax = (nmax + 1) >> 1;
-              duo_gather_level<CH, D, NB>(q, mine, hole_row, gmask, h);  // slots [smax, NB) become holes again
-            } else {
-              gmask = duo_scatter<M, CH, D, NB>(q, mine, gmask, smax, h);
-              __syncthreads();
-              const int sprev = smax;
-              nmax = wave_max(active ? np : 0, 2 * smax - 2);
-              smax = (nmax + 1) >> 1;
-              duo_gather_slots<M, CH, D, NB>(q, mine, gmask, sprev, h);  // slots [smax, sprev) become holes again
+          const unsigned st = (end_sort && t + 1 == nsteps) ? (stages & ~(unsigned)HK_STAGE_RESCALE) : stages;
+          rescale_pending = end_sort && t + 1 == nsteps && (stages & HK_STAGE_RESCALE);
+          const int np_new = d_stages<CH, D, NB, true, (NB == 1)>(q, c, axis, np, h, flags, st, mask);
+#ifdef HK_DUO_PROBE
+          if (lane == 0 && t == 0) probe_buf[20] = (int32_t)wall_clock64();  // step 0: the stages are done
+#endif
+          // (the finished-game counts: ballots over the games' first finished steps after the loop -- a finished game
+          // stays finished --, not an atomic per step in here)
+          if constexpr (NB == 1) {
+            // one slot per lane: a game is not finished while both lanes of its pair hold a row -- the ballot of the live
+            // slots against itself one lane up, on the pair's first lane; the number of rows is never materialised
+            const uint64_t live = duo_ballot(q[0] < INFINITY);
+            const uint64_t open = live & (live >> 1) & lmask;
+            open_steps += __builtin_amdgcn_inverse_ballot_w64(open) ? 1 : 0;
+            np = __builtin_amdgcn_inverse_ballot_w64(open | (open << 1)) ? 2 : 0;  // (Zeillinger's host and the torch shift read it)
+            // Fixed point: a game that is down to ONE point sitting at the origin (or to none) does not change any
+            // more -- whatever the subset and the axis: the shift adds zeros, reposition / rescale find nothing to move,
+            // the Newton stage has nothing to compare.  Once every game of the wave is there (a game reaches it one
+            // step after it ends when reposition is on; the mean game lasts 5 steps, the longest of 32 about 13), the
+            // rest of the episode changes nothing.
+            if (open == 0) {
+              // (the slot holds the game's point, a hole, or nothing; coordinates are bit patterns in [+0, +inf]: the
+              // point is at the origin when the OR of its words is zero)
+              uint32_t any_bits = __float_as_uint(q[0]);
+#pragma unroll
+              for (int k = 1; k < D; ++k) any_bits |= __float_as_uint(q[k]);
+              if ((duo_ballot(any_bits != 0u) & live & amask) == 0) {
+                stop = true;
+                tend = 0;
+              }
+            }
+          } else {
+            np = np_new;
+            open_steps += (leader && np >= 2) ? 1 : 0;
+            // re-deal the rows when the widest game of the wave fits fewer slots per lane
+            if ((duo_ballot(np >= 2 * smax - 1) & amask) == 0) {
+              // (the test for the last step stays inside: pinned, or the two conditions are merged into one mask and the
+              // branch on the vote's own condition code is lost)
+              int left = nsteps - 1 - t;
+              asm volatile("" : "+s"(left));
+              if (left > 0) {
+                __syncthreads();
+                if constexpr (kLevelDeal) {  // (LO < smax <= NB: this level's straight-line deal, no dispatch)
+                  gmask = lanes_or<2>(duo_scatter_level<CH, D, NB>(q, mine, gmask, h));
+                  __syncthreads();
+                  nmax = wave_max(active ? np : 0, 2 * smax - 2);
+                  smax = (nmax + 1) >> 1;
+                  duo_gather_level<CH, D, NB>(q, mine, hole_row, gmask, h);  // slots [smax, NB) become holes again
+                } else {
+                  gmask = duo_scatter<M, CH, D, NB>(q, mine, gmask, smax, h);
+                  __syncthreads();
+                  const int sprev = smax;
+                  nmax = wave_max(active ? np : 0, 2 * smax - 2);
+                  smax = (nmax + 1) >> 1;
+                  duo_gather_slots<M, CH, D, NB>(q, mine, gmask, sprev, h);  // slots [smax, sprev) become holes again
+                }
+                tend = smax <= LO ? 0 : tend;  // the next level down takes over
+              }
             }
           }
-        }
 #ifdef HK_DUO_PROBE  // per-step stamps: the clock and the slots per lane after the step
-        if (lane == 0 && t < 24) probe_buf[t] = (int32_t)((((uint32_t)wall_clock64()) << 4) | (uint32_t)(smax & 15));
+          if (lane == 0 && t < 24) probe_buf[t] = (int32_t)((((uint32_t)wall_clock64()) << 4) | (uint32_t)(smax & 15));
 #endif
-        ++t;
+          ++t;
+        }
+      };
+      if constexpr (NB == 1) {
+        // the last level raises its priority at step 10: two loops, not a compare in every step
+        play(tw < 10 ? tw : 10);
+        if (t < tw && !stop) {
+#ifndef HK_NO_SETPRIO
+          __builtin_amdgcn_s_setprio(3);
+#endif
+          play(tw);
+        }
+      } else {
+        play(tw);
       }
     });
     }
+    length = length_at(t);
 #ifdef HK_DUO_PROBE
     probe_steps = t;
     probe_t2 = wall_clock64();
