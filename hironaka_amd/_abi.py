@@ -55,6 +55,7 @@ HK_SEARCH_NODE_LIMIT = 2
 HK_SEARCH_STACK_LIMIT = 4
 HK_SEARCH_INEXACT = 8
 HK_SEARCH_ROOT_ENDED = 16
+HK_SEARCH_ROOT_INVALID = 32  # hk_search_morin_tree
 
 SEMANTICS = {"jax": HK_SEM_JAX, "torch": HK_SEM_TORCH, "list": HK_SEM_LIST}
 
@@ -184,6 +185,9 @@ PROTOTYPES = {
     "hk_search_game_tree_workspace_bytes": (C.c_uint64, [_i, _i, _i, _i, _i, _i]),
     "hk_search_game_tree": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _vp, _u64, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _vp]),
+    "hk_search_morin_tree_workspace_bytes": (C.c_uint64, [_i, _i, _i, _i, _i, _i]),
+    "hk_search_morin_tree": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _vp, _u64, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 STATUS_TEXT = {

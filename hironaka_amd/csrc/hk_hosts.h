@@ -1,7 +1,8 @@
 // The deterministic hosts of hironaka/host.py beyond Zeillinger, on one game in list semantics (ListPoints): a row is
 // a point when p[i*d] >= 0 (the availability test of zeillinger_list_game: a NaN coordinate 0 is a hole), rows are
 // read in row order and holes may sit anywhere.  Each routine returns the class id (encode_mask) of the host's subset,
-// or -1 for "no subset".  Runtime m and d; d <= 6 for the hitting-set hosts (their support bitmap has 2^d bits).
+// or -1 for "no subset".  Runtime m and d; d <= 6 for the hitting-set hosts (their support bitmap has 2^d bits), d = 7
+// with the two-word bitmap that hk_search_morin_tree alone uses.
 //
 //   zeillinger_list_pair      Zeillinger / ZeillingerLex as ordered pairs (hk_search_game_tree's child order)
 //   zeillinger_lex_list_game  ZeillingerLex      host.py:116-127  (Zeillinger's key, ties broken lexicographically)
@@ -72,45 +73,85 @@ __device__ inline int zeillinger_lex_list_game(const T* p, int m, int d) {
   return r < 0 ? -1 : encode_mask((1u << (r >> 3)) | (1u << (r & 7)));
 }
 
+// The hitting-set hosts keep one bit per possible support: 2^d bits.  uint64_t serves d <= 6; Bits128 is the two-word
+// form for d = 7, which only hk_search_morin_tree instantiates.  The bm_* helpers are all the hosts need of either.
+struct Bits128 {
+  uint64_t lo, hi;
+};
+
+__device__ inline uint64_t bm_one(uint64_t) { return 1ull; }
+__device__ inline Bits128 bm_one(Bits128) { return Bits128{1ull, 0ull}; }
+__device__ inline void bm_set(uint64_t& b, uint32_t s) { b |= 1ull << s; }
+__device__ inline void bm_set(Bits128& b, uint32_t s) {
+  if (s < 64u) b.lo |= 1ull << s;
+  else b.hi |= 1ull << (s - 64u);
+}
+__device__ inline bool bm_test(uint64_t b, uint32_t s) { return ((b >> s) & 1ull) != 0; }
+__device__ inline bool bm_test(const Bits128& b, uint32_t s) {
+  return (((s < 64u ? b.lo : b.hi) >> (s & 63u)) & 1ull) != 0;
+}
+// b | (b << n), n a power of two: 1..32 for one word, 1..64 for two
+__device__ inline uint64_t bm_or_shl(uint64_t b, uint32_t n) { return b | (b << n); }
+__device__ inline Bits128 bm_or_shl(const Bits128& b, uint32_t n) {
+  if (n >= 64u) return Bits128{b.lo, b.hi | b.lo};
+  return Bits128{b.lo | (b.lo << n), b.hi | (b.hi << n) | (b.lo >> (64u - n))};
+}
+__device__ inline bool bm_disjoint(uint64_t a, uint64_t b) { return (a & b) == 0; }
+__device__ inline bool bm_disjoint(const Bits128& a, const Bits128& b) { return ((a.lo & b.lo) | (a.hi & b.hi)) == 0; }
+template <typename B>
+struct bm_log2 {
+  static constexpr int value = 6;
+};
+template <>
+struct bm_log2<Bits128> {
+  static constexpr int value = 7;
+};
+
 // Which supports occur: bit s of the result is set when some point's set of nonzero coordinates is s (x != 0: NaN
-// counts as nonzero and -0.0 as zero, as np.nonzero does).  d <= 6.  `npts` receives the number of points.
-template <typename T>
-__device__ inline uint64_t support_bitmap(const T* p, int m, int d, int& npts) {
-  uint64_t occ = 0;
+// counts as nonzero and -0.0 as zero, as np.nonzero does).  d <= 6 (B = uint64_t) or d <= 7 (Bits128).  `npts` receives
+// the number of points.
+template <typename T, typename B = uint64_t>
+__device__ inline B support_bitmap(const T* p, int m, int d, int& npts) {
+  B occ{};
   int n = 0;
   for (int i = 0; i < m; ++i) {
     if (!(p[i * d] >= (T)0)) continue;
     uint32_t s = 0;
     for (int k = 0; k < d; ++k) s |= (p[i * d + k] != (T)0) ? (1u << k) : 0u;
-    occ |= 1ull << s;
+    bm_set(occ, s);
     ++n;
   }
   npts = n;
   return occ;
 }
 
-// bit s set for every s that is a subset of x (x < 64): the supports a candidate with complement x misses
-__device__ inline uint64_t subsets_of(uint32_t x) {
-  uint64_t b = 1;  // {empty set}
-  for (int k = 0; k < 6; ++k)
-    if ((x >> k) & 1u) b |= b << (1u << k);
+// bit s set for every s that is a subset of x (x < 2^6, or 2^7 for Bits128): the supports a candidate with complement x
+// misses
+template <typename B = uint64_t>
+__device__ inline B subsets_of(uint32_t x) {
+  B b = bm_one(B{});  // {empty set}
+  for (int k = 0; k < bm_log2<B>::value; ++k)
+    if ((x >> k) & 1u) b = bm_or_shl(b, 1u << k);
   return b;
 }
 
 // c meets every occurring support: no support lies inside the complement of c
-__device__ inline bool hits_all(uint64_t occ, uint32_t c, uint32_t full) { return (occ & subsets_of(full & ~c)) == 0; }
+template <typename B>
+__device__ inline bool hits_all(const B& occ, uint32_t c, uint32_t full) {
+  return bm_disjoint(occ, subsets_of<B>(full & ~c));
+}
 
 // WeakSpivakovsky._select_coord (host.py:357-378): U = the union of the supports; candidates are the c within U with
 // |c| >= 2 that meet every support.  combinations(U, i) runs over sorted coordinate tuples in lexicographic order, so
 // the host takes the smallest |c|, then the lexicographically first tuple: for equal sizes, the largest bit-reversed c.
-template <typename T>
+template <typename T, typename B = uint64_t>
 __device__ inline int weak_spivakovsky_game(const T* p, int m, int d) {
   int npts;
-  const uint64_t occ = support_bitmap(p, m, d, npts);
+  const B occ = support_bitmap<T, B>(p, m, d, npts);
   if (npts < 2) return -1;
   const uint32_t full = (1u << d) - 1u;
   uint32_t U = 0;
-  for (uint32_t s = 0; s <= full; ++s) U |= ((occ >> s) & 1ull) ? s : 0u;
+  for (uint32_t s = 0; s <= full; ++s) U |= bm_test(occ, s) ? s : 0u;
   int best = -1, bestPc = 0;
   uint32_t bestRev = 0;
   for (uint32_t c = 3; c <= full; ++c) {
@@ -130,10 +171,10 @@ __device__ inline int weak_spivakovsky_game(const T* p, int m, int d) {
 // WeakSpivakovskyMinHitting._select_coord (host.py:381-427): candidates are all c with |c| >= 2 that meet every
 // support; subset_route orders them by (|c|, c).  The reference's masks have 16 bits: a bit >= d meets no support, so
 // the first hit lies within the d coordinates.
-template <typename T>
+template <typename T, typename B = uint64_t>
 __device__ inline int min_hitting_game(const T* p, int m, int d) {
   int npts;
-  const uint64_t occ = support_bitmap(p, m, d, npts);
+  const B occ = support_bitmap<T, B>(p, m, d, npts);
   if (npts < 2) return -1;
   const uint32_t full = (1u << d) - 1u;
   int best = -1, bestPc = 0;
@@ -147,13 +188,14 @@ __device__ inline int min_hitting_game(const T* p, int m, int d) {
 }
 
 // the class id a fixed host (HOST: HK_HOST_ALL_COORD .. HK_HOST_MIN_HITTING) picks on one game in list semantics
-template <typename T, int HOST>
+// (B: the support bitmap of the hitting-set hosts, uint64_t for d <= 6)
+template <typename T, int HOST, typename B = uint64_t>
 __device__ inline int host_class_game(const T* p, int m, int d) {
   if (HOST == HK_HOST_ALL_COORD) return encode_mask((1u << d) - 1u);
   if (HOST == HK_HOST_ZEILLINGER) return zeillinger_list_game(p, m, d);
   if (HOST == HK_HOST_ZEILLINGER_LEX) return zeillinger_lex_list_game(p, m, d);
-  if (HOST == HK_HOST_WEAK_SPIVAKOVSKY) return weak_spivakovsky_game(p, m, d);
-  return min_hitting_game(p, m, d);
+  if (HOST == HK_HOST_WEAK_SPIVAKOVSKY) return weak_spivakovsky_game<T, B>(p, m, d);
+  return min_hitting_game<T, B>(p, m, d);
 }
 
 // ---- host side of the fixed-host operators (hk_host_select, hk_search_depth, hk_search_game_tree) -------------------

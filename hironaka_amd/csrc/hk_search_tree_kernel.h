@@ -21,6 +21,8 @@
 // (L+2, ...): the children after the path child, the deepest parent first, as the reference creates them while its
 // recursion unwinds.  Last, the records are scattered into the outputs by id.
 //
+// The renumbering and the scatter are tree_finish, which hk_search_morin_kernel.h calls as well.
+//
 // Bounded by construction: records stop at max_nodes, the stack at stack_nodes, depth at max_depth; every loop of the
 // renumbering runs over recorded batches or up a parent chain of strictly decreasing record indices.
 #pragma once
@@ -54,8 +56,8 @@ inline uint64_t search_tree_int_words(int max_nodes, int stack_nodes) {
 
 // The host's list for one game, in the reference's order.  Zeillinger and ZeillingerLex return [argmin v, argmax v]
 // of the chosen pair (host.py:90-95, :116-127), or [0, 1] when they coincide: `order` packs the axes 3 bits each.  The
-// other hosts' lists are ascending.  Returns the class id of the set, -1 for no list (nc = 0).
-template <typename T, int HOST>
+// other hosts' lists are ascending.  Returns the class id of the set, -1 for no list (nc = 0).  B as in host_class_game.
+template <typename T, int HOST, typename B = uint64_t>
 __device__ inline int host_order_game(const T* p, int m, int d, uint32_t& order, int& nc) {
   order = 0;
   nc = 0;
@@ -66,12 +68,137 @@ __device__ inline int host_order_game(const T* p, int m, int d, uint32_t& order,
     nc = 2;
     return encode_mask((1u << (r >> 3)) | (1u << (r & 7)));
   }
-  const int cls = host_class_game<T, HOST>(p, m, d);
+  const int cls = host_class_game<T, HOST, B>(p, m, d);
   if (cls < 0) return -1;
   const uint32_t sub = decode_class(cls, d);
   for (int j = 0; j < d; ++j)
     if ((sub >> j) & 1u) order |= (uint32_t)j << (3 * nc++);
   return cls;
+}
+
+// The record fields of one root in rec_ints, each max_nodes long, then the batch starts and the stack
+struct TreeRecords {
+  int32_t *par, *chd, *ax, *dep, *np, *cls, *first, *size, *id, *bstart, *stk;
+  __device__ TreeRecords(int32_t* iw, int M)
+      : par(iw), chd(par + M), ax(chd + M), dep(ax + M), np(dep + M), cls(np + M), first(cls + M), size(first + M),
+        id(size + M), bstart(id + M),  // M + 1: batch b holds the records [bstart[b], bstart[b+1])
+        stk(bstart + M + 1) {}
+};
+
+// the outputs the tree operators share, [batch, max_nodes] each
+template <typename T>
+struct TreeOutputs {
+  int32_t *parent, *child_index, *axis, *depth, *num_points, *host_class;
+  T* states;
+  int32_t *count, *status;
+};
+
+// After the traversal: the renumbering and the scatter by id (see the head of this file), for hk_search_game_tree and
+// hk_search_morin_tree.  children(r): the child records of an expanded record r, contiguous from first[r]; rank(r): r's
+// position among its siblings' records; expandable(r): whether the reference would expand r (apart from its depth);
+// extra(r, o): writes the operator's own outputs of record r to slot o.
+template <typename T, typename Children, typename Rank, typename Expandable, typename Extra>
+__device__ inline void tree_finish(const TreeRecords& rec, const T* rst, const TreeOutputs<T>& out, size_t root, int lane,
+                                   int n, int M, int d, int nrec, int nb, long long L, int max_depth, int status,
+                                   int* slot_dst, int& sh_last, int& sh_count, Children children, Rank rank,
+                                   Expandable expandable, Extra extra) {
+  int32_t *const rpar = rec.par, *const rchd = rec.chd, *const rax = rec.ax, *const rdep = rec.dep, *const rnp = rec.np,
+                 *const rcls = rec.cls, *const rfirst = rec.first, *const rsize = rec.size, *const rid = rec.id,
+                 *const bstart = rec.bstart;
+  const size_t out0 = root * (size_t)M;
+  if (status & (HK_SEARCH_NODE_LIMIT | HK_SEARCH_STACK_LIMIT | HK_SEARCH_INEXACT)) {
+    if (lane == 0) {
+      out.count[root] = nrec;
+      out.status[root] = status;
+    }
+    return;
+  }
+
+  // subtree sizes, bottom-up: a batch's children lie in later batches
+  for (int b = nb - 1; b >= 0; --b) {
+    for (int r = bstart[b] + lane; r < bstart[b + 1]; r += kWave) {
+      const int f = rfirst[r];
+      if (f < 0) continue;
+      const int cnt = children(r);
+      int s = 1;
+      for (int i = 0; i < cnt; ++i) s += rsize[f + i];
+      rsize[r] = s;
+    }
+    __syncthreads();
+  }
+  // preorder ids, top-down; -1 beyond L+1
+  if (lane == 0) {
+    rid[0] = 0;
+    sh_last = -1;  // the record numbered L+1, if the tree has one
+  }
+  __syncthreads();
+  for (int b = 1; b < nb; ++b) {
+    for (int r = bstart[b] + lane; r < bstart[b + 1]; r += kWave) {
+      const int pid = rid[rpar[r]];
+      int id = -1;
+      if (pid >= 0) {
+        long long v = (long long)pid + 1;
+        for (int t = 1, e = rank(r); t <= e; ++t) v += rsize[r - t];
+        if (v <= L + 1) id = (int)v;
+        if (v == L + 1) sh_last = r;
+      }
+      rid[r] = id;
+    }
+    __syncthreads();
+  }
+  // the trailing siblings, numbered from L+2 while walking up from node L+1
+  if (lane == 0) {
+    int count = nrec;
+    if (sh_last >= 0) {
+      int next = (int)(L + 2);
+      for (int cur = sh_last; cur > 0;) {
+        const int p = rpar[cur], ci = rank(cur);
+        const int cnt = children(p);
+        for (int k = ci + 1; k < cnt; ++k) rid[cur - ci + k] = next++;
+        cur = p;
+      }
+      count = next;
+    }
+    sh_count = count;
+  }
+  __syncthreads();
+  const int count = sh_count;
+
+  // scatter by id
+  T* sout = out.states;
+  bool cut = false;
+  for (int cb = 0; cb < nrec; cb += kWave) {
+    const int r = cb + lane;
+    int id = r < nrec ? rid[r] : -1;
+    if (id >= count) id = -1;  // not reached: ids are < count by construction
+    if (id >= 0) {
+      const size_t o = out0 + (size_t)id;
+      const bool inside = id <= L;  // expanded by the reference when it holds >= 2 points
+      out.parent[o] = r == 0 ? -1 : rid[rpar[r]];
+      out.child_index[o] = rchd[r];
+      out.axis[o] = rax[r];
+      out.depth[o] = rdep[r];
+      out.num_points[o] = rnp[r];
+      out.host_class[o] = inside && expandable(r) && rdep[r] < max_depth ? rcls[r] : -1;
+      cut |= inside && expandable(r) && rdep[r] >= max_depth;
+      extra(r, o);
+    }
+    if (sout) {
+      slot_dst[lane] = id;
+      __syncthreads();
+      const int cn = nrec - cb < kWave ? nrec - cb : kWave;
+      for (int e = lane; e < cn * n; e += kWave) {  // wave_copy_states, but only the records that have an id
+        const int s = e / n;
+        if (slot_dst[s] >= 0) sout[(out0 + (size_t)slot_dst[s]) * n + (e - s * n)] = rst[(size_t)(cb + s) * n + (e - s * n)];
+      }
+      __syncthreads();
+    }
+  }
+  if (__ballot(cut)) status |= HK_SEARCH_DEPTH_LIMIT;
+  if (lane == 0) {
+    out.count[root] = count;
+    out.status[root] = status;
+  }
 }
 
 // HOST: the host code, one instantiation per host
@@ -88,19 +215,10 @@ __global__ void __launch_bounds__(kWave) search_tree_kernel(SearchTreeArgs a) {
   const size_t root = blockIdx.x;
   const T* src = static_cast<const T*>(a.points) + root * (size_t)n;
   T* rst = static_cast<T*>(a.rec_states) + root * (size_t)M * n;
-  int32_t* iw = a.rec_ints + root * a.rec_int_stride;
-  int32_t* rpar = iw;
-  int32_t* rchd = rpar + M;
-  int32_t* rax = rchd + M;
-  int32_t* rdep = rax + M;
-  int32_t* rnp = rdep + M;
-  int32_t* rcls = rnp + M;
-  int32_t* rfirst = rcls + M;
-  int32_t* rsize = rfirst + M;
-  int32_t* rid = rsize + M;
-  int32_t* bstart = rid + M;   // M + 1: batch b holds the records [bstart[b], bstart[b+1])
-  int32_t* stk = bstart + M + 1;
-  const size_t out0 = root * (size_t)M;
+  const TreeRecords rec(a.rec_ints + root * a.rec_int_stride, M);
+  int32_t *const rpar = rec.par, *const rchd = rec.chd, *const rax = rec.ax, *const rdep = rec.dep, *const rnp = rec.np,
+                 *const rcls = rec.cls, *const rfirst = rec.first, *const rsize = rec.size, *const bstart = rec.bstart,
+                 *const stk = rec.stk;
   const long long L = a.expand_limit < 0 ? LLONG_MAX - 1 : a.expand_limit;
 
   // the root: record 0, batch 0
@@ -192,98 +310,12 @@ __global__ void __launch_bounds__(kWave) search_tree_kernel(SearchTreeArgs a) {
   }
   __syncthreads();
 
-  if (status & (HK_SEARCH_NODE_LIMIT | HK_SEARCH_STACK_LIMIT | HK_SEARCH_INEXACT)) {
-    if (lane == 0) {
-      a.count_out[root] = nrec;
-      a.status_out[root] = status;
-    }
-    return;
-  }
-
-  // subtree sizes, bottom-up: a batch's children lie in later batches
-  for (int b = nb - 1; b >= 0; --b) {
-    for (int r = bstart[b] + lane; r < bstart[b + 1]; r += kWave) {
-      const int f = rfirst[r];
-      if (f < 0) continue;
-      const int cnt = __popc(decode_class(rcls[r], d));
-      int s = 1;
-      for (int i = 0; i < cnt; ++i) s += rsize[f + i];
-      rsize[r] = s;
-    }
-    __syncthreads();
-  }
-  // preorder ids, top-down; -1 beyond L+1
-  if (lane == 0) {
-    rid[0] = 0;
-    sh_last = -1;  // the record numbered L+1, if the tree has one
-  }
-  __syncthreads();
-  for (int b = 1; b < nb; ++b) {
-    for (int r = bstart[b] + lane; r < bstart[b + 1]; r += kWave) {
-      const int pid = rid[rpar[r]];
-      int id = -1;
-      if (pid >= 0) {
-        long long v = (long long)pid + 1;
-        for (int t = 1; t <= rchd[r]; ++t) v += rsize[r - t];
-        if (v <= L + 1) id = (int)v;
-        if (v == L + 1) sh_last = r;
-      }
-      rid[r] = id;
-    }
-    __syncthreads();
-  }
-  // the trailing siblings, numbered from L+2 while walking up from node L+1
-  if (lane == 0) {
-    int count = nrec;
-    if (sh_last >= 0) {
-      int next = (int)(L + 2);
-      for (int cur = sh_last; cur > 0;) {
-        const int p = rpar[cur], ci = rchd[cur];
-        const int cnt = __popc(decode_class(rcls[p], d));
-        for (int k = ci + 1; k < cnt; ++k) rid[cur - ci + k] = next++;
-        cur = p;
-      }
-      count = next;
-    }
-    sh_count = count;
-  }
-  __syncthreads();
-  const int count = sh_count;
-
-  // scatter by id
-  T* sout = static_cast<T*>(a.states_out);
-  bool cut = false;
-  for (int cb = 0; cb < nrec; cb += kWave) {
-    const int r = cb + lane;
-    int id = r < nrec ? rid[r] : -1;
-    if (id >= count) id = -1;  // not reached: ids are < count by construction
-    if (id >= 0) {
-      const size_t o = out0 + (size_t)id;
-      const bool inside = id <= L;  // expanded by the reference when it holds >= 2 points
-      a.parent_out[o] = r == 0 ? -1 : rid[rpar[r]];
-      a.child_index_out[o] = rchd[r];
-      a.axis_out[o] = rax[r];
-      a.depth_out[o] = rdep[r];
-      a.num_points_out[o] = rnp[r];
-      a.host_class_out[o] = inside && rnp[r] >= 2 && rdep[r] < a.max_depth ? rcls[r] : -1;
-      cut |= inside && rnp[r] >= 2 && rdep[r] >= a.max_depth;
-    }
-    if (sout) {
-      slot_dst[lane] = id;
-      __syncthreads();
-      const int cn = nrec - cb < kWave ? nrec - cb : kWave;
-      for (int e = lane; e < cn * n; e += kWave) {  // wave_copy_states, but only the records that have an id
-        const int s = e / n;
-        if (slot_dst[s] >= 0) sout[(out0 + (size_t)slot_dst[s]) * n + (e - s * n)] = rst[(size_t)(cb + s) * n + (e - s * n)];
-      }
-      __syncthreads();
-    }
-  }
-  if (__ballot(cut)) status |= HK_SEARCH_DEPTH_LIMIT;
-  if (lane == 0) {
-    a.count_out[root] = count;
-    a.status_out[root] = status;
-  }
+  const TreeOutputs<T> out{a.parent_out, a.child_index_out, a.axis_out, a.depth_out, a.num_points_out,
+                           a.host_class_out, static_cast<T*>(a.states_out), a.count_out, a.status_out};
+  tree_finish(
+      rec, rst, out, root, lane, n, M, d, nrec, nb, L, a.max_depth, status, slot_dst, sh_last, sh_count,
+      [&](int r) { return __popc(decode_class(rcls[r], d)); }, [&](int r) { return rchd[r]; },
+      [&](int r) { return rnp[r] >= 2; }, [](int, size_t) {});
 }
 
 }  // namespace hk

@@ -1,6 +1,6 @@
-// What hk_search_depth and hk_search_game_tree share: one workgroup of one wave per root, whose lanes expand one node
-// each in a private slice of the dynamic LDS; and the whole-wave copy of states between those slices and memory that
-// hk_search_game_tree uses.
+// What hk_search_depth, hk_search_game_tree and hk_search_morin_tree share: one workgroup of one wave per root, whose
+// lanes expand one node each in a private slice of the dynamic LDS; and the whole-wave copy of states between those
+// slices and memory that the two tree operators use.
 #pragma once
 
 #include "hk_hosts.h"
@@ -9,9 +9,9 @@ namespace hk {
 
 constexpr int kSearchLdsBytes = 64 * 1024;  // dynamic LDS per workgroup: two or more roots share a CU
 
-// LDS elements per lane: parent, child, the shift coefficients c and sort_compact's row scratch; odd, so that the
-// lanes' private slices start in different banks
-inline int search_lds_stride(int m, int d) { return (2 * m * d + 2 * d) | 1; }
+// LDS elements per lane: parent, child, the shift coefficients c, sort_compact's row scratch and `extra` elements
+// behind them that a kernel keeps for itself; odd, so that the lanes' private slices start in different banks
+inline int search_lds_stride(int m, int d, int extra = 0) { return (2 * m * d + 2 * d + extra) | 1; }
 
 // A lane's slice of the dynamic LDS, laid out as search_lds_stride counts it
 template <typename T>
@@ -23,9 +23,10 @@ struct LaneSlice {
 
 // Launches kernel over `batch` roots, one wave each, after filling in a.lds_stride and a.lanes (the lanes whose slices
 // fit into kSearchLdsBytes, at most a wave).  Args: the kernel's argument block, with m, d, lds_stride and lanes.
+// extra_lds: elements a lane keeps behind LaneSlice::row.
 template <typename T, typename Args>
-int launch_search(void (*kernel)(Args), Args a, int batch, hipStream_t stream) {
-  a.lds_stride = search_lds_stride(a.m, a.d);
+int launch_search(void (*kernel)(Args), Args a, int batch, hipStream_t stream, int extra_lds = 0) {
+  a.lds_stride = search_lds_stride(a.m, a.d, extra_lds);
   const int per_lane = a.lds_stride * (int)sizeof(T);
   a.lanes = kSearchLdsBytes / per_lane < kWave ? kSearchLdsBytes / per_lane : kWave;
   const size_t lds = (size_t)a.lanes * per_lane;
@@ -54,11 +55,12 @@ __device__ inline int lane_rank(unsigned long long b) {
   return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
 }
 
-// exclusive prefix over the lanes of a per-lane count in 0..6, and the wave's total
+// exclusive prefix over the lanes of a per-lane count in 0..MAXV, and the wave's total
+template <int MAXV = 6>
 __device__ inline int lane_prefix(int v, int& total) {
   int pre = 0;
   total = 0;
-  for (int j = 0; j < 6; ++j) {
+  for (int j = 0; j < MAXV; ++j) {
     const unsigned long long b = __ballot(v > j);
     pre += lane_rank(b);
     total += (int)__popcll(b);

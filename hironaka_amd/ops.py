@@ -753,3 +753,46 @@ def search_game_tree(points: torch.Tensor, host: str, *, expand_limit: Optional[
             [((b,), torch.int32, 0)] * 2)
     return tuple(_search_launch(lib().hk_search_game_tree, "hk_search_game_tree", pts, host,
                                 (lim, max_depth, max_nodes, stack_nodes), per_root, outs))
+
+
+def search_morin_tree(points: torch.Tensor, weights: torch.Tensor, distinguished: torch.Tensor, host: str, *,
+                      expand_limit: Optional[int], max_depth: int, max_nodes: int, stack_nodes: int,
+                      states: bool = True) -> Tuple[torch.Tensor, ...]:
+    """The Morin game tree under a fixed host (hironaka/util/search.py:53-93 search_tree_morin,
+    hk_search_morin_tree): search_game_tree's tree with integer weights and a distinguished point per node, actions
+    pruned by weight and "No contribution" leaves where the point is lost.  points: [B, m, d] float32/float64 roots
+    as for search_game_tree, d in 2..7.  weights: [B, d] integers >= 0.  distinguished: [B] row indices.  Returns
+    (parent, child_index, axis, depth, num_points, host_class, kind, distinguished) int32 [B, max_nodes], weights
+    int32 [B, max_nodes, d], states [B, max_nodes, m, d] (None unless ``states``), count int32 [B] and status int32
+    [B].  Slots from count on hold -1.  HK_SEARCH_ROOT_INVALID marks a root whose distinguished index addresses no
+    point or that has a negative weight (count 1)."""
+    pts = _search_checks(points, host, max_depth, max_nodes, stack_nodes, 31, expand_limit)
+    b, m, d = pts.shape
+    for t, name, shape in ((weights, "weights", (b, d)), (distinguished, "distinguished", (b,))):
+        _require_device(t, name)
+        if t.dtype not in (torch.int32, torch.int64) or tuple(t.shape) != shape or t.device != pts.device:
+            raise ValueError(f"{name} must be an int32/int64 tensor of shape {shape} on the roots' device. Got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}.")
+        if t.numel() and int(t.abs().max()) >= 2 ** 31:
+            raise ValueError(f"{name} must fit int32.")
+    wts = weights.to(torch.int32).contiguous()
+    dist = distinguished.to(torch.int32).contiguous()
+    lim = -1 if expand_limit is None else int(expand_limit)
+    per_root = lib().hk_search_morin_tree_workspace_bytes(1, m, d, _TORCH2HK[pts.dtype], max_nodes, stack_nodes)
+    fn, name = lib().hk_search_morin_tree, "hk_search_morin_tree"
+    head = (m, d, _TORCH2HK[pts.dtype], SEARCH_HOSTS[host], lim, max_depth, max_nodes, stack_nodes)
+    n_out = 12
+    if per_root == 0:  # the C entry refuses the arguments: one call with batch 1 and no buffers raises its status
+        check(fn(None, None, None, 1, *head, None, 0, *([None] * n_out), None), name)
+    outs = ([torch.full((b, max_nodes), -1, dtype=torch.int32, device=pts.device) for _ in range(8)] +
+            [torch.full((b, max_nodes, d), -1, dtype=torch.int32, device=pts.device),
+             torch.full((b, max_nodes, m, d), -1, dtype=pts.dtype, device=pts.device) if states else None,
+             torch.zeros(b, dtype=torch.int32, device=pts.device), torch.zeros(b, dtype=torch.int32, device=pts.device)])
+    chunk = max(1, min(b, _SEARCH_WORKSPACE_BYTES // max(per_root, 1)))
+    with torch.cuda.device(pts.device):
+        ws = torch.empty(per_root * chunk if b else 0, dtype=torch.uint8, device=pts.device)
+        for lo in range(0, b, chunk):
+            ptrs = [None if t is None else t[lo].data_ptr() for t in outs]
+            check(fn(pts[lo].data_ptr(), wts[lo].data_ptr(), dist[lo].data_ptr(), min(chunk, b - lo), *head,
+                     ws.data_ptr(), ws.numel(), *ptrs, _stream(pts)), name)
+    return tuple(outs)

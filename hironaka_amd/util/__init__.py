@@ -1,6 +1,6 @@
 """Tools that study a host strategy itself -- the counterpart of ``hironaka/util`` (search.py)."""
-from .search import (SearchDepthResult, SearchTreeResult, TreeNodeData, search_depth, search_depths, search_tree,
-                     search_trees)
+from .search import (MorinTreeResult, SearchDepthResult, SearchTreeResult, TreeNodeData, search_depth, search_depths,
+                     search_tree, search_tree_morin, search_trees, search_trees_morin)
 
-__all__ = ["SearchDepthResult", "SearchTreeResult", "TreeNodeData", "search_depth", "search_depths", "search_tree",
-           "search_trees"]
+__all__ = ["MorinTreeResult", "SearchDepthResult", "SearchTreeResult", "TreeNodeData", "search_depth", "search_depths",
+           "search_tree", "search_tree_morin", "search_trees", "search_trees_morin"]

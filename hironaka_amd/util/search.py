@@ -6,9 +6,18 @@ any number of roots per call.
 order, built on the GPU (hk_search_game_tree) and handed to any tree object with ``size()`` and ``create_node``
 (treelib's ``Tree`` among them).  ``search_trees`` returns the trees of a batch of roots as tensors.
 
-The reference's ``search_tree_morin`` and the JAX ``search_tree_fix_host`` are not built here.
+``search_tree_morin`` (hironaka/util/search.py:53-93): the Morin game tree, where every node also carries integer
+weights and a distinguished point; actions are pruned by weight and a child that loses the point is a
+"No contribution" leaf.  Built on the GPU (hk_search_morin_tree, dim 2..7) and handed over like ``search_tree``,
+with the reference's "...more..." nodes added where it stops at ``max_size``.  ``search_trees_morin`` returns the
+trees of a batch of roots as tensors.
+
+The JAX ``search_tree_fix_host`` is not built here.
 """
+from collections import namedtuple
 from typing import NamedTuple, Optional
+
+import numpy as np
 
 import torch
 
@@ -22,6 +31,7 @@ DEFAULT_STACK_NODES = 1 << 16  # per root, for one root (the 5552-deep reference
 DEFAULT_BATCH_STACK_NODES = 1 << 12  # per root of a batch; ops.search_depth splits a batch to bound the workspace
 DEFAULT_TREE_NODES = 1 << 21  # search_tree: one root; the 5552-deep reference tree has 1 128 897 nodes
 DEFAULT_BATCH_TREE_NODES = 1 << 14  # search_trees: per root of a batch
+DEFAULT_MORIN_NODES = 1 << 18  # search_tree_morin: one root; weight pruning keeps the Thom trees in the hundreds
 
 _LIMITS = ((A.HK_SEARCH_DEPTH_LIMIT, "max_depth"), (A.HK_SEARCH_NODE_LIMIT, "max_nodes"),
            (A.HK_SEARCH_STACK_LIMIT, "stack_nodes"),
@@ -189,4 +199,128 @@ def search_tree(points, tree, curr_node, host, max_size=100, *, max_depth: Optio
     ident = [curr_node] + [s0 + j - 1 for j in range(1, count)]
     for j in range(1, count):
         tree.create_node(ident[j], ident[j], parent=ident[par[j]], data=TreeNodeData(_node_points(states[j])))
+    return tree
+
+
+class MorinTreeResult(NamedTuple):
+    parent: torch.Tensor         # int32 [B, max_nodes]: as SearchTreeResult
+    child_index: torch.Tensor    # int32 [B, max_nodes]: the position in the parent's host list; pruned actions are gaps
+    axis: torch.Tensor           # int32 [B, max_nodes]
+    depth: torch.Tensor          # int32 [B, max_nodes]
+    num_points: torch.Tensor     # int32 [B, max_nodes]
+    host_class: torch.Tensor     # int32 [B, max_nodes]: an expanded node's host subset (class id), else -1
+    kind: torch.Tensor           # int32 [B, max_nodes]: 0 a contributing node, 1 "No contribution"
+    distinguished: torch.Tensor  # int32 [B, max_nodes]: the distinguished point's row in states, -1 for kind 1
+    weights: torch.Tensor        # int32 [B, max_nodes, d]
+    states: Optional[torch.Tensor]  # [B, max_nodes, m, d]: list semantics, padding -1; None unless states=True
+    count: torch.Tensor          # int32 [B]: the nodes; slots from count on hold -1
+    status: torch.Tensor         # int32 [B]: 0, or an OR of A.HK_SEARCH_* bits
+
+
+MorinNode = namedtuple("Node", ["points"])  # a node's data, as the reference's namedtuple Node(points=str)
+NO_CONTRIBUTION = "No contribution"
+MORE = "...more..."
+
+
+def _int_vector(values, name: str) -> list:
+    # a list of Python ints; integral floats are accepted, anything else is a ValueError
+    if isinstance(values, torch.Tensor):
+        values = values.tolist()
+    arr = np.asarray(values)
+    if arr.ndim != 1 or arr.dtype.kind not in "iuf" or (arr.dtype.kind == "f" and not np.all(arr == np.floor(arr))):
+        raise ValueError(f"{name} must be a list or array of integers. Got {values!r}.")
+    return [int(v) for v in arr.tolist()]
+
+
+def search_trees_morin(points, weights, distinguished, host, *, max_size: Optional[int] = None,
+                       max_depth: int = DEFAULT_MAX_DEPTH, max_nodes: int = DEFAULT_BATCH_TREE_NODES,
+                       stack_nodes: int = DEFAULT_BATCH_STACK_NODES, states: bool = True,
+                       dtype: Optional[torch.dtype] = None) -> MorinTreeResult:
+    """The reference's ``search_tree_morin`` for a batch of roots [B, m, d] with weights [B, d] and distinguished row
+    indices [B] (tensors or nested lists), as padded tensors.  ``max_size`` counts as in ``search_trees``.  The
+    result holds the kernel's nodes only, no "...more..." nodes.  Nothing is raised for a non-zero status: read
+    ``status`` (A.HK_SEARCH_ROOT_INVALID: the index addresses no point, or a weight is negative)."""
+    name = _host_name(host)
+    if max_size is not None and max_size < 1:
+        raise ValueError(f"max_size must be None or >= 1 (the root is in the tree). Got {max_size}.")
+    roots = _roots(points, dtype)
+    wts = torch.as_tensor(weights).to(roots.device)
+    dist = torch.as_tensor(distinguished).to(roots.device)
+    if wts.dim() == 1:
+        wts = wts.unsqueeze(0)
+    if dist.dim() == 0:
+        dist = dist.unsqueeze(0)
+    res = ops.search_morin_tree(roots, wts, dist, name, expand_limit=None if max_size is None else max_size - 1,
+                                max_depth=max_depth, max_nodes=max_nodes, stack_nodes=stack_nodes, states=states)
+    return MorinTreeResult(*res)
+
+
+def search_tree_morin(points, tree, curr_node, curr_weights, host, max_size=100, *, distinguished: Optional[int] = None,
+                      max_depth: Optional[int] = None, max_nodes: Optional[int] = None,
+                      stack_nodes: Optional[int] = None):
+    """The reference's ``search_tree_morin(points, tree, curr_node, curr_weights, host, max_size=100)``: builds the
+    Morin game tree under ``host`` below ``curr_node``, which the caller has already created in ``tree``, and adds
+    its nodes with ``tree.create_node(node_id, node_id, parent=..., data=Node(points=str))`` in the reference's
+    order, node_id = tree.size().  A node's data string is ``str([state]) + ", [dist]"``, "No contribution" where the
+    distinguished point was lost, or "...more..." below every contributing node that the reference reaches with
+    ``tree.size() > max_size``.  Always returns ``tree``.  ``max_size`` None builds the whole tree.
+    ``points``: a HipPoints of batch 1 whose ``distinguished_points[0]`` names the point, or a [m, d] / [1, m, d]
+    tensor or nested lists with ``distinguished=``.  ``curr_weights``: a list or numpy array of non-negative integers.
+    ValueError when no index is given or it addresses no point; RuntimeError names the limit when the tree did not
+    fit (``max_nodes``, ``stack_nodes``) or left the exact integer range.  ``max_nodes`` bounds the nodes the traversal
+    records, which with a ``max_size`` exceed the nodes kept: up to one node per lane and iteration is expanded before
+    the ones beyond ``max_size`` are dropped (23 018 records for the 151 nodes of the Thom N = 4 root under
+    AllCoordHost at max_size=100)."""
+    name = _host_name(host)
+    weights = _int_vector(curr_weights, "curr_weights")
+    if distinguished is None:
+        given = getattr(points, "distinguished_points", None)
+        distinguished = given[0] if given else None
+    if distinguished is None or isinstance(distinguished, bool) or int(distinguished) != distinguished:
+        raise ValueError("search_tree_morin needs the distinguished point's row index: a HipPoints with "
+                         f"distinguished_points, or distinguished=. Got {distinguished!r}.")
+    distinguished = int(distinguished)
+    roots = _one_root(points, "search_tree_morin")
+    if len(weights) != roots.shape[2]:
+        raise ValueError(f"curr_weights must have one weight per coordinate ({roots.shape[2]}). Got {len(weights)}.")
+    if min(weights) < 0:
+        raise ValueError(f"curr_weights must not be negative. Got {weights}.")
+    s0 = tree.size()
+    if max_size is not None and s0 > max_size:
+        tree.create_node(s0, s0, parent=curr_node, data=MorinNode(MORE))
+        return tree
+    if not 0 <= distinguished < roots.shape[1]:
+        raise ValueError(f"distinguished must address a point of the root. Got {distinguished}.")
+    dev = roots.device
+    res = ops.search_morin_tree(roots, torch.tensor([weights], dtype=torch.int64, device=dev),
+                                torch.tensor([distinguished], dtype=torch.int64, device=dev), name,
+                                expand_limit=None if max_size is None else max_size - s0,
+                                max_depth=DEFAULT_MAX_DEPTH if max_depth is None else max_depth,
+                                max_nodes=DEFAULT_MORIN_NODES if max_nodes is None else max_nodes,
+                                stack_nodes=DEFAULT_STACK_NODES if stack_nodes is None else stack_nodes)
+    res = MorinTreeResult(*res)
+    status, count = int(res.status[0]), int(res.count[0])
+    if status & A.HK_SEARCH_ROOT_INVALID:
+        raise ValueError(f"distinguished must address a point of the root. Got {distinguished}.")
+    if status & A.HK_SEARCH_ROOT_ENDED:
+        return tree
+    msg = _limit_message("search_tree_morin", status, ignore=A.HK_SEARCH_DEPTH_LIMIT)
+    if msg:
+        raise RuntimeError(msg)
+    par = res.parent[0, :count].tolist()
+    kind = res.kind[0, :count].tolist()
+    dist = res.distinguished[0, :count].tolist()
+    states = res.states[0, :count].cpu().numpy()
+    limit = None if max_size is None else max_size - s0  # kernel ids above it are reached with tree.size() > max_size
+    ident = [curr_node] + [None] * (count - 1)
+    for j in range(1, count):
+        ident[j] = tree.size()
+        if kind[j]:
+            tree.create_node(ident[j], ident[j], parent=ident[par[j]], data=MorinNode(NO_CONTRIBUTION))
+            continue
+        tree.create_node(ident[j], ident[j], parent=ident[par[j]],
+                         data=MorinNode(str(_node_points(states[j])) + f", {[dist[j]]}"))
+        if limit is not None and j > limit:
+            more = tree.size()
+            tree.create_node(more, more, parent=ident[j], data=MorinNode(MORE))
     return tree

@@ -489,6 +489,38 @@ int hk_search_game_tree(const void* points, int batch, int max_points, int dim, 
                         uint64_t workspace_bytes, int32_t* parent_out, int32_t* child_index_out, int32_t* axis_out,
                         int32_t* depth_out, int32_t* num_points_out, int32_t* host_class_out, void* states_out,
                         int32_t* count_out, int32_t* status_out, void* stream);
+/* ---- the Morin game tree under a fixed host (an addition within ABI 6; hironaka/util/search.py:53-93
+ * search_tree_morin) ----
+ * hk_search_game_tree's tree with integer weights and a distinguished point per node.  A node is expanded when it is
+ * a contributing node (kind 0) with >= 2 points, depth < max_depth and id <= L.  With `coords` the host's list, in
+ * hk_search_game_tree's order, each action a of the list
+ *   - is pruned when w[a] > min_{i in coords} w[i]: no node; the later children keep their position in the list as
+ *     child_index, so pruned positions show as gaps;
+ *   - else makes a child with weights w'[i] = w[i] - w[a] for i in coords, i != a, w'[i] = w[i] otherwise, and the
+ *     state shift (x_a <- sum_{k in coords} x_k), reposition (every column minus its minimum), Newton sorted +
+ *     compacted.  With p the distinguished row after shift and reposition, the point is lost when another row q has
+ *     q_k <= p_k for all k (an identical row counts); the child is then a "No contribution" leaf (kind 1,
+ *     distinguished -1, never expanded; its state and weights are written as computed).  Otherwise kind is 0 and
+ *     distinguished is p's row in the child's state.
+ * Ids, expand_limit and the truncated tree's numbering are hk_search_game_tree's.  Inputs per root: points (used as
+ * given), weights[batch, dim] (int32, >= 0), distinguished[batch] (int32, a point's row index in the root).  Outputs
+ * as hk_search_game_tree, plus
+ *   kind_out           0 a contributing node (the root too), 1 a "No contribution" leaf
+ *   distinguished_out  the distinguished point's row in states_out, -1 for kind 1 (the root: as given)
+ *   weights_out        [batch, max_nodes, dim]
+ * status_out has hk_search_game_tree's bits, and HK_SEARCH_ROOT_INVALID when the root's distinguished index does not
+ * address a point or a weight is negative: count is 1 then and nothing is expanded.
+ * dim 2..7 (one more than the other fixed-host operators), max_points 1..64, HK_F32 / HK_F64; anything else is
+ * HK_ERR_UNSUPPORTED / HK_ERR_SHAPE before any launch.  A consumer of ABI 6 detects this entry point by its symbol. */
+#define HK_SEARCH_ROOT_INVALID 32 /* hk_search_morin_tree: bad distinguished index or negative weight at the root */
+uint64_t hk_search_morin_tree_workspace_bytes(int batch, int max_points, int dim, int dtype, int max_nodes,
+                                              int stack_nodes);
+int hk_search_morin_tree(const void* points, const int32_t* weights, const int32_t* distinguished, int batch,
+                         int max_points, int dim, int dtype, int host, int64_t expand_limit, int max_depth,
+                         int max_nodes, int stack_nodes, void* workspace, uint64_t workspace_bytes, int32_t* parent_out,
+                         int32_t* child_index_out, int32_t* axis_out, int32_t* depth_out, int32_t* num_points_out,
+                         int32_t* host_class_out, int32_t* kind_out, int32_t* distinguished_out, int32_t* weights_out,
+                         void* states_out, int32_t* count_out, int32_t* status_out, void* stream);
 
 #ifdef __cplusplus
 }
