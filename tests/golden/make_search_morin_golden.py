@@ -26,8 +26,9 @@ curr_node of a tree that already holds several nodes.  A root whose full tree ex
 finite sizes only under AllCoordHost (whose Thom trees do not end) and skipped under the other hosts; roots where the
 reference raises are skipped.
 
-A plain restatement of the rules (walk) follows every reference run node for node; it is what counts the events
-of `stats`, and the coverage assertions at the end keep a weak fixture from being written.
+The plain restatement of the rules (morin_tree of tests/search_rules.py, here with the reference's own hosts) follows
+every reference run node for node; it is what counts the events of `stats`, and the coverage assertions at the end
+keep a weak fixture from being written.
 
 Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_search_morin_golden.py
 """
@@ -40,7 +41,9 @@ sys.dont_write_bytecode = True  # never write __pycache__ into the read-only ref
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from make_golden import OUT, _load, load_reference  # noqa: E402
+from search_rules import created, morin_data, morin_tree, rows_of  # noqa: E402
 
 HOSTS = {"zeillinger": "Zeillinger", "all_coord": "AllCoordHost", "zeillinger_lex": "ZeillingerLex",
          "weak_spivakovsky": "WeakSpivakovsky", "weak_spivakovsky_min_hitting": "WeakSpivakovskyMinHitting"}
@@ -65,48 +68,6 @@ class StubTree:
         self.calls.append((identifier, parent, data))
 
 
-def walk(rows, dist, weights, select, max_size, tree, curr, stats):
-    """The rules of search_tree_morin restated; select(state) is the host's list"""
-    d = len(rows[0])
-
-    def rec(state, dist, w, node):
-        if len(state) <= 1 or tree.size() > max_size:
-            if tree.size() > max_size:
-                stats[3] += len(state) <= 1
-                tree.create_node(tree.size(), tree.size(), parent=node, data="...more...")
-            return
-        coords = select(state)
-        for a in coords:
-            if w[a] > min(w[i] for i in coords):
-                stats[2] += 1
-                continue
-            w2 = [w[i] - w[a] if i in coords and i != a else w[i] for i in range(d)]
-            new = [[sum(x[k] for k in coords) if i == a else x[i] for i in range(d)] for x in state]
-            mins = [min(x[i] for x in new) for i in range(d)]
-            new = [[x[i] - mins[i] for i in range(d)] for x in new]
-            p = new[dist]
-            others = [x for j, x in enumerate(new) if j != dist]
-            identical = any(x == p for x in others)
-            smaller = any(x != p and all(x[k] <= p[k] for k in range(d)) for x in others)
-            uniq = []
-            for x in new:
-                if x not in uniq:
-                    uniq.append(x)
-            kept = sorted((x for x in uniq if not any(y != x and all(y[k] <= x[k] for k in range(d)) for y in uniq)),
-                          reverse=True)
-            ident = tree.size()
-            if identical or smaller:
-                stats[0] += identical
-                stats[1] += smaller and not identical
-                tree.create_node(ident, ident, parent=node, data="No contribution")
-                continue
-            nd = kept.index(p)
-            tree.create_node(ident, ident, parent=node, data=str([kept]) + f", {[nd]}")
-            rec(kept, nd, w2, ident)
-
-    rec([list(r) for r in rows], dist, list(weights), curr)
-
-
 def run(ref, morin, host_name, rows, weights, dist, max_size, n0=1, curr=0, stats=None):
     """the reference's run; with `stats`, the restatement must follow it node for node"""
     ms = FULL if max_size is None else max_size
@@ -117,10 +78,11 @@ def run(ref, morin, host_name, rows, weights, dist, max_size, n0=1, curr=0, stat
     assert out is tree
     new = [(c[0], c[1], c[2].points) for c in tree.calls[n0:]]
     if stats is not None:
-        mine, local = StubTree(n0), [0, 0, 0, 0]
-        walk(rows, dist, weights, lambda st: host.select_coord(ref.ListPoints([[list(r) for r in st]]))[0], ms, mine, curr,
-             local)
-        assert mine.calls[n0:] == new, (host_name, rows, weights, dist, max_size)
+        local = [0, 0, 0, 0]
+        mine = morin_tree(rows, weights, dist, lambda st: host.select_coord(ref.ListPoints([rows_of(st)]))[0], ms, s0=n0,
+                          stats=local)
+        calls = [c + (morin_data(mine, j + 1),) for j, c in enumerate(created(mine, n0, curr))]
+        assert calls == new, (host_name, rows, weights, dist, max_size)
         for i in range(4):
             stats[i] += local[i]
     return new

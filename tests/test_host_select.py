@@ -5,7 +5,6 @@ three selection rules against the fixture made by running the reference's own cl
 import ctypes
 import os
 import re
-from itertools import combinations
 
 import numpy as np
 import pytest
@@ -15,6 +14,7 @@ from hironaka_amd import _abi as A
 from hironaka_amd import _lib
 from hironaka_amd import host as H
 from hironaka_amd.util import search as S
+from search_rules import rule_min_hitting, rule_weak, rule_zeillinger
 
 HOSTS = ("zeillinger_lex", "weak_spivakovsky", "weak_spivakovsky_min_hitting", "zeillinger")
 INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
@@ -89,60 +89,7 @@ def test_search_depth_accepts_the_new_host_codes_only():
         assert L.hk_search_depth(a, 1, 4, 7, A.HK_F32, h, 4, 8, 4, a, ws, a, a, a, None) == A.HK_ERR_UNSUPPORTED, h
 
 
-# ---- the selection rules, restated in numpy (row order, holes anywhere) ------------------------------------------
-
-def _points(state):
-    return [r for r in state if r[0] >= 0]
-
-
-def _key(v):
-    mx, mn = v.max(), v.min()
-    return (mx - mn, int((v == mx).sum() + (v == mn).sum()))
-
-
-def _r(v):
-    lo, hi = int(np.argmin(v)), int(np.argmax(v))
-    return (0, 1) if lo == hi else (lo, hi)
-
-
-def rule_zeillinger(state, lex):
-    pts = _points(state)
-    if len(pts) < 2:
-        return None
-    vs = [pts[i] - pts[j] for i, j in combinations(range(len(pts)), 2)]
-    keys = [_key(v) for v in vs]
-    best = min(keys)
-    if not lex:
-        return set(_r(vs[keys.index(best)]))
-    return set(min(_r(v) for v, k in zip(vs, keys) if k == best))
-
-
-def _supports(state):
-    return {frozenset(np.nonzero(p)[0].tolist()) for p in _points(state)}
-
-
-def rule_weak(state):
-    pts, sup = _points(state), _supports(state)
-    U = sorted(set().union(*sup)) if sup else []
-    if len(pts) < 2:
-        return None
-    for size in range(2, len(U) + 1):
-        for c in combinations(U, size):  # sorted tuples in lexicographic order
-            if all(set(c) & s for s in sup):
-                return set(c)
-    return None
-
-
-def rule_min_hitting(state, d):
-    pts, sup = _points(state), _supports(state)
-    if len(pts) < 2:
-        return None
-    for c in sorted(range(1 << d), key=lambda c: (bin(c).count("1"), c)):
-        cs = {k for k in range(d) if (c >> k) & 1}
-        if len(cs) >= 2 and all(cs & s for s in sup):
-            return cs
-    return None
-
+# ---- the selection rules, restated in numpy (tests/search_rules.py: row order, holes anywhere) --------------------
 
 def rule(host, state, d):
     if host == "zeillinger_lex":
