@@ -57,6 +57,13 @@ HK_SEARCH_INEXACT = 8
 HK_SEARCH_ROOT_ENDED = 16
 HK_SEARCH_ROOT_INVALID = 32  # hk_search_morin_tree
 
+# hk_search_morin_play: outcomes, tie modes, weight rules, flag, the "every class is forced" host code
+HK_MORIN_RUNNING, HK_MORIN_ENDED, HK_MORIN_NO_CONTRIBUTION, HK_MORIN_NO_MOVE, HK_MORIN_INEXACT = 0, 1, 2, 3, 4
+HK_MORIN_TIE_LOWEST, HK_MORIN_TIE_HIGHEST, HK_MORIN_TIE_RANDOM = 0, 1, 2
+HK_MORIN_WEIGHTS_AGENT, HK_MORIN_WEIGHTS_SEARCH = 0, 1
+HK_MORIN_REDUCE_ROOT = 1
+HK_MORIN_HOST_FORCED = -1
+
 SEMANTICS = {"jax": HK_SEM_JAX, "torch": HK_SEM_TORCH, "list": HK_SEM_LIST}
 
 
@@ -141,6 +148,37 @@ class hk_search_tree(C.Structure):
     ]
 
 
+class hk_morin_play_desc(C.Structure):
+    _fields_ = [
+        ("points_in", C.c_void_p),
+        ("points_out", C.c_void_p),
+        ("in_stride", C.c_int64),
+        ("out_stride", C.c_int64),
+        ("weights_in", C.c_void_p),
+        ("weights_out", C.c_void_p),
+        ("distinguished_in", C.c_void_p),
+        ("distinguished_out", C.c_void_p),
+        ("class_in", C.c_void_p),
+        ("axis_in", C.c_void_p),
+        ("class_out", C.c_void_p),
+        ("axis_out", C.c_void_p),
+        ("length_out", C.c_void_p),
+        ("outcome_out", C.c_void_p),
+        ("seed", C.c_uint64),
+        ("game_offset", C.c_uint64),
+        ("batch", C.c_int32),
+        ("max_points", C.c_int32),
+        ("dim", C.c_int32),
+        ("dtype", C.c_int32),
+        ("host", C.c_int32),
+        ("max_steps", C.c_int32),
+        ("tie", C.c_int32),
+        ("weight_rule", C.c_int32),
+        ("flags", C.c_uint32),
+        ("step_offset", C.c_uint32),
+    ]
+
+
 _vp, _i, _i64, _u32, _u64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
 
 # name -> (restype, argtypes) of every symbol the header declares.  `stream` is the trailing
@@ -188,6 +226,7 @@ PROTOTYPES = {
     "hk_search_morin_tree_workspace_bytes": (C.c_uint64, [_i, _i, _i, _i, _i, _i]),
     "hk_search_morin_tree": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _vp, _u64, _vp, _vp, _vp,
                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hk_search_morin_play": (C.c_int, [C.POINTER(hk_morin_play_desc), _vp]),
 }
 
 STATUS_TEXT = {

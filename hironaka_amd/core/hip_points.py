@@ -12,8 +12,14 @@ torch sibling: an axis outside the host's subset and (by default) a finished gam
 ``semantics="list"`` turns the container into the padded form of ``ListPoints``
 (hironaka/core/list_points.py:20-135): the Newton polytope comes out sorted (descending, coordinate 0
 primary) and compacted to the front (_list_ops.py:25-41), which is what ``GameHironaka`` and the gym
-environments step.
+environments step.  With ``distinguished_points`` (a list of row indices with ``None`` for a lost point, or an int32
+device tensor with -1) ``get_newton_polytope()`` moves each index to its row's place in the sorted state, as
+ListPoints does (list_points.py:86-116), and loses it when another point lies at or below the row in every coordinate;
+``shift``, ``reposition`` and ``rescale`` do not reorder rows and leave it alone.  The tracking runs in
+hk_search_morin_play, so it covers dimension 2..7, at most 64 points per game and a negative padding value; any
+other container is reduced as one without marks, with a warning, and keeps ``distinguished_points`` as given.
 """
+import warnings
 from typing import List, Optional, Type, Union
 
 import numpy as np
@@ -22,6 +28,9 @@ import torch
 from .. import _abi as A
 from .. import ops
 from .points_base import PointsBase
+
+
+_TRACK_MAX_DIM, _TRACK_MAX_POINTS = 7, 64  # hk_search_morin_play's sizes
 
 
 def _pad_ragged(points, new_length: int, constant_value: float) -> np.ndarray:
@@ -110,6 +119,42 @@ class HipPoints(PointsBase):
                        out=work, want=want)
         self._commit(work, back)
         return res
+
+    # ---- the distinguished point (list semantics) ------------------------------------------------
+    def get_newton_polytope(self, inplace=True, **kwargs):
+        if self.semantics != "list" or self.distinguished_points is None:
+            return super().get_newton_polytope(inplace=inplace, **kwargs)
+        if not (2 <= self.dimension <= _TRACK_MAX_DIM and self.points.shape[1] <= _TRACK_MAX_POINTS
+                and self.padding_value < 0):
+            warnings.warn(f"distinguished_points are tracked for dimension 2..{_TRACK_MAX_DIM}, at most "
+                          f"{_TRACK_MAX_POINTS} points per game and a negative padding value. This container is "
+                          f"{tuple(self.points.shape)} with padding {self.padding_value}: it is reduced with "
+                          f"distinguished_points left as they are.", stacklevel=2)
+            return super().get_newton_polytope(inplace=inplace, **kwargs)
+        given = self.distinguished_points
+        if isinstance(given, torch.Tensor):
+            dist = given.to(self.device)
+        else:
+            if len(given) != self.batch_size or any(
+                    v is not None and not 0 <= int(v) < self.points.shape[1] for v in given):
+                raise ValueError(f"distinguished_points must hold one row index in [0, {self.points.shape[1]}) or None "
+                                 f"per game. Got {given}.")
+            dist = torch.tensor([-1 if v is None else int(v) for v in given], dtype=torch.int32, device=self.device)
+        work, back = self._work()
+        ones = torch.ones((self.batch_size, self.dimension), dtype=torch.int32, device=self.device)
+        res = ops.morin_play(work, ones, dist, max_steps=0, reduce_root=True, out=work if inplace else None,
+                             validate=False)
+        if self.padding_value != -1.0:  # the launch pads with -1
+            res.points.masked_fill_(res.points < 0, self.padding_value)
+        moved = res.distinguished.to(given.dtype) if isinstance(given, torch.Tensor) else [
+            None if v < 0 else v for v in res.distinguished.tolist()]
+        if inplace:
+            self._commit(work, back)
+            self.distinguished_points = moved
+            return self
+        new = self.copy(points=res.points.to(self.dtype) if back else res.points)
+        new.distinguished_points = moved
+        return new
 
     # ---- PointsBase hooks ----------------------------------------------------------------------
     def _work(self):

@@ -1,0 +1,81 @@
+// C ABI of hk_search_morin_play (include/hironaka_hip.h, an addition within ABI 6): argument validation and launch of
+// hk::morin_play_kernel.  No allocation, no synchronisation; every status is decided before the launch.
+#include "hk_morin_play_kernel.h"
+
+using namespace hk;
+
+extern "C" {
+
+int hk_search_morin_play(const hk_morin_play_desc* q, void* stream) {
+  if (!q) return HK_ERR_NULL;
+  if (q->dtype != HK_F32 && q->dtype != HK_F64) return HK_ERR_UNSUPPORTED;
+  if (q->batch < 0 || q->max_points < 1 || q->dim < 2 || q->max_steps < 0) return HK_ERR_SHAPE;
+  if (q->max_points > kFixedHostMaxPoints || q->dim > kMorinMaxDim) return HK_ERR_UNSUPPORTED;
+  if (!fixed_host(q->host) && q->host != HK_MORIN_HOST_FORCED) return HK_ERR_UNSUPPORTED;
+  if (q->tie < HK_MORIN_TIE_LOWEST || q->tie > HK_MORIN_TIE_RANDOM) return HK_ERR_UNSUPPORTED;
+  if (q->weight_rule != HK_MORIN_WEIGHTS_AGENT && q->weight_rule != HK_MORIN_WEIGHTS_SEARCH) return HK_ERR_UNSUPPORTED;
+  if (q->flags & ~(uint32_t)HK_MORIN_REDUCE_ROOT) return HK_ERR_UNSUPPORTED;
+  if (q->batch == 0) return HK_OK;
+  if (!q->points_in || !q->points_out || !q->weights_in || !q->weights_out || !q->distinguished_in ||
+      !q->distinguished_out || !q->length_out || !q->outcome_out)
+    return HK_ERR_NULL;
+  if (q->host == HK_MORIN_HOST_FORCED && q->max_steps > 0 && !q->class_in) return HK_ERR_NULL;
+  const int64_t n = (int64_t)q->max_points * q->dim;
+  if (q->in_stride < n || q->out_stride < n) return HK_ERR_SHAPE;
+  if (q->points_in == q->points_out && q->in_stride != q->out_stride) return HK_ERR_SHAPE;
+  const size_t es = elem_size(q->dtype);
+  if (q->points_in != q->points_out) {
+    // a workgroup's write-back must not meet another's staging read: other than in place, the two do not overlap
+    const uintptr_t in = (uintptr_t)q->points_in, out = (uintptr_t)q->points_out;
+    const uint64_t in_bytes = ((uint64_t)(q->batch - 1) * (uint64_t)q->in_stride + (uint64_t)n) * es;
+    const uint64_t out_bytes = ((uint64_t)(q->batch - 1) * (uint64_t)q->out_stride + (uint64_t)n) * es;
+    if (in < out + out_bytes && out < in + in_bytes) return HK_ERR_SHAPE;
+  }
+  const int32_t* ints[] = {q->weights_in, q->weights_out, q->distinguished_in, q->distinguished_out, q->class_in,
+                           q->axis_in,    q->class_out,   q->axis_out,         q->length_out,        q->outcome_out};
+  for (const int32_t* p : ints)
+    if (!aligned(p, 4)) return HK_ERR_ALIGN;
+  if (!aligned(q->points_in, es) || !aligned(q->points_out, es)) return HK_ERR_ALIGN;
+  MorinPlayArgs a{};
+  a.points = q->points_in;
+  a.points_out = q->points_out;
+  a.weights = q->weights_in;
+  a.weights_out = q->weights_out;
+  a.dist = q->distinguished_in;
+  a.dist_out = q->distinguished_out;
+  a.class_in = q->class_in;
+  a.axis_in = q->axis_in;
+  a.class_out = q->class_out;
+  a.axis_out = q->axis_out;
+  a.length_out = q->length_out;
+  a.outcome_out = q->outcome_out;
+  a.in_stride = q->in_stride;
+  a.out_stride = q->out_stride;
+  a.seed = q->seed;
+  a.game_offset = q->game_offset;
+  a.step_offset = q->step_offset;
+  a.batch = q->batch;
+  a.m = q->max_points;
+  a.d = q->dim;
+  a.max_steps = q->max_steps;
+  a.tie = q->tie;
+  a.weight_rule = q->weight_rule;
+  a.reduce_root = (q->flags & HK_MORIN_REDUCE_ROOT) ? 1 : 0;
+  a.lds_stride = search_lds_stride(a.m, a.d, morin_lds_extra(a.d));
+  const int per_game = a.lds_stride * (int)es;
+  a.games_per_block = kSearchLdsBytes / per_game < kWave ? kSearchLdsBytes / per_game : kWave;
+  const unsigned grid = (unsigned)(((int64_t)a.batch + a.games_per_block - 1) / a.games_per_block);
+  const size_t lds = (size_t)a.games_per_block * per_game;
+  auto launch = [&](auto t, auto h) {
+    launch_prepare();
+    hipLaunchKernelGGL((morin_play_kernel<decltype(t), h>), dim3(grid), dim3(kWave), lds, (hipStream_t)stream, a);
+    return launch_status();
+  };
+  if (q->host == HK_MORIN_HOST_FORCED) {
+    const std::integral_constant<int, HK_MORIN_HOST_FORCED> forced;
+    return q->dtype == HK_F32 ? launch(float(), forced) : launch(double(), forced);
+  }
+  return with_fixed_host(q->dtype, q->host, launch);
+}
+
+}  // extern "C"

@@ -135,7 +135,7 @@ __global__ void __launch_bounds__(kWave) search_morin_kernel(SearchMorinArgs a) 
   int nrec = 1, nb = 1;
 
   const LaneSlice<T> sl(lds, lane, a.lds_stride, m, d);
-  int32_t* w = reinterpret_cast<int32_t*>(sl.row + d);  // d weights, one per element of T
+  int32_t* w = reinterpret_cast<int32_t*>(sl.row + d);  // d int32 in the space of d elements
   T* prow = sl.row + 2 * d;
   for (long long it = 0; top > 0 && it <= L; ++it) {
     int k = top < a.lanes ? top : a.lanes;

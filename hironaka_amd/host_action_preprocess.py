@@ -100,6 +100,13 @@ def encode(multi_binary: torch.Tensor) -> torch.Tensor:
     return batch_encode(multi_binary.reshape(1, -1))[0]
 
 
+def encode_host_class(coords: torch.Tensor) -> torch.Tensor:
+    """a host's subsets [B, dim] (any entry > 0 is a chosen coordinate) -> class ids int32 [B] as `batch_encode`, with
+    -1 for a subset of fewer than two coordinates: "no move" to the kernels that take forced classes"""
+    chosen = coords > 0
+    return torch.where(chosen.sum(dim=-1) >= 2, batch_encode(chosen), -1).to(torch.int32)
+
+
 def batch_encode_one_hot(multi_binary: torch.Tensor) -> torch.Tensor:
     """masks [B, dim] -> one-hot class vectors [B, A] float32 (host_action_preprocess.py:90-99)."""
     dimension = multi_binary.shape[-1]

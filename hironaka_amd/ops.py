@@ -11,6 +11,7 @@ _list_ops.py on padded arrays).
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes as C
 from typing import Dict, Optional, Sequence, Tuple
@@ -796,3 +797,140 @@ def search_morin_tree(points: torch.Tensor, weights: torch.Tensor, distinguished
             check(fn(pts[lo].data_ptr(), wts[lo].data_ptr(), dist[lo].data_ptr(), min(chunk, b - lo), *head,
                      ws.data_ptr(), ws.numel(), *ptrs, _stream(pts)), name)
     return tuple(outs)
+
+
+MORIN_TIES = {"lowest": A.HK_MORIN_TIE_LOWEST, "highest": A.HK_MORIN_TIE_HIGHEST, "random": A.HK_MORIN_TIE_RANDOM}
+MORIN_WEIGHT_RULES = {"agent": A.HK_MORIN_WEIGHTS_AGENT, "search": A.HK_MORIN_WEIGHTS_SEARCH}
+MORIN_OUTCOMES = {A.HK_MORIN_RUNNING: "running", A.HK_MORIN_ENDED: "ended",
+                  A.HK_MORIN_NO_CONTRIBUTION: "no contribution", A.HK_MORIN_NO_MOVE: "no move",
+                  A.HK_MORIN_INEXACT: "inexact"}
+
+MorinPlayResult = collections.namedtuple("MorinPlayResult", "points weights distinguished length outcome classes axes")
+
+
+def _record_stride(t: torch.Tensor) -> Optional[int]:
+    """the element stride between the games of a [B, m, d] tensor whose games are contiguous records, else None"""
+    b, m, d = t.shape
+    if t.stride(2) != 1 or (m > 1 and t.stride(1) != d):
+        return None
+    if b > 1:
+        return t.stride(0) if t.stride(0) >= m * d else None
+    return m * d
+
+
+def _records_overlap(x: torch.Tensor, y: torch.Tensor) -> bool:
+    """whether the byte ranges that the records of two [B, m, d] record tensors span meet"""
+    def span(t):
+        b, m, d = t.shape
+        return t.data_ptr(), t.data_ptr() + ((b - 1) * _record_stride(t) + m * d) * t.element_size()
+    if not x.numel() or not y.numel():
+        return False
+    (x0, x1), (y0, y1) = span(x), span(y)
+    return x0 < y1 and y0 < x1
+
+
+def _morin_range_error(weights: torch.Tensor, distinguished: torch.Tensor, classes: Optional[torch.Tensor],
+                       axes: Optional[torch.Tensor], max_points: int, weight_rule: str) -> Optional[str]:
+    """morin_play's range check: the message of what it refuses, else None.  Weights lie in [0, 2^31) under the
+    agent's rule; the search rule can leave a negative weight (a coordinate of the subset lighter than the axis), so
+    under it, as for classes and axes, any value that fits int32 is taken.  distinguished lies in [-1, max_points).
+    One synchronisation when the tensors are on a device."""
+    w64, d64 = weights.to(torch.int64), distinguished.to(torch.int64)
+    low = -2 ** 31 if weight_rule == "search" else 0
+    bad = (w64 < low).any() | (w64 >= 2 ** 31).any() | (d64 < -1).any() | (d64 >= max_points).any()
+    for t in (classes, axes):
+        if t is not None and t.numel():
+            bad = bad | (t.to(torch.int64).abs() >= 2 ** 31).any()
+    if bool(bad):
+        return (f"weights must lie in [{low}, 2^31) under weight_rule={weight_rule!r}, distinguished in "
+                f"[-1, {max_points}), classes and axes must fit int32.")
+    return None
+
+
+def morin_play(points: torch.Tensor, weights: torch.Tensor, distinguished: torch.Tensor, *, host: Optional[str] = None,
+               max_steps: int, classes: Optional[torch.Tensor] = None, axes: Optional[torch.Tensor] = None,
+               tie: str = "lowest", weight_rule: str = "agent", seed: int = 0, game_offset: int = 0,
+               step_offset: int = 0, reduce_root: bool = False, record: bool = False, out: Optional[torch.Tensor] = None,
+               validate: bool = True) -> MorinPlayResult:
+    """Morin games played forward, one game per lane, up to ``max_steps`` moves in one launch (hk_search_morin_play;
+    hironaka/game.py:122-154 GameMorin with hironaka/agent.py:114-136 AgentMorin).  points: [B, m, d] float32/float64
+    in list semantics (padding -1), d in 2..7, m <= 64; games that are contiguous records at any stride are read in
+    place, any other view through a copy.  weights: [B, d] integers, >= 0 under weight_rule="agent"; the search rule
+    can leave a negative weight, and a game that continues under it may bring any int32.  distinguished: [B] row
+    indices, -1 for lost / none.  host: a key of SEARCH_HOSTS, or None when ``classes`` forces every move.  classes /
+    axes: [B, max_steps] forced class ids / axes, entries < 0 leave the move to the host / the agent's rule.  tie: a
+    key of MORIN_TIES (the agent's choice when the two lowest coordinates of the subset weigh the same; "random" draws
+    from Philox keyed by (seed, game_offset + b, step_offset + move), so shards and launches that continue a game
+    reproduce one launch).  weight_rule: a key of MORIN_WEIGHT_RULES.  reduce_root: Newton with the row tracked before
+    any move (with max_steps=0: the tracked get_newton_polytope).  record: return the moves played as classes / axes
+    [B, max_steps], -1 from length on.  out: where the final points go; default a new tensor.  It may be ``points``
+    itself (in place); an ``out`` that shares memory with ``points`` in any other way is served through a copy of
+    ``points``.  validate=False skips the range checks of weights and distinguished, which cost a synchronisation.
+    Returns MorinPlayResult(points, weights, distinguished, length, outcome, classes, axes); outcome holds the
+    HK_MORIN_* codes of include/hironaka_hip.h (MORIN_OUTCOMES names them)."""
+    if host is not None and host not in SEARCH_HOSTS:
+        raise ValueError(f"host must be None or one of {sorted(SEARCH_HOSTS)}. Got {host!r}.")
+    if tie not in MORIN_TIES or weight_rule not in MORIN_WEIGHT_RULES:
+        raise ValueError(f"tie must be one of {sorted(MORIN_TIES)} and weight_rule one of {sorted(MORIN_WEIGHT_RULES)}. "
+                         f"Got {tie!r}, {weight_rule!r}.")
+    if not (0 <= max_steps < 2 ** 31 and 0 <= seed < 2 ** 64 and 0 <= game_offset < 2 ** 64
+            and 0 <= step_offset < 2 ** 32 - max_steps):
+        raise ValueError(f"need 0 <= max_steps < 2^31, seed and game_offset in [0, 2^64), step_offset + max_steps < 2^32. "
+                         f"Got {max_steps}, {seed}, {game_offset}, {step_offset}.")
+    _require_device(points, "points")
+    if points.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"points must be float32 or float64. Got {points.dtype}.")
+    if points.dim() != 3:
+        raise ValueError(f"points must be [B, max_points, dim]. Got shape {tuple(points.shape)}.")
+    b, m, d = points.shape
+    dev = points.device
+    ints = {}
+    for t, name, shape in ((weights, "weights", (b, d)), (distinguished, "distinguished", (b,)),
+                           (classes, "classes", (b, max_steps)), (axes, "axes", (b, max_steps))):
+        if t is None and name in ("classes", "axes"):
+            ints[name] = None
+            continue
+        _require_device(t, name)
+        if t.dtype not in (torch.int32, torch.int64) or tuple(t.shape) != shape or t.device != dev:
+            raise ValueError(f"{name} must be an int32/int64 tensor of shape {shape} on the points' device. Got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}.")
+        ints[name] = t
+    if host is None and classes is None and max_steps > 0:
+        raise ValueError("without a host every move needs a forced class: pass classes.")
+    if validate and b:
+        refused = _morin_range_error(weights, distinguished, ints["classes"], ints["axes"], m, weight_rule)
+        if refused:
+            raise ValueError(refused)
+    ints = {k: None if t is None else t.to(torch.int32).contiguous() for k, t in ints.items()}
+    if out is not None:
+        _require_device(out, "out")
+        if out.shape != points.shape or out.dtype != points.dtype or out.device != dev:
+            raise ValueError(f"out must match points: {tuple(points.shape)} {points.dtype} on {dev}. Got "
+                             f"{tuple(out.shape)} {out.dtype} on {out.device}.")
+    src = points if _record_stride(points) is not None else points.contiguous()
+    dst = out if out is not None and _record_stride(out) is not None else torch.empty((b, m, d), dtype=points.dtype,
+                                                                                      device=dev)
+    if _records_overlap(src, dst) and not (dst.data_ptr() == src.data_ptr() and dst.stride() == src.stride()):
+        src = src.clone()  # only an exact in-place call may share memory: workgroups write back while others still read
+    new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    w_out, d_out, length, outcome = new(b, d), new(b), new(b), new(b)
+    c_out, a_out = (new(b, max_steps), new(b, max_steps)) if record else (None, None)
+    q = A.hk_morin_play_desc()
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    q.points_in, q.points_out = src.data_ptr(), dst.data_ptr()
+    q.in_stride, q.out_stride = _record_stride(src), _record_stride(dst)
+    q.weights_in, q.weights_out = ints["weights"].data_ptr(), w_out.data_ptr()
+    q.distinguished_in, q.distinguished_out = ints["distinguished"].data_ptr(), d_out.data_ptr()
+    q.class_in, q.axis_in, q.class_out, q.axis_out = ptr(ints["classes"]), ptr(ints["axes"]), ptr(c_out), ptr(a_out)
+    q.length_out, q.outcome_out = length.data_ptr(), outcome.data_ptr()
+    q.seed, q.game_offset, q.step_offset = seed, game_offset, step_offset
+    q.batch, q.max_points, q.dim, q.dtype = b, m, d, _TORCH2HK[points.dtype]
+    q.host = A.HK_MORIN_HOST_FORCED if host is None else SEARCH_HOSTS[host]
+    q.max_steps, q.tie, q.weight_rule = max_steps, MORIN_TIES[tie], MORIN_WEIGHT_RULES[weight_rule]
+    q.flags = A.HK_MORIN_REDUCE_ROOT if reduce_root else 0
+    with torch.cuda.device(dev):
+        check(lib().hk_search_morin_play(C.byref(q), _stream(points)), "hk_search_morin_play")
+    if out is not None and dst is not out:
+        out.copy_(dst)
+        dst = out
+    return MorinPlayResult(dst, w_out, d_out, length, outcome, c_out, a_out)

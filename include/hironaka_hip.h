@@ -50,6 +50,9 @@
  *                            action mask jax/util.py:287-305
  *   hk_search_depth          hironaka/util/search.py:9-32 search_depth (one tree per root, a batch of roots)
  *   hk_search_game_tree      hironaka/util/search.py:35-50 search_tree (the nodes themselves, in preorder)
+ *   hk_search_morin_tree     hironaka/util/search.py:53-93 search_tree_morin (weights and a distinguished point per node)
+ *   hk_search_morin_play     hironaka/game.py:122-154 GameMorin with agent.py:114-136 AgentMorin, one game per lane;
+ *                            core/list_points.py:86-116 the distinguished point that get_newton_polytope tracks
  *   hk_host_select           (hironaka_hip_hosts.h) host.py:48-51 AllCoordHost, host.py:54-95 Zeillinger, host.py:116-127 ZeillingerLex,
  *                            host.py:357-378 WeakSpivakovsky, host.py:381-427 WeakSpivakovskyMinHitting
  *                            (select_coord on ListPoints)
@@ -521,6 +524,89 @@ int hk_search_morin_tree(const void* points, const int32_t* weights, const int32
                          int32_t* child_index_out, int32_t* axis_out, int32_t* depth_out, int32_t* num_points_out,
                          int32_t* host_class_out, int32_t* kind_out, int32_t* distinguished_out, int32_t* weights_out,
                          void* states_out, int32_t* count_out, int32_t* status_out, void* stream);
+
+/* ---- the Morin game played forward (an addition within ABI 6; hironaka/game.py:122-154 GameMorin with
+ * hironaka/agent.py:114-136 AgentMorin, and core/list_points.py:86-116, the distinguished point that get_newton_polytope
+ * tracks) ----
+ * One game per lane plays the paths that hk_search_morin_tree enumerates.  Per game: points (list semantics, padding
+ * -1, rows with coordinate 0 >= 0 are the points), weights [dim] (int32) and distinguished (int32: a row index, or -1 =
+ * lost / none; an index that addresses no point counts as -1).  They are read once and written once; points_out may
+ * equal points_in (with equal strides), weights_out weights_in, distinguished_out distinguished_in.  Otherwise the
+ * byte ranges the records of points_in and of points_out span must not overlap (HK_ERR_SHAPE): workgroups write back
+ * while others still read.  The reference's weights start as ones and stay >= 0 under HK_MORIN_WEIGHTS_AGENT;
+ * HK_MORIN_WEIGHTS_SEARCH can leave a negative weight (a coordinate of the subset lighter than the axis), and any
+ * int32 is taken as it comes: only the comparison and the wrapping subtraction below touch them.
+ *
+ * HK_MORIN_REDUCE_ROOT: before any move, Newton sorted + compacted with the row tracked (Game.__init__'s
+ * get_newton_polytope): the row is lost when another point lies at or below it in every coordinate (an identical row
+ * counts), else distinguished becomes its row in the sorted state.  A game that enters with distinguished -1 is then
+ * reduced and played without tracking: it is never "no contribution" and leaves with -1.  With max_steps 0 the call
+ * is the tracked get_newton_polytope.
+ *
+ * Move t < max_steps of a game that is running (>= 2 points, and a distinguished point unless tracking is off):
+ *   host    class_in[b, t] when class_in is given and the entry is >= 0, else the fixed host `host` (hk_host_select's
+ *           codes 1..5; HK_MORIN_HOST_FORCED: none).  No class (-1, or an id beyond the dim's classes): the game stops
+ *           with HK_MORIN_NO_MOVE, untouched.
+ *   agent   axis_in[b, t] when given and >= 0; an axis outside the subset stops the game with HK_MORIN_NO_MOVE,
+ *           untouched.  Else, with c0 < c1 the two lowest coordinates of the subset: the one with the smaller weight;
+ *           on a tie c0 (HK_MORIN_TIE_LOWEST), the subset's largest coordinate (HK_MORIN_TIE_HIGHEST), or uniform over
+ *           the subset (HK_MORIN_TIE_RANDOM: word 0 of Philox4x32-10 with key `seed` and counter (game_offset + b,
+ *           step_offset + t, stream 2), so that shards and launches that continue a game reproduce the one launch;
+ *           the j-th coordinate of the subset in ascending order for j = (word * |subset|) >> 32).
+ *   weights HK_MORIN_WEIGHTS_AGENT (agent.py:129-136): w[i] = 0 for i in the subset, i != axis;
+ *           HK_MORIN_WEIGHTS_SEARCH (util/search.py:73-77): w[i] -= w[axis] for those i.  Others are kept.
+ *   state   hk_search_morin_tree's child: shift, reposition, the loss test, Newton sorted + compacted.  Lost: the game
+ *           stops with HK_MORIN_NO_CONTRIBUTION, distinguished -1, the state the child's.  Else distinguished moves to
+ *           its row; fewer than 2 points: HK_MORIN_ENDED.  A shifted coordinate that reached 2^24 (float32) / 2^53
+ *           (float64) stops the game with HK_MORIN_INEXACT after that move: its values are not to be trusted.
+ * Outputs: the final points, weights and distinguished; length_out [batch] the moves played; outcome_out [batch] one
+ * of the codes below; class_out / axis_out [batch, max_steps] (each may be NULL) the moves played, -1 from length on.
+ * A game that is not running on entry is copied through bit for bit with length 0 and outcome HK_MORIN_NO_CONTRIBUTION
+ * (tracked, distinguished -1) or HK_MORIN_ENDED.
+ * dim 2..7, max_points 1..64, HK_F32 / HK_F64, strides >= max_points*dim, max_steps >= 0; anything else is
+ * HK_ERR_UNSUPPORTED / HK_ERR_SHAPE before any launch (HK_HOST_RANDOM included).  A consumer of ABI 6 detects this
+ * entry point by its symbol. */
+#define HK_MORIN_RUNNING 0         /* stopped by max_steps only                                         */
+#define HK_MORIN_ENDED 1           /* fewer than 2 points                                               */
+#define HK_MORIN_NO_CONTRIBUTION 2 /* the distinguished point was lost                                  */
+#define HK_MORIN_NO_MOVE 3         /* no class from the host, or a forced axis outside the subset       */
+#define HK_MORIN_INEXACT 4         /* a coordinate left the exact integers                              */
+#define HK_MORIN_TIE_LOWEST 0
+#define HK_MORIN_TIE_HIGHEST 1
+#define HK_MORIN_TIE_RANDOM 2
+#define HK_MORIN_WEIGHTS_AGENT 0
+#define HK_MORIN_WEIGHTS_SEARCH 1
+#define HK_MORIN_REDUCE_ROOT 1u   /* hk_morin_play_desc.flags                                          */
+#define HK_MORIN_HOST_FORCED (-1) /* hk_morin_play_desc.host: every class comes from class_in          */
+typedef struct hk_morin_play_desc {
+  const void* points_in;           /* [batch] records of in_stride elements                            */
+  void* points_out;                /* [batch] records of out_stride elements; the first max_points*dim are written */
+  int64_t in_stride;
+  int64_t out_stride;
+  const int32_t* weights_in;       /* [batch, dim]                                                     */
+  int32_t* weights_out;
+  const int32_t* distinguished_in; /* [batch]                                                          */
+  int32_t* distinguished_out;
+  const int32_t* class_in;         /* [batch, max_steps] or NULL                                       */
+  const int32_t* axis_in;          /* [batch, max_steps] or NULL                                       */
+  int32_t* class_out;              /* [batch, max_steps] or NULL                                       */
+  int32_t* axis_out;               /* [batch, max_steps] or NULL                                       */
+  int32_t* length_out;             /* [batch]                                                          */
+  int32_t* outcome_out;            /* [batch]                                                          */
+  uint64_t seed;
+  uint64_t game_offset;
+  int32_t batch;
+  int32_t max_points;
+  int32_t dim;
+  int32_t dtype;
+  int32_t host;
+  int32_t max_steps;
+  int32_t tie;
+  int32_t weight_rule;
+  uint32_t flags;
+  uint32_t step_offset;            /* the number of the launch's first move in the random tie's counter */
+} hk_morin_play_desc;
+int hk_search_morin_play(const hk_morin_play_desc* desc, void* stream);
 
 #ifdef __cplusplus
 }
