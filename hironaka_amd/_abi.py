@@ -64,6 +64,11 @@ HK_MORIN_WEIGHTS_AGENT, HK_MORIN_WEIGHTS_SEARCH = 0, 1
 HK_MORIN_REDUCE_ROOT = 1
 HK_MORIN_HOST_FORCED = -1
 
+# hk_game_play: outcomes (the numbers of the HK_MORIN_* codes they share), flags, the "every class is forced" host code
+HK_PLAY_RUNNING, HK_PLAY_ENDED, HK_PLAY_NO_MOVE, HK_PLAY_INEXACT, HK_PLAY_VALUE_LIMIT = 0, 1, 3, 4, 5
+HK_PLAY_REPOSITION, HK_PLAY_RESCALE, HK_PLAY_REDUCE_ROOT, HK_PLAY_RESCALE_ROOT = 1, 2, 4, 8
+HK_PLAY_HOST_FORCED = -1
+
 SEMANTICS = {"jax": HK_SEM_JAX, "torch": HK_SEM_TORCH, "list": HK_SEM_LIST}
 
 
@@ -179,6 +184,34 @@ class hk_morin_play_desc(C.Structure):
     ]
 
 
+class hk_game_play_desc(C.Structure):
+    _fields_ = [
+        ("points_in", C.c_void_p),
+        ("points_out", C.c_void_p),
+        ("in_stride", C.c_int64),
+        ("out_stride", C.c_int64),
+        ("class_in", C.c_void_p),
+        ("axis_in", C.c_void_p),
+        ("class_out", C.c_void_p),
+        ("axis_out", C.c_void_p),
+        ("length_out", C.c_void_p),
+        ("outcome_out", C.c_void_p),
+        ("seed", C.c_uint64),
+        ("game_offset", C.c_uint64),
+        ("value_threshold", C.c_double),
+        ("batch", C.c_int32),
+        ("max_points", C.c_int32),
+        ("dim", C.c_int32),
+        ("dtype", C.c_int32),
+        ("host", C.c_int32),
+        ("agent", C.c_int32),
+        ("max_steps", C.c_int32),
+        ("flags", C.c_uint32),
+        ("step_offset", C.c_uint32),
+        ("reserved_", C.c_uint32),
+    ]
+
+
 _vp, _i, _i64, _u32, _u64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
 
 # name -> (restype, argtypes) of every symbol the header declares.  `stream` is the trailing
@@ -245,12 +278,17 @@ DEVICE_PROTOTYPES = {
     "hk_host_select": (C.c_int, [_vp, _i64, _vp, _i, _i, _i, _i, _i, _vp]),
 }
 
+# the entry point of include/hironaka_hip_play.h: the device library's only, as above
+PLAY_PROTOTYPES = {
+    "hk_game_play": (C.c_int, [C.POINTER(hk_game_play_desc), _vp]),
+}
+
 
 def bind(lib: C.CDLL, prototypes=None) -> None:
-    """Attach restype/argtypes (default: PROTOTYPES and DEVICE_PROTOTYPES); raises AttributeError for a symbol the
-    library lacks."""
+    """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES and PLAY_PROTOTYPES); raises AttributeError for
+    a symbol the library lacks."""
     if prototypes is None:
-        prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES}
+        prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES}
     for name, (res, args) in prototypes.items():
         fn = getattr(lib, name)
         fn.restype = res

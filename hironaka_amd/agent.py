@@ -39,6 +39,11 @@ class Agent(abc.ABC):
     def _get_actions(self, points: torch.Tensor, coords: torch.Tensor) -> torch.Tensor:
         ...
 
+    def _play(self, agent: str, points, **kwargs):
+        """ops.game_play with this agent's rule and USE_REPOSITION (RandomAgent.play, ChooseFirstAgent.play)"""
+        pts = points.points if hasattr(points, "points") else points
+        return ops.game_play(pts, agent=agent, reposition=self.USE_REPOSITION, **kwargs)
+
 
 class RandomAgent(Agent):
     """agent.py:85-90 -- uniform over the host's subset."""
@@ -46,6 +51,20 @@ class RandomAgent(Agent):
     def __init__(self, seed: Optional[Union[int, torch.Generator]] = None):
         self._gen = seed if isinstance(seed, torch.Generator) else None
         self._seed = seed if isinstance(seed, int) else None
+        self._play_seed = None
+        self.moves = 0  # moves play() may have drawn for: the move number in the random agent's counter
+
+    def play(self, points, **kwargs):
+        """whole games in one launch (ops.game_play, agent="random"): the draws come from Philox keyed by this agent's
+        seed (the generator's initial seed, or a fresh one when the agent has none), the game and the move number"""
+        if self._play_seed is None:
+            given = self._gen.initial_seed() if self._gen is not None else self._seed
+            self._play_seed = (random.getrandbits(63) if given is None else int(given)) % 2 ** 64
+        kwargs.setdefault("seed", self._play_seed)
+        kwargs.setdefault("step_offset", self.moves)
+        res = self._play("random", points, **kwargs)
+        self.moves += kwargs["max_steps"]
+        return res
 
     def _get_actions(self, points, coords):
         if self._gen is None and self._seed is not None:
@@ -60,6 +79,10 @@ class ChooseFirstAgent(Agent):
 
     def _get_actions(self, points, coords):
         return torch.argmax((coords > 0).to(torch.int32), dim=1).to(torch.int32)
+
+    def play(self, points, **kwargs):
+        """whole games in one launch (ops.game_play, agent="choose_first")"""
+        return self._play("choose_first", points, **kwargs)
 
 
 class PolicyAgent(Agent):

@@ -15,7 +15,7 @@ import torch
 
 from . import _abi as A
 from . import ops
-from .agent import Agent, AgentMorin
+from .agent import Agent, AgentMorin, ChooseFirstAgent, RandomAgent
 from .core import HipPoints
 from .host import AllCoordHost, Host, WeakSpivakovsky, WeakSpivakovskyMinHitting, Zeillinger, ZeillingerLex
 from .host_action_preprocess import encode_host_class
@@ -64,7 +64,56 @@ class Game(abc.ABC):
 
 
 class GameHironaka(Game):
-    """game.py:84-119"""
+    """game.py:84-119.  ``step()`` is one move of every game in up to three launches (the host's, the agent's fused
+    move, the rescale).  ``play(n)`` runs up to n further moves of every game in ONE launch of hk_game_play when the
+    host is one of the five deterministic hosts and the agent a `RandomAgent` or a `ChooseFirstAgent`, on a state in
+    list semantics with padding -1; it is also the only way the hitting-set hosts play at dimension 7.  It appends the
+    ``coord_history`` / ``move_history`` entries that ``step()`` would (zeros / -1 for a game that did not move) and
+    keeps, per game, ``length`` [B] (the moves ``play`` has made), ``outcome`` [B] (the HK_PLAY_* code,
+    ops.PLAY_OUTCOMES) and ``stopped_batch`` [B]; ``stopped`` is true once every game has stopped."""
+
+    def __init__(self, state: Optional[HipPoints], host: Host, agent: Agent, **kwargs):
+        super().__init__(state, host, agent, **kwargs)
+        self.stopped_batch = self.outcome = self.length = None
+        self._host_name = _KERNEL_HOSTS.get(type(self.host))  # exact types: a subclass may override select_coord
+        self._may_hold_frozen = False  # a game stopped by something other than its end: play() must not touch it again
+
+    def play(self, max_steps: int) -> bool:
+        """up to max_steps further moves of every game in one launch; True if games go on"""
+        if self._host_name is None or type(self.agent) not in (RandomAgent, ChooseFirstAgent):
+            raise TypeError("play() runs the host and the agent inside the launch: it needs one of the five "
+                            "deterministic hosts and a RandomAgent or a ChooseFirstAgent. Got "
+                            f"{type(self.host).__name__} and {type(self.agent).__name__}; use step().")
+        if self.state is None or self.stopped or max_steps < 1:
+            return not self.stopped
+        if getattr(self.state, "semantics", None) != "list" or self.state.padding_value != -1.0:
+            raise ValueError("play() needs a HipPoints with semantics='list' and padding_value=-1; use step().")
+        pts = self.state.points
+        b, _, d = pts.shape
+        if self.outcome is None:
+            self.outcome = torch.zeros(b, dtype=torch.int32, device=pts.device)
+            self.length = torch.zeros(b, dtype=torch.int32, device=pts.device)
+        work = pts if pts.dtype in (torch.float32, torch.float64) else pts.float()
+        frozen = (self.outcome != A.HK_PLAY_RUNNING) & (self.outcome != A.HK_PLAY_ENDED)
+        classes = None
+        if self._may_hold_frozen and bool(frozen.any()):
+            # a class id beyond the dimension's classes: the launch leaves such a game as it is
+            classes = torch.where(frozen, (1 << d) - d - 1, -1).to(torch.int32).unsqueeze(1).repeat(1, max_steps)
+        res = self.agent.play(work, host=self._host_name, max_steps=max_steps, classes=classes,
+                              rescale=bool(self.scale_observation), record=True, out=work)
+        if work is not pts:
+            pts.copy_(work)
+        self.outcome = torch.where(frozen, self.outcome, res.outcome)
+        self.length = self.length + res.length
+        self.stopped_batch = self.outcome != A.HK_PLAY_RUNNING
+        for t in range(int(res.length.max())):  # (the one synchronisation of a fused run)
+            played = res.classes[:, t] >= 0
+            mask = ops.decode_host_class(res.classes[:, t].clamp(min=0), d, torch.int32)
+            self.coord_history.append(mask * played.unsqueeze(1).to(torch.int32))
+            self.move_history.append(res.axes[:, t])
+        self._may_hold_frozen = bool(((self.outcome != A.HK_PLAY_RUNNING) & (self.outcome != A.HK_PLAY_ENDED)).any())
+        self.stopped = bool(self.stopped_batch.all())
+        return not self.stopped
 
     def step(self, verbose: int = 0) -> bool:
         if self.stopped:

@@ -934,3 +934,93 @@ def morin_play(points: torch.Tensor, weights: torch.Tensor, distinguished: torch
         out.copy_(dst)
         dst = out
     return MorinPlayResult(dst, w_out, d_out, length, outcome, c_out, a_out)
+
+
+PLAY_AGENTS = {"random": A.HK_AGENT_RANDOM_LEGAL, "choose_first": A.HK_AGENT_CHOOSE_FIRST,
+               "choose_last": A.HK_AGENT_CHOOSE_LAST}
+PLAY_OUTCOMES = {A.HK_PLAY_RUNNING: "running", A.HK_PLAY_ENDED: "ended", A.HK_PLAY_NO_MOVE: "no move",
+                 A.HK_PLAY_INEXACT: "inexact", A.HK_PLAY_VALUE_LIMIT: "value limit"}
+
+GamePlayResult = collections.namedtuple("GamePlayResult", "points length outcome classes axes")
+
+
+def game_play(points: torch.Tensor, *, host: Optional[str] = None, agent: str = "choose_first", max_steps: int,
+              classes: Optional[torch.Tensor] = None, axes: Optional[torch.Tensor] = None, reposition: bool = False,
+              rescale: bool = False, reduce_root: bool = False, rescale_root: bool = False,
+              value_threshold: Optional[float] = None, seed: int = 0, game_offset: int = 0, step_offset: int = 0,
+              record: bool = False, out: Optional[torch.Tensor] = None) -> GamePlayResult:
+    """Plain Hironaka games played forward, one game per lane, up to ``max_steps`` moves in one launch (hk_game_play;
+    hironaka/game.py:84-119 GameHironaka with hironaka/agent.py:85-98 RandomAgent / ChooseFirstAgent).  points:
+    [B, m, d] float32/float64 in list semantics (padding -1), d in 2..7, m <= 64; games that are contiguous records at
+    any stride are read in place, any other view through a copy.  host: a key of SEARCH_HOSTS, or None when ``classes``
+    forces every move.  agent: a key of PLAY_AGENTS ("random" draws from Philox keyed by (seed, game_offset + b,
+    step_offset + move), so shards and launches that continue a game reproduce one launch).  classes / axes:
+    [B, max_steps] forced class ids / axes, entries < 0 leave the move to the host / the agent.  reposition: the stage
+    between shift and Newton that Agent.USE_REPOSITION stands for.  rescale: the list rescale after every move
+    (scale_observation).  reduce_root / rescale_root: Newton sorted + compacted, then the rescale, before any move (with
+    max_steps=0 the call is just these); a root that is not reduced is played as given.  value_threshold: a game one of
+    whose coordinates exceeds it after a move stops with HK_PLAY_VALUE_LIMIT; None or <= 0 for none.  record: return the
+    moves played as classes / axes [B, max_steps], -1 from length on.  out: where the final points go; default a new
+    tensor.  It may be ``points`` itself (in place); an ``out`` that shares memory with ``points`` in any other way is
+    served through a copy of ``points``.  Returns GamePlayResult(points, length, outcome, classes, axes); outcome holds
+    the HK_PLAY_* codes of include/hironaka_hip_play.h (PLAY_OUTCOMES names them)."""
+    if host is not None and host not in SEARCH_HOSTS:
+        raise ValueError(f"host must be None or one of {sorted(SEARCH_HOSTS)}. Got {host!r}.")
+    if agent not in PLAY_AGENTS:
+        raise ValueError(f"agent must be one of {sorted(PLAY_AGENTS)}. Got {agent!r}.")
+    if not (0 <= max_steps < 2 ** 31 and 0 <= seed < 2 ** 64 and 0 <= game_offset < 2 ** 64
+            and 0 <= step_offset < 2 ** 32 - max_steps):
+        raise ValueError(f"need 0 <= max_steps < 2^31, seed and game_offset in [0, 2^64), step_offset + max_steps < 2^32. "
+                         f"Got {max_steps}, {seed}, {game_offset}, {step_offset}.")
+    if value_threshold is not None and value_threshold != value_threshold:
+        raise ValueError("value_threshold must be a number or None. Got NaN.")
+    _require_device(points, "points")
+    if points.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"points must be float32 or float64. Got {points.dtype}.")
+    if points.dim() != 3:
+        raise ValueError(f"points must be [B, max_points, dim]. Got shape {tuple(points.shape)}.")
+    b, m, d = points.shape
+    dev = points.device
+    ints = {}
+    for t, name in ((classes, "classes"), (axes, "axes")):
+        if t is not None:
+            _require_device(t, name)
+            if t.dtype not in (torch.int32, torch.int64) or tuple(t.shape) != (b, max_steps) or t.device != dev:
+                raise ValueError(f"{name} must be an int32/int64 tensor of shape {(b, max_steps)} on the points' device. "
+                                 f"Got {t.dtype} {tuple(t.shape)} on {t.device}.")
+            t = t.clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
+        ints[name] = t
+    if host is None and classes is None and max_steps > 0:
+        raise ValueError("without a host every move needs a forced class: pass classes.")
+    if out is not None:
+        _require_device(out, "out")
+        if out.shape != points.shape or out.dtype != points.dtype or out.device != dev:
+            raise ValueError(f"out must match points: {tuple(points.shape)} {points.dtype} on {dev}. Got "
+                             f"{tuple(out.shape)} {out.dtype} on {out.device}.")
+    src = points if _record_stride(points) is not None else points.contiguous()
+    dst = out if out is not None and _record_stride(out) is not None else torch.empty((b, m, d), dtype=points.dtype,
+                                                                                      device=dev)
+    if _records_overlap(src, dst) and not (dst.data_ptr() == src.data_ptr() and dst.stride() == src.stride()):
+        src = src.clone()  # only an exact in-place call may share memory: workgroups write back while others still read
+    new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    length, outcome = new(b), new(b)
+    c_out, a_out = (new(b, max_steps), new(b, max_steps)) if record else (None, None)
+    q = A.hk_game_play_desc()
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    q.points_in, q.points_out = src.data_ptr(), dst.data_ptr()
+    q.in_stride, q.out_stride = _record_stride(src), _record_stride(dst)
+    q.class_in, q.axis_in, q.class_out, q.axis_out = ptr(ints["classes"]), ptr(ints["axes"]), ptr(c_out), ptr(a_out)
+    q.length_out, q.outcome_out = length.data_ptr(), outcome.data_ptr()
+    q.seed, q.game_offset, q.step_offset = seed, game_offset, step_offset
+    q.value_threshold = 0.0 if value_threshold is None else float(value_threshold)
+    q.batch, q.max_points, q.dim, q.dtype = b, m, d, _TORCH2HK[points.dtype]
+    q.host = A.HK_PLAY_HOST_FORCED if host is None else SEARCH_HOSTS[host]
+    q.agent, q.max_steps = PLAY_AGENTS[agent], max_steps
+    q.flags = ((A.HK_PLAY_REPOSITION if reposition else 0) | (A.HK_PLAY_RESCALE if rescale else 0)
+               | (A.HK_PLAY_REDUCE_ROOT if reduce_root else 0) | (A.HK_PLAY_RESCALE_ROOT if rescale_root else 0))
+    with torch.cuda.device(dev):
+        check(lib().hk_game_play(C.byref(q), _stream(points)), "hk_game_play")
+    if out is not None and dst is not out:
+        out.copy_(dst)
+        dst = out
+    return GamePlayResult(dst, length, outcome, c_out, a_out)

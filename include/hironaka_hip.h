@@ -53,6 +53,8 @@
  *   hk_search_morin_tree     hironaka/util/search.py:53-93 search_tree_morin (weights and a distinguished point per node)
  *   hk_search_morin_play     hironaka/game.py:122-154 GameMorin with agent.py:114-136 AgentMorin, one game per lane;
  *                            core/list_points.py:86-116 the distinguished point that get_newton_polytope tracks
+ *   hk_game_play             (hironaka_hip_play.h) hironaka/game.py:84-119 GameHironaka with agent.py:85-98 RandomAgent /
+ *                            ChooseFirstAgent, one game per lane; validator/hironaka_validator.py:30-48 playoff's games
  *   hk_host_select           (hironaka_hip_hosts.h) host.py:48-51 AllCoordHost, host.py:54-95 Zeillinger, host.py:116-127 ZeillingerLex,
  *                            host.py:357-378 WeakSpivakovsky, host.py:381-427 WeakSpivakovskyMinHitting
  *                            (select_coord on ListPoints)
@@ -614,5 +616,7 @@ int hk_search_morin_play(const hk_morin_play_desc* desc, void* stream);
 
 /* ABI 6: hk_host_select, an entry point with no CPU-oracle counterpart */
 #include "hironaka_hip_hosts.h"
+/* within ABI 6: hk_game_play, likewise */
+#include "hironaka_hip_play.h"
 
 #endif /* HIRONAKA_HIP_H */
