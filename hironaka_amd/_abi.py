@@ -69,6 +69,10 @@ HK_PLAY_RUNNING, HK_PLAY_ENDED, HK_PLAY_NO_MOVE, HK_PLAY_INEXACT, HK_PLAY_VALUE_
 HK_PLAY_REPOSITION, HK_PLAY_RESCALE, HK_PLAY_REDUCE_ROOT, HK_PLAY_RESCALE_ROOT = 1, 2, 4, 8
 HK_PLAY_HOST_FORCED = -1
 
+# hk_tree_expand: descriptor flags, the bit of its status word
+HK_TREE_REPOSITION, HK_TREE_ZERO_TAIL = 1, 2
+HK_TREE_OVERFLOW = 1
+
 SEMANTICS = {"jax": HK_SEM_JAX, "torch": HK_SEM_TORCH, "list": HK_SEM_LIST}
 
 
@@ -212,6 +216,30 @@ class hk_game_play_desc(C.Structure):
     ]
 
 
+class hk_tree_expand_desc(C.Structure):
+    _fields_ = [
+        ("parents_in", C.c_void_p),
+        ("children_out", C.c_void_p),
+        ("in_stride", C.c_int64),
+        ("out_stride", C.c_int64),
+        ("class_id", C.c_void_p),
+        ("child_offset", C.c_void_p),
+        ("child_parent", C.c_void_p),
+        ("child_axis", C.c_void_p),
+        ("child_num_points", C.c_void_p),
+        ("child_done", C.c_void_p),
+        ("status", C.c_void_p),
+        ("n_parents", C.c_int32),
+        ("capacity", C.c_int32),
+        ("max_points", C.c_int32),
+        ("dim", C.c_int32),
+        ("dtype", C.c_int32),
+        ("sem", C.c_int32),
+        ("flags", C.c_uint32),
+        ("reserved_", C.c_uint32),
+    ]
+
+
 _vp, _i, _i64, _u32, _u64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
 
 # name -> (restype, argtypes) of every symbol the header declares.  `stream` is the trailing
@@ -283,12 +311,17 @@ PLAY_PROTOTYPES = {
     "hk_game_play": (C.c_int, [C.POINTER(hk_game_play_desc), _vp]),
 }
 
+# the entry point of include/hironaka_hip_tree.h: the device library's only, as above
+TREE_PROTOTYPES = {
+    "hk_tree_expand": (C.c_int, [C.POINTER(hk_tree_expand_desc), _vp]),
+}
+
 
 def bind(lib: C.CDLL, prototypes=None) -> None:
-    """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES and PLAY_PROTOTYPES); raises AttributeError for
-    a symbol the library lacks."""
+    """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES and TREE_PROTOTYPES); raises
+    AttributeError for a symbol the library lacks."""
     if prototypes is None:
-        prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES}
+        prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES, **TREE_PROTOTYPES}
     for name, (res, args) in prototypes.items():
         fn = getattr(lib, name)
         fn.restype = res

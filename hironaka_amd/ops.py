@@ -1024,3 +1024,114 @@ def game_play(points: torch.Tensor, *, host: Optional[str] = None, agent: str = 
         out.copy_(dst)
         dst = out
     return GamePlayResult(dst, length, outcome, c_out, a_out)
+
+
+# ---- one level of a game tree under any host (hk_tree_expand) -------------------------------------------------------
+
+TreeExpandResult = collections.namedtuple(
+    "TreeExpandResult", "children child_parent child_axis child_num_points child_done total status")
+_class_sizes_cache: Dict[Tuple[int, torch.device], torch.Tensor] = {}
+
+
+def _class_sizes(d: int, device: torch.device) -> torch.Tensor:
+    """int64 [2^d - d - 1]: the number of coordinates of every host class of dimension d"""
+    key = (d, device)
+    if key not in _class_sizes_cache:
+        sizes = [bin(v).count("1") for v in range(1, 1 << d) if v & (v - 1)]
+        _class_sizes_cache[key] = torch.tensor(sizes, dtype=torch.int64, device=device)
+    return _class_sizes_cache[key]
+
+
+def _tree_records(t: torch.Tensor, m: int, d: int, name: str) -> torch.Tensor:
+    """the [N, m, d] view of states given as [N, m, d], [N, m*d] or records [N, m*d + d]: a view where the states
+    are contiguous records at any stride and offset, else a copy"""
+    if t.dim() == 3 and tuple(t.shape[1:]) == (m, d):
+        v = t
+    elif t.dim() == 2 and t.shape[1] in (m * d, m * d + d):
+        if t.stride(1) == 1:
+            v = t.as_strided((t.shape[0], m, d), (t.stride(0), d, 1), t.storage_offset())
+        else:
+            v = t[:, :m * d].contiguous().view(-1, m, d)
+    else:
+        raise ValueError(f"{name} must be [N, {m}, {d}], [N, {m * d}] or records [N, {m * d + d}]. "
+                         f"Got shape {tuple(t.shape)}.")
+    return v if _record_stride(v) is not None else v.contiguous()
+
+
+def tree_expand(parents: torch.Tensor, class_id: torch.Tensor, *, spec: Tuple[int, int], sem: str = "jax",
+                reposition: bool = True, out: Optional[torch.Tensor] = None, capacity: Optional[int] = None,
+                zero_tail: bool = False) -> TreeExpandResult:
+    """One level of hironaka/jax/search.py:73-113 search_tree_fix_host over a whole frontier, in one launch
+    (hk_tree_expand).  parents: N states of spec=(m, d) as [N, m, d], [N, m*d] or records [N, m*d + d], float32 or
+    float64; contiguous records at any stride and offset are read in place, any other view through a copy.  class_id:
+    int32/int64 [N], the host's subset per parent; an id < 0 (or beyond the dimension's classes) means "do not
+    expand".  A parent has one child per coordinate of its subset in ascending order; the children are packed in
+    parent order.  sem: "jax" (shift, [reposition], Newton polytope; rows keep their places) or "list" (the same,
+    then sorted and compacted).  out: the children's buffer, [capacity, m, d], [capacity, m*d] or records
+    [capacity, m*d + d] of contiguous records; default a new one, records when ``zero_tail`` else [capacity, m, d],
+    uninitialised from ``total`` on.  capacity: the child slots that exist, default all of ``out``, or N*d.  A child
+    without a slot is dropped and HK_TREE_OVERFLOW is set in ``status``.  zero_tail: write d zeros behind every child's
+    state (``out`` must be records then); otherwise only the states are written.  Returns TreeExpandResult(children,
+    child_parent, child_axis, child_num_points, child_done, total, status): the per-child tensors have ``capacity``
+    entries, ``total`` (int64 scalar on the device) of which are children when nothing was dropped; status is an int32
+    scalar on the device.  Nothing here synchronises."""
+    if sem not in ("jax", "list"):
+        raise ValueError(f"sem must be 'jax' or 'list'. Got {sem!r}.")
+    m, d = (int(v) for v in spec)
+    _require_device(parents, "parents")
+    _require_device(class_id, "class_id")
+    if parents.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"parents must be float32 or float64. Got {parents.dtype}.")
+    dev = parents.device
+    src = _tree_records(parents, m, d, "parents")
+    n = src.shape[0]
+    if class_id.dtype not in (torch.int32, torch.int64) or tuple(class_id.shape) != (n,) or class_id.device != dev:
+        raise ValueError(f"class_id must be an int32/int64 tensor of shape {(n,)} on the parents' device. Got "
+                         f"{class_id.dtype} {tuple(class_id.shape)} on {class_id.device}.")
+    sizes = _class_sizes(d, dev)
+    cls64 = class_id.to(torch.int64)
+    valid = (cls64 >= 0) & (cls64 < sizes.numel())
+    cls = torch.where(valid, cls64, cls64.new_full((), -1)).to(torch.int32)
+    counts = torch.where(valid, sizes[cls64.clamp(0, sizes.numel() - 1)], cls64.new_zeros(()))
+    ends = torch.cumsum(counts, 0)
+    offsets = (ends - counts).contiguous()
+    total = ends[-1] if n else torch.zeros((), dtype=torch.int64, device=dev)
+    if out is not None:
+        _require_device(out, "out")
+        if out.dtype != parents.dtype or out.device != dev:
+            raise ValueError(f"out must be {parents.dtype} on {dev}. Got {out.dtype} on {out.device}.")
+        if zero_tail and not (out.dim() == 2 and out.shape[1] == m * d + d):
+            raise ValueError(f"zero_tail needs out as records [capacity, {m * d + d}]. Got shape {tuple(out.shape)}.")
+        dst = _tree_records(out, m, d, "out")
+        if out.numel() and dst.data_ptr() != out.data_ptr():
+            raise ValueError("out must hold contiguous records (any stride between them): the children are written "
+                             "in place.")
+        capacity = out.shape[0] if capacity is None else capacity
+        if not 0 <= capacity <= out.shape[0]:
+            raise ValueError(f"capacity must lie in [0, {out.shape[0]}] (the records of out). Got {capacity}.")
+        children = out
+    else:
+        capacity = n * d if capacity is None else capacity
+        if not 0 <= capacity < 2 ** 31:
+            raise ValueError(f"capacity must lie in [0, 2^31). Got {capacity}.")
+        children = torch.empty((capacity, m * d + d) if zero_tail else (capacity, m, d), dtype=parents.dtype, device=dev)
+        dst = _tree_records(children, m, d, "out")
+    if n >= 2 ** 31:
+        raise ValueError(f"at most 2^31 - 1 parents per call. Got {n}.")
+    new = lambda dtype: torch.empty(capacity, dtype=dtype, device=dev)  # noqa: E731
+    c_par, c_ax, c_np, c_done = new(torch.int32), new(torch.int32), new(torch.int32), new(torch.bool)
+    status = torch.zeros((), dtype=torch.int32, device=dev)
+    q = A.hk_tree_expand_desc()
+    q.parents_in, q.children_out = src.data_ptr(), dst.data_ptr()
+    q.in_stride = _record_stride(src)
+    # (a buffer of one record has no stride between records: with a tail, the tail belongs to the record)
+    q.out_stride = m * d + d if zero_tail and dst.shape[0] <= 1 else _record_stride(dst)
+    q.class_id, q.child_offset = cls.data_ptr(), offsets.data_ptr()
+    q.child_parent, q.child_axis = c_par.data_ptr(), c_ax.data_ptr()
+    q.child_num_points, q.child_done, q.status = c_np.data_ptr(), c_done.data_ptr(), status.data_ptr()
+    q.n_parents, q.capacity, q.max_points, q.dim = n, capacity, m, d
+    q.dtype, q.sem = _TORCH2HK[parents.dtype], A.SEMANTICS[sem]
+    q.flags = (A.HK_TREE_REPOSITION if reposition else 0) | (A.HK_TREE_ZERO_TAIL if zero_tail else 0)
+    with torch.cuda.device(dev):
+        check(lib().hk_tree_expand(C.byref(q), _stream(parents)), "hk_tree_expand")
+    return TreeExpandResult(children, c_par, c_ax, c_np, c_done, total, status)

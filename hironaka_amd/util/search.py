@@ -12,7 +12,7 @@ weights and a distinguished point; actions are pruned by weight and a child that
 with the reference's "...more..." nodes added where it stops at ``max_size``.  ``search_trees_morin`` returns the
 trees of a batch of roots as tensors.
 
-The JAX ``search_tree_fix_host`` is not built here.
+The JAX ``search_tree_fix_host`` (any callable host, level by level) lives in ``hironaka_amd.host_tree``.
 """
 from collections import namedtuple
 from typing import NamedTuple, Optional
