@@ -19,10 +19,34 @@
 #pragma once
 
 #include "hk_fast_kernel.h"
+#include "hk_lds_dma.h"
 
 namespace hk {
 
 constexpr int kDuoGames = kWave / 2;
+
+// The two parts around the step loops that won their alternations, one bit each, so that a dev build can take one out
+// again (-DHK_DUO_LEGS=<mask>; scripts/build_probe.sh passes it on: mask 0 is the time line "before"; the product builds
+// with both): 1 the slab by LDS-DMA, 2 the scan's guard as a word and the wave maximum by DPP.
+// profiles/duo_prologue_ab.txt holds each one's alternation and those of the two parts that tied and are gone: a
+// full wave's final stores without per-chunk predicates, and the finished-game counts behind the final stores (in
+// profiles/duo_prologue_timeline*.txt the counts are 0.9 us of the wave's end wherever they stand).
+#ifndef HK_DUO_LEGS
+#define HK_DUO_LEGS 3
+#endif
+#ifdef HK_DUO_PROBE
+// dev builds (scripts/build_probe.sh): a row of time stamps per wave in a buffer of the probe's own -- one copy per
+// translation unit; the unit that instantiates the kernels reads it back (hk_duo_spec.hip: hk_duo_probe_read)
+constexpr int kDuoProbeRow = 48, kDuoProbeWaves = 4096;
+static __device__ int32_t duo_probe_rows[kDuoProbeWaves * kDuoProbeRow];
+// (the final store takes two stamps: a parameter of the probe build only)
+#define HK_DUO_PROBE_PARAM , int32_t* probe = nullptr
+#define HK_DUO_PROBE_ARG(p) , p
+#else
+#define HK_DUO_PROBE_PARAM
+#define HK_DUO_PROBE_ARG(p)
+#endif
+constexpr bool kDuoLegDma = (HK_DUO_LEGS & 1) != 0, kDuoLegScan = (HK_DUO_LEGS & 2) != 0;
 
 // the partner lane's value: DPP quad_perm [1, 0, 3, 2]
 __device__ __forceinline__ int duo_other_i(int v) { return qperm_i<0xB1>(v); }
@@ -87,6 +111,48 @@ __device__ __forceinline__ void duo_slab_commit(DuoSlabRegs<M, D>& r, float* lds
   }
 }
 
+// The slab by LDS-DMA (hk_quad_kernel.h: quad_slab_load), where the two-lane image IS the contiguous slab -- 16-byte
+// chunks, no row padding in LDS (FastGeom::S == N: (20,3), (4,3)) -- and the caller's records are contiguous and 16-byte
+// aligned (the kernel checks both, wave-uniform): lane l of request `it` moves 16 B to image + (it * 64 + l) * 16.  No
+// registers, no ds_write, no commit under per-chunk masks: one VGPR offset, the slab's base in SGPRs, the rest in the
+// instructions' immediate offsets.  A full wave's requests are whole but for the constant mask of the last one; on the
+// batch's last slab the lanes past its end sit out (nothing is written past the games the wave owns).  Completion is the
+// wave's vmcnt.  Every other layout (strided or unaligned records, other chunk widths, padded images) stays on the
+// register path above.
+template <int M, int D>
+struct DuoDma {
+  using G = FastGeom<M, D>;
+  static constexpr bool kShape = kDuoLegDma && G::W == 4 && G::S == G::N;
+};
+
+template <int M, int D>
+__device__ __forceinline__ void duo_slab_dma(const float* base, float* image, int ngames, int lane) {
+  using G = FastGeom<M, D>;
+  constexpr int FULL = kDuoGames * G::Q;  // requests of a full slab
+  constexpr int QH = DuoGeom<M, D>::QH;   // ... per lane
+  constexpr int kImm = kDmaImm;  // (the immediate offset moves the global AND the LDS address)
+  static_assert(DuoDma<M, D>::kShape, "the image is the slab");
+  const float* src = base + (unsigned)lane * 4;  // request `it`: + it * 64 * 4 floats, in the immediate
+  const unsigned total = (unsigned)ngames * G::Q;
+  if (ngames == kDuoGames) {  // (wave-uniform) every request but the last one whole
+    unrolled_while<0, QH>([&](auto ic) {
+      constexpr int it = decltype(ic)::value;
+      if ((it + 1) * kWave <= FULL || lane < FULL - it * kWave)
+        lds_dma<16, (it * kWave * 16) % kImm>(src + (it * kWave * 16) / kImm * (kImm / 4),
+                                             image + (it * kWave * 16) / kImm * (kImm / 4));
+      return true;
+    });
+  } else {  // the batch's last slab: lanes past its end sit out
+    unrolled_while<0, QH>([&](auto ic) {
+      constexpr int it = decltype(ic)::value;
+      if ((unsigned)lane + it * kWave < total)
+        lds_dma<16, (it * kWave * 16) % kImm>(src + (it * kWave * 16) / kImm * (kImm / 4),
+                                             image + (it * kWave * 16) / kImm * (kImm / 4));
+      return true;
+    });
+  }
+}
+
 // How a slab's chunks leave for memory.  Plain and non-temporal stores keep their lines, dirty, in the XCD's L2.
 // Write-through stores (sc1) cost a plain store each, drain while the launch's other waves still play and leave nothing
 // to write back; the line is dropped from the writer's L2, so the next reader is served from the Infinity Cache.
@@ -100,7 +166,7 @@ constexpr int kStorePlain = 0, kStoreNT = 1, kStoreWT = 2;
 // range check bounds every store once more; other chunk widths and strided records stay non-temporal)
 template <int M, int D, bool CONTIG, int kBatch, int ST = kStorePlain>
 __device__ __forceinline__ void duo_store_slab_impl(const float* lds, float* base, int64_t out_stride, int ngames,
-                                                    int lane) {
+                                                    int lane HK_DUO_PROBE_PARAM) {
   using G = FastGeom<M, D>;
   using V = typename VecOf<G::W>::type;
   constexpr int QH = DuoGeom<M, D>::QH;
@@ -117,6 +183,9 @@ __device__ __forceinline__ void duo_store_slab_impl(const float* lds, float* bas
     }
 #pragma unroll
     for (int u = 0; u < kBatch; ++u) asm volatile("" : "+v"(v[u]));
+#ifdef HK_DUO_PROBE
+    if (probe && lane == 0) probe[0] = (int32_t)wall_clock64();  // the image is in registers
+#endif
     if constexpr (kWT) {
       typedef unsigned int vu4 __attribute__((ext_vector_type(4)));
       // (the descriptor from wave-uniform values: the slab's base as two scalar halves, its bytes)
@@ -147,10 +216,13 @@ __device__ __forceinline__ void duo_store_slab_impl(const float* lds, float* bas
 
 template <int M, int D, int kBatch = DuoGeom<M, D>::QH, int ST = kStorePlain>
 __device__ inline void duo_store_slab(const float* lds, float* out, int64_t out_stride, int64_t g0, int ngames,
-                                      int lane) {
+                                      int lane HK_DUO_PROBE_PARAM) {
   float* base = out + g0 * out_stride;
-  if (out_stride == FastGeom<M, D>::N) duo_store_slab_impl<M, D, true, kBatch, ST>(lds, base, out_stride, ngames, lane);
-  else duo_store_slab_impl<M, D, false, kBatch, ST>(lds, base, out_stride, ngames, lane);
+  if (out_stride == FastGeom<M, D>::N) duo_store_slab_impl<M, D, true, kBatch, ST>(lds, base, out_stride, ngames, lane HK_DUO_PROBE_ARG(probe));
+  else duo_store_slab_impl<M, D, false, kBatch, ST>(lds, base, out_stride, ngames, lane HK_DUO_PROBE_ARG(probe));
+#ifdef HK_DUO_PROBE
+  if (probe && lane == 0) probe[1] = (int32_t)wall_clock64();  // the stores are issued
+#endif
 }
 
 struct DuoLadder {  // slots per lane: 1..6, 8, 10, ...
@@ -286,8 +358,13 @@ __device__ __forceinline__ void duo_scan_half(const float* mine, float fill, int
   const int i0 = h * C;
   const float* base = mine + i0 * D;
   uint32_t mask = 0;
-  ok = true;
   const uint32_t fill_bits = __float_as_uint(fill);
+  // The guard as a word per lane: a row that is neither available nor the fill row ORs the bits in which its extrema
+  // differ from the fill value into `off` (not zero: one of the two differs), an available row ORs zero -- the select
+  // rides on the compare the row's mask bit needs anyway; one compare after the last row.  (As a bool per row it was two
+  // more compares and three scalar and/or instructions chained through SGPR pairs, row after row.)
+  uint32_t off = 0;
+  bool okb = true;
 #pragma unroll
   for (int r = 0; r < C; ++r) {
     // (M odd: the second lane's last row lies past the game -- its read stays inside the wave's image and is not counted)
@@ -300,12 +377,36 @@ __device__ __forceinline__ void duo_scan_half(const float* mine, float fill, int
       lo = u < lo ? u : lo;
     }
     const bool ge = hi < 0x7F800000u;
-    const bool fl = (lo == fill_bits) && (hi == fill_bits);
-    ok &= (ge | fl | !valid);
+    if constexpr (DuoGeom<M, D>::kLean && kDuoLegScan) {
+      const uint32_t differs = (hi ^ fill_bits) | (lo ^ fill_bits);  // zero: the fill row
+      off |= (ge || !valid) ? 0u : differs;
+    } else {  // ((20,4) sits at the registers of its third wave: it keeps the chain of scalar masks)
+      const bool fl = (lo == fill_bits) && (hi == fill_bits);
+      okb &= (ge | fl | !valid);
+    }
     mask |= (ge && valid) ? (1u << r) : 0u;
   }
+  ok = (DuoGeom<M, D>::kLean && kDuoLegScan) ? off == 0u : okb;
   mask <<= i0;
   live = lanes_or<2>(mask);
+}
+
+// wave-wide maximum of a small non-negative int, in straight line: a running maximum within rows of 16 lanes by DPP row
+// shifts, the rows' maxima carried over by two row broadcasts, lane 63 read (wave_sum_u32 in hk_fast_kernel.h is the
+// same walk with a sum).  hk::wave_max counts down from its bound `hi`, a compare, two branches and four scalar
+// instructions per candidate: about ten rounds from 20 after the scan.  Whole wave active (callers sit under wave-uniform
+// branches).  DPP false ((20,4): DuoGeom::kLean, the registers of its third wave): the countdown.
+template <bool DPP>
+__device__ __forceinline__ int duo_wave_max(int v, int hi) {
+  if constexpr (!DPP) return wave_max(v, hi);
+  auto mx = [](int a, int b) { return a > b ? a : b; };
+  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true));   // row_shr:1 (lanes shifted in: 0)
+  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true));   // row_shr:2
+  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true));   // row_shr:4
+  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true));   // row_shr:8
+  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false));  // row_bcast:15 -> rows 1, 3
+  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false));  // row_bcast:31 -> rows 2, 3
+  return __builtin_amdgcn_readlane(v, kWave - 1);
 }
 
 // ---- the stages on NB slots per lane ----------------------------------------------------------------------
@@ -656,9 +757,10 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
   const bool active = gi < ngames;
   const bool leader = active && h == 0;
   const int64_t g = g0 + gi;
-#ifdef HK_DUO_PROBE  // dev builds (scripts/build_probe.sh): a time line per wave, written over game_length_out
-  __shared__ int32_t probe_buf[24];
-  if (lane < 24) probe_buf[lane] = 0;
+#ifdef HK_DUO_PROBE  // dev builds (scripts/build_probe.sh): a time line per wave, written to duo_probe_rows
+  // [0, 20) steps, 20 - 23 prologue, 24 scanned, 25 counts and lengths out, 26 published, 27 image read, 28 stores issued
+  __shared__ int32_t probe_buf[32];
+  if (lane < 32) probe_buf[lane] = 0;
   const long long probe_t0 = wall_clock64();
   long long probe_t1 = 0, probe_t2 = 0;
   int probe_steps = 0, probe_smax = 0;
@@ -668,12 +770,37 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
   // the slab requests follow it at once; nothing touches the id before they are out)
   const bool has_ids = kRoll && prm.game_ids != nullptr;
   uint32_t raw_id = 0;  // (positions: non-negative; zero-extended below -- a sign extension would wait for the load here)
-  if (has_ids && active) raw_id = (uint32_t)prm.game_ids[g];
-  __builtin_amdgcn_sched_barrier(0);
   DuoSlabRegs<M, D> slab;
-  duo_slab_issue<M, D>(slab, in0, in_stride0, g0, ngames, lane);
-  __builtin_amdgcn_sched_barrier(0);
-  const uint64_t gg = prm.game_offset + (has_ids ? (uint64_t)raw_id : (uint64_t)g);
+  uint64_t gg;
+  // (wave-uniform) the slab by LDS-DMA: contiguous, 16-byte aligned records of a shape whose image is the slab
+  bool dma = false;
+  if constexpr (DuoDma<M, D>::kShape) {
+    // Launches with game ids keep the register path: with the id's load in flight beside LDS-DMA requests the compiler
+    // waits for ALL of them where the id is first used (it does not count across the two kinds of request) -- for the
+    // slab, before the action window that is meant to hide behind it.  For the same reason the two cases are two
+    // branches from the id's load to its first use: joined in between, the launches WITHOUT ids waited for the register
+    // the load might have been written to.
+    if (has_ids) {
+      if (active) raw_id = (uint32_t)prm.game_ids[g];
+      __builtin_amdgcn_sched_barrier(0);
+      duo_slab_issue<M, D>(slab, in0, in_stride0, g0, ngames, lane);
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("" : "+v"(raw_id));  // (the id has arrived: the slab's loads are counted behind it)
+      gg = prm.game_offset + (uint64_t)raw_id;
+    } else {
+      dma = in_stride0 == G::N && ((uintptr_t)in0 & 15u) == 0;
+      if (dma) duo_slab_dma<M, D>(in0 + g0 * G::N, lds, ngames, lane);
+      else duo_slab_issue<M, D>(slab, in0, in_stride0, g0, ngames, lane);
+      __builtin_amdgcn_sched_barrier(0);
+      gg = prm.game_offset + (uint64_t)g;
+    }
+  } else {
+    if (has_ids && active) raw_id = (uint32_t)prm.game_ids[g];
+    __builtin_amdgcn_sched_barrier(0);
+    duo_slab_issue<M, D>(slab, in0, in_stride0, g0, ngames, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    gg = prm.game_offset + (has_ids ? (uint64_t)raw_id : (uint64_t)g);
+  }
   // plain rollouts: the first window of policy words, computed while the slab is in flight
   uint32_t pol_b0 = prm.step_offset >> 2;  // first block of the window (wave-uniform)
   const uint32_t pol_last = (prm.steps > 0) ? (prm.step_offset + (uint32_t)prm.steps - 1u) >> 2 : pol_b0;
@@ -708,7 +835,12 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
   RawActions<D> raw;
   const bool fetch_actions = !kRoll && (stages & HK_STAGE_SHIFT) && active;
   if (fetch_actions) fast_fetch_actions<D>(prm, g, M, raw);
-  duo_slab_commit<M, D>(slab, lds, ngames, lane);
+  if constexpr (DuoDma<M, D>::kShape) {
+    if (dma) wait_vmem_all();  // the slab is in the image
+    else duo_slab_commit<M, D>(slab, lds, ngames, lane);
+  } else {
+    duo_slab_commit<M, D>(slab, lds, ngames, lane);
+  }
   if (kLevelDeal && lane < D) hole_row[lane] = INFINITY;
   if (fetch_actions) fast_decode_actions<D>(prm, raw, c, axis_in);
   __syncthreads();
@@ -726,7 +858,11 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
     ok = true;
   }
   int np = mask_pop(gmask);
-  int nmax = wave_max(np, M);
+#ifdef HK_DUO_PROBE
+  asm volatile("" : "+v"(np));
+  if (lane == 0) probe_buf[24] = (int32_t)wall_clock64();  // scanned (the guard's vote and the wave maximum follow: probe_t1)
+#endif
+  int nmax = duo_wave_max<DuoGeom<M, D>::kLean && kDuoLegScan>(np, M);
   const bool exact = (fill == pad) && __all(ok) && nmax <= G::C;
 
   if (!exact) {
@@ -977,14 +1113,14 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
                 if constexpr (kLevelDeal) {  // (LO < smax <= NB: this level's straight-line deal, no dispatch)
                   gmask = lanes_or<2>(duo_scatter_level<CH, D, NB>(q, mine, gmask, h));
                   __syncthreads();
-                  nmax = wave_max(active ? np : 0, 2 * smax - 2);
+                  nmax = duo_wave_max<DuoGeom<M, D>::kLean && kDuoLegScan>(active ? np : 0, 2 * smax - 2);
                   smax = (nmax + 1) >> 1;
                   duo_gather_level<CH, D, NB>(q, mine, hole_row, gmask, h);  // slots [smax, NB) become holes again
                 } else {
                   gmask = duo_scatter<M, CH, D, NB>(q, mine, gmask, smax, h);
                   __syncthreads();
                   const int sprev = smax;
-                  nmax = wave_max(active ? np : 0, 2 * smax - 2);
+                  nmax = duo_wave_max<DuoGeom<M, D>::kLean && kDuoLegScan>(active ? np : 0, 2 * smax - 2);
                   smax = (nmax + 1) >> 1;
                   duo_gather_slots<M, CH, D, NB>(q, mine, gmask, sprev, h);  // slots [smax, sprev) become holes again
                 }
@@ -1098,12 +1234,15 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
       gmask = duo_scatter<M, CH, D>(q, mine, gmask, smax, h);
       __syncthreads();
       const int sprev = smax;
-      nmax = wave_max(active ? np : 0, 2 * smax - 2);
+      nmax = duo_wave_max<DuoGeom<M, D>::kLean && kDuoLegScan>(active ? np : 0, 2 * smax - 2);
       smax = (nmax + 1) >> 1;
       duo_gather_slots<M, CH, D>(q, mine, gmask, sprev, h);  // slots [smax, sprev) become holes again
     }
   }
   if (kRoll && leader && prm.game_length_out) prm.game_length_out[g] = length;
+#ifdef HK_DUO_PROBE
+  if (lane == 0) probe_buf[25] = (int32_t)wall_clock64();  // the counts and the lengths are out
+#endif
 
   // ---- publish ---------------------------------------------------------------------------------------------------
   __syncthreads();
@@ -1128,12 +1267,16 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
     }
   }
   __syncthreads();
+#ifdef HK_DUO_PROBE
+  if (lane == 0) probe_buf[26] = (int32_t)wall_clock64();  // published: the image holds the final state
+#endif
   // (plain rollouts: write-through for the lean shapes; at (20,4) the descriptor's registers cost the third wave: nt)
   constexpr int kFinalStore = MODE != kModeRollout ? kStorePlain : DuoGeom<M, D>::kLean ? kStoreWT : kStoreNT;
-  duo_store_slab<M, D, DuoGeom<M, D>::QH, kFinalStore>(lds, (float*)prm.out, prm.out_stride, g0, ngames, lane);
+  duo_store_slab<M, D, DuoGeom<M, D>::QH, kFinalStore>(lds, (float*)prm.out, prm.out_stride, g0, ngames,
+                                                       lane HK_DUO_PROBE_ARG(probe_buf + 27));
 #ifdef HK_DUO_PROBE
-  if (kRoll && lane == 0 && prm.game_length_out && ngames >= 8) {
-    int32_t* w = prm.game_length_out + g0;
+  if (kRoll && lane == 0 && blockIdx.x < (unsigned)kDuoProbeWaves) {
+    int32_t* w = duo_probe_rows + blockIdx.x * kDuoProbeRow;
     w[0] = (int32_t)probe_t0;
     w[1] = (int32_t)probe_t1;
     w[2] = (int32_t)probe_t2;
@@ -1142,8 +1285,7 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
     w[5] = probe_smax;
     w[6] = (int32_t)blockIdx.x;
     w[7] = (int32_t)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));  // HW_ID
-    if (ngames >= 32)
-      for (int i = 0; i < 24; ++i) w[8 + i] = probe_buf[i];
+    for (int i = 0; i < 32; ++i) w[8 + i] = probe_buf[i];
   }
 #endif
 }

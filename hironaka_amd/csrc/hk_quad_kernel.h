@@ -23,6 +23,7 @@
 #pragma once
 
 #include "hk_fast_kernel.h"
+#include "hk_lds_dma.h"
 
 namespace hk {
 
@@ -69,16 +70,6 @@ struct QuadGeom {
 // whole slab, the global address in SGPRs (saddr form), the rest in the instructions' immediate offsets -- the
 // per-request 64-bit address arithmetic was a third of the VALU instructions of the I/O skeleton, and at four waves
 // per SIMD every VALU instruction of the wave program is 16 cycles of the launch.
-// the instruction's immediate offset is 12 bits unsigned here (it moves the LDS address too); what exceeds it goes
-// into both base pointers
-constexpr int kDmaImm = 4096;
-template <int BYTES, int OFFSET>
-__device__ __forceinline__ void lds_dma(const float* src, float* dst) {
-  static_assert(BYTES == 16 || BYTES == 4, "request size");
-  if constexpr (BYTES == 16) __builtin_amdgcn_global_load_lds(src, dst, 16, OFFSET, 0);
-  else __builtin_amdgcn_global_load_lds(src, dst, 4, OFFSET, 0);
-}
-
 template <int M, int D>
 __device__ __forceinline__ void quad_slab_load(const float* base, float* image, int ngames, int lane) {
   using G = QuadGeom<M, D>;
@@ -106,8 +97,6 @@ __device__ __forceinline__ void quad_slab_load(const float* base, float* image, 
     });
   }
 }
-
-__device__ __forceinline__ void wait_vmem_all() { __builtin_amdgcn_s_waitcnt(0x0F70); }  // vmcnt(0)
 
 // NT: non-temporal stores (write-once streams: the per-step observations of a recording rollout)
 template <int M, int D, bool NT = false>

@@ -1,9 +1,13 @@
 """Dev probe: per-wave time line of the fused rollout (two-lane kernel, probe build with HK_DUO_PROBE): when each wave
-starts, has its slab, leaves the step loop and ends; how many steps it ran."""
+starts, has its slab, leaves the step loop and ends; how many steps it ran; the stages of its prologue and epilogue.
+The stamps come from the probe's own buffer (hk_duo_probe_read), not from an output.  HK_PROBE_LIB names another probe
+library than build_probe/libhk_probe.so (e.g. one built with -DHK_DUO_LEGS=0: the parts around the loops as before)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hironaka_amd import _lib
-_lib.LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "build_probe", "libhk_probe.so")
+_lib.LIB_PATH = os.environ.get("HK_PROBE_LIB") or os.path.join(
+    os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "build_probe", "libhk_probe.so")
+import ctypes
 import numpy as np
 import torch
 from hironaka_amd import ops
@@ -14,7 +18,11 @@ Q = torch.empty_like(P)
 for rep in range(3):
     res = ops.rollout(Q, T, 1 + rep, initial=P, record=("game_length",))
 torch.cuda.synchronize()
-full = res["game_length"].cpu().numpy().reshape(-1, 32).astype(np.int64)
+ROW, waves = 48, b // 32
+rows = np.zeros((waves, ROW), dtype=np.int32)
+rc = _lib.lib().hk_duo_probe_read(rows.ctypes.data_as(ctypes.c_void_p), waves)
+assert rc == 0, f"hk_duo_probe_read: {rc}"
+full = rows.astype(np.int64)
 gl = full[:, :8]
 t0, t1, t2, t3, steps, smax, blk, hwid = (gl[:, i] for i in range(8))
 base = t0.min()
@@ -62,3 +70,16 @@ for k in range(20):
     print(f"  step {k:2d}: waves {ran.sum():5d}  mean {dt[ran].mean():6.3f}  with re-deal {dt[shr].mean() if shr.sum() else 0:6.3f} (n={shr.sum()})  without {dt[ran & ~shr].mean() if (ran & ~shr).sum() else 0:6.3f}  slots after {sm[ran, k].mean():.2f}")
     prev = np.where(ran, clk[:, k], prev)
     prev_s = np.where(ran, sm[:, k], prev_s)
+
+# the stages inside the prologue and the epilogue (means over all waves, us since the previous stamp)
+stamp = lambda k: usp(full[:, 8 + k] & 0xFFFFFFFF)
+t0u, t1u, t2u, t3u = us(t0), us(t1), us(t2), us(t3)
+pro = (("action window filled", stamp(21) - t0u), ("slab in LDS (wait, barrier)", stamp(22) - stamp(21)),
+       ("scanned", stamp(24) - stamp(22)), ("guard vote + wave maximum", t1u - stamp(24)), ("rows dealt", stamp(23) - t1u))
+epi = (("counts and lengths out", stamp(25) - t2u), ("published", stamp(26) - stamp(25)),
+       ("image read back", stamp(27) - stamp(26)), ("stores issued", stamp(28) - stamp(27)),
+       ("to the end", t3u - stamp(28)))
+for title, parts in (("prologue", pro), ("epilogue", epi)):
+    print(f"{title} stages: " + "; ".join(f"{n} {v.mean():.2f}" for n, v in parts) + f"; total {sum(v.mean() for _, v in parts):.2f} us")
+full_waves = steps >= 19
+print(f"epilogue of the {full_waves.sum()} waves that ran 19-20 steps: " + "; ".join(f"{n} {v[full_waves].mean():.2f}" for n, v in epi))
