@@ -27,12 +27,15 @@ constexpr int kDuoGames = kWave / 2;
 
 // The two parts around the step loops that won their alternations, one bit each, so that a dev build can take one out
 // again (-DHK_DUO_LEGS=<mask>; scripts/build_probe.sh passes it on: mask 0 is the time line "before"; the product builds
-// with both): 1 the slab by LDS-DMA, 2 the scan's guard as a word and the wave maximum by DPP.
-// profiles/duo_prologue_ab.txt holds each one's alternation and those of the two parts that tied and are gone: a
+// with all of them): 1 the slab by LDS-DMA, 2 the scan's guard as a word and the wave maximum by DPP, 4 the
+// finished-game counts of a plain rollout as a histogram in LDS and a prefix sum across lanes (duo_length_counts).
+// profiles/duo_prologue_ab.txt holds the alternations of 1 and 2 and those of the two parts that tied and are gone: a
 // full wave's final stores without per-chunk predicates, and the finished-game counts behind the final stores (in
-// profiles/duo_prologue_timeline*.txt the counts are 0.9 us of the wave's end wherever they stand).
+// profiles/duo_prologue_timeline*.txt the counts are 0.9 us of the wave's end wherever they stand);
+// profiles/duo_epilogue_ab.txt those of 4, of the action window's variants (HK_DUO_PRE_BLOCKS, HK_DUO_FILL_CHAINS
+// below) and of the part that lost and is gone: the publish's padding rows in straight line.
 #ifndef HK_DUO_LEGS
-#define HK_DUO_LEGS 3
+#define HK_DUO_LEGS 7
 #endif
 #ifdef HK_DUO_PROBE
 // dev builds (scripts/build_probe.sh): a row of time stamps per wave in a buffer of the probe's own -- one copy per
@@ -47,6 +50,7 @@ static __device__ int32_t duo_probe_rows[kDuoProbeWaves * kDuoProbeRow];
 #define HK_DUO_PROBE_ARG(p)
 #endif
 constexpr bool kDuoLegDma = (HK_DUO_LEGS & 1) != 0, kDuoLegScan = (HK_DUO_LEGS & 2) != 0;
+constexpr bool kDuoLegCounts = (HK_DUO_LEGS & 4) != 0;
 
 // the partner lane's value: DPP quad_perm [1, 0, 3, 2]
 __device__ __forceinline__ int duo_other_i(int v) { return qperm_i<0xB1>(v); }
@@ -337,6 +341,8 @@ __device__ __forceinline__ uint32_t duo_scatter(const float (&q)[CH * D], float*
 }
 
 // `dead`: rows of the game's image to overwrite with the padding row; the pair shares them by rank
+// (in straight line over the slots per lane at entry, as duo_scatter, it lost its alternation -- x1.008 alone,
+// profiles/duo_epilogue_ab.txt -- and took the (20,3) records instantiation from 168 to 191 VGPRs)
 template <int D>
 __device__ __forceinline__ void duo_pad_rows(float* mine, uint32_t dead, float pad, int h) {
   dead = h ? (dead & (dead - 1)) : dead;
@@ -407,6 +413,32 @@ __device__ __forceinline__ int duo_wave_max(int v, int hi) {
   v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false));  // row_bcast:15 -> rows 1, 3
   v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false));  // row_bcast:31 -> rows 2, 3
   return __builtin_amdgcn_readlane(v, kWave - 1);
+}
+
+// The per-step finished-game counts of a wave (add_length_counts in hk_common.h: step s counts the games whose first
+// finished step is <= s) in closed form, for episodes of at most kWave - 1 steps: they are the running sum of a histogram
+// of at most 32 small integers.  `hist` is 64 words of LDS: every lane zeroes its word, the lane that speaks for a
+// finished game adds one to hist[length] (ds_add_u32), lane s reads hist[s] -- a wave's LDS instructions complete in
+// order, so the three need no wait between them --, an inclusive prefix sum across the lanes follows -- DPP row shifts
+// within rows of 16, two row broadcasts, the walk of wave_sum_u32 without its v_readlane -- and lane s <= nsteps with a
+// non-zero total issues the one atomic of add_length_counts.  Step 0 is part of the sum (games finished at entry:
+// length 0), so there is no entry count of its own.  The ballot form went VALU -> SGPR pair -> s_bcnt1 -> VALU once per
+// step: 20 dependent rounds, 1 us of every wave's end.  Whole wave active.
+// (The zeroing store stands here and not in the prologue, where the wave waits for its slab anyway: from there -- from
+// anywhere ahead of the step loops -- it cost (10,3) six to eight registers and a wave per SIMD, (20,4) its third wave.)
+__device__ __forceinline__ void duo_length_counts(uint32_t* hist, uint32_t* slot, uint32_t stride, int nsteps, bool counted,
+                                                  int length, int lane) {
+  hist[lane] = 0u;
+  if (counted && length >= 0) __hip_atomic_fetch_add(hist + length, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  __syncthreads();  // (a workgroup is one wave)
+  uint32_t v = hist[lane];
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);   // row_shr:1 (lanes shifted in: 0)
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);   // row_shr:2
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);   // row_shr:4
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);   // row_shr:8
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
+  if (lane <= nsteps && v) count_add(slot + (size_t)lane * stride, v);
 }
 
 // ---- the stages on NB slots per lane ----------------------------------------------------------------------
@@ -685,15 +717,32 @@ __device__ __forceinline__ int duo_zeillinger(const float (&q)[CH * D], int h, f
 // rounds: computed inside the step loop (one block per lane every four steps) it was a fifth of the loop's
 // instructions and most of a late step's latency (a step on one slot per lane is ~40 instructions without it).  The
 // words depend on (game, step) only, not on the state: a WINDOW of kDuoPreBlocks blocks per game (24 steps: four per block) is
-// computed before the first step -- while the wave would otherwise only wait for its slab -- two independent chains at
-// a time, DECODED (subset mask, axis: the decode was another ~15 instructions of every step) and parked in LDS, one byte
-// per game and step; a step reads its byte (both lanes of a pair the same address).  Episodes longer than a window
-// refill it between two passes over the staircase.
-constexpr int kDuoPreBlocks = 6;  // (a block serves four steps)
+// computed before the first step -- while the wave would otherwise only wait for its slab -- the lane's three blocks as
+// three independent chains in ONE pass where the window has five or six blocks (no rows are in registers yet; as two
+// chains and then one alone, the last pass -- the blocks of steps 16 .. 23, which 86 % of the headline's waves never
+// play -- was the one with the least parallelism), DECODED (subset mask, axis: the decode was another ~15 instructions
+// of every step) and parked in LDS, one byte per game and step; a step reads its byte (both lanes of a pair the same
+// address).  Episodes longer than a window refill it between two passes over the staircase.
+// Dev builds may change the window (-DHK_DUO_PRE_BLOCKS=<blocks>) and the number of independent Philox chains a lane
+// runs at a time (-DHK_DUO_FILL_CHAINS=2 or 3); scripts/build_probe.sh passes both on.  A window of 16 steps (4 blocks:
+// one pass of two chains, the refill for the waves that reach step 16) lost its alternation against the window of 24
+// (profiles/duo_epilogue_ab.txt).
+#ifndef HK_DUO_PRE_BLOCKS
+#define HK_DUO_PRE_BLOCKS 6
+#endif
+#ifndef HK_DUO_FILL_CHAINS
+#define HK_DUO_FILL_CHAINS 3
+#endif
+constexpr int kDuoPreBlocks = HK_DUO_PRE_BLOCKS;  // (a block serves four steps)
+constexpr int kDuoFillChains = HK_DUO_FILL_CHAINS;
+static_assert(kDuoPreBlocks >= 2 && kDuoPreBlocks % 2 == 0, "a pair of lanes fills two blocks at a time");
+static_assert(kDuoFillChains == 2 || kDuoFillChains == 3, "two or three chains per lane");
 
 // blocks [wb0, wb0 + nb) of the wave's games: lane (gi, h) computes blocks wb0 + h, wb0 + h + 2, ... and stores the
 // DECODED actions of their steps, one byte per game and step: subset mask (D bits) | axis << 5
-template <int D>
+// CHAINS: independent Philox chains per lane and pass -- kDuoFillChains before the first step, two in a refill (the rows
+// are in registers there: three chains cost (10,3), (8,4), (20,4) and the (20,3) records instantiations a wave per SIMD)
+template <int D, int CHAINS = 2>
 __device__ __forceinline__ void duo_policy_fill(uint8_t* act, uint64_t gg, uint32_t wb0, int nb, uint64_t seed,
                                                 int host_policy, int agent_policy, int gi, int h) {
   static_assert(D <= 5 && D <= kPolicyShortDim, "an action travels as a byte; four steps per Philox block");
@@ -708,10 +757,18 @@ __device__ __forceinline__ void duo_policy_fill(uint8_t* act, uint64_t gg, uint3
     }
   };
 #pragma nounroll
-  for (int i = 0; i < kDuoPreBlocks; i += 4) {
+  for (int i = 0; i < kDuoPreBlocks; i += 2 * CHAINS) {
     if (i >= nb) break;  // wave-uniform
     const int b0 = i + h, b1 = b0 + 2;
-    if (i + 2 < nb) {  // (wave-uniform) two independent chains
+    if (CHAINS == 3 && i + 4 < nb) {  // (wave-uniform) three independent chains
+      const int b2 = b0 + 4;
+      const U4 r0 = philox4x32((uint32_t)gg, (uint32_t)(gg >> 32), wb0 + (uint32_t)b0, kStreamPolicy, seed);
+      const U4 r1 = philox4x32((uint32_t)gg, (uint32_t)(gg >> 32), wb0 + (uint32_t)b1, kStreamPolicy, seed);
+      const U4 r2 = philox4x32((uint32_t)gg, (uint32_t)(gg >> 32), wb0 + (uint32_t)b2, kStreamPolicy, seed);
+      put(r0, b0);
+      put(r1, b1);
+      if (b2 < kDuoPreBlocks) put(r2, b2);
+    } else if (i + 2 < nb) {  // (wave-uniform) two independent chains
       const U4 r0 = philox4x32((uint32_t)gg, (uint32_t)(gg >> 32), wb0 + (uint32_t)b0, kStreamPolicy, seed);
       const U4 r1 = philox4x32((uint32_t)gg, (uint32_t)(gg >> 32), wb0 + (uint32_t)b1, kStreamPolicy, seed);
       put(r0, b0);
@@ -749,6 +806,9 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
   // plain rollouts: the policy words of a window of steps (duo_policy_fill)
   // (one row more than the window: the step loop requests the NEXT step's byte while it works on this one)
   __shared__ __align__(16) uint8_t pol[(MODE == kModeRollout) ? (4 * kDuoPreBlocks + 1) * kDuoGames : 16];
+  // plain rollouts of at most kWave - 1 steps: the histogram of the games' first finished steps (duo_length_counts)
+  constexpr bool kHistCounts = MODE == kModeRollout && kDuoLegCounts;
+  __shared__ uint32_t hist[kHistCounts ? kWave : 1];
   const int lane = threadIdx.x;
   const int h = lane & 1, gi = lane >> 1;
   const int64_t g0 = (int64_t)blockIdx.x * kDuoGames;
@@ -758,7 +818,8 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
   const bool leader = active && h == 0;
   const int64_t g = g0 + gi;
 #ifdef HK_DUO_PROBE  // dev builds (scripts/build_probe.sh): a time line per wave, written to duo_probe_rows
-  // [0, 20) steps, 20 - 23 prologue, 24 scanned, 25 counts and lengths out, 26 published, 27 image read, 28 stores issued
+  // [0, 20) steps, 20 - 23 prologue, 24 scanned, 25 counts and lengths out, 26 published, 27 image read, 28 stores issued,
+  // 29 counts out (plain rollouts: the counts alone, ahead of the records' flush and the lengths' store)
   __shared__ int32_t probe_buf[32];
   if (lane < 32) probe_buf[lane] = 0;
   const long long probe_t0 = wall_clock64();
@@ -806,7 +867,7 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
   const uint32_t pol_last = (prm.steps > 0) ? (prm.step_offset + (uint32_t)prm.steps - 1u) >> 2 : pol_b0;
   if constexpr (MODE == kModeRollout && !ZEIL) {
     const uint32_t nb = pol_last - pol_b0 + 1u;
-    duo_policy_fill<D>(pol, gg, pol_b0, (int)(nb < (uint32_t)kDuoPreBlocks ? nb : (uint32_t)kDuoPreBlocks), prm.seed,
+    duo_policy_fill<D, kDuoFillChains>(pol, gg, pol_b0, (int)(nb < (uint32_t)kDuoPreBlocks ? nb : (uint32_t)kDuoPreBlocks), prm.seed,
                        HOT ? (int)HK_HOST_RANDOM : prm.host_policy,
                        (HOT == kHotJax) ? (int)HK_AGENT_RANDOM
                                         : (HOT == kHotTorch) ? (int)HK_AGENT_RANDOM_LEGAL : prm.agent_policy, gi, h);
@@ -947,7 +1008,9 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
 #endif
   if (!active) np = 2;
   int length = (np < 2) ? 0 : -1;
-  if (kRoll && prm.count_ws) {
+  // (wave-uniform) the counts of every step, step 0 included, in closed form after the loop
+  const bool hist_counts = kHistCounts && nsteps < kWave;
+  if (kRoll && prm.count_ws && !hist_counts) {
     const unsigned long long b0 = __ballot(leader && np < 2);
     if (lane == 0) count_add(prm.count_ws + blockIdx.x, (uint32_t)__popcll(b0));
   }
@@ -1153,8 +1216,15 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
     probe_steps = t;
     probe_t2 = wall_clock64();
 #endif
-    // games whose first finished step is <= s, for every step s >= 1 (s = 0 was counted at entry)
-    if (count_slot) add_length_counts(count_slot, count_stride, 1, nsteps, leader, length, lane);
+    // games whose first finished step is <= s: every step s >= 0 from the histogram, or -- episodes of kWave steps and
+    // more -- every step s >= 1 by ballots (s = 0 was counted at entry)
+    if (count_slot) {
+      if (hist_counts) duo_length_counts(hist, count_slot, count_stride, nsteps, leader, length, lane);
+      else add_length_counts(count_slot, count_stride, 1, nsteps, leader, length, lane);
+    }
+#ifdef HK_DUO_PROBE
+    if (lane == 0) probe_buf[29] = (int32_t)wall_clock64();  // the counts are out
+#endif
     if constexpr (want_small) {  // window by window up to the last step (the loop may have left at a fixed point)
       for (;;) {
         const uint32_t wend = ((pol_b0 + (uint32_t)kDuoPreBlocks) << 2) - step0;  // steps (from 0) the window reaches

@@ -4,11 +4,12 @@
 # HEAD in alternation on the SAME box.
 #   build:  compile the variant's objects into hironaka_amd/csrc/alt_<name>.so (not tracked; it travels with gpurun)
 #   usage:  scripts/ab_headline.sh <rounds> <name> [<name> ...]      ("base" is always the first leg of a round)
+#   AB_STEPS / AB_WARMUP in the environment: bench.py's --steps / --warmup (default 20 / 5; 2000 / 200 for a decision)
 set -u
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 C=$ROOT/hironaka_amd/csrc
 ROUNDS=$1; shift
-B="python $ROOT/bench.py --steps 20 --warmup 5 --no-search --no-cpu-baseline --no-single-step"
+B="python $ROOT/bench.py --steps ${AB_STEPS:-20} --warmup ${AB_WARMUP:-5} --no-search --no-cpu-baseline --no-single-step"
 cp $C/libhironaka_hip.so /tmp/hk_base.so
 for i in $(seq 1 $ROUNDS); do
   for v in base "$@"; do

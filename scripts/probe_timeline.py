@@ -76,10 +76,14 @@ stamp = lambda k: usp(full[:, 8 + k] & 0xFFFFFFFF)
 t0u, t1u, t2u, t3u = us(t0), us(t1), us(t2), us(t3)
 pro = (("action window filled", stamp(21) - t0u), ("slab in LDS (wait, barrier)", stamp(22) - stamp(21)),
        ("scanned", stamp(24) - stamp(22)), ("guard vote + wave maximum", t1u - stamp(24)), ("rows dealt", stamp(23) - t1u))
-epi = (("counts and lengths out", stamp(25) - t2u), ("published", stamp(26) - stamp(25)),
+# (stamp 29: the counts alone, ahead of the small records' flush and the lengths' store; older probe builds leave it zero)
+has29 = bool((full[:, 8 + 29] != 0).any())
+epi = ((("counts out", stamp(29) - t2u), ("lengths out", stamp(25) - stamp(29))) if has29 else ()) + (
+       ("counts and lengths out", stamp(25) - t2u), ("published", stamp(26) - stamp(25)),
        ("image read back", stamp(27) - stamp(26)), ("stores issued", stamp(28) - stamp(27)),
        ("to the end", t3u - stamp(28)))
 for title, parts in (("prologue", pro), ("epilogue", epi)):
-    print(f"{title} stages: " + "; ".join(f"{n} {v.mean():.2f}" for n, v in parts) + f"; total {sum(v.mean() for _, v in parts):.2f} us")
+    total = sum(v.mean() for n, v in parts if n not in ("counts out", "lengths out"))  # (the two are parts of the third)
+    print(f"{title} stages: " + "; ".join(f"{n} {v.mean():.2f}" for n, v in parts) + f"; total {total:.2f} us")
 full_waves = steps >= 19
 print(f"epilogue of the {full_waves.sum()} waves that ran 19-20 steps: " + "; ".join(f"{n} {v[full_waves].mean():.2f}" for n, v in epi))
