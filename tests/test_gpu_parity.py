@@ -423,6 +423,26 @@ def test_generate_families_match_oracle(spec):
             assert np.array_equal(host(got), want), (c, fam)
 
 
+@pytest.mark.parametrize("max_value", [64, 65, 127, 128])
+@pytest.mark.parametrize("spec", [(20, 3), (50, 4)])
+def test_generate_value_edges_match_oracle(spec, max_value):
+    """hk_generate_points on both sides of the generator's two value edges, on every family: max_value 64 | 65 (eight
+    against four elements per Philox block) and 127 | 128 (largest draw 126 | 127: the packed byte test against the
+    float loop of the Newton stage) -- a batch that ends inside a wave and one of several workgroups"""
+    m, d = spec
+    N, R, S = A.HK_STAGE_NEWTON, A.HK_STAGE_REPOSITION, A.HK_STAGE_RESCALE
+    families = (0, A.HK_FLAG_FORCE_FOUR_LANES, A.HK_FLAG_FORCE_ONE_LANE, A.HK_FLAG_FORCE_TEAM, A.HK_FLAG_FORCE_GENERIC)
+    for b in (17, 200):
+        raw = CO.generate_points(b, m, d, max_value, 9, 3, stages=0)
+        assert raw.max() == max_value - 1, "the batch does not draw the largest value"
+        for st in (0, N, N | R, N | R | S):
+            want = CO.generate_points(b, m, d, max_value, 9, 3, stages=st)
+            for fam in families:
+                got = ops.generate_points(b, m, d, max_value, seed=9, game_offset=3, newton=bool(st & N),
+                                          reposition=bool(st & R), rescale=bool(st & S), flags=fam)
+                assert np.array_equal(host(got).view(np.int32), want.view(np.int32)), (spec, max_value, b, st, fam)
+
+
 @pytest.mark.parametrize("spec,force_generic", [((20, 3), False), ((20, 3), True), ((10, 3), False), ((8, 4), False),
                                                 ((6, 5), True), ((50, 4), False), ((7, 3), False), ((6, 5), False)])
 def test_rollout_matches_oracle(spec, force_generic):
