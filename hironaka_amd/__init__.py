@@ -1,2 +1,13 @@
 """hironaka_amd -- MI355X-native batched Hironaka-game environment."""
 __version__ = "0.1.0"
+
+_VEC_ENVS = ("HironakaHostVecEnv", "HironakaAgentVecEnv")
+__all__ = list(_VEC_ENVS)
+
+
+def __getattr__(name):
+    # resolved on first use: importing the package alone loads neither torch nor the HIP library
+    if name in _VEC_ENVS:
+        from . import vec_env
+        return getattr(vec_env, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -69,6 +69,11 @@ HK_PLAY_RUNNING, HK_PLAY_ENDED, HK_PLAY_NO_MOVE, HK_PLAY_INEXACT, HK_PLAY_VALUE_
 HK_PLAY_REPOSITION, HK_PLAY_RESCALE, HK_PLAY_REDUCE_ROOT, HK_PLAY_RESCALE_ROOT = 1, 2, 4, 8
 HK_PLAY_HOST_FORCED = -1
 
+# hk_env_step: modes, descriptor flags
+HK_ENV_MODE_HOST, HK_ENV_MODE_AGENT = 0, 1
+HK_ENV_SCALE_OBSERVATION, HK_ENV_STOP_AFTER_INVALID, HK_ENV_STOP_AT_THRESHOLD, HK_ENV_POINT_REDUCTION_REWARD = 1, 2, 4, 8
+HK_ENV_IMPROVE_EFFICIENCY, HK_ENV_AGENT_REPOSITION, HK_ENV_AUTO_RESET, HK_ENV_RESET_ALL = 16, 32, 64, 128
+
 # hk_tree_expand: descriptor flags, the bit of its status word
 HK_TREE_REPOSITION, HK_TREE_ZERO_TAIL = 1, 2
 HK_TREE_OVERFLOW = 1
@@ -216,6 +221,42 @@ class hk_game_play_desc(C.Structure):
     ]
 
 
+class hk_env_step_desc(C.Structure):
+    _fields_ = [
+        ("points_in", C.c_void_p),
+        ("points_out", C.c_void_p),
+        ("class_io", C.c_void_p),
+        ("step_count", C.c_void_p),
+        ("episode", C.c_void_p),
+        ("action", C.c_void_p),
+        ("reward", C.c_void_p),
+        ("stopped", C.c_void_p),
+        ("exceed", C.c_void_p),
+        ("obs_points", C.c_void_p),
+        ("obs_coords", C.c_void_p),
+        ("final_points", C.c_void_p),
+        ("final_coords", C.c_void_p),
+        ("agent_axis", C.c_void_p),
+        ("seed", C.c_uint64),
+        ("agent_seed", C.c_uint64),
+        ("game_offset", C.c_uint64),
+        ("world_games", C.c_uint64),
+        ("value_threshold", C.c_double),
+        ("invalid_move_penalty", C.c_double),
+        ("threshold_penalty", C.c_double),
+        ("batch", C.c_int32),
+        ("max_points", C.c_int32),
+        ("dim", C.c_int32),
+        ("dtype", C.c_int32),
+        ("mode", C.c_int32),
+        ("host", C.c_int32),
+        ("agent", C.c_int32),
+        ("max_value", C.c_int32),
+        ("step_threshold", C.c_int32),
+        ("flags", C.c_uint32),
+    ]
+
+
 class hk_tree_expand_desc(C.Structure):
     _fields_ = [
         ("parents_in", C.c_void_p),
@@ -316,12 +357,17 @@ TREE_PROTOTYPES = {
     "hk_tree_expand": (C.c_int, [C.POINTER(hk_tree_expand_desc), _vp]),
 }
 
+# the entry point of include/hironaka_hip_env.h: the device library's only, as above
+ENV_PROTOTYPES = {
+    "hk_env_step": (C.c_int, [C.POINTER(hk_env_step_desc), _vp]),
+}
+
 
 def bind(lib: C.CDLL, prototypes=None) -> None:
-    """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES and TREE_PROTOTYPES); raises
-    AttributeError for a symbol the library lacks."""
+    """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES, TREE_PROTOTYPES and
+    ENV_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
     if prototypes is None:
-        prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES, **TREE_PROTOTYPES}
+        prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES, **TREE_PROTOTYPES, **ENV_PROTOTYPES}
     for name, (res, args) in prototypes.items():
         fn = getattr(lib, name)
         fn.restype = res

@@ -54,13 +54,18 @@ class RandomAgent(Agent):
         self._play_seed = None
         self.moves = 0  # moves play() may have drawn for: the move number in the random agent's counter
 
-    def play(self, points, **kwargs):
-        """whole games in one launch (ops.game_play, agent="random"): the draws come from Philox keyed by this agent's
-        seed (the generator's initial seed, or a fresh one when the agent has none), the game and the move number"""
+    def play_seed(self) -> int:
+        """the Philox key of the draws made on the device (play, vec_env.HironakaAgentVecEnv): the generator's initial
+        seed, or the agent's, or a fresh one when the agent has none"""
         if self._play_seed is None:
             given = self._gen.initial_seed() if self._gen is not None else self._seed
             self._play_seed = (random.getrandbits(63) if given is None else int(given)) % 2 ** 64
-        kwargs.setdefault("seed", self._play_seed)
+        return self._play_seed
+
+    def play(self, points, **kwargs):
+        """whole games in one launch (ops.game_play, agent="random"): the draws come from Philox keyed by this agent's
+        seed (the generator's initial seed, or a fresh one when the agent has none), the game and the move number"""
+        kwargs.setdefault("seed", self.play_seed())
         kwargs.setdefault("step_offset", self.moves)
         res = self._play("random", points, **kwargs)
         self.moves += kwargs["max_steps"]

@@ -1026,6 +1026,119 @@ def game_play(points: torch.Tensor, *, host: Optional[str] = None, agent: str = 
     return GamePlayResult(dst, length, outcome, c_out, a_out)
 
 
+# ---- one move of a vectorised environment, resets included (hk_env_step) ---------------------------------------------
+
+ENV_MODES = {"host": A.HK_ENV_MODE_HOST, "agent": A.HK_ENV_MODE_AGENT}
+ENV_AGENTS = {"random": A.HK_AGENT_RANDOM_LEGAL, "choose_first": A.HK_AGENT_CHOOSE_FIRST}
+
+
+def _env_buffer(t, name: str, dtype, shape, dev, optional: bool = False) -> Optional[int]:
+    """the address of a buffer hk_env_step reads or writes in place: exactly this dtype and shape, contiguous, on dev"""
+    if t is None:
+        if optional:
+            return None
+        raise ValueError(f"{name} is required.")
+    _require_device(t, name)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}. Got {t.dtype} "
+                         f"{tuple(t.shape)} on {t.device}, contiguous: {t.is_contiguous()}.")
+    return t.data_ptr()
+
+
+def env_step(points: torch.Tensor, *, mode: str, step_count: torch.Tensor, episode: torch.Tensor, reward: torch.Tensor,
+             stopped: torch.Tensor, obs_points: torch.Tensor, action: Optional[torch.Tensor] = None,
+             class_io: Optional[torch.Tensor] = None, obs_coords: Optional[torch.Tensor] = None,
+             final_points: Optional[torch.Tensor] = None, final_coords: Optional[torch.Tensor] = None,
+             agent_axis: Optional[torch.Tensor] = None, exceed: Optional[torch.Tensor] = None,
+             out: Optional[torch.Tensor] = None, host: Optional[str] = None, agent: Optional[str] = None, seed: int = 0,
+             agent_seed: int = 0, game_offset: int = 0, world_games: Optional[int] = None, max_value: int = 0,
+             value_threshold: Optional[float] = None, step_threshold: int = 2 ** 31 - 1,
+             invalid_move_penalty: float = -1e-3, threshold_penalty: float = 0.0, scale_observation: bool = True,
+             stop_after_invalid: bool = False, stop_at_threshold: bool = True, point_reduction_reward: bool = False,
+             improve_efficiency: bool = False, reposition: bool = False, auto_reset: bool = True,
+             reset_all: bool = False) -> None:
+    """One move of every game of a vectorised environment in one launch, the next episode of a stopped game included
+    (hk_env_step, include/hironaka_hip_env.h: the step of gym_env.HironakaHostEnv / HironakaAgentEnv per game).  Every
+    tensor is a buffer the caller owns, read and written in place: nothing is copied or converted, so each must have
+    exactly the dtype and shape below, be contiguous and live on the points' device.
+
+    points [B, m, d] float32/float64, list semantics, d in 2..7, m <= 64; out: where the new state goes, default
+    ``points`` itself (otherwise the two must not share memory).  mode "host": ``host`` is a key of SEARCH_HOSTS,
+    action int32 [B] the agent's axis, class_io int32 [B] the pending subset as a class id (in and out), obs_coords
+    float64 [B, d].  mode "agent": ``agent`` is a key of ENV_AGENTS, action int32 [B] the host's subset as a bit mask,
+    agent_axis int32 [B] (optional) the axis chosen.  step_count, episode int32 [B] (in and out); reward float64 [B];
+    stopped, exceed (optional) uint8 [B]; obs_points float32 [B, m, d]; final_points float32 [B, m, d] and final_coords
+    float64 [B, d] (optional) receive the terminal observation of the games that stopped and were reset.  seed keys the
+    generator, agent_seed the random agent; the game index of both streams is game_offset + episode * world_games + b
+    (world_games: default B).  reset_all: play no move and give every game a fresh episode (episode += 1)."""
+    if mode not in ENV_MODES:
+        raise ValueError(f"mode must be one of {sorted(ENV_MODES)}. Got {mode!r}.")
+    host_mode = mode == "host"
+    if host_mode and host not in SEARCH_HOSTS:
+        raise ValueError(f"host must be one of {sorted(SEARCH_HOSTS)}. Got {host!r}.")
+    if not host_mode and agent not in ENV_AGENTS:
+        raise ValueError(f"agent must be one of {sorted(ENV_AGENTS)}. Got {agent!r}.")
+    _require_device(points, "points")
+    if points.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"points must be float32 or float64. Got {points.dtype}.")
+    if points.dim() != 3 or not points.is_contiguous():
+        raise ValueError(f"points must be a contiguous [B, max_points, dim]. Got shape {tuple(points.shape)}, "
+                         f"strides {points.stride()}.")
+    b, m, d = points.shape
+    dev = points.device
+    if not (2 <= d <= 7 and 1 <= m <= 64 and b < 2 ** 31):
+        raise ValueError(f"hk_env_step serves dim 2..7, max_points 1..64 and fewer than 2^31 games. Got {(b, m, d)}.")
+    world_games = b if world_games is None else world_games
+    if not (0 <= seed < 2 ** 64 and 0 <= agent_seed < 2 ** 64 and 0 <= game_offset < 2 ** 64
+            and 0 <= world_games < 2 ** 64):
+        raise ValueError(f"seed, agent_seed, game_offset and world_games must be in [0, 2^64). Got {seed}, {agent_seed}, "
+                         f"{game_offset}, {world_games}.")
+    if not (0 <= max_value < 2 ** 31 and -2 ** 31 <= step_threshold < 2 ** 31):
+        raise ValueError(f"max_value and step_threshold must fit an int32. Got {max_value}, {step_threshold}.")
+    if (auto_reset or reset_all) and max_value < 1:
+        raise ValueError(f"a reset draws integers in [0, max_value): max_value must be at least 1. Got {max_value}.")
+    for v, name in ((value_threshold, "value_threshold"), (invalid_move_penalty, "invalid_move_penalty"),
+                    (threshold_penalty, "threshold_penalty")):
+        if v is not None and v != v:
+            raise ValueError(f"{name} must be a number. Got NaN.")
+    q = A.hk_env_step_desc()
+    q.points_in = points.data_ptr()
+    q.points_out = q.points_in if out is None or out is points else _env_buffer(out, "out", points.dtype, (b, m, d), dev)
+    if q.points_out != q.points_in and _records_overlap(points, out):
+        raise ValueError("out must be points itself or share no memory with it.")
+    i32, f64, f32, u8 = torch.int32, torch.float64, torch.float32, torch.uint8
+    q.step_count = _env_buffer(step_count, "step_count", i32, (b,), dev)
+    q.episode = _env_buffer(episode, "episode", i32, (b,), dev)
+    q.action = _env_buffer(action, "action", i32, (b,), dev, optional=reset_all)
+    q.reward = _env_buffer(reward, "reward", f64, (b,), dev)
+    q.stopped = _env_buffer(stopped, "stopped", u8, (b,), dev)
+    q.exceed = _env_buffer(exceed, "exceed", u8, (b,), dev, optional=True)
+    q.obs_points = _env_buffer(obs_points, "obs_points", f32, (b, m, d), dev)
+    q.final_points = _env_buffer(final_points, "final_points", f32, (b, m, d), dev, optional=True)
+    if host_mode:
+        q.class_io = _env_buffer(class_io, "class_io", i32, (b,), dev)
+        q.obs_coords = _env_buffer(obs_coords, "obs_coords", f64, (b, d), dev)
+        q.final_coords = _env_buffer(final_coords, "final_coords", f64, (b, d), dev, optional=True)
+        q.host = SEARCH_HOSTS[host]
+    else:
+        q.agent_axis = _env_buffer(agent_axis, "agent_axis", i32, (b,), dev, optional=True)
+        q.agent = ENV_AGENTS[agent]
+    q.seed, q.agent_seed, q.game_offset, q.world_games = seed, agent_seed, game_offset, world_games
+    q.value_threshold = 0.0 if value_threshold is None else float(value_threshold)
+    q.invalid_move_penalty, q.threshold_penalty = float(invalid_move_penalty), float(threshold_penalty)
+    q.batch, q.max_points, q.dim, q.dtype, q.mode = b, m, d, _TORCH2HK[points.dtype], ENV_MODES[mode]
+    q.max_value, q.step_threshold = max_value, step_threshold
+    q.flags = ((A.HK_ENV_SCALE_OBSERVATION if scale_observation else 0)
+               | (A.HK_ENV_STOP_AFTER_INVALID if stop_after_invalid else 0)
+               | (A.HK_ENV_STOP_AT_THRESHOLD if stop_at_threshold else 0)
+               | (A.HK_ENV_POINT_REDUCTION_REWARD if point_reduction_reward else 0)
+               | (A.HK_ENV_IMPROVE_EFFICIENCY if improve_efficiency else 0)
+               | (A.HK_ENV_AGENT_REPOSITION if reposition else 0) | (A.HK_ENV_AUTO_RESET if auto_reset else 0)
+               | (A.HK_ENV_RESET_ALL if reset_all else 0))
+    with torch.cuda.device(dev):
+        check(lib().hk_env_step(C.byref(q), _stream(points)), "hk_env_step")
+
+
 # ---- one level of a game tree under any host (hk_tree_expand) -------------------------------------------------------
 
 TreeExpandResult = collections.namedtuple(

@@ -55,6 +55,9 @@
  *                            core/list_points.py:86-116 the distinguished point that get_newton_polytope tracks
  *   hk_game_play             (hironaka_hip_play.h) hironaka/game.py:84-119 GameHironaka with agent.py:85-98 RandomAgent /
  *                            ChooseFirstAgent, one game per lane; validator/hironaka_validator.py:30-48 playoff's games
+ *   hk_env_step              (hironaka_hip_env.h) hironaka/gym_env/hironaka_host_env.py:41-74 and hironaka_agent_env.py:44-80
+ *                            step, hironaka_base.py:86-114 reset: one move of every game of a vectorised environment, a
+ *                            stopped game's next episode drawn inside the launch
  *   hk_tree_expand           (hironaka_hip_tree.h) hironaka/jax/search.py:73-113 search_tree_fix_host, one level of the
  *                            tree over a whole frontier: the children of every node under the subsets a host chose
  *   hk_host_select           (hironaka_hip_hosts.h) host.py:48-51 AllCoordHost, host.py:54-95 Zeillinger, host.py:116-127 ZeillingerLex,
@@ -622,5 +625,7 @@ int hk_search_morin_play(const hk_morin_play_desc* desc, void* stream);
 #include "hironaka_hip_play.h"
 /* within ABI 6: hk_tree_expand, likewise */
 #include "hironaka_hip_tree.h"
+/* within ABI 6: hk_env_step, likewise */
+#include "hironaka_hip_env.h"
 
 #endif /* HIRONAKA_HIP_H */

@@ -1,0 +1,555 @@
+"""hk_env_step / ops.env_step / vec_env on the GPU.  The yardstick is never the new code: every (game, episode, move)
+the vectorised environments play is replayed on gym_env's HironakaHostEnv / HironakaAgentEnv (reset e + 1 times for
+episode e) and, for the random agent, on ops.game_play one move at a time.  Actions come from a table
+act[game, episode, move within the episode] drawn once with numpy, so that a game meets the same actions whenever it
+reaches a move, in whichever launch."""
+import numpy as np
+import pytest
+import torch
+
+from hironaka_amd import _abi as A
+from hironaka_amd import ops
+from hironaka_amd.agent import AgentMorin, ChooseFirstAgent, PolicyAgent, RandomAgent
+from hironaka_amd.gym_env import HironakaAgentEnv, HironakaHostEnv
+from hironaka_amd.host import (AllCoordHost, PolicyHost, RandomHost, WeakSpivakovsky, WeakSpivakovskyMinHitting,
+                               Zeillinger, ZeillingerLex)
+from hironaka_amd.vec_env import HironakaAgentVecEnv, HironakaHostVecEnv
+
+pytestmark = pytest.mark.gpu
+
+T = 12
+HOSTS = {"zeillinger": Zeillinger, "all_coord": AllCoordHost, "zeillinger_lex": ZeillingerLex,
+         "weak_spivakovsky": WeakSpivakovsky, "weak_spivakovsky_min_hitting": WeakSpivakovskyMinHitting}
+PENALTY = -0.125
+
+
+def games_per_wave(m, d, itemsize=8):
+    """the games a workgroup of hk_env_step owns: slices of (m d + 2 d) | 1 elements in 64 KiB, at most a wave"""
+    return min(64, 65536 // (((m * d + 2 * d) | 1) * itemsize))
+
+
+def cu(a, dtype=None):
+    t = torch.as_tensor(np.ascontiguousarray(a), device="cuda")
+    return t if dtype is None else t.to(dtype)
+
+
+def host_actions(n, d, seed, steps=T):
+    """axes, a fifth of them drawn from [-1, d]: outside the subset now and then, outside [0, d) too"""
+    rng = np.random.default_rng(seed)
+    shape = (n, steps + 1, steps + 2)
+    wide = rng.integers(-1, d + 1, shape)
+    return np.where(rng.random(shape) < 0.2, wide, rng.integers(0, d, shape)).astype(np.int32)
+
+
+def agent_masks(n, d, seed, steps=T):
+    """subsets as bit masks: mostly 2 or more coordinates, a fifth of them anything, masks with 0 and 1 bits included"""
+    rng = np.random.default_rng(seed)
+    shape = (n, steps + 1, steps + 2)
+    legal = np.asarray([v for v in range(1 << d) if bin(v).count("1") >= 2], np.int32)
+    masks = np.where(rng.random(shape) < 0.2, rng.integers(0, 1 << d, shape), legal[rng.integers(0, len(legal), shape)])
+    masks[:, :, 1] = np.where(rng.random((n, steps + 1)) < 0.3, 1 << rng.integers(0, d, (n, steps + 1)), masks[:, :, 1])
+    masks[::7, :, 2] = 0
+    return masks.astype(np.int32)
+
+
+def mask_bits(masks, d):
+    return ((masks[:, None] >> np.arange(d)) & 1).astype(np.int32)
+
+
+def mask_class(masks, d):
+    """class ids of bit masks (hk_common.h encode_mask), -1 for fewer than 2 coordinates"""
+    v = masks & ((1 << d) - 1)
+    ok = np.asarray([bin(int(x)).count("1") >= 2 for x in v])
+    lg = np.floor(np.log2(np.maximum(v, 1))).astype(np.int64)
+    return np.where(ok, v - lg - 2, -1).astype(np.int32)
+
+
+def snap(obs):
+    if isinstance(obs, dict):
+        return obs["points"].cpu().numpy().copy(), obs["coords"].cpu().numpy().copy()
+    return obs.cpu().numpy().copy(), None
+
+
+def num_points(points):
+    return (points[..., 0] >= 0).sum(axis=-1)
+
+
+def run_vec(env, act, steps, to_action):
+    """reset, then `steps` steps fed from the table; every output of every step, copied to the host"""
+    rows = np.arange(env.num_envs)
+    first = snap(env.reset())
+    ep, sc = env.episode.cpu().numpy().copy(), env.current_step.cpu().numpy().copy()
+    final = snap(env._final_observation())
+    start, recs = (ep, sc), []
+    for _ in range(steps):
+        a = act[rows, ep, sc]
+        obs, reward, stopped, info = env.step(to_action(a))
+        assert reward.dtype == torch.float64 and stopped.dtype == torch.bool
+        assert info["episode"].dtype == torch.int32 and info["current_step"].dtype == torch.int32
+        rec = dict(ep=ep, sc=sc, act=a, obs=snap(obs), reward=reward.cpu().numpy().copy(),
+                   stopped=stopped.cpu().numpy().copy(), final=snap(info["final_observation"]), prev_final=final,
+                   exceed=info["exceed_threshold"].cpu().numpy().copy(), ep_after=info["episode"].cpu().numpy().copy(),
+                   sc_after=info["current_step"].cpu().numpy().copy(),
+                   axis=info["agent_axis"].cpu().numpy().copy() if "agent_axis" in info else None)
+        ep, sc, final = rec["ep_after"], rec["sc_after"], rec["final"]
+        recs.append(rec)
+    return first, start, recs
+
+
+def parent_trajectories(make_parent, act, episodes, first_move, to_action, steps=T):
+    """per episode e: the parent's observation after its (e + 1)-th reset and, for every move k of the table, what its
+    step with act[:, e, k] returns"""
+    out = []
+    for e in range(episodes):
+        env = make_parent()
+        for _ in range(e + 1):
+            obs = env.reset()
+        tr = dict(reset=snap(obs), obs={}, reward={}, stopped={}, exceed={})
+        for k in range(first_move, steps + 2):
+            obs, reward, stopped, _ = env.step(to_action(act[:, e, k]))
+            tr["obs"][k] = snap(obs)
+            tr["reward"][k] = reward.cpu().numpy().copy()
+            tr["stopped"][k] = stopped.cpu().numpy().copy()
+            tr["exceed"][k] = env.exceed_threshold.cpu().numpy().copy()
+        out.append(tr)
+    return out
+
+
+def same(got, want, b, label):
+    """bit for bit: points and, in host mode, coords of row b"""
+    assert got[0].dtype == want[0].dtype == np.float32
+    assert np.array_equal(got[0][b], want[0][b]), (label, b, got[0][b], want[0][b])
+    if want[1] is not None:
+        assert got[1].dtype == want[1].dtype == np.float64
+        assert np.array_equal(got[1][b], want[1][b]), (label, b, got[1][b], want[1][b])
+
+
+def check_replay(first, start, recs, make_parent, act, first_move, to_action, auto_reset):
+    """every (game, episode, move) of the run against the parent's row; returns (episodes reached, games that stopped
+    ended, games that stopped otherwise)"""
+    n = len(start[0])
+    episodes = int(max(r["ep_after"].max() for r in recs)) + 1
+    par = parent_trajectories(make_parent, act, episodes, first_move, to_action)
+    assert (start[0] == 0).all() and (start[1] == first_move).all()
+    for b in range(n):
+        same(first, par[0]["reset"], b, "reset")
+    ended_stops = other_stops = 0
+    for t, r in enumerate(recs):
+        for b in range(n):
+            e, k = int(r["ep"][b]), int(r["sc"][b])
+            tr, label = par[e], (t, e, k)
+            assert r["reward"][b] == tr["reward"][k][b], (label, b, r["reward"][b], tr["reward"][k][b])
+            assert r["stopped"][b] == tr["stopped"][k][b], (label, b)
+            assert r["exceed"][b] == tr["exceed"][k][b], (label, b)
+            if r["stopped"][b] and auto_reset:
+                same(r["final"], tr["obs"][k], b, ("final",) + label)
+                same(r["obs"], par[e + 1]["reset"], b, ("fresh",) + label)
+                assert (r["ep_after"][b], r["sc_after"][b]) == (e + 1, first_move), (label, b)
+                if num_points(tr["obs"][k][0][b]) < 2:
+                    ended_stops += 1
+                else:
+                    other_stops += 1
+            else:
+                same(r["obs"], tr["obs"][k], b, ("obs",) + label)
+                same(r["final"], r["prev_final"], b, ("final untouched",) + label)
+                assert (r["ep_after"][b], r["sc_after"][b]) == (e, k + 1), (label, b)
+    return episodes, ended_stops, other_stops
+
+
+# ---- host mode ----------------------------------------------------------------------------------------------------
+
+def host_replay(m, d, n, max_value, host="zeillinger", scale=True, stop_invalid=False, thr=None, seed=5, steps=T,
+                auto_reset=True, improve=False):
+    cfg = dict(dimension=d, max_num_points=m, max_value=max_value, value_threshold=thr, scale_observation=scale,
+               improve_efficiency=improve, seed=seed)
+    kw = dict(invalid_move_penalty=PENALTY, stop_after_invalid_move=stop_invalid)
+    act = host_actions(n, d, 1000 + seed)
+    to_action = lambda a: cu(a)  # noqa: E731
+    env = HironakaHostVecEnv(HOSTS[host](), n, auto_reset=auto_reset, **kw, **cfg)
+    assert env.observation_space["points"].shape == (m, d) and env.action_space.n == d
+    first, start, recs = run_vec(env, act, steps, to_action)
+    make_parent = lambda: HironakaHostEnv(HOSTS[host](), num_envs=n, **kw, **cfg)  # noqa: E731
+    return check_replay(first, start, recs, make_parent, act, 1, to_action, auto_reset)
+
+
+@pytest.mark.parametrize("scale", [True, False])
+@pytest.mark.parametrize("stop_invalid", [False, True])
+@pytest.mark.parametrize("m,d,max_value", [(2, 2, 4), (5, 3, 3), (20, 3, 20), (19, 7, 4), (64, 7, 3)])
+def test_host_replay_shapes(m, d, max_value, stop_invalid, scale):
+    """three waves of games and one more, every flag pair, at the smallest and the largest shapes"""
+    host = "all_coord" if d == 7 and stop_invalid else "zeillinger"  # (d = 7: a legal move now and then)
+    episodes, _, _ = host_replay(m, d, 3 * games_per_wave(m, d) + 1, max_value, host=host, scale=scale,
+                                 stop_invalid=stop_invalid)
+    if (m, d) in ((5, 3), (20, 3)) and stop_invalid:
+        assert episodes >= 3
+
+
+@pytest.mark.parametrize("m,d,max_value,scale,thr", [(5, 3, 3, True, 1.0), (5, 3, 3, False, 3.0), (20, 3, 20, True, 1.0),
+                                                     (20, 3, 20, False, 30.0)])
+def test_host_replay_value_threshold_trips(m, d, max_value, scale, thr):
+    """games end, pass the value threshold, and re-enter: both stop causes, at least three episodes within 12 steps"""
+    episodes, ended, other = host_replay(m, d, 3 * games_per_wave(m, d) + 1, max_value, scale=scale, thr=thr)
+    assert episodes >= 3 and ended > 0 and other > 0, (episodes, ended, other)
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65])
+def test_host_replay_batch_sizes(n):
+    host_replay(5, 3, n, 3, stop_invalid=True, thr=4.0, scale=False)
+
+
+@pytest.mark.parametrize("host", sorted(HOSTS))
+def test_host_replay_every_host(host):
+    episodes, _, _ = host_replay(6, 3, 65, 5, host=host, stop_invalid=True, improve=True)
+    assert episodes >= 3
+
+
+def test_host_replay_single_point_states():
+    """max_value 1: every fresh state is the one point 0, so every step stops and resets"""
+    episodes, ended, other = host_replay(5, 3, 65, 1)
+    assert episodes == T + 1 and ended == 65 * T and other == 0
+
+
+@pytest.mark.parametrize("max_value", [64, 65])
+def test_host_replay_generator_forms(max_value):
+    """the generator's short (16-bit draws) and long form, through two resets"""
+    host_replay(7, 3, 65, max_value, stop_invalid=True, steps=4)
+
+
+@pytest.mark.parametrize("scale", [True, False])
+def test_host_without_auto_reset(scale):
+    """the parent's environment step for step on the whole batch, stopped games included"""
+    episodes, _, _ = host_replay(5, 3, 65, 3, scale=scale, thr=None if scale else 4.0, auto_reset=False)
+    assert episodes == 1
+
+
+# ---- agent mode ---------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("discrete", [False, True])
+@pytest.mark.parametrize("m,d,max_value,cfg", [
+    (5, 3, 3, dict(step_threshold=3)),
+    (5, 3, 3, dict(step_threshold=4, fixed_penalty_crossing_threshold=-7, reward_based_on_point_reduction=True,
+                   scale_observation=False, value_threshold=4.0)),
+    (20, 3, 20, dict(step_threshold=5, reward_based_on_point_reduction=True)),
+    (20, 3, 20, dict(stop_at_threshold=False, scale_observation=False, value_threshold=30.0)),
+    (2, 2, 4, dict(step_threshold=3)), (19, 7, 4, dict(step_threshold=6)), (64, 7, 3, dict(step_threshold=4)),
+])
+def test_agent_replay_choose_first(m, d, max_value, cfg, discrete):
+    n = 3 * games_per_wave(m, d) + 1
+    cfg = dict(dimension=d, max_num_points=m, max_value=max_value, seed=9, use_discrete_actions_for_host=discrete,
+               compressed_host_output=False, **cfg)
+    act = agent_masks(n, d, 77)
+    to_action = (lambda a: cu(a)) if discrete else (lambda a: cu(mask_bits(a, d)))
+    env = HironakaAgentVecEnv(ChooseFirstAgent(), n, **cfg)
+    assert env.observation_space.shape == (m, d)
+    assert env.action_space.n == (2 ** d if discrete else d)
+    first, start, recs = run_vec(env, act, T, to_action)
+    make_parent = lambda: HironakaAgentEnv(ChooseFirstAgent(), num_envs=n, **cfg)  # noqa: E731
+    episodes, ended, other = check_replay(first, start, recs, make_parent, act, 0, to_action, True)
+    for r in recs:  # the axis reported: the lowest coordinate of a subset of 2 or more
+        sub = r["act"] & ((1 << d) - 1)
+        want = [(int(v) & -int(v)).bit_length() - 1 if bin(int(v)).count("1") >= 2 else -1 for v in sub]
+        assert r["axis"].tolist() == want
+    if cfg.get("stop_at_threshold", True) and (m, d) in ((5, 3), (20, 3)):
+        assert episodes >= 3 and ended > 0 and other > 0, (episodes, ended, other)
+
+
+@pytest.mark.parametrize("m,d,max_value,cfg", [
+    (5, 3, 3, dict(step_threshold=4, reward_based_on_point_reduction=True)),
+    (20, 3, 20, dict(step_threshold=6, fixed_penalty_crossing_threshold=-7, reward_based_on_point_reduction=True,
+                     scale_observation=False, value_threshold=30.0)),
+    (19, 7, 4, dict(step_threshold=5)),
+])
+def test_agent_replay_random_agent(m, d, max_value, cfg):
+    """RandomAgent(seed) against ops.game_play one move at a time from the parent's reset states: axes, states and
+    the reward formula of hironaka_agent_env.py in numpy"""
+    n, seed, agent_seed = 2 * games_per_wave(m, d) + 1, 11, 4242
+    scale, thr = cfg.get("scale_observation", True), cfg.get("value_threshold")
+    limit, reduction = cfg["step_threshold"], cfg.get("reward_based_on_point_reduction", False)
+    fixed = cfg.get("fixed_penalty_crossing_threshold")
+    penalty = -float(limit) if fixed is None else float(fixed)
+    base = dict(dimension=d, max_num_points=m, max_value=max_value, seed=seed, **cfg)
+    act = agent_masks(n, d, 78)
+    env = HironakaAgentVecEnv(RandomAgent(agent_seed), n, **base)
+    first, start, recs = run_vec(env, act, T, lambda a: cu(mask_bits(a, d)))
+    episodes = int(max(r["ep_after"].max() for r in recs)) + 1
+    assert (start[0] == 0).all() and (start[1] == 0).all()
+    # the yardstick: per episode the parent's reset state, then single moves of game_play chained on their own results
+    chain, untouched, no_moves = [], 0, 0
+    for e in range(episodes):
+        parent = HironakaAgentEnv(ChooseFirstAgent(), num_envs=n, **base)
+        for _ in range(e + 1):
+            obs = parent.reset()
+        state, moves = parent._points.clone(), {}
+        for k in range(T + 2):
+            cls = cu(mask_class(act[:, e, k], d)).unsqueeze(1)
+            kw = dict(agent="random", max_steps=1, classes=cls, seed=agent_seed, game_offset=e * n, step_offset=k,
+                      record=True)
+            raw = ops.game_play(state, rescale=False, **kw)
+            res = ops.game_play(state, rescale=scale, **kw)
+            played = res.length == 1
+            # no class: no shift, and the stages behind it as the parent's launch over the whole batch runs them --
+            # the state untouched, but where its rescale has merged coordinates an ulp apart
+            idle = ops.get_newton_polytope(state, -1.0, sem="list")
+            idle_scaled = ops.rescale(idle, -1.0, sem="list") if scale else idle
+            after = torch.where(played.view(n, 1, 1), res.points, idle_scaled)
+            before_rescale = torch.where(played.view(n, 1, 1), raw.points, idle)
+            untouched += int(((idle_scaled == state).all(dim=2).all(dim=1) & (cls[:, 0] < 0)).sum())
+            no_moves += int((cls[:, 0] < 0).sum())
+            moves[k] = dict(before=num_points(state.cpu().numpy()), state=after.cpu().numpy(),
+                            raw_max=before_rescale.amax(dim=(1, 2)).cpu().numpy(), played=played.cpu().numpy(),
+                            axis=res.axes[:, 0].cpu().numpy(), cls=cls[:, 0].cpu().numpy())
+            state = after
+        chain.append(dict(reset=snap(obs), moves=moves))
+    for b in range(n):
+        same(first, chain[0]["reset"], b, "reset")
+    compared = stops = 0
+    for t, r in enumerate(recs):
+        for b in range(n):
+            e, k = int(r["ep"][b]), int(r["sc"][b])
+            mv, label = chain[e]["moves"][k], (t, e, k, b)
+            no_class = mv["cls"][b] < 0
+            if not (mv["played"][b] or no_class):
+                assert mv["before"][b] < 2 and r["stopped"][b], label  # a fresh state of one point: game_play has no move
+                continue
+            compared += 1
+            assert r["axis"][b] == (-1 if no_class else mv["axis"][b]), label
+            want = mv["state"][b].astype(np.float32)
+            got = r["final"][0][b] if r["stopped"][b] else r["obs"][0][b]
+            assert np.array_equal(got, want), (label, got, want)
+            after = num_points(mv["state"][b])
+            ended = after < 2
+            exceed = thr is not None and mv["raw_max"][b] > thr
+            trip = exceed or k + 1 >= limit
+            reward = 0.0 + float(trip) * penalty
+            if reduction:
+                reward += float(mv["before"][b] - after)
+            reward += float(ended)
+            assert r["reward"][b] == reward, (label, r["reward"][b], reward)
+            assert r["stopped"][b] == (ended or trip) and r["exceed"][b] == exceed, label
+            if r["stopped"][b]:
+                stops += 1
+                same(r["obs"], chain[e + 1]["reset"], b, ("fresh",) + label)
+                assert (r["ep_after"][b], r["sc_after"][b]) == (e + 1, 0), label
+            else:
+                assert (r["ep_after"][b], r["sc_after"][b]) == (e, k + 1), label
+    # not vacuous: most moves were compared (the rest met a fresh state of one point), and a mask that is no class
+    # left the state untouched (all but the rare states the note above speaks of)
+    assert compared > n * T // 2 and stops > 0 and episodes >= 3, (compared, stops, episodes)
+    assert no_moves > 0 and untouched >= no_moves - no_moves // 20, (untouched, no_moves)
+
+
+# ---- sharding -----------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("mode", ["host", "agent"])
+def test_shards_reproduce_the_batch(mode):
+    """two environments of N / 2 games with game_offset 0 and N / 2 and world_games = N play the games of one of N"""
+    m, d, n = 5, 3, 130
+    cfg = dict(dimension=d, max_num_points=m, max_value=3, seed=21, step_threshold=4)
+    if mode == "host":
+        make = lambda k, **kw: HironakaHostVecEnv(Zeillinger(), k, stop_after_invalid_move=True, **cfg, **kw)  # noqa: E731
+        act, to_action = host_actions(n, d, 3), lambda a: cu(a)
+    else:
+        make = lambda k, **kw: HironakaAgentVecEnv(RandomAgent(99), k, **cfg, **kw)  # noqa: E731
+        act, to_action = agent_masks(n, d, 3), lambda a: cu(mask_bits(a, d))
+    whole = run_vec(make(n), act, T, to_action)
+    half = n // 2
+    parts = [run_vec(make(half, game_offset=lo, world_games=n), act[lo:lo + half], T, to_action) for lo in (0, half)]
+    assert max(r["ep_after"].max() for r in whole[2]) >= 2
+
+    def joined(pick):
+        return np.concatenate([pick(p) for p in parts])
+    assert np.array_equal(whole[0][0], joined(lambda p: p[0][0]))
+    for t in range(T):
+        for key in ("reward", "stopped", "exceed", "ep_after", "sc_after", "act"):
+            assert np.array_equal(whole[2][t][key], joined(lambda p: p[2][t][key])), (t, key)
+        for key in ("obs", "final"):
+            for i in (0, 1):
+                if whole[2][t][key][i] is not None:
+                    assert np.array_equal(whole[2][t][key][i], joined(lambda p: p[2][t][key][i])), (t, key, i)
+        if mode == "agent":
+            assert np.array_equal(whole[2][t]["axis"], joined(lambda p: p[2][t]["axis"])), t
+
+
+# ---- ops.env_step itself: float32, layout, refusals ------------------------------------------------------------------
+
+GUARD = 37
+
+
+def guarded(shape, dtype, fill):
+    """a contiguous tensor of `shape` inside a larger buffer whose every other element is a sentinel"""
+    count = int(np.prod(shape))
+    whole = torch.full((count + 2 * GUARD,), fill, dtype=dtype, device="cuda")
+    return whole, whole[GUARD:GUARD + count].view(*shape)
+
+
+def guards_intact(whole, fill):
+    return bool((whole[:GUARD] == fill).all()) and bool((whole[-GUARD:] == fill).all())
+
+
+def env_buffers(n, m, d, dtype, host_mode):
+    spec = dict(points=((n, m, d), dtype, 7), step_count=((n,), torch.int32, 77), episode=((n,), torch.int32, 77),
+                action=((n,), torch.int32, 77), reward=((n,), torch.float64, 7.5), stopped=((n,), torch.uint8, 9),
+                exceed=((n,), torch.uint8, 9), obs_points=((n, m, d), torch.float32, 7.5),
+                final_points=((n, m, d), torch.float32, 7.5))
+    if host_mode:
+        spec.update(class_io=((n,), torch.int32, 77), obs_coords=((n, d), torch.float64, 7.5),
+                    final_coords=((n, d), torch.float64, 7.5))
+    else:
+        spec.update(agent_axis=((n,), torch.int32, 77))
+    whole, view = {}, {}
+    for name, (shape, dt, fill) in spec.items():
+        whole[name], view[name] = guarded(shape, dt, fill)
+        whole[name] = (whole[name], fill)
+    return whole, view
+
+
+@pytest.mark.parametrize("m,d", [(5, 3), (20, 3), (64, 7)])
+def test_env_step_float32_host_mode_layout(m, d):
+    """float32 through ops.env_step: the reset path against ops.generate_points + the reset stages + ops.host_select,
+    a step against ops.step + ops.host_select + ops.rescale; guard regions around every buffer; points aliased and
+    not; final_* untouched where stopped is 0"""
+    host = "zeillinger"
+    n, max_value, seed = 2 * games_per_wave(m, d, 4) + 1, 6, 31
+    whole, v = env_buffers(n, m, d, torch.float32, True)
+    common = dict(mode="host", host=host, seed=seed, max_value=max_value, invalid_move_penalty=PENALTY,
+                  scale_observation=True, auto_reset=True)
+    bufs = {k: t for k, t in v.items() if k != "points"}
+    v["episode"].fill_(-1)
+    v["step_count"].zero_()
+    ops.env_step(v["points"], reset_all=True, **bufs, **common)
+    flags = ops.make_flags("list", noop_if_invalid=True)
+    raw = ops.generate_points(n, m, d, max_value, seed, dtype=torch.float32, device="cuda", newton=False,
+                              reposition=False)
+    want = ops.step(raw, stages=A.HK_STAGE_NEWTON | A.HK_STAGE_RESCALE, flags=flags)["points"]
+    want = ops.get_newton_polytope(want, -1.0, sem="list")
+    assert torch.equal(v["points"], want) and torch.equal(v["obs_points"], want)
+    alive = ops.get_num_points(want) >= 2
+    cls = torch.where(alive, ops.zeillinger(want, sem="list"), torch.full_like(v["class_io"], -1))
+    assert torch.equal(v["class_io"], cls)
+    assert (v["episode"] == 0).all() and (v["step_count"] == 1).all()
+    assert (v["stopped"] == 0).all() and (v["reward"] == 0).all() and (v["exceed"] == 0).all()
+    assert (v["final_points"] == 7.5).all() and (v["final_coords"] == 7.5).all()
+    # one step that stops after an invalid move, not in place, then the same step in place
+    common["stop_after_invalid"] = True
+    rng = np.random.default_rng(4)
+    v["action"].copy_(cu(rng.integers(-1, d + 1, n).astype(np.int32)))
+    state, cls0 = v["points"].clone(), v["class_io"].clone()
+    out_whole, out = guarded((n, m, d), torch.float32, 7)
+    ops.env_step(v["points"], out=out, **bufs, **common)
+    assert torch.equal(v["points"], state) and guards_intact(out_whole, 7)
+    coords = ops.decode_host_class(cls0.clamp(min=0), d, torch.int32) * (cls0 >= 0).unsqueeze(1)
+    act = v["action"]
+    legal = (act >= 0) & (act < d) & (coords.gather(1, act.clamp(0, d - 1).long().unsqueeze(1)).squeeze(1) > 0)
+    moved = ops.step(state, coords, act, stages=A.HK_STAGE_SHIFT | A.HK_STAGE_NEWTON, flags=flags)["points"]
+    ended = ops.get_num_points(moved) <= 1
+    stop = ended | ~legal
+    reward = torch.where(legal, (~ended).to(torch.float64), torch.full_like(v["reward"], PENALTY))
+    assert torch.equal(v["reward"], reward) and torch.equal(v["stopped"].bool(), stop)
+    assert stop.any() and not stop.all()
+    terminal = ops.rescale(moved, -1.0, sem="list")
+    keep = ~stop
+    assert torch.equal(out[keep], terminal[keep]) and torch.equal(v["obs_points"][keep], terminal[keep])
+    assert torch.equal(v["final_points"][stop], terminal[stop]) and (v["final_points"][keep] == 7.5).all()
+    assert (v["final_coords"][stop] == 0).all() and (v["final_coords"][keep] == 7.5).all()
+    nxt = ops.generate_points(n, m, d, max_value, seed, game_offset=n, dtype=torch.float32, device="cuda",
+                              newton=False, reposition=False)
+    nxt = ops.step(nxt, stages=A.HK_STAGE_NEWTON | A.HK_STAGE_RESCALE, flags=flags)["points"]
+    nxt = ops.get_newton_polytope(nxt, -1.0, sem="list")
+    assert torch.equal(out[stop], nxt[stop]) and torch.equal(v["obs_points"][stop], nxt[stop])
+    assert torch.equal(v["episode"], stop.to(torch.int32))
+    assert torch.equal(v["step_count"], torch.where(stop, 1, 2).to(torch.int32))
+    # the pending subset: the host on the state before the rescale; none after a reset whose step(None) "stopped"
+    new_cls = torch.where(stop, torch.full_like(cls0, -1), ops.zeillinger(moved, sem="list"))
+    assert torch.equal(v["class_io"], new_cls)
+    want_coords = ops.decode_host_class(new_cls.clamp(min=0), d, torch.float64) * (new_cls >= 0).unsqueeze(1)
+    assert torch.equal(v["obs_coords"], want_coords)
+    for name, (t, fill) in whole.items():
+        assert guards_intact(t, fill), name
+    # in place: the same outputs from the same inputs
+    results = {k: t.clone() for k, t in bufs.items()}
+    v["class_io"].copy_(cls0)
+    v["episode"].zero_()
+    v["step_count"].fill_(1)
+    ops.env_step(v["points"], **bufs, **common)
+    assert torch.equal(v["points"], out)
+    for k, t in results.items():
+        assert torch.equal(bufs[k], t), k
+    for name, (t, fill) in whole.items():
+        assert guards_intact(t, fill), name
+
+
+@pytest.mark.parametrize("m,d", [(5, 3), (19, 7)])
+def test_env_step_float32_agent_mode(m, d):
+    """float32, agent mode without auto reset: a step is one move of ops.game_play; final_* and the counters of a
+    stopped game stay"""
+    n, seed = 2 * games_per_wave(m, d, 4) + 1, 8
+    whole, v = env_buffers(n, m, d, torch.float32, False)
+    bufs = {k: t for k, t in v.items() if k != "points"}
+    common = dict(mode="agent", agent="random", agent_seed=seed, seed=3, max_value=4, scale_observation=False,
+                  stop_at_threshold=False, auto_reset=False, game_offset=1000, world_games=5000)
+    v["episode"].fill_(1)
+    v["step_count"].fill_(2)
+    raw = ops.generate_points(n, m, d, 4, 12, dtype=torch.float32, device="cuda", newton=False, reposition=False)
+    v["points"].copy_(ops.get_newton_polytope(raw, -1.0, sem="list"))
+    masks = agent_masks(n, d, 5)[:, 0, 0]
+    v["action"].copy_(cu(masks))
+    state = v["points"].clone()
+    res = ops.game_play(state, agent="random", max_steps=1, classes=cu(mask_class(masks, d)).unsqueeze(1), seed=seed,
+                        game_offset=1000 + 5000, step_offset=2, record=True)
+    ops.env_step(v["points"], **bufs, **common)
+    running = ops.get_num_points(state) >= 2  # game_play leaves a game of one point alone
+    assert running.sum() > n // 2
+    assert torch.equal(v["points"][running], res.points[running])
+    assert torch.equal(v["obs_points"], v["points"])
+    assert torch.equal(v["agent_axis"][running], res.axes[:, 0][running])
+    ended = ops.get_num_points(v["points"]) <= 1
+    assert torch.equal(v["stopped"].bool(), ended) and torch.equal(v["reward"], ended.to(torch.float64))
+    assert (v["episode"] == 1).all() and (v["step_count"] == 3).all()
+    assert (v["final_points"] == 7.5).all()
+    for name, (t, fill) in whole.items():
+        assert guards_intact(t, fill), name
+
+
+def test_refusals():
+    class MyZeillinger(Zeillinger):
+        pass
+
+    class MyFirst(ChooseFirstAgent):
+        pass
+
+    for host in (RandomHost(), PolicyHost(None), MyZeillinger()):
+        with pytest.raises(TypeError, match="gym_env"):
+            HironakaHostVecEnv(host, 4)
+    for agent in (PolicyAgent(None), AgentMorin(), MyFirst()):
+        with pytest.raises(TypeError, match="gym_env"):
+            HironakaAgentVecEnv(agent, 4)
+    with pytest.raises(TypeError):
+        HironakaHostVecEnv(Zeillinger(), 4, device="cpu")
+    n, m, d = 4, 5, 3
+    _, v = env_buffers(n, m, d, torch.float64, True)
+    bufs = {k: t for k, t in v.items() if k != "points"}
+    common = dict(mode="host", host="zeillinger", max_value=5)
+    with pytest.raises(TypeError):
+        ops.env_step(v["points"].cpu(), **bufs, **common)
+    for name, bad in (("reward", v["reward"].cpu()), ("reward", v["reward"].float()),
+                      ("step_count", v["step_count"].long()), ("obs_points", v["obs_points"][:, :, :2]),
+                      ("obs_coords", v["obs_coords"].t().contiguous().t()), ("stopped", v["stopped"][:3]),
+                      ("action", None), ("class_io", None)):
+        with pytest.raises((TypeError, ValueError)):
+            ops.env_step(v["points"], **{**bufs, name: bad}, **common)
+    with pytest.raises(ValueError):
+        ops.env_step(v["points"], **bufs, mode="host", host="random", max_value=5)
+    with pytest.raises(ValueError):
+        ops.env_step(v["points"], **bufs, mode="host", host="zeillinger", max_value=0)
+    big = torch.zeros(n * m * d + 1, dtype=torch.float64, device="cuda")
+    with pytest.raises(ValueError):  # out overlaps points without being points
+        ops.env_step(big[:-1].view(n, m, d), out=big[1:].view(n, m, d), **bufs, **common)
+    env = HironakaHostVecEnv(Zeillinger(), 4)
+    with pytest.raises(RuntimeError):
+        env.step(torch.zeros(4, dtype=torch.int32, device="cuda"))
+
+
+def test_package_exports():
+    import hironaka_amd
+    assert hironaka_amd.HironakaHostVecEnv is HironakaHostVecEnv
+    assert hironaka_amd.HironakaAgentVecEnv is HironakaAgentVecEnv
