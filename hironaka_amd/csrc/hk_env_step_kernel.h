@@ -52,9 +52,10 @@ struct EnvSlice {
       : par(lds + (size_t)lane * stride), c(par + n), row(c + d) {}
 };
 
-// shift along ax by the subset sub (ax < 0: no move, no shift), [reposition], Newton sorted + compacted, in place.  The
-// stages behind the shift run on a game without a move too, as the environments' one launch over the whole batch runs
-// them: on a reduced state they change nothing, unless its rescale has merged coordinates that were an ulp apart.
+// shift along ax by the subset sub (ax < 0: no axis, no shift), [reposition], Newton sorted + compacted, in place.  Agent
+// mode comes here without an axis too (a subset of fewer than 2 coordinates): Agent.move runs the stages behind the shift
+// all the same.  On a reduced state they change nothing, unless its rescale has merged coordinates that were an ulp
+// apart.  Host mode does not come here without a legal axis: HironakaHostEnv.step leaves such a game untouched.
 template <typename T>
 __device__ inline void env_move(const EnvSlice<T>& s, int m, int d, uint32_t sub, int ax, bool reposition) {
   if (ax >= 0) {
@@ -76,10 +77,10 @@ __device__ inline int extent_game(const T* p, int m, int d) {
 }
 
 // HironakaBase.reset on the game gg of the generator's stream (hk_generic_kernel.h kModeGenerate without stages), then
-// Newton -> [rescale] -> [Newton]; `again`: whether the second Newton runs here (host mode leaves it to step(None),
-// whose Newton is the same stage on the same state).  Returns the number of points: the state is compacted.
+// Newton -> [rescale] -> [Newton, unless HK_ENV_IMPROVE_EFFICIENCY] in both modes: host mode's step(None) is a step
+// without a legal axis, which runs no stage.  Returns the number of points: the state is compacted.
 template <typename T>
-__device__ inline int env_fresh(const EnvStepArgs& a, const EnvSlice<T>& s, uint64_t gg, bool again) {
+__device__ inline int env_fresh(const EnvStepArgs& a, const EnvSlice<T>& s, uint64_t gg) {
   const int m = a.m, d = a.d, n = m * d;
   const bool sh = gen_short((uint32_t)a.max_value);
   const int per = sh ? 8 : 4;
@@ -93,7 +94,7 @@ __device__ inline int env_fresh(const EnvStepArgs& a, const EnvSlice<T>& s, uint
   sort_compact_game(s.par, m, d, (T)-1, s.row);
   int np = num_points(s.par, m, d);
   if (a.flags & HK_ENV_SCALE_OBSERVATION) rescale_game(s.par, np, d, (T)-1, kEnvListFlags);
-  if (again && !(a.flags & HK_ENV_IMPROVE_EFFICIENCY)) {
+  if (!(a.flags & HK_ENV_IMPROVE_EFFICIENCY)) {
     newton_game(s.par, np, d, (T)-1, kEnvListFlags);
     sort_compact_game(s.par, np, d, (T)-1, s.row);
     np = num_points(s.par, np, d);
@@ -107,14 +108,14 @@ struct EnvOutcome {
 };
 
 // HironakaHostEnv.step on one game of m rows (its extent): act is the agent's axis, cls the pending class on entry and
-// the new one on return
+// the new one on return.  Without a legal axis the state is looked at as it is: no shift and no Newton.
 template <typename T, int HOST>
 __device__ inline EnvOutcome env_host_step(const EnvStepArgs& a, const EnvSlice<T>& s, int m, int act, int& cls) {
   const int d = a.d;
   const int ncls = (1 << d) - d - 1;
   const uint32_t sub = (cls >= 0 && cls < ncls) ? decode_class(cls, d) : 0u;
   const bool legal = act >= 0 && act < d && ((sub >> act) & 1u);
-  env_move(s, m, d, sub, legal ? act : -1, false);
+  if (legal) env_move(s, m, d, sub, act, false);
   const bool ended = num_points(s.par, m, d) < 2;
   EnvOutcome o;
   o.reward = legal ? (ended ? 0.0 : 1.0) : a.invalid_move_penalty;
@@ -222,7 +223,7 @@ __global__ void __launch_bounds__(kWave) env_step_kernel(EnvStepArgs a) {
         for (int j = 0; j < d; ++j) a.final_coords[g * d + j] = 0.0;
       ep += 1;
       const uint64_t gg = a.game_offset + (uint64_t)(int64_t)ep * a.world_games + (uint64_t)g;
-      const int np = env_fresh<T>(a, s, gg, HOST == 0);
+      const int np = env_fresh<T>(a, s, gg);
       sc = 0;
       if constexpr (HOST != 0) {  // _post_reset_update: step(None)
         sc = 1;

@@ -209,9 +209,11 @@ class HironakaHostEnv(HironakaBase):
             act = torch.as_tensor(action, device=self.device).reshape(n).to(torch.int32)
         in_range = (act >= 0) & (act < d)
         legal = in_range & (self._coords.gather(1, act.clamp(0, d - 1).long().unsqueeze(1)).squeeze(1) > 0)
-        # shift + newton in one launch; an axis outside the subset leaves the (already reduced) game as is
-        self._points = ops.step(self._points, self._coords, act, stages=A.HK_STAGE_SHIFT | A.HK_STAGE_NEWTON,
-                                flags=self._list_flags(), padding_value=self.padding_value, out=self._points)["points"]
+        # shift + newton in one launch; a game whose axis is outside its subset keeps its rows untouched
+        # (hironaka_host_env.py:46-52: Newton would change a state whose rescale merged coordinates an ulp apart)
+        moved = ops.step(self._points, self._coords, act, stages=A.HK_STAGE_SHIFT | A.HK_STAGE_NEWTON,
+                         flags=self._list_flags(), padding_value=self.padding_value)["points"]
+        self._points = torch.where(legal.view(n, 1, 1), moved, self._points)
         ended = self._ended()
         reward = torch.where(legal, (~ended).to(torch.float64),
                              torch.full((n,), float(self.invalid_move_penalty), dtype=torch.float64, device=self.device))

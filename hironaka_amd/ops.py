@@ -1101,6 +1101,9 @@ def env_step(points: torch.Tensor, *, mode: str, step_count: torch.Tensor, episo
                     (threshold_penalty, "threshold_penalty")):
         if v is not None and v != v:
             raise ValueError(f"{name} must be a number. Got NaN.")
+    if value_threshold is not None and value_threshold <= 0:
+        raise ValueError(f"hk_env_step reads a value_threshold <= 0 as none, while the environments test any threshold "
+                         f"that is not None. Got {value_threshold}; use hironaka_amd.gym_env's environments for it.")
     q = A.hk_env_step_desc()
     q.points_in = points.data_ptr()
     q.points_out = q.points_in if out is None or out is points else _env_buffer(out, "out", points.dtype, (b, m, d), dev)

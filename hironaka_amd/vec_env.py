@@ -30,6 +30,7 @@ from .host import Host
 from .util.search import _SEARCH_HOSTS
 
 _FALLBACK = "use hironaka_amd.gym_env.HironakaHostEnv / HironakaAgentEnv for any other host or agent"
+_FALLBACK_THRESHOLD = "use hironaka_amd.gym_env.HironakaHostEnv / HironakaAgentEnv for such a threshold"
 
 
 class HironakaVecBase:
@@ -47,6 +48,9 @@ class HironakaVecBase:
             raise ValueError(f"num_envs must be a positive number of games. Got {num_envs}.")
         if padding_value != -1.0:
             raise ValueError(f"hk_env_step pads with -1. Got padding_value {padding_value}.")
+        if value_threshold is not None and value_threshold <= 0:
+            raise ValueError(f"hk_env_step reads a value_threshold <= 0 as none, while the environments test any "
+                             f"threshold that is not None. Got {value_threshold}; {_FALLBACK_THRESHOLD}.")
         self.dimension, self.max_num_points, self.max_value = dimension, max_num_points, max_value
         self.padding_value = padding_value
         self.value_threshold, self.step_threshold = value_threshold, step_threshold

@@ -24,7 +24,7 @@ extern "C" {
  * HK_ENV_MODE_HOST (the environment fixes a host, the learner is the agent), per game:
  *   step_count += 1.  legal = 0 <= action < dim and the action is a coordinate of the pending subset class_io (a class
  *   id, -1: none; an action outside [0, dim) indexes nothing).  A legal move is shift + Newton, sorted and compacted; an
- *   illegal one has no shift (see "no move" below).  ended = fewer than 2 points.  reward = invalid_move_penalty if not
+ *   illegal one leaves the state untouched (see "no move" below).  ended = fewer than 2 points.  reward = invalid_move_penalty if not
  *   legal, else 1 if not ended, else 0.  exceed = value_threshold > 0 and a coordinate of the state > value_threshold, tested
  *   before this step's rescale.  stopped = ended | exceed | (not legal and HK_ENV_STOP_AFTER_INVALID).  The new pending
  *   subset is the host's class on the state before the rescale, -1 if stopped or the host has none.  The list rescale
@@ -41,16 +41,18 @@ extern "C" {
  *   step_count >= step_threshold; stopped |= trip; reward += trip * threshold_penalty.  The list rescale follows if
  *   HK_ENV_SCALE_OBSERVATION; reward += points before - points after if HK_ENV_POINT_REDUCTION_REWARD; reward += 1 if
  *   ended.  Observation: the points as float32.
- * No move (an illegal axis, a mask with fewer than 2 bits): the shift is skipped and the stages behind it run, as the
- *   environments' launch over the whole batch runs them.  They leave a state that is reduced already as it is, except
- *   where its rescale has merged coordinates that were an ulp apart: Newton then drops the row that has become
- *   dominated.
+ * No move.  Host mode, an illegal axis: no stage runs (hironaka_host_env.py:46-52 touches the points only where the
+ *   action is in the pending list); ended, exceed and the host look at the state as it is, and the rescale follows.
+ *   Agent mode, a mask with fewer than 2 bits: the shift is skipped and the stages behind it run, as Agent.move runs
+ *   them.  They leave a state that is reduced already as it is, except where its rescale has merged coordinates that
+ *   were an ulp apart: Newton then drops the row that has become dominated.
  * HK_ENV_AUTO_RESET, for a game with stopped set: its terminal observation goes to final_points / final_coords (where
  *   given; untouched for every other game), episode += 1, and max_points * dim integers in [0, max_value) are drawn by
  *   the generator's element rule for the global game index game_offset + episode * world_games + b with key seed -- row
  *   b of hk_generate_points(batch = world_games, game_offset = episode * world_games, no stages) -- followed by Newton
  *   sorted and compacted, the list rescale if HK_ENV_SCALE_OBSERVATION, and Newton again unless
- *   HK_ENV_IMPROVE_EFFICIENCY.  Host mode then does what the environment's first step(None) does: step_count = 1 and
+ *   HK_ENV_IMPROVE_EFFICIENCY.  Host mode then does what the environment's first step(None) does, a step without a
+ *   move, which leaves the fresh state as it is: step_count = 1 and
  *   the pending subset is the host's class on the fresh state, -1 if that state has fewer than 2 points, exceeds
  *   value_threshold, or HK_ENV_STOP_AFTER_INVALID is set (the environment counts step(None) as an invalid move).  Agent
  *   mode: step_count = 0.  The observation, the state and the counters returned are the fresh episode's; reward,

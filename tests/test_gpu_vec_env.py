@@ -287,8 +287,9 @@ def test_agent_replay_random_agent(m, d, max_value, cfg):
             raw = ops.game_play(state, rescale=False, **kw)
             res = ops.game_play(state, rescale=scale, **kw)
             played = res.length == 1
-            # no class: no shift, and the stages behind it as the parent's launch over the whole batch runs them --
-            # the state untouched, but where its rescale has merged coordinates an ulp apart
+            # no class: no shift, and the stages behind it as Agent.move runs them in agent mode (host mode leaves a
+            # game without a legal axis untouched) -- the state as it was, but where its rescale has merged
+            # coordinates an ulp apart
             idle = ops.get_newton_polytope(state, -1.0, sem="list")
             idle_scaled = ops.rescale(idle, -1.0, sem="list") if scale else idle
             after = torch.where(played.view(n, 1, 1), res.points, idle_scaled)
@@ -441,6 +442,7 @@ def test_env_step_float32_host_mode_layout(m, d):
     act = v["action"]
     legal = (act >= 0) & (act < d) & (coords.gather(1, act.clamp(0, d - 1).long().unsqueeze(1)).squeeze(1) > 0)
     moved = ops.step(state, coords, act, stages=A.HK_STAGE_SHIFT | A.HK_STAGE_NEWTON, flags=flags)["points"]
+    moved = torch.where(legal.view(n, 1, 1), moved, state)  # host mode: an illegal axis touches nothing
     ended = ops.get_num_points(moved) <= 1
     stop = ended | ~legal
     reward = torch.where(legal, (~ended).to(torch.float64), torch.full_like(v["reward"], PENALTY))
@@ -544,6 +546,13 @@ def test_refusals():
     big = torch.zeros(n * m * d + 1, dtype=torch.float64, device="cuda")
     with pytest.raises(ValueError):  # out overlaps points without being points
         ops.env_step(big[:-1].view(n, m, d), out=big[1:].view(n, m, d), **bufs, **common)
+    for thr in (0.0, -0.5):  # the environments test `is not None`; hk_env_step would read these as "none"
+        with pytest.raises(ValueError, match="gym_env"):
+            ops.env_step(v["points"], **bufs, value_threshold=thr, **common)
+        with pytest.raises(ValueError, match="gym_env"):
+            HironakaHostVecEnv(Zeillinger(), 4, value_threshold=thr)
+        with pytest.raises(ValueError, match="gym_env"):
+            HironakaAgentVecEnv(ChooseFirstAgent(), 4, value_threshold=thr)
     env = HironakaHostVecEnv(Zeillinger(), 4)
     with pytest.raises(RuntimeError):
         env.step(torch.zeros(4, dtype=torch.int32, device="cuda"))
