@@ -2,7 +2,7 @@
 __version__ = "0.1.0"
 
 _VEC_ENVS = ("HironakaHostVecEnv", "HironakaAgentVecEnv")
-__all__ = list(_VEC_ENVS)
+__all__ = list(_VEC_ENVS) + ["ReplayBuffer"]
 
 
 def __getattr__(name):
@@ -10,4 +10,7 @@ def __getattr__(name):
     if name in _VEC_ENVS:
         from . import vec_env
         return getattr(vec_env, name)
+    if name == "ReplayBuffer":
+        from .replay_buffer import ReplayBuffer
+        return ReplayBuffer
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

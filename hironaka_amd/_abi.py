@@ -78,6 +78,13 @@ HK_ENV_IMPROVE_EFFICIENCY, HK_ENV_AGENT_REPOSITION, HK_ENV_AUTO_RESET, HK_ENV_RE
 HK_TREE_REPOSITION, HK_TREE_ZERO_TAIL = 1, 2
 HK_TREE_OVERFLOW = 1
 
+# hk_replay_push / hk_replay_sample: the cursor's words, the Philox stream of the sample indices, rows per workgroup
+HK_REPLAY_MAX_COLS, HK_REPLAY_CURSOR_WORDS = 8, 8
+HK_REPLAY_POS, HK_REPLAY_FULL, HK_REPLAY_LAST_COUNT, HK_REPLAY_TOTAL_PUSHED = 0, 1, 2, 3
+HK_REPLAY_SAMPLES_DRAWN, HK_REPLAY_TICKET = 4, 5
+HK_REPLAY_STREAM = 4
+HK_REPLAY_TILE_ROWS = 128
+
 SEMANTICS = {"jax": HK_SEM_JAX, "torch": HK_SEM_TORCH, "list": HK_SEM_LIST}
 
 
@@ -281,6 +288,27 @@ class hk_tree_expand_desc(C.Structure):
     ]
 
 
+class hk_replay_col(C.Structure):
+    _fields_ = [
+        ("ring", C.c_void_p),
+        ("rows", C.c_void_p),
+        ("row_bytes", C.c_int64),
+        ("rows_stride_bytes", C.c_int64),
+    ]
+
+
+class hk_replay_desc(C.Structure):
+    _fields_ = [
+        ("col", hk_replay_col * HK_REPLAY_MAX_COLS),
+        ("keep", C.c_void_p),
+        ("cursor", C.c_void_p),
+        ("ncols", C.c_int32),
+        ("batch", C.c_int32),
+        ("capacity", C.c_int32),
+        ("reserved_", C.c_int32),
+    ]
+
+
 _vp, _i, _i64, _u32, _u64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
 
 # name -> (restype, argtypes) of every symbol the header declares.  `stream` is the trailing
@@ -362,12 +390,19 @@ ENV_PROTOTYPES = {
     "hk_env_step": (C.c_int, [C.POINTER(hk_env_step_desc), _vp]),
 }
 
+# the entry points of include/hironaka_hip_replay.h: the device library's only, as above
+REPLAY_PROTOTYPES = {
+    "hk_replay_push": (C.c_int, [C.POINTER(hk_replay_desc), _vp]),
+    "hk_replay_sample": (C.c_int, [C.POINTER(hk_replay_desc), _i, _u64, _vp, _vp]),
+}
+
 
 def bind(lib: C.CDLL, prototypes=None) -> None:
-    """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES, TREE_PROTOTYPES and
-    ENV_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
+    """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES, TREE_PROTOTYPES, ENV_PROTOTYPES
+    and REPLAY_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
     if prototypes is None:
-        prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES, **TREE_PROTOTYPES, **ENV_PROTOTYPES}
+        prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES, **TREE_PROTOTYPES, **ENV_PROTOTYPES,
+                      **REPLAY_PROTOTYPES}
     for name, (res, args) in prototypes.items():
         fn = getattr(lib, name)
         fn.restype = res

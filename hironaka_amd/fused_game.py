@@ -101,6 +101,43 @@ class FusedGame:
                 self._rewards(sample_for, output_obs, next_out, next_done).reshape(-1, 1),
                 next_done.reshape(-1, 1), next_out)
 
+    def collect(self, points: HipPoints, sample_for: str, replay_buffer, masked=True, scale_observation=True,
+                exploration_rate=0.2) -> None:
+        """`step` with its experiences written straight into `replay_buffer` (hironaka_amd.replay_buffer.ReplayBuffer):
+        the same moves -- the same network calls and the same `torch.rand` draws in the same order -- but instead of
+        compacting the outputs with `[keep]`, whose sizes have to come back to the host, the uncompacted tensors are
+        pushed with keep = ~done in one launch.  The buffer ends up as after `replay_buffer.add(*step(...))`.  Nothing
+        here synchronises: no timer runs, whatever `log_time` says.  The rewards are computed on the full batch: the
+        default reward gives `step`'s rows exactly, while a custom `reward_func` sees the finished games' rows too
+        (they do not enter the buffer).  Returns None."""
+        assert sample_for in ["host", "agent"], f"sample_for must be one of 'host' and 'agent'. Got {sample_for}."
+        if points.dtype != self.dtype:
+            points.type(self.dtype)
+        log_time, self.log_time = self.log_time, False  # a running timer synchronises the stream
+        try:
+            observations = points.get_features()
+            done = points.ended_batch_in_tensor
+            host_move, chosen_actions = self.host_move(
+                points, exploration_rate=exploration_rate if sample_for == "host" else 0.0, features=observations)
+            agent_move = self.agent_move(
+                points, host_move, masked=masked, scale_observation=scale_observation, inplace=True,
+                exploration_rate=exploration_rate if sample_for == "agent" else 0.0, features=observations)
+            next_done = points.ended_batch_in_tensor
+            next_observations = points.get_features()
+            if sample_for == "host":
+                output_obs, output_actions, next_out = observations, chosen_actions, next_observations
+            else:
+                next_host_move, _ = self.host_move(points, exploration_rate=exploration_rate,
+                                                   features=next_observations)
+                output_obs = {"points": observations, "coords": host_move}
+                output_actions = agent_move
+                next_out = {"points": next_observations, "coords": next_host_move}
+            rewards = self._rewards(sample_for, output_obs, next_out, next_done)
+            replay_buffer.add(output_obs, output_actions.reshape(-1, 1), rewards.reshape(-1, 1),
+                              next_done.reshape(-1, 1), next_out, keep=~done)
+        finally:
+            self.log_time = log_time
+
     def host_move(self, points: HipPoints, masked=True, exploration_rate=0.0,
                   features: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """the host net's argmax class (uniform noise instead with probability `exploration_rate`) and its

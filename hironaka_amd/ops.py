@@ -1142,6 +1142,118 @@ def env_step(points: torch.Tensor, *, mode: str, step_count: torch.Tensor, episo
         check(lib().hk_env_step(C.byref(q), _stream(points)), "hk_env_step")
 
 
+# ---- the replay buffer as a ring on the device (hk_replay_push / hk_replay_sample) ---------------------------------
+
+REPLAY_TILE_ROWS = A.HK_REPLAY_TILE_ROWS
+
+
+def replay_cursor(device) -> torch.Tensor:
+    """a zeroed cursor block: an empty buffer (int64 [8]; the words are the HK_REPLAY_* indices of _abi)"""
+    return torch.zeros(A.HK_REPLAY_CURSOR_WORDS, dtype=torch.int64, device=device)
+
+
+def _row_bytes(t: torch.Tensor) -> int:
+    n = t.element_size()
+    for k in t.shape[1:]:
+        n *= k
+    return n
+
+
+def _rows_of(t: torch.Tensor, ring: torch.Tensor, name: str, rows: int) -> int:
+    """checks the batch side of a column against its ring; returns its row stride in bytes"""
+    _require_device(t, name)
+    if t.device != ring.device or t.dtype != ring.dtype or tuple(t.shape[1:]) != tuple(ring.shape[1:]) or t.dim() < 1:
+        raise ValueError(f"{name} must hold rows of the ring's kind ({ring.dtype} {tuple(ring.shape[1:])} on "
+                         f"{ring.device}). Got {t.dtype} {tuple(t.shape)} on {t.device}.")
+    if t.shape[0] != rows:
+        raise ValueError(f"{name} must have {rows} rows. Got {t.shape[0]}.")
+    row = _row_bytes(ring)
+    if rows == 0:
+        return row
+    stride = t.stride(0) * t.element_size() if rows > 1 else row
+    if not t[0].is_contiguous() or stride < row:
+        raise ValueError(f"the rows of {name} must each be contiguous and must not overlap. Got strides {t.stride()}.")
+    return stride
+
+
+def _replay_desc(ring_cols: Sequence[torch.Tensor], cursor: torch.Tensor) -> "A.hk_replay_desc":
+    if not 1 <= len(ring_cols) <= A.HK_REPLAY_MAX_COLS:
+        raise ValueError(f"a replay buffer has 1..{A.HK_REPLAY_MAX_COLS} columns. Got {len(ring_cols)}.")
+    _require_device(cursor, "cursor")
+    if cursor.dtype != torch.int64 or tuple(cursor.shape) != (A.HK_REPLAY_CURSOR_WORDS,) or not cursor.is_contiguous():
+        raise ValueError(f"cursor must be a contiguous int64 [{A.HK_REPLAY_CURSOR_WORDS}]. Got {cursor.dtype} "
+                         f"{tuple(cursor.shape)}.")
+    q = A.hk_replay_desc()
+    capacity = None
+    for c, ring in enumerate(ring_cols):
+        _require_device(ring, f"ring_cols[{c}]")
+        if ring.dim() < 1 or not ring.is_contiguous() or ring.device != cursor.device:
+            raise ValueError(f"ring_cols[{c}] must be a contiguous [capacity, ...] tensor on {cursor.device}.")
+        capacity = ring.shape[0] if capacity is None else capacity
+        if ring.shape[0] != capacity:
+            raise ValueError(f"every ring has the same number of rows. Got {capacity} and {ring.shape[0]}.")
+        q.col[c].ring = ring.data_ptr()
+        q.col[c].row_bytes = _row_bytes(ring)
+    if not 1 <= capacity < 2 ** 31:
+        raise ValueError(f"the capacity must be in [1, 2^31). Got {capacity}.")
+    q.ncols, q.capacity, q.cursor = len(ring_cols), capacity, cursor.data_ptr()
+    return q
+
+
+def replay_push(ring_cols: Sequence[torch.Tensor], row_cols: Sequence[torch.Tensor], cursor: torch.Tensor,
+                keep: Optional[torch.Tensor] = None) -> None:
+    """Push a batch of experiences into the rings in one launch (hk_replay_push, include/hironaka_hip_replay.h).
+
+    ring_cols: 1..8 contiguous tensors [capacity, ...], one per column.  row_cols: the batch, one tensor [B, ...] per
+    column with its ring's dtype and trailing shape; the rows may be strided (a slice of wider records), each row
+    contiguous.  keep: bool or uint8 [B], the rows to push (None: all).  The kept rows go, in batch order, to the slots
+    the cursor points at and the cursor moves on, all on the device: nothing here synchronises.  B < capacity."""
+    q = _replay_desc(ring_cols, cursor)
+    if len(row_cols) != len(ring_cols):
+        raise ValueError(f"{len(ring_cols)} rings but {len(row_cols)} columns of rows.")
+    batch = row_cols[0].shape[0] if isinstance(row_cols[0], torch.Tensor) and row_cols[0].dim() else 0
+    for c, (ring, rows) in enumerate(zip(ring_cols, row_cols)):
+        q.col[c].rows_stride_bytes = _rows_of(rows, ring, f"row_cols[{c}]", batch)
+        q.col[c].rows = rows.data_ptr()
+    if batch >= q.capacity:
+        raise ValueError(f"a push must be smaller than the buffer. Got {batch} rows for a capacity of {q.capacity}.")
+    if keep is not None:
+        _require_device(keep, "keep")
+        if keep.dtype not in (torch.bool, torch.uint8) or tuple(keep.shape) != (batch,) or keep.device != cursor.device:
+            raise ValueError(f"keep must be a bool or uint8 [{batch}] on {cursor.device}. Got {keep.dtype} "
+                             f"{tuple(keep.shape)} on {keep.device}.")
+        keep = keep.contiguous()
+        q.keep = keep.data_ptr()
+    q.batch = batch
+    with torch.cuda.device(cursor.device):
+        check(lib().hk_replay_push(C.byref(q), _stream(cursor)), "hk_replay_push")
+
+
+def replay_sample(ring_cols: Sequence[torch.Tensor], cursor: torch.Tensor, batch_size: int, seed: int,
+                  out: Optional[Sequence[torch.Tensor]] = None) -> Tuple[list, torch.Tensor]:
+    """Draw batch_size rows uniformly from the filled part of the rings in one launch (hk_replay_sample).
+
+    Returns (cols, index): cols[c] [batch_size, ...] holds row index[j] of ring_cols[c] at row j (``out``: tensors to
+    write into instead of fresh ones), index int64 [batch_size].  The indices are Philox words keyed by ``seed`` and the
+    cursor's samples_drawn, which the launch advances.  An empty buffer gives index -1 and leaves the rows as they
+    are (fresh ones: zero)."""
+    q = _replay_desc(ring_cols, cursor)
+    if not (0 <= batch_size < 2 ** 31 and 0 <= seed < 2 ** 64):
+        raise ValueError(f"batch_size must be in [0, 2^31) and seed in [0, 2^64). Got {batch_size}, {seed}.")
+    if out is None:
+        out = [torch.zeros((batch_size,) + tuple(r.shape[1:]), dtype=r.dtype, device=r.device) for r in ring_cols]
+    elif len(out) != len(ring_cols):
+        raise ValueError(f"{len(ring_cols)} rings but {len(out)} output columns.")
+    for c, (ring, rows) in enumerate(zip(ring_cols, out)):
+        q.col[c].rows_stride_bytes = _rows_of(rows, ring, f"out[{c}]", batch_size)
+        q.col[c].rows = rows.data_ptr()
+    index = torch.full((batch_size,), -1, dtype=torch.int64, device=cursor.device)
+    with torch.cuda.device(cursor.device):
+        check(lib().hk_replay_sample(C.byref(q), batch_size, seed, index.data_ptr(), _stream(cursor)),
+              "hk_replay_sample")
+    return list(out), index
+
+
 # ---- one level of a game tree under any host (hk_tree_expand) -------------------------------------------------------
 
 TreeExpandResult = collections.namedtuple(

@@ -627,5 +627,7 @@ int hk_search_morin_play(const hk_morin_play_desc* desc, void* stream);
 #include "hironaka_hip_tree.h"
 /* within ABI 6: hk_env_step, likewise */
 #include "hironaka_hip_env.h"
+/* within ABI 6: hk_replay_push / hk_replay_sample, likewise */
+#include "hironaka_hip_replay.h"
 
 #endif /* HIRONAKA_HIP_H */
