@@ -34,9 +34,13 @@ constexpr int kModeRolloutRec = 4;
 // kernel, which then carries neither their code nor their registers
 constexpr int kModeStepAux = 5;
 
-// RNG stream ids (DESIGN.md "Randomness"); the oracle uses the same two numbers.
+// RNG stream ids (DESIGN.md "Randomness"): the fourth counter word of every Philox block.  The oracle uses the same
+// numbers, and fixtures pin them.
 constexpr uint32_t kStreamPolicy = 0u;
 constexpr uint32_t kStreamGenerate = 1u;
+constexpr uint32_t kStreamMorinTie = 2u;               // hk_search_morin_play: the agent's random tie-break
+constexpr uint32_t kStreamPlayAgent = 3u;              // hk_game_play, hk_env_step: the random-legal agent
+constexpr uint32_t kStreamReplay = HK_REPLAY_STREAM;  // hk_replay_sample: the sample indices
 
 // Kernel argument block (passed by value).  Union of what the modes need.
 struct Params {

@@ -11,7 +11,7 @@ int hk_env_step(const hk_env_step_desc* q, void* stream) {
   if (q->dtype != HK_F32 && q->dtype != HK_F64) return HK_ERR_UNSUPPORTED;
   if (q->mode != HK_ENV_MODE_HOST && q->mode != HK_ENV_MODE_AGENT) return HK_ERR_UNSUPPORTED;
   if (q->batch < 0 || q->max_points < 1 || q->dim < 2) return HK_ERR_SHAPE;
-  if (q->max_points > kFixedHostMaxPoints || q->dim > kGamePlayMaxDim) return HK_ERR_UNSUPPORTED;
+  if (q->max_points > kFixedHostMaxPoints || q->dim > kLaneGameMaxDim) return HK_ERR_UNSUPPORTED;
   const bool host_mode = q->mode == HK_ENV_MODE_HOST;
   if (host_mode && !fixed_host(q->host)) return HK_ERR_UNSUPPORTED;
   if (!host_mode && q->agent != HK_AGENT_RANDOM_LEGAL && q->agent != HK_AGENT_CHOOSE_FIRST) return HK_ERR_UNSUPPORTED;
@@ -29,18 +29,13 @@ int hk_env_step(const hk_env_step_desc* q, void* stream) {
   if (!reset_all && (!q->points_in || !q->action)) return HK_ERR_NULL;
   if (host_mode && (!q->class_io || !q->obs_coords)) return HK_ERR_NULL;
   const size_t es = elem_size(q->dtype);
-  const uint64_t n = (uint64_t)q->max_points * (uint64_t)q->dim;
-  if (!reset_all && q->points_in != q->points_out) {
-    // a workgroup's write-back must not meet another's staging read: other than in place, the two do not overlap
-    const uintptr_t in = (uintptr_t)q->points_in, out = (uintptr_t)q->points_out;
-    const uint64_t bytes = (uint64_t)q->batch * n * es;
-    if (in < out + bytes && out < in + bytes) return HK_ERR_SHAPE;
-  }
-  const void* words[] = {q->class_io, q->step_count, q->episode, q->action, q->obs_points, q->final_points, q->agent_axis};
-  for (const void* p : words)
-    if (!aligned(p, 4)) return HK_ERR_ALIGN;
-  if (!aligned(q->reward, 8) || !aligned(q->obs_coords, 8) || !aligned(q->final_coords, 8)) return HK_ERR_ALIGN;
-  if (!aligned(q->points_in, es) || !aligned(q->points_out, es)) return HK_ERR_ALIGN;
+  const int64_t n = (int64_t)q->max_points * q->dim;
+  if (!reset_all && q->points_in != q->points_out &&
+      records_overlap(q->points_in, n, q->batch, n, q->points_out, n, q->batch, n, es))
+    return HK_ERR_SHAPE;
+  if (!all_aligned({q->class_io, q->step_count, q->episode, q->action, q->obs_points, q->final_points, q->agent_axis}, 4) ||
+      !all_aligned({q->reward, q->obs_coords, q->final_coords}, 8) || !all_aligned({q->points_in, q->points_out}, es))
+    return HK_ERR_ALIGN;
   EnvStepArgs a{};
   a.points = q->points_in;
   a.points_out = q->points_out;
@@ -71,20 +66,14 @@ int hk_env_step(const hk_env_step_desc* q, void* stream) {
   a.step_threshold = q->step_threshold;
   a.flags = q->flags;
   a.lds_stride = env_lds_stride(a.m, a.d);
-  const int per_game = a.lds_stride * (int)es;
-  a.games_per_block = kSearchLdsBytes / per_game < kWave ? kSearchLdsBytes / per_game : kWave;
-  const unsigned grid = (unsigned)(((int64_t)a.batch + a.games_per_block - 1) / a.games_per_block);
-  const size_t lds = (size_t)a.games_per_block * per_game;
-  auto launch = [&](auto t, auto h) {
+  const LaneGeometry geo = lane_geometry(a.lds_stride, es, a.batch);
+  a.games_per_block = geo.per_block;
+  // agent mode: no host, the kernel's HOST is 0
+  return with_fixed_host_or(q->dtype, host_mode ? q->host : 0, std::integral_constant<int, 0>(), [&](auto t, auto h) {
     launch_prepare();
-    hipLaunchKernelGGL((env_step_kernel<decltype(t), h>), dim3(grid), dim3(kWave), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((env_step_kernel<decltype(t), h>), dim3(geo.grid), dim3(kWave), geo.lds, (hipStream_t)stream, a);
     return launch_status();
-  };
-  if (!host_mode) {
-    const std::integral_constant<int, 0> none;
-    return q->dtype == HK_F32 ? launch(float(), none) : launch(double(), none);
-  }
-  return with_fixed_host(q->dtype, q->host, launch);
+  });
 }
 
 }  // extern "C"

@@ -2,21 +2,16 @@
 // HironakaAgentEnv.step read per row), and the next episode of a game that stopped (HironakaBase.reset) drawn inside the
 // same launch, one game per lane.
 //
-// The frame is hk_game_play_kernel.h's: a workgroup is one wave that owns `games_per_block` consecutive games, as many
-// as have slices in kSearchLdsBytes, at most a wave.  Their rows are staged with the coalesced slab copy into slices of
-// the odd stride env_lds_stride counts, and lane g works on game g alone in its slice with the per-game routines of
-// hk_game_generic.h and hk_hosts.h.  Every stage works in place: the move has no use for the state before it, so a slice
-// holds one state, not hk_game_play's two.  The terminal observations of the games that stopped leave with a coalesced
-// store of the wave before those lanes draw their next episode into the same slices.  HBM traffic: one read and one write of the
-// state, one write of the float32 observation, one of the terminal observation for the games that stopped, and the
-// per-game scalars.  No communication between workgroups; every loop is bounded by m, d or m * d.
+// The frame is hk_lane_games.h's, with slices of its own (env_lds_stride).  Every stage works in place: the move has no
+// use for the state before it, so a slice holds one state, not hk_game_play's two.  The terminal observations of the
+// games that stopped leave with a coalesced store of the wave before those lanes draw their next episode into the same
+// slices.  HBM traffic: one read and one write of the state, one write of the float32 observation, one of the terminal
+// observation for the games that stopped, and the per-game scalars.  Every loop is bounded by m, d or m * d.
 #pragma once
 
-#include "hk_game_play_kernel.h"
+#include "hk_lane_games.h"
 
 namespace hk {
-
-constexpr int kEnvStepBatch = 16;  // loads per lane in flight while staging (hk_host_select_kernel.h)
 
 struct EnvStepArgs {
   const void* points;
@@ -39,8 +34,6 @@ struct EnvStepArgs {
   uint32_t flags;
 };
 
-constexpr unsigned kEnvListFlags = HK_SEM_LIST | HK_FLAG_COMPACT_SORTED;
-
 // LDS elements per lane: the game, the shift coefficients c and sort_compact's row scratch; odd, so that the lanes'
 // slices start in different banks.  Half of search_lds_stride's: twice the waves per CU.
 inline int env_lds_stride(int m, int d) { return (m * d + 2 * d) | 1; }
@@ -59,11 +52,11 @@ struct EnvSlice {
 template <typename T>
 __device__ inline void env_move(const EnvSlice<T>& s, int m, int d, uint32_t sub, int ax, bool reposition) {
   if (ax >= 0) {
-    for (int j = 0; j < d; ++j) s.c[j] = ((sub >> j) & 1u) ? (T)1 : (T)0;
-    shift_game(s.par, m, d, s.c, ax, (T)-1, kEnvListFlags);
+    subset_coeffs(s.c, sub, d);
+    shift_game(s.par, m, d, s.c, ax, (T)-1, kListFlags);
   }
-  if (reposition) reposition_game(s.par, m, d, (T)-1, kEnvListFlags);
-  newton_game(s.par, m, d, (T)-1, kEnvListFlags);
+  if (reposition) reposition_game(s.par, m, d, (T)-1, kListFlags);
+  newton_game(s.par, m, d, (T)-1, kListFlags);
   sort_compact_game(s.par, m, d, (T)-1, s.row);
 }
 
@@ -90,12 +83,12 @@ __device__ inline int env_fresh(const EnvStepArgs& a, const EnvSlice<T>& s, uint
     gen_block_values(r, (uint32_t)a.max_value, sh, v);
     for (int q = 0; q < per && e + q < n; ++q) s.par[e + q] = (T)v[q];
   }
-  newton_game(s.par, m, d, (T)-1, kEnvListFlags);
+  newton_game(s.par, m, d, (T)-1, kListFlags);
   sort_compact_game(s.par, m, d, (T)-1, s.row);
   int np = num_points(s.par, m, d);
-  if (a.flags & HK_ENV_SCALE_OBSERVATION) rescale_game(s.par, np, d, (T)-1, kEnvListFlags);
+  if (a.flags & HK_ENV_SCALE_OBSERVATION) rescale_game(s.par, np, d, (T)-1, kListFlags);
   if (!(a.flags & HK_ENV_IMPROVE_EFFICIENCY)) {
-    newton_game(s.par, np, d, (T)-1, kEnvListFlags);
+    newton_game(s.par, np, d, (T)-1, kListFlags);
     sort_compact_game(s.par, np, d, (T)-1, s.row);
     np = num_points(s.par, np, d);
   }
@@ -122,11 +115,9 @@ __device__ inline EnvOutcome env_host_step(const EnvStepArgs& a, const EnvSlice<
   o.exceed = a.value_threshold > 0.0 && exceeds_game(s.par, m, d, a.value_threshold);
   o.stopped = ended || o.exceed || (!legal && (a.flags & HK_ENV_STOP_AFTER_INVALID));
   cls = -1;
-  if (!o.stopped)
-    cls = d < kGamePlayMaxDim ? host_class_game<T, HOST, uint64_t>(s.par, m, d)
-                              : host_class_game<T, HOST, Bits128>(s.par, m, d);
+  if (!o.stopped) cls = host_class_any<T, HOST>(s.par, m, d);
   if (cls >= ncls) cls = -1;
-  if (a.flags & HK_ENV_SCALE_OBSERVATION) rescale_game(s.par, m, d, (T)-1, kEnvListFlags);
+  if (a.flags & HK_ENV_SCALE_OBSERVATION) rescale_game(s.par, m, d, (T)-1, kListFlags);
   return o;
 }
 
@@ -140,12 +131,8 @@ __device__ inline EnvOutcome env_agent_step(const EnvStepArgs& a, const EnvSlice
   const int before = num_points(s.par, m, d);
   ax = -1;
   if (__popc(sub) >= 2) {
-    if (a.agent == HK_AGENT_CHOOSE_FIRST) {
-      ax = __ffs((int)sub) - 1;
-    } else {
-      const U4 r = philox4x32((uint32_t)gg, (uint32_t)(gg >> 32), (uint32_t)(sc - 1), kStreamPlayAgent, a.agent_seed);
-      ax = nth_bit(sub, (int)mulhi32(r.x, (uint32_t)__popc(sub)));
-    }
+    ax = a.agent == HK_AGENT_CHOOSE_FIRST ? __ffs((int)sub) - 1
+                                          : random_legal_axis(sub, gg, (uint32_t)(sc - 1), kStreamPlayAgent, a.agent_seed);
   }
   env_move(s, m, d, sub, ax, (a.flags & HK_ENV_AGENT_REPOSITION) != 0);
   const bool ended = num_points(s.par, m, d) < 2;
@@ -158,7 +145,7 @@ __device__ inline EnvOutcome env_agent_step(const EnvStepArgs& a, const EnvSlice
     o.stopped = o.stopped || trip;
     o.reward = o.reward + (trip ? 1.0 : 0.0) * a.threshold_penalty;
   }
-  if (a.flags & HK_ENV_SCALE_OBSERVATION) rescale_game(s.par, m, d, (T)-1, kEnvListFlags);
+  if (a.flags & HK_ENV_SCALE_OBSERVATION) rescale_game(s.par, m, d, (T)-1, kListFlags);
   if (a.flags & HK_ENV_POINT_REDUCTION_REWARD) o.reward = o.reward + (double)(before - num_points(s.par, m, d));
   o.reward = o.reward + (ended ? 1.0 : 0.0);
   return o;
@@ -181,13 +168,11 @@ __global__ void __launch_bounds__(kWave) env_step_kernel(EnvStepArgs a) {
   T* lds = reinterpret_cast<T*>(hk_env_lds);
   const int lane = threadIdx.x;
   const int m = a.m, d = a.d, n = m * d;
-  const int64_t g0 = (int64_t)blockIdx.x * a.games_per_block;
-  const int64_t left = (int64_t)a.batch - g0;
-  const int ngames = left < a.games_per_block ? (int)left : a.games_per_block;
+  const LaneBlock blk = lane_block(a.batch, a.games_per_block);
+  const int64_t g0 = blk.g0;
+  const int ngames = blk.ngames;
   const bool reset_all = (a.flags & HK_ENV_RESET_ALL) != 0;
-  if (!reset_all)
-    copy_slab<T, true, kEnvStepBatch>(lds, const_cast<T*>(static_cast<const T*>(a.points)), (int64_t)n, n, a.lds_stride,
-                                      g0, ngames, lane);
+  if (!reset_all) stage_games(lds, a.points, (int64_t)n, n, a.lds_stride, blk, lane);
   __syncthreads();
   const bool active = lane < ngames;
   const int64_t g = g0 + lane;
@@ -245,7 +230,7 @@ __global__ void __launch_bounds__(kWave) env_step_kernel(EnvStepArgs a) {
     }
   }
   __syncthreads();
-  copy_slab<T, false, kEnvStepBatch>(lds, static_cast<T*>(a.points_out), (int64_t)n, n, a.lds_stride, g0, ngames, lane);
+  unstage_games(lds, a.points_out, (int64_t)n, n, a.lds_stride, blk, lane);
   store_obs(lds, a.obs_points, n, a.lds_stride, g0, ngames, lane, ~0ull);
 }
 

@@ -10,7 +10,7 @@ int hk_search_morin_play(const hk_morin_play_desc* q, void* stream) {
   if (!q) return HK_ERR_NULL;
   if (q->dtype != HK_F32 && q->dtype != HK_F64) return HK_ERR_UNSUPPORTED;
   if (q->batch < 0 || q->max_points < 1 || q->dim < 2 || q->max_steps < 0) return HK_ERR_SHAPE;
-  if (q->max_points > kFixedHostMaxPoints || q->dim > kMorinMaxDim) return HK_ERR_UNSUPPORTED;
+  if (q->max_points > kFixedHostMaxPoints || q->dim > kLaneGameMaxDim) return HK_ERR_UNSUPPORTED;
   if (!fixed_host(q->host) && q->host != HK_MORIN_HOST_FORCED) return HK_ERR_UNSUPPORTED;
   if (q->tie < HK_MORIN_TIE_LOWEST || q->tie > HK_MORIN_TIE_RANDOM) return HK_ERR_UNSUPPORTED;
   if (q->weight_rule != HK_MORIN_WEIGHTS_AGENT && q->weight_rule != HK_MORIN_WEIGHTS_SEARCH) return HK_ERR_UNSUPPORTED;
@@ -24,18 +24,13 @@ int hk_search_morin_play(const hk_morin_play_desc* q, void* stream) {
   if (q->in_stride < n || q->out_stride < n) return HK_ERR_SHAPE;
   if (q->points_in == q->points_out && q->in_stride != q->out_stride) return HK_ERR_SHAPE;
   const size_t es = elem_size(q->dtype);
-  if (q->points_in != q->points_out) {
-    // a workgroup's write-back must not meet another's staging read: other than in place, the two do not overlap
-    const uintptr_t in = (uintptr_t)q->points_in, out = (uintptr_t)q->points_out;
-    const uint64_t in_bytes = ((uint64_t)(q->batch - 1) * (uint64_t)q->in_stride + (uint64_t)n) * es;
-    const uint64_t out_bytes = ((uint64_t)(q->batch - 1) * (uint64_t)q->out_stride + (uint64_t)n) * es;
-    if (in < out + out_bytes && out < in + in_bytes) return HK_ERR_SHAPE;
-  }
-  const int32_t* ints[] = {q->weights_in, q->weights_out, q->distinguished_in, q->distinguished_out, q->class_in,
-                           q->axis_in,    q->class_out,   q->axis_out,         q->length_out,        q->outcome_out};
-  for (const int32_t* p : ints)
-    if (!aligned(p, 4)) return HK_ERR_ALIGN;
-  if (!aligned(q->points_in, es) || !aligned(q->points_out, es)) return HK_ERR_ALIGN;
+  if (q->points_in != q->points_out &&
+      records_overlap(q->points_in, q->in_stride, q->batch, n, q->points_out, q->out_stride, q->batch, n, es))
+    return HK_ERR_SHAPE;
+  if (!all_aligned({q->weights_in, q->weights_out, q->distinguished_in, q->distinguished_out, q->class_in, q->axis_in,
+                    q->class_out, q->axis_out, q->length_out, q->outcome_out}, 4) ||
+      !all_aligned({q->points_in, q->points_out}, es))
+    return HK_ERR_ALIGN;
   MorinPlayArgs a{};
   a.points = q->points_in;
   a.points_out = q->points_out;
@@ -62,20 +57,13 @@ int hk_search_morin_play(const hk_morin_play_desc* q, void* stream) {
   a.weight_rule = q->weight_rule;
   a.reduce_root = (q->flags & HK_MORIN_REDUCE_ROOT) ? 1 : 0;
   a.lds_stride = search_lds_stride(a.m, a.d, morin_lds_extra(a.d));
-  const int per_game = a.lds_stride * (int)es;
-  a.games_per_block = kSearchLdsBytes / per_game < kWave ? kSearchLdsBytes / per_game : kWave;
-  const unsigned grid = (unsigned)(((int64_t)a.batch + a.games_per_block - 1) / a.games_per_block);
-  const size_t lds = (size_t)a.games_per_block * per_game;
-  auto launch = [&](auto t, auto h) {
+  const LaneGeometry geo = lane_geometry(a.lds_stride, es, a.batch);
+  a.games_per_block = geo.per_block;
+  return with_fixed_host_or(q->dtype, q->host, std::integral_constant<int, HK_MORIN_HOST_FORCED>(), [&](auto t, auto h) {
     launch_prepare();
-    hipLaunchKernelGGL((morin_play_kernel<decltype(t), h>), dim3(grid), dim3(kWave), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((morin_play_kernel<decltype(t), h>), dim3(geo.grid), dim3(kWave), geo.lds, (hipStream_t)stream, a);
     return launch_status();
-  };
-  if (q->host == HK_MORIN_HOST_FORCED) {
-    const std::integral_constant<int, HK_MORIN_HOST_FORCED> forced;
-    return q->dtype == HK_F32 ? launch(float(), forced) : launch(double(), forced);
-  }
-  return with_fixed_host(q->dtype, q->host, launch);
+  });
 }
 
 }  // extern "C"

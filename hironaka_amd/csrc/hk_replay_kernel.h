@@ -25,9 +25,8 @@ namespace hk {
 
 constexpr int kReplayThreads = 256;
 constexpr int kReplayTile = HK_REPLAY_TILE_ROWS;
-constexpr int kReplayUnroll = 4;                      // units per lane in flight
-constexpr uint32_t kStreamReplay = HK_REPLAY_STREAM;  // RNG stream id of the sample indices (next to kStreamPlayAgent)
-constexpr int64_t kReplayMaxRowBytes = 1 << 20;       // a tile's units are counted in 32 bits
+constexpr int kReplayUnroll = 4;                 // units per lane in flight
+constexpr int64_t kReplayMaxRowBytes = 1 << 20;  // a tile's units are counted in 32 bits
 
 static_assert(kReplayTile % kWave == 0 && kReplayTile <= kReplayThreads, "a lane per row of the tile");
 

@@ -10,7 +10,7 @@ namespace {
 int morin_spec(int batch, int m, int d, int dtype, int max_nodes, int stack_nodes) {
   if (dtype != HK_F32 && dtype != HK_F64) return HK_ERR_UNSUPPORTED;
   if (batch < 0 || m < 1 || d < 2 || max_nodes < 1 || stack_nodes < 1) return HK_ERR_SHAPE;
-  if (m > kFixedHostMaxPoints || d > kMorinMaxDim) return HK_ERR_UNSUPPORTED;
+  if (m > kFixedHostMaxPoints || d > kLaneGameMaxDim) return HK_ERR_UNSUPPORTED;
   return HK_OK;
 }
 

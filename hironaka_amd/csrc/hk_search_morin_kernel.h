@@ -15,20 +15,16 @@
 //            contained).  Then the child is a "No contribution" leaf: kind 1, dist -1, never expanded.
 //   kept     kind 0, dist = the position of p in the sorted, compacted state, where p is unique.
 //
-// The lane's weights and the saved row p live behind LaneSlice::row in its LDS slice (morin_lds_extra): indexed at run
-// time, they would land in scratch as register arrays.
+// The lane's weights and the saved row p live behind LaneSlice::row in its LDS slice (morin_lds_extra), and a child is
+// expand_morin_child, both in hk_lane_games.h.
 //
 // Dimension 7: the hitting-set hosts run on the two-word support bitmap (Bits128) there, on uint64_t below.
 #pragma once
 
+#include "hk_lane_games.h"
 #include "hk_search_tree_kernel.h"
 
 namespace hk {
-
-constexpr int kMorinMaxDim = 7;
-
-// LDS elements per lane behind LaneSlice::row: d weights (int32, one per element) and the row p
-inline int morin_lds_extra(int d) { return 2 * d; }
 
 struct SearchMorinArgs {
   const void* points;            // [batch, m, d] roots, used as given
@@ -56,40 +52,6 @@ struct SearchMorinArgs {
 // int32 words per root in rec_ints: search_tree's, then child count, sibling rank, kind, dist and d weights per record
 inline uint64_t search_morin_int_words(int max_nodes, int stack_nodes, int d) {
   return search_tree_int_words(max_nodes, stack_nodes) + (4ull + (uint64_t)d) * (uint64_t)max_nodes;
-}
-
-// One Morin child of the game in s.par whose distinguished row is `pd`: the state goes to s.chd as expand_child's does,
-// with the reposition between shift and Newton.  prow: d elements of scratch for the row p.  Returns the number of
-// points; `dist` receives p's position in the child, -1 when it was lost.
-template <typename T>
-__device__ inline int expand_morin_child(const LaneSlice<T>& s, T* prow, int m, int d, int ax, int pd, bool& inexact,
-                                         int& dist) {
-  const T limit = sizeof(T) == 4 ? (T)16777216.0 : (T)9007199254740992.0;
-  const unsigned flags = HK_SEM_LIST | HK_FLAG_COMPACT_SORTED;
-  for (int e = 0; e < m * d; ++e) s.chd[e] = s.par[e];
-  shift_game(s.chd, m, d, s.c, ax, (T)-1, flags);
-  for (int i = 0; i < m; ++i) inexact |= s.chd[i * d + ax] >= limit;
-  reposition_game(s.chd, m, d, (T)-1, flags);
-  for (int k = 0; k < d; ++k) prow[k] = s.chd[pd * d + k];
-  bool lost = false;
-  for (int q = 0; q < m; ++q) {
-    if (q == pd || !(s.chd[q * d] >= (T)0)) continue;
-    bool below = true;
-    for (int k = 0; k < d; ++k) below &= s.chd[q * d + k] <= prow[k];
-    lost |= below;
-  }
-  newton_game(s.chd, m, d, (T)-1, flags);
-  sort_compact_game(s.chd, m, d, (T)-1, s.row);
-  const int np = num_points(s.chd, m, d);
-  dist = -1;
-  if (!lost) {
-    for (int i = 0; i < np; ++i) {
-      bool same = true;
-      for (int k = 0; k < d; ++k) same &= s.chd[i * d + k] == prow[k];
-      if (same) dist = i;
-    }
-  }
-  return np;
 }
 
 // HOST: the host code, one instantiation per host
@@ -154,8 +116,8 @@ __global__ void __launch_bounds__(kWave) search_morin_kernel(SearchMorinArgs a) 
     uint32_t order = 0, keep = 0;  // keep, bit j: the j-th action of the host's list is not pruned
     int nc = 0, cls = -1;
     if (active) {
-      cls = d < kMorinMaxDim ? host_order_game<T, HOST, uint64_t>(sl.par, m, d, order, nc)
-                             : host_order_game<T, HOST, Bits128>(sl.par, m, d, order, nc);
+      cls = d < kLaneGameMaxDim ? host_order_game<T, HOST, uint64_t>(sl.par, m, d, order, nc)
+                                : host_order_game<T, HOST, Bits128>(sl.par, m, d, order, nc);
       for (int i = 0; i < d; ++i) w[i] = rw[(size_t)me * d + i];
       int wmin = INT_MAX;
       for (int j = 0; j < nc; ++j) {
@@ -166,7 +128,7 @@ __global__ void __launch_bounds__(kWave) search_morin_kernel(SearchMorinArgs a) 
     }
     const int made = __popc(keep);
     int tot;
-    const int rbase = nrec + lane_prefix<kMorinMaxDim>(made, tot);  // this lane's first child record
+    const int rbase = nrec + lane_prefix<kLaneGameMaxDim>(made, tot);  // this lane's first child record
     if (tot > M - nrec) {
       status |= HK_SEARCH_NODE_LIMIT;
       break;
@@ -176,7 +138,7 @@ __global__ void __launch_bounds__(kWave) search_morin_kernel(SearchMorinArgs a) 
       rcls[me] = cls;
       rfirst[me] = made ? rbase : -1;
       rcnt[me] = made;
-      for (int j = 0; j < d; ++j) sl.c[j] = ((sub >> j) & 1u) ? (T)1 : (T)0;
+      subset_coeffs(sl.c, sub, d);
     }
     uint32_t push = 0;  // bit j: the child of the lane's j-th action may be expanded
     bool stop = false;
@@ -216,7 +178,7 @@ __global__ void __launch_bounds__(kWave) search_morin_kernel(SearchMorinArgs a) 
     }
     if (stop) break;
     int ptot;
-    const int ppre = lane_prefix<kMorinMaxDim>(__popc(push), ptot);
+    const int ppre = lane_prefix<kLaneGameMaxDim>(__popc(push), ptot);
     if (ptot > a.stack_nodes - top) {
       status |= HK_SEARCH_STACK_LIMIT;
       break;

@@ -10,7 +10,7 @@ int hk_tree_expand(const hk_tree_expand_desc* q, void* stream) {
   if (!q) return HK_ERR_NULL;
   if (q->dtype != HK_F32 && q->dtype != HK_F64) return HK_ERR_UNSUPPORTED;
   if (q->n_parents < 0 || q->capacity < 0 || q->max_points < 1 || q->dim < 2) return HK_ERR_SHAPE;
-  if (q->dim > kTreeExpandMaxDim) return HK_ERR_UNSUPPORTED;
+  if (q->dim > kLaneGameMaxDim) return HK_ERR_UNSUPPORTED;
   if (q->sem != HK_SEM_JAX && q->sem != HK_SEM_LIST) return HK_ERR_UNSUPPORTED;
   if (q->flags & ~(HK_TREE_REPOSITION | HK_TREE_ZERO_TAIL)) return HK_ERR_UNSUPPORTED;
   const size_t es = elem_size(q->dtype);
@@ -25,18 +25,13 @@ int hk_tree_expand(const hk_tree_expand_desc* q, void* stream) {
   const int64_t n = (int64_t)q->max_points * q->dim;
   const int64_t len = n + ((q->flags & HK_TREE_ZERO_TAIL) ? q->dim : 0);
   if (q->in_stride < n || q->out_stride < len) return HK_ERR_SHAPE;
-  if (q->capacity > 0) {
-    // a workgroup writes children while others still stage parents: the two buffers do not overlap
-    const uintptr_t in = (uintptr_t)q->parents_in, out = (uintptr_t)q->children_out;
-    const uint64_t in_bytes = ((uint64_t)(q->n_parents - 1) * (uint64_t)q->in_stride + (uint64_t)n) * es;
-    const uint64_t out_bytes = ((uint64_t)(q->capacity - 1) * (uint64_t)q->out_stride + (uint64_t)len) * es;
-    if (in < out + out_bytes && out < in + in_bytes) return HK_ERR_SHAPE;
-  }
-  const void* words[] = {q->class_id, q->child_parent, q->child_axis, q->child_num_points, q->status};
-  for (const void* p : words)
-    if (!aligned(p, 4)) return HK_ERR_ALIGN;
-  if (!aligned(q->child_offset, 8)) return HK_ERR_ALIGN;
-  if (!aligned(q->parents_in, es) || !aligned(q->children_out, es)) return HK_ERR_ALIGN;
+  // a workgroup writes children while others still stage parents: the two buffers do not overlap
+  if (q->capacity > 0 && records_overlap(q->parents_in, q->in_stride, q->n_parents, n, q->children_out, q->out_stride,
+                                         q->capacity, len, es))
+    return HK_ERR_SHAPE;
+  if (!all_aligned({q->class_id, q->child_parent, q->child_axis, q->child_num_points, q->status}, 4) ||
+      !aligned(q->child_offset, 8) || !all_aligned({q->parents_in, q->children_out}, es))
+    return HK_ERR_ALIGN;
   TreeExpandArgs a{};
   a.parents = q->parents_in;
   a.children = q->children_out;
@@ -57,15 +52,13 @@ int hk_tree_expand(const hk_tree_expand_desc* q, void* stream) {
   a.reposition = (q->flags & HK_TREE_REPOSITION) ? 1 : 0;
   a.zero_tail = (q->flags & HK_TREE_ZERO_TAIL) ? 1 : 0;
   a.lds_stride = search_lds_stride(a.m, a.d);
-  const int per_parent = a.lds_stride * (int)es;
-  a.parents_per_block = kSearchLdsBytes / per_parent < kWave ? kSearchLdsBytes / per_parent : kWave;
-  const unsigned grid = (unsigned)(((int64_t)a.n_parents + a.parents_per_block - 1) / a.parents_per_block);
-  const size_t lds = (size_t)a.parents_per_block * per_parent;
+  const LaneGeometry geo = lane_geometry(a.lds_stride, es, a.n_parents);
+  a.parents_per_block = geo.per_block;
   launch_prepare();
   if (q->dtype == HK_F32)
-    hipLaunchKernelGGL((tree_expand_kernel<float>), dim3(grid), dim3(kWave), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((tree_expand_kernel<float>), dim3(geo.grid), dim3(kWave), geo.lds, (hipStream_t)stream, a);
   else
-    hipLaunchKernelGGL((tree_expand_kernel<double>), dim3(grid), dim3(kWave), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((tree_expand_kernel<double>), dim3(geo.grid), dim3(kWave), geo.lds, (hipStream_t)stream, a);
   return launch_status();
 }
 

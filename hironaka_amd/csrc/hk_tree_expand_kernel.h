@@ -2,24 +2,18 @@
 // whole frontier).  The host ran outside; a launch makes, for every parent, one child per coordinate of the subset the
 // host chose, and packs the children at the slots the caller's prefix sum assigns.
 //
-// The frame is hk_game_play_kernel.h's: a workgroup is one wave that owns `parents_per_block` consecutive parents, as
-// many as have slices in kSearchLdsBytes, at most a wave.  Their rows are staged with the coalesced slab copy into
-// slices of the odd stride search_lds_stride counts, and lane g makes parent g's children one after another in the
-// child half of its slice with the per-game routines of hk_game_generic.h.  Round r: every lane whose parent has more
-// than r children makes child r, then the whole wave copies the round's children from LDS to their slots, consecutive
-// lanes writing consecutive elements of a record.  The coefficients c sit right behind the child half, so the zero tail
-// of a record (search.py:107) leaves in the same copy.  HBM traffic: one read of each parent however many children it
-// has, one write of each child, 13 B of bookkeeping per child.  No communication between workgroups, no spinning: a
-// child's slot is known before the launch, and every loop is bounded by m, d or the parents of the block.
+// The frame is hk_lane_games.h's, with search_lds_stride's slices: lane g makes parent g's children one after another
+// in the child half of its slice.  The child sequence is its own: it takes its semantics at run time and has no inexact
+// test.  Round r: every lane whose parent has more than r children makes child r, then the whole wave copies the round's
+// children from LDS to their slots, consecutive lanes writing consecutive elements of a record.  The coefficients c sit
+// right behind the child half, so the zero tail of a record (search.py:107) leaves in the same copy.  HBM traffic: one
+// read of each parent however many children it has, one write of each child, 13 B of bookkeeping per child.  No
+// spinning: a child's slot is known before the launch, and every loop is bounded by m, d or the parents of the block.
 #pragma once
 
-#include "hk_generic_kernel.h"
-#include "hk_morin_play_kernel.h"
+#include "hk_lane_games.h"
 
 namespace hk {
-
-constexpr int kTreeExpandBatch = 16;  // loads per lane in flight while staging (hk_host_select_kernel.h)
-constexpr int kTreeExpandMaxDim = 7;
 
 struct TreeExpandArgs {
   const void* parents;  // [n_parents] records of in_stride elements; the state is the first m*d
@@ -41,9 +35,9 @@ __global__ void __launch_bounds__(kWave) tree_expand_kernel(TreeExpandArgs a) {
   T* lds = reinterpret_cast<T*>(hk_te_lds);
   const int lane = threadIdx.x;
   const int m = a.m, d = a.d, n = m * d;
-  const int64_t g0 = (int64_t)blockIdx.x * a.parents_per_block;
-  const int64_t left = (int64_t)a.n_parents - g0;
-  const int nparents = left < a.parents_per_block ? (int)left : a.parents_per_block;
+  const LaneBlock blk = lane_block(a.n_parents, a.parents_per_block);
+  const int64_t g0 = blk.g0;
+  const int nparents = blk.ngames;
   // the subsets first: a block none of whose parents is expanded reads no state
   uint32_t sub = 0u;
   int64_t first = 0;
@@ -54,11 +48,10 @@ __global__ void __launch_bounds__(kWave) tree_expand_kernel(TreeExpandArgs a) {
   }
   const int count = __popc(sub);
   if (__ballot(count > 0) == 0ull) return;
-  copy_slab<T, true, kTreeExpandBatch>(lds, const_cast<T*>(static_cast<const T*>(a.parents)), a.in_stride, n,
-                                       a.lds_stride, g0, nparents, lane);
+  stage_games(lds, a.parents, a.in_stride, n, a.lds_stride, blk, lane);
   __syncthreads();
   const LaneSlice<T> s(lds, lane < nparents ? lane : 0, a.lds_stride, m, d);
-  const unsigned flags = a.list ? (HK_SEM_LIST | HK_FLAG_COMPACT_SORTED) : HK_SEM_JAX;
+  const unsigned flags = a.list ? kListFlags : HK_SEM_JAX;
   const int len = n + (a.zero_tail ? d : 0);  // elements of a record that leave: the state, then c
   const int dg = kWave / len, de = kWave % len;
   bool overflow = false;
@@ -67,7 +60,7 @@ __global__ void __launch_bounds__(kWave) tree_expand_kernel(TreeExpandArgs a) {
     int slot = -1;  // where this lane's child of the round goes; -1: it has none, or no room
     if (count > r) {
       const int ax = nth_bit(sub, r);
-      for (int j = 0; j < d; ++j) s.c[j] = ((sub >> j) & 1u) ? (T)1 : (T)0;
+      subset_coeffs(s.c, sub, d);
       for (int e = 0; e < n; ++e) s.chd[e] = s.par[e];
       shift_game(s.chd, m, d, s.c, ax, (T)-1, flags);
       if (a.reposition) reposition_game(s.chd, m, d, (T)-1, flags);

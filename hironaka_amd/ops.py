@@ -83,6 +83,17 @@ def _state(points: torch.Tensor, name="points") -> Tuple[torch.Tensor, torch.dty
     return points.contiguous(), orig
 
 
+def _batch_spec(pts: torch.Tensor, spec: Optional[Tuple[int, int]]) -> Tuple[int, int, int, int]:
+    """(B, m, d, stride) of states given as [B, m, d], or as [B, stride] records together with spec=(m, d)"""
+    if pts.dim() == 3:
+        b, m, d = pts.shape
+        return b, m, d, m * d
+    if pts.dim() == 2 and spec is not None:
+        m, d = spec
+        return pts.shape[0], m, d, pts.shape[1]
+    raise ValueError("points must be [B, m, d], or [B, stride] together with spec=(m, d)")
+
+
 def _stream(t: torch.Tensor) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
@@ -123,14 +134,7 @@ def step(points: torch.Tensor, coords=None, axis=None, *, stages: int, flags: in
         four-lane step kernel, class-id coords; HironakaHipError(HK_ERR_UNSUPPORTED) otherwise).
     Returns {"points": [B, m, d] (or `out`), ...}."""
     pts, orig = _state(points)
-    if pts.dim() == 3:
-        b, m, d = pts.shape
-        in_stride = m * d
-    elif pts.dim() == 2 and spec is not None:
-        b, in_stride = pts.shape
-        m, d = spec
-    else:
-        raise ValueError("points must be [B, m, d], or [B, stride] together with spec=(m, d)")
+    b, m, d, in_stride = _batch_spec(pts, spec)
     dev = pts.device
     s = A.hk_step_desc()
     if out is None:
@@ -237,14 +241,7 @@ def rescale(points, padding_value: float = -1.0, sem: str = "jax", **kw) -> torc
 
 def _counts(points: torch.Tensor, spec, fn_name: str, out_dtype) -> torch.Tensor:
     pts, _ = _state(points)
-    if pts.dim() == 3:
-        b, m, d = pts.shape
-        stride = m * d
-    elif pts.dim() == 2 and spec is not None:
-        b, stride = pts.shape
-        m, d = spec
-    else:
-        raise ValueError("points must be [B, m, d], or [B, stride] together with spec=(m, d)")
+    b, m, d, stride = _batch_spec(pts, spec)
     out = torch.empty(b, dtype=out_dtype, device=pts.device)
     with torch.cuda.device(pts.device):
         check(getattr(lib(), fn_name)(pts.data_ptr(), stride, out.data_ptr(), b, m, d,
@@ -284,14 +281,7 @@ def zeillinger(points: torch.Tensor, sem: str = "jax", spec=None, force_generic:
     if sem not in ("jax", "list"):
         raise ValueError(f"sem must be 'jax' or 'list'. Got {sem}.")
     pts, _ = _state(points)
-    if pts.dim() == 3:
-        b, m, d = pts.shape
-        stride = m * d
-    elif pts.dim() == 2 and spec is not None:
-        b, stride = pts.shape
-        m, d = spec
-    else:
-        raise ValueError("points must be [B, m, d], or [B, stride] together with spec=(m, d)")
+    b, m, d, stride = _batch_spec(pts, spec)
     out = torch.empty(b, dtype=torch.int32, device=pts.device)
     flags = (A.SEMANTICS[sem] | (A.HK_FLAG_FORCE_GENERIC if force_generic else 0)
              | (A.HK_FLAG_FORCE_TEAM if force_team else 0))
@@ -301,9 +291,10 @@ def zeillinger(points: torch.Tensor, sem: str = "jax", spec=None, force_generic:
     return out
 
 
-HOSTS = {"all_coord": A.HK_HOST_ALL_COORD, "zeillinger": A.HK_HOST_ZEILLINGER,
-         "zeillinger_lex": A.HK_HOST_ZEILLINGER_LEX, "weak_spivakovsky": A.HK_HOST_WEAK_SPIVAKOVSKY,
-         "weak_spivakovsky_min_hitting": A.HK_HOST_MIN_HITTING}
+# the fixed hosts, under the two names their operators grew up with
+HOSTS = SEARCH_HOSTS = {"all_coord": A.HK_HOST_ALL_COORD, "zeillinger": A.HK_HOST_ZEILLINGER,
+                        "zeillinger_lex": A.HK_HOST_ZEILLINGER_LEX, "weak_spivakovsky": A.HK_HOST_WEAK_SPIVAKOVSKY,
+                        "weak_spivakovsky_min_hitting": A.HK_HOST_MIN_HITTING}
 
 
 def host_select(points: torch.Tensor, host: str, spec=None) -> torch.Tensor:
@@ -315,14 +306,7 @@ def host_select(points: torch.Tensor, host: str, spec=None) -> torch.Tensor:
     if host not in HOSTS:
         raise ValueError(f"host must be one of {sorted(HOSTS)}. Got {host!r}.")
     pts, _ = _state(points)
-    if pts.dim() == 3:
-        b, m, d = pts.shape
-        stride = m * d
-    elif pts.dim() == 2 and spec is not None:
-        b, stride = pts.shape
-        m, d = spec
-    else:
-        raise ValueError("points must be [B, m, d], or [B, stride] together with spec=(m, d)")
+    b, m, d, stride = _batch_spec(pts, spec)
     out = torch.empty(b, dtype=torch.int32, device=pts.device)
     with torch.cuda.device(pts.device):
         check(lib().hk_host_select(pts.data_ptr(), stride, out.data_ptr(), b, m, d, _TORCH2HK[pts.dtype], HOSTS[host],
@@ -335,14 +319,7 @@ def get_features(points: torch.Tensor, scale_observation: bool = True, padding_v
     """order_and_rescale (jax/util.py:186-197): [B, m*d] rows sorted descending, last coordinate
     primary, optionally rescaled first."""
     pts, orig = _state(points)
-    if pts.dim() == 3:
-        b, m, d = pts.shape
-        in_stride = m * d
-    elif pts.dim() == 2 and spec is not None:
-        b, in_stride = pts.shape
-        m, d = spec
-    else:
-        raise ValueError("points must be [B, m, d], or [B, stride] together with spec=(m, d)")
+    b, m, d, in_stride = _batch_spec(pts, spec)
     if out is None:
         out = torch.empty((b, m * d), dtype=pts.dtype, device=pts.device)
     elif (not out.is_cuda or out.dtype != pts.dtype or tuple(out.shape) != (b, m * d) or not out.is_contiguous()):
@@ -449,6 +426,42 @@ def reduce_counts(workspace: torch.Tensor, done_count: torch.Tensor, batch: int,
     return done_count
 
 
+def _rollout_counts(r: "A.hk_rollout_desc", res: Dict[str, torch.Tensor], batch: int, steps: int, dev: torch.device,
+                    flags: int, game_ids: Optional[torch.Tensor], done_count: Optional[torch.Tensor],
+                    defer_counts: bool, workspace: Optional[torch.Tensor]) -> int:
+    """What rollout and rollout_generated share ahead of their descriptors: game_ids, and where the finished-game counts
+    go -- deferred into the caller's workspace, or into done_count (a new one unless given), which then joins res.
+    Fills r.game_ids and r.done_count; returns the flags."""
+    if game_ids is not None:
+        _require_device(game_ids, "game_ids")
+        if (game_ids.dtype != torch.int32 or game_ids.shape != (batch,) or not game_ids.is_contiguous()
+                or game_ids.device != dev):
+            raise ValueError("game_ids must be a contiguous int32 [B] tensor on the device of the games")
+        r.game_ids = game_ids.data_ptr()
+    if defer_counts:
+        if workspace is None:
+            raise ValueError("defer_counts=True needs the caller's own workspace (ops.rollout_workspace)")
+        _require_device(workspace, "workspace")
+        flags |= A.HK_FLAG_DEFER_COUNTS
+    elif done_count is None:
+        done_count = torch.zeros(steps + 1, dtype=torch.int64, device=dev)
+    elif done_count.dtype != torch.int64 or done_count.numel() != steps + 1 or not done_count.is_cuda:
+        raise ValueError("done_count must be an int64 device tensor of steps+1 elements")
+    if done_count is not None:
+        res["done_count"] = done_count
+    r.done_count = done_count.data_ptr() if (done_count is not None and not defer_counts) else None
+    return flags
+
+
+def _rollout_launch(r: "A.hk_rollout_desc", dev: torch.device, defer_counts: bool,
+                    workspace: Optional[torch.Tensor]) -> None:
+    """hk_rollout on the filled descriptor, with the caller's workspace or this stream's own"""
+    with torch.cuda.device(dev):
+        ws = workspace if defer_counts else _workspace(dev, lib().hk_rollout_workspace_bytes(C.byref(r)))
+        r.workspace, r.workspace_bytes = ws.data_ptr(), ws.numel()
+        check(lib().hk_rollout(C.byref(r), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "hk_rollout")
+
+
 def rollout(points: torch.Tensor, steps: int, seed: int, *, game_offset: int = 0, step_offset: int = 0,
             host_policy: int = A.HK_HOST_RANDOM, agent_policy: int = A.HK_AGENT_RANDOM,
             stages: int = A.HK_STAGE_SHIFT | A.HK_STAGE_REPOSITION | A.HK_STAGE_NEWTON, flags: int = 0,
@@ -481,23 +494,8 @@ def rollout(points: torch.Tensor, steps: int, seed: int, *, game_offset: int = 0
                 or initial.device != dev):
             raise ValueError("initial must match points in shape, dtype, device and be contiguous")
     r = A.hk_rollout_desc()
-    if game_ids is not None:
-        _require_device(game_ids, "game_ids")
-        if game_ids.dtype != torch.int32 or game_ids.shape != (b,) or not game_ids.is_contiguous() or game_ids.device != dev:
-            raise ValueError("game_ids must be a contiguous int32 [B] tensor on the device of points")
-        r.game_ids = game_ids.data_ptr()
     res: Dict[str, torch.Tensor] = {}
-    if defer_counts:
-        if workspace is None:
-            raise ValueError("defer_counts=True needs the caller's own workspace (ops.rollout_workspace)")
-        _require_device(workspace, "workspace")
-        flags |= A.HK_FLAG_DEFER_COUNTS
-    elif done_count is None:
-        done_count = torch.zeros(steps + 1, dtype=torch.int64, device=dev)
-    elif done_count.dtype != torch.int64 or done_count.numel() != steps + 1 or not done_count.is_cuda:
-        raise ValueError("done_count must be an int64 device tensor of steps+1 elements")
-    if done_count is not None:
-        res["done_count"] = done_count
+    flags = _rollout_counts(r, res, b, steps, dev, flags, game_ids, done_count, defer_counts, workspace)
     for key in record:
         if key == "obs":
             res[key] = torch.empty((steps, b, m, d), dtype=points.dtype, device=dev)
@@ -513,7 +511,6 @@ def rollout(points: torch.Tensor, steps: int, seed: int, *, game_offset: int = 0
             raise ValueError(f"unknown record {key}")
     ptr = lambda k: res[k].data_ptr() if k in res else None
     r.points = points.data_ptr()
-    r.done_count = done_count.data_ptr() if (done_count is not None and not defer_counts) else None
     r.points_in = initial.data_ptr() if initial is not None else None
     r.obs_out, r.host_class_out, r.axis_out = ptr("obs"), ptr("host_class"), ptr("axis")
     r.done_out, r.reward_out, r.game_length_out = ptr("done"), ptr("reward"), ptr("game_length")
@@ -522,10 +519,7 @@ def rollout(points: torch.Tensor, steps: int, seed: int, *, game_offset: int = 0
     r.batch, r.max_points, r.dim, r.dtype, r.steps = b, m, d, _TORCH2HK[points.dtype], steps
     r.host_policy, r.agent_policy, r.stages, r.flags = host_policy, agent_policy, stages, flags | _forced_flags
     r.episodes = int(episodes)
-    ws = workspace if defer_counts else _workspace(dev, lib().hk_rollout_workspace_bytes(C.byref(r)))
-    r.workspace, r.workspace_bytes = ws.data_ptr(), ws.numel()
-    with torch.cuda.device(dev):
-        check(lib().hk_rollout(C.byref(r), _stream(points)), "hk_rollout")
+    _rollout_launch(r, dev, defer_counts, workspace)
     res["points"] = points
     return res
 
@@ -558,27 +552,12 @@ def rollout_generated(batch: int, spec: Tuple[int, int], steps: int, seed: int, 
         dtype = out.dtype
     r = A.hk_rollout_desc()
     res: Dict[str, torch.Tensor] = {}
-    if game_ids is not None:
-        _require_device(game_ids, "game_ids")
-        if game_ids.dtype != torch.int32 or game_ids.shape != (batch,) or not game_ids.is_contiguous():
-            raise ValueError("game_ids must be a contiguous int32 [B] tensor")
-        r.game_ids = game_ids.data_ptr()
-    if defer_counts:
-        if workspace is None:
-            raise ValueError("defer_counts=True needs the caller's own workspace (ops.rollout_workspace)")
-        flags |= A.HK_FLAG_DEFER_COUNTS
-    elif done_count is None:
-        done_count = torch.zeros(steps + 1, dtype=torch.int64, device=dev)
-    elif done_count.dtype != torch.int64 or done_count.numel() != steps + 1 or not done_count.is_cuda:
-        raise ValueError("done_count must be an int64 device tensor of steps+1 elements")
-    if done_count is not None:
-        res["done_count"] = done_count
+    flags = _rollout_counts(r, res, batch, steps, dev, flags, game_ids, done_count, defer_counts, workspace)
     for key in record:
         if key != "game_length":
             raise ValueError(f"rollout_generated records game_length only. Got {key}.")
         res[key] = torch.empty(batch, dtype=torch.int32, device=dev)
     r.points = out.data_ptr() if out is not None else None
-    r.done_count = done_count.data_ptr() if (done_count is not None and not defer_counts) else None
     r.game_length_out = res["game_length"].data_ptr() if "game_length" in res else None
     r.seed, r.game_offset, r.step_offset = seed, game_offset, step_offset
     r.padding_value, r.reward_sign = float(padding_value), 1.0
@@ -586,11 +565,7 @@ def rollout_generated(batch: int, spec: Tuple[int, int], steps: int, seed: int, 
     r.host_policy, r.agent_policy, r.stages, r.flags = host_policy, agent_policy, stages, flags | _forced_flags
     r.gen_max_value, r.gen_seed = int(max_value), int(seed if gen_seed is None else gen_seed)
     r.gen_stages, r.episodes = make_stages(False, reposition, newton, rescale), int(episodes)
-    with torch.cuda.device(dev):
-        ws = workspace if defer_counts else _workspace(dev, lib().hk_rollout_workspace_bytes(C.byref(r)))
-        r.workspace, r.workspace_bytes = ws.data_ptr(), ws.numel()
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        check(lib().hk_rollout(C.byref(r), stream), "hk_rollout")
+    _rollout_launch(r, dev, defer_counts, workspace)
     if out is not None:
         res["points"] = out
     return res
@@ -664,9 +639,6 @@ def has_fast_path(max_points: int, dim: int, dtype=torch.float32) -> bool:
     return bool(lib().hk_has_fast_path(max_points, dim, _TORCH2HK.get(dtype, -1)))
 
 
-SEARCH_HOSTS = {"zeillinger": A.HK_HOST_ZEILLINGER, "all_coord": A.HK_HOST_ALL_COORD,
-                "zeillinger_lex": A.HK_HOST_ZEILLINGER_LEX, "weak_spivakovsky": A.HK_HOST_WEAK_SPIVAKOVSKY,
-                "weak_spivakovsky_min_hitting": A.HK_HOST_MIN_HITTING}
 _SEARCH_WORKSPACE_BYTES = 4 << 30  # per launch; a larger batch runs as several launches
 
 
@@ -700,15 +672,17 @@ def _search_checks(points: torch.Tensor, host: str, max_depth: int, max_nodes: i
     return _search_roots(points)
 
 
-def _search_launch(fn, name: str, pts: torch.Tensor, host: str, params: tuple, per_root: int, outs: list) -> list:
-    """fn(points, batch, m, d, dtype, host, *params, workspace, workspace_bytes, *outs, stream) over the roots, in
-    chunks that share one workspace of at most _SEARCH_WORKSPACE_BYTES.  per_root == 0: the C entry refuses the
+def _search_launch(fn, name: str, pts: torch.Tensor, host: str, params: tuple, per_root: int, outs: list,
+                   extra: Sequence[torch.Tensor] = ()) -> list:
+    """fn(points, *extra, batch, m, d, dtype, host, *params, workspace, workspace_bytes, *outs, stream) over the roots,
+    in chunks that share one workspace of at most _SEARCH_WORKSPACE_BYTES.  per_root == 0: the C entry refuses the
     arguments; one call with batch 1 and no buffers raises its status.  outs: (shape, dtype, fill or None) of each
-    output, batch first, or None for an output not wanted; they are made once the arguments pass, and returned."""
+    output, batch first, or None for an output not wanted; they are made once the arguments pass, and returned.
+    extra: further inputs per root, batch first."""
     b, m, d = pts.shape
     head = (m, d, _TORCH2HK[pts.dtype], SEARCH_HOSTS[host], *params)
     if per_root == 0:
-        check(fn(None, 1, *head, None, 0, *([None] * len(outs)), None), name)
+        check(fn(*([None] * (1 + len(extra))), 1, *head, None, 0, *([None] * len(outs)), None), name)
     outs = [None if o is None else torch.empty(o[0], dtype=o[1], device=pts.device) if o[2] is None else
             torch.full(o[0], o[2], dtype=o[1], device=pts.device) for o in outs]
     chunk = max(1, min(b, _SEARCH_WORKSPACE_BYTES // max(per_root, 1)))
@@ -716,8 +690,8 @@ def _search_launch(fn, name: str, pts: torch.Tensor, host: str, params: tuple, p
         ws = torch.empty(per_root * chunk if b else 0, dtype=torch.uint8, device=pts.device)
         for lo in range(0, b, chunk):
             ptrs = [None if t is None else t[lo].data_ptr() for t in outs]
-            check(fn(pts[lo].data_ptr(), min(chunk, b - lo), *head, ws.data_ptr(), ws.numel(), *ptrs, _stream(pts)),
-                  name)
+            ins = [t[lo].data_ptr() for t in (pts, *extra)]
+            check(fn(*ins, min(chunk, b - lo), *head, ws.data_ptr(), ws.numel(), *ptrs, _stream(pts)), name)
     return outs
 
 
@@ -780,23 +754,10 @@ def search_morin_tree(points: torch.Tensor, weights: torch.Tensor, distinguished
     dist = distinguished.to(torch.int32).contiguous()
     lim = -1 if expand_limit is None else int(expand_limit)
     per_root = lib().hk_search_morin_tree_workspace_bytes(1, m, d, _TORCH2HK[pts.dtype], max_nodes, stack_nodes)
-    fn, name = lib().hk_search_morin_tree, "hk_search_morin_tree"
-    head = (m, d, _TORCH2HK[pts.dtype], SEARCH_HOSTS[host], lim, max_depth, max_nodes, stack_nodes)
-    n_out = 12
-    if per_root == 0:  # the C entry refuses the arguments: one call with batch 1 and no buffers raises its status
-        check(fn(None, None, None, 1, *head, None, 0, *([None] * n_out), None), name)
-    outs = ([torch.full((b, max_nodes), -1, dtype=torch.int32, device=pts.device) for _ in range(8)] +
-            [torch.full((b, max_nodes, d), -1, dtype=torch.int32, device=pts.device),
-             torch.full((b, max_nodes, m, d), -1, dtype=pts.dtype, device=pts.device) if states else None,
-             torch.zeros(b, dtype=torch.int32, device=pts.device), torch.zeros(b, dtype=torch.int32, device=pts.device)])
-    chunk = max(1, min(b, _SEARCH_WORKSPACE_BYTES // max(per_root, 1)))
-    with torch.cuda.device(pts.device):
-        ws = torch.empty(per_root * chunk if b else 0, dtype=torch.uint8, device=pts.device)
-        for lo in range(0, b, chunk):
-            ptrs = [None if t is None else t[lo].data_ptr() for t in outs]
-            check(fn(pts[lo].data_ptr(), wts[lo].data_ptr(), dist[lo].data_ptr(), min(chunk, b - lo), *head,
-                     ws.data_ptr(), ws.numel(), *ptrs, _stream(pts)), name)
-    return tuple(outs)
+    outs = ([((b, max_nodes), torch.int32, -1)] * 8 + [((b, max_nodes, d), torch.int32, -1)] +
+            [((b, max_nodes, m, d), pts.dtype, -1) if states else None] + [((b,), torch.int32, 0)] * 2)
+    return tuple(_search_launch(lib().hk_search_morin_tree, "hk_search_morin_tree", pts, host,
+                                (lim, max_depth, max_nodes, stack_nodes), per_root, outs, extra=(wts, dist)))
 
 
 MORIN_TIES = {"lowest": A.HK_MORIN_TIE_LOWEST, "highest": A.HK_MORIN_TIE_HIGHEST, "random": A.HK_MORIN_TIE_RANDOM}
@@ -827,6 +788,71 @@ def _records_overlap(x: torch.Tensor, y: torch.Tensor) -> bool:
         return False
     (x0, x1), (y0, y1) = span(x), span(y)
     return x0 < y1 and y0 < x1
+
+
+def _play_checks(points: torch.Tensor, host: Optional[str], max_steps: int, seed: int, game_offset: int,
+                 step_offset: int) -> None:
+    """what game_play and morin_play ask of their host, their counters and their points"""
+    if host is not None and host not in SEARCH_HOSTS:
+        raise ValueError(f"host must be None or one of {sorted(SEARCH_HOSTS)}. Got {host!r}.")
+    if not (0 <= max_steps < 2 ** 31 and 0 <= seed < 2 ** 64 and 0 <= game_offset < 2 ** 64
+            and 0 <= step_offset < 2 ** 32 - max_steps):
+        raise ValueError(f"need 0 <= max_steps < 2^31, seed and game_offset in [0, 2^64), step_offset + max_steps < 2^32. "
+                         f"Got {max_steps}, {seed}, {game_offset}, {step_offset}.")
+    _require_device(points, "points")
+    if points.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"points must be float32 or float64. Got {points.dtype}.")
+    if points.dim() != 3:
+        raise ValueError(f"points must be [B, max_points, dim]. Got shape {tuple(points.shape)}.")
+
+
+def _int_input(t: torch.Tensor, name: str, shape: tuple, dev: torch.device) -> None:
+    _require_device(t, name)
+    if t.dtype not in (torch.int32, torch.int64) or tuple(t.shape) != shape or t.device != dev:
+        raise ValueError(f"{name} must be an int32/int64 tensor of shape {shape} on the points' device. Got "
+                         f"{t.dtype} {tuple(t.shape)} on {t.device}.")
+
+
+def _forced_moves(classes: Optional[torch.Tensor], axes: Optional[torch.Tensor], host: Optional[str], batch: int,
+                  max_steps: int, dev: torch.device, clamp: bool) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """The forced classes / axes [B, max_steps] of game_play and morin_play as contiguous int32, None where not given.
+    The two differ in what a value beyond int32 becomes, on purpose.  game_play never synchronises, so it clamps: such a
+    value stays beyond every class and axis, and the game stops with "no move" as it would unclamped.  morin_play pays
+    one synchronisation for the range of its weights under validate=True and refuses such a value there with the rest,
+    so it converts as is (clamp=False)."""
+    moves = []
+    for t, name in ((classes, "classes"), (axes, "axes")):
+        if t is not None:
+            _int_input(t, name, (batch, max_steps), dev)
+            t = (t.clamp(-1, 2 ** 31 - 1) if clamp else t).to(torch.int32).contiguous()
+        moves.append(t)
+    if host is None and classes is None and max_steps > 0:
+        raise ValueError("without a host every move needs a forced class: pass classes.")
+    return moves[0], moves[1]
+
+
+def _play_records(points: torch.Tensor, out: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(src, dst) of game_play and morin_play: the [B, m, d] record tensors the launch reads and writes.  Games that are
+    contiguous records at any stride are used in place, any other view through a copy (_play_result copies dst back)."""
+    if out is not None:
+        _require_device(out, "out")
+        if out.shape != points.shape or out.dtype != points.dtype or out.device != points.device:
+            raise ValueError(f"out must match points: {tuple(points.shape)} {points.dtype} on {points.device}. Got "
+                             f"{tuple(out.shape)} {out.dtype} on {out.device}.")
+    src = points if _record_stride(points) is not None else points.contiguous()
+    dst = out if out is not None and _record_stride(out) is not None else torch.empty(
+        tuple(points.shape), dtype=points.dtype, device=points.device)
+    if _records_overlap(src, dst) and not (dst.data_ptr() == src.data_ptr() and dst.stride() == src.stride()):
+        src = src.clone()  # only an exact in-place call may share memory: workgroups write back while others still read
+    return src, dst
+
+
+def _play_result(out: Optional[torch.Tensor], dst: torch.Tensor) -> torch.Tensor:
+    """the final points where the caller wants them"""
+    if out is not None and dst is not out:
+        out.copy_(dst)
+        return out
+    return dst
 
 
 def _morin_range_error(weights: torch.Tensor, distinguished: torch.Tensor, classes: Optional[torch.Tensor],
@@ -868,50 +894,21 @@ def morin_play(points: torch.Tensor, weights: torch.Tensor, distinguished: torch
     ``points``.  validate=False skips the range checks of weights and distinguished, which cost a synchronisation.
     Returns MorinPlayResult(points, weights, distinguished, length, outcome, classes, axes); outcome holds the
     HK_MORIN_* codes of include/hironaka_hip.h (MORIN_OUTCOMES names them)."""
-    if host is not None and host not in SEARCH_HOSTS:
-        raise ValueError(f"host must be None or one of {sorted(SEARCH_HOSTS)}. Got {host!r}.")
     if tie not in MORIN_TIES or weight_rule not in MORIN_WEIGHT_RULES:
         raise ValueError(f"tie must be one of {sorted(MORIN_TIES)} and weight_rule one of {sorted(MORIN_WEIGHT_RULES)}. "
                          f"Got {tie!r}, {weight_rule!r}.")
-    if not (0 <= max_steps < 2 ** 31 and 0 <= seed < 2 ** 64 and 0 <= game_offset < 2 ** 64
-            and 0 <= step_offset < 2 ** 32 - max_steps):
-        raise ValueError(f"need 0 <= max_steps < 2^31, seed and game_offset in [0, 2^64), step_offset + max_steps < 2^32. "
-                         f"Got {max_steps}, {seed}, {game_offset}, {step_offset}.")
-    _require_device(points, "points")
-    if points.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"points must be float32 or float64. Got {points.dtype}.")
-    if points.dim() != 3:
-        raise ValueError(f"points must be [B, max_points, dim]. Got shape {tuple(points.shape)}.")
+    _play_checks(points, host, max_steps, seed, game_offset, step_offset)
     b, m, d = points.shape
     dev = points.device
-    ints = {}
-    for t, name, shape in ((weights, "weights", (b, d)), (distinguished, "distinguished", (b,)),
-                           (classes, "classes", (b, max_steps)), (axes, "axes", (b, max_steps))):
-        if t is None and name in ("classes", "axes"):
-            ints[name] = None
-            continue
-        _require_device(t, name)
-        if t.dtype not in (torch.int32, torch.int64) or tuple(t.shape) != shape or t.device != dev:
-            raise ValueError(f"{name} must be an int32/int64 tensor of shape {shape} on the points' device. Got "
-                             f"{t.dtype} {tuple(t.shape)} on {t.device}.")
-        ints[name] = t
-    if host is None and classes is None and max_steps > 0:
-        raise ValueError("without a host every move needs a forced class: pass classes.")
+    _int_input(weights, "weights", (b, d), dev)
+    _int_input(distinguished, "distinguished", (b,), dev)
+    c_in, a_in = _forced_moves(classes, axes, host, b, max_steps, dev, clamp=False)
     if validate and b:
-        refused = _morin_range_error(weights, distinguished, ints["classes"], ints["axes"], m, weight_rule)
+        refused = _morin_range_error(weights, distinguished, classes, axes, m, weight_rule)
         if refused:
             raise ValueError(refused)
-    ints = {k: None if t is None else t.to(torch.int32).contiguous() for k, t in ints.items()}
-    if out is not None:
-        _require_device(out, "out")
-        if out.shape != points.shape or out.dtype != points.dtype or out.device != dev:
-            raise ValueError(f"out must match points: {tuple(points.shape)} {points.dtype} on {dev}. Got "
-                             f"{tuple(out.shape)} {out.dtype} on {out.device}.")
-    src = points if _record_stride(points) is not None else points.contiguous()
-    dst = out if out is not None and _record_stride(out) is not None else torch.empty((b, m, d), dtype=points.dtype,
-                                                                                      device=dev)
-    if _records_overlap(src, dst) and not (dst.data_ptr() == src.data_ptr() and dst.stride() == src.stride()):
-        src = src.clone()  # only an exact in-place call may share memory: workgroups write back while others still read
+    w_in, d_in = weights.to(torch.int32).contiguous(), distinguished.to(torch.int32).contiguous()
+    src, dst = _play_records(points, out)
     new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
     w_out, d_out, length, outcome = new(b, d), new(b), new(b), new(b)
     c_out, a_out = (new(b, max_steps), new(b, max_steps)) if record else (None, None)
@@ -919,9 +916,9 @@ def morin_play(points: torch.Tensor, weights: torch.Tensor, distinguished: torch
     ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     q.points_in, q.points_out = src.data_ptr(), dst.data_ptr()
     q.in_stride, q.out_stride = _record_stride(src), _record_stride(dst)
-    q.weights_in, q.weights_out = ints["weights"].data_ptr(), w_out.data_ptr()
-    q.distinguished_in, q.distinguished_out = ints["distinguished"].data_ptr(), d_out.data_ptr()
-    q.class_in, q.axis_in, q.class_out, q.axis_out = ptr(ints["classes"]), ptr(ints["axes"]), ptr(c_out), ptr(a_out)
+    q.weights_in, q.weights_out = w_in.data_ptr(), w_out.data_ptr()
+    q.distinguished_in, q.distinguished_out = d_in.data_ptr(), d_out.data_ptr()
+    q.class_in, q.axis_in, q.class_out, q.axis_out = ptr(c_in), ptr(a_in), ptr(c_out), ptr(a_out)
     q.length_out, q.outcome_out = length.data_ptr(), outcome.data_ptr()
     q.seed, q.game_offset, q.step_offset = seed, game_offset, step_offset
     q.batch, q.max_points, q.dim, q.dtype = b, m, d, _TORCH2HK[points.dtype]
@@ -930,10 +927,7 @@ def morin_play(points: torch.Tensor, weights: torch.Tensor, distinguished: torch
     q.flags = A.HK_MORIN_REDUCE_ROOT if reduce_root else 0
     with torch.cuda.device(dev):
         check(lib().hk_search_morin_play(C.byref(q), _stream(points)), "hk_search_morin_play")
-    if out is not None and dst is not out:
-        out.copy_(dst)
-        dst = out
-    return MorinPlayResult(dst, w_out, d_out, length, outcome, c_out, a_out)
+    return MorinPlayResult(_play_result(out, dst), w_out, d_out, length, outcome, c_out, a_out)
 
 
 PLAY_AGENTS = {"random": A.HK_AGENT_RANDOM_LEGAL, "choose_first": A.HK_AGENT_CHOOSE_FIRST,
@@ -964,44 +958,15 @@ def game_play(points: torch.Tensor, *, host: Optional[str] = None, agent: str = 
     tensor.  It may be ``points`` itself (in place); an ``out`` that shares memory with ``points`` in any other way is
     served through a copy of ``points``.  Returns GamePlayResult(points, length, outcome, classes, axes); outcome holds
     the HK_PLAY_* codes of include/hironaka_hip_play.h (PLAY_OUTCOMES names them)."""
-    if host is not None and host not in SEARCH_HOSTS:
-        raise ValueError(f"host must be None or one of {sorted(SEARCH_HOSTS)}. Got {host!r}.")
     if agent not in PLAY_AGENTS:
         raise ValueError(f"agent must be one of {sorted(PLAY_AGENTS)}. Got {agent!r}.")
-    if not (0 <= max_steps < 2 ** 31 and 0 <= seed < 2 ** 64 and 0 <= game_offset < 2 ** 64
-            and 0 <= step_offset < 2 ** 32 - max_steps):
-        raise ValueError(f"need 0 <= max_steps < 2^31, seed and game_offset in [0, 2^64), step_offset + max_steps < 2^32. "
-                         f"Got {max_steps}, {seed}, {game_offset}, {step_offset}.")
     if value_threshold is not None and value_threshold != value_threshold:
         raise ValueError("value_threshold must be a number or None. Got NaN.")
-    _require_device(points, "points")
-    if points.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"points must be float32 or float64. Got {points.dtype}.")
-    if points.dim() != 3:
-        raise ValueError(f"points must be [B, max_points, dim]. Got shape {tuple(points.shape)}.")
+    _play_checks(points, host, max_steps, seed, game_offset, step_offset)
     b, m, d = points.shape
     dev = points.device
-    ints = {}
-    for t, name in ((classes, "classes"), (axes, "axes")):
-        if t is not None:
-            _require_device(t, name)
-            if t.dtype not in (torch.int32, torch.int64) or tuple(t.shape) != (b, max_steps) or t.device != dev:
-                raise ValueError(f"{name} must be an int32/int64 tensor of shape {(b, max_steps)} on the points' device. "
-                                 f"Got {t.dtype} {tuple(t.shape)} on {t.device}.")
-            t = t.clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
-        ints[name] = t
-    if host is None and classes is None and max_steps > 0:
-        raise ValueError("without a host every move needs a forced class: pass classes.")
-    if out is not None:
-        _require_device(out, "out")
-        if out.shape != points.shape or out.dtype != points.dtype or out.device != dev:
-            raise ValueError(f"out must match points: {tuple(points.shape)} {points.dtype} on {dev}. Got "
-                             f"{tuple(out.shape)} {out.dtype} on {out.device}.")
-    src = points if _record_stride(points) is not None else points.contiguous()
-    dst = out if out is not None and _record_stride(out) is not None else torch.empty((b, m, d), dtype=points.dtype,
-                                                                                      device=dev)
-    if _records_overlap(src, dst) and not (dst.data_ptr() == src.data_ptr() and dst.stride() == src.stride()):
-        src = src.clone()  # only an exact in-place call may share memory: workgroups write back while others still read
+    c_in, a_in = _forced_moves(classes, axes, host, b, max_steps, dev, clamp=True)
+    src, dst = _play_records(points, out)
     new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
     length, outcome = new(b), new(b)
     c_out, a_out = (new(b, max_steps), new(b, max_steps)) if record else (None, None)
@@ -1009,7 +974,7 @@ def game_play(points: torch.Tensor, *, host: Optional[str] = None, agent: str = 
     ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     q.points_in, q.points_out = src.data_ptr(), dst.data_ptr()
     q.in_stride, q.out_stride = _record_stride(src), _record_stride(dst)
-    q.class_in, q.axis_in, q.class_out, q.axis_out = ptr(ints["classes"]), ptr(ints["axes"]), ptr(c_out), ptr(a_out)
+    q.class_in, q.axis_in, q.class_out, q.axis_out = ptr(c_in), ptr(a_in), ptr(c_out), ptr(a_out)
     q.length_out, q.outcome_out = length.data_ptr(), outcome.data_ptr()
     q.seed, q.game_offset, q.step_offset = seed, game_offset, step_offset
     q.value_threshold = 0.0 if value_threshold is None else float(value_threshold)
@@ -1020,10 +985,7 @@ def game_play(points: torch.Tensor, *, host: Optional[str] = None, agent: str = 
                | (A.HK_PLAY_REDUCE_ROOT if reduce_root else 0) | (A.HK_PLAY_RESCALE_ROOT if rescale_root else 0))
     with torch.cuda.device(dev):
         check(lib().hk_game_play(C.byref(q), _stream(points)), "hk_game_play")
-    if out is not None and dst is not out:
-        out.copy_(dst)
-        dst = out
-    return GamePlayResult(dst, length, outcome, c_out, a_out)
+    return GamePlayResult(_play_result(out, dst), length, outcome, c_out, a_out)
 
 
 # ---- one move of a vectorised environment, resets included (hk_env_step) ---------------------------------------------

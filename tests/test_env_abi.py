@@ -103,5 +103,12 @@ def test_env_step_validation_without_gpu():
     q.points_out = q.points_in + 8
     assert L.hk_env_step(ctypes.byref(q), None) == A.HK_ERR_SHAPE
     q = _desc()
+    q.points_in = q.points_out + 8  # the input starts inside the output's span
+    assert L.hk_env_step(ctypes.byref(q), None) == A.HK_ERR_SHAPE
+    for dtype, off in ((A.HK_F64, 4), (A.HK_F32, 2)):  # a pointer misaligned for its type
+        q = _desc(dtype=dtype)
+        q.points_in = q.points_out = q.points_in + off
+        assert L.hk_env_step(ctypes.byref(q), None) == A.HK_ERR_ALIGN
+    q = _desc()
     q.step_count = q.step_count + 2
     assert L.hk_env_step(ctypes.byref(q), None) == A.HK_ERR_ALIGN

@@ -145,11 +145,16 @@ def test_argument_validation_without_gpu():
         assert call(**bad) == A.HK_ERR_NULL, bad
     base = ctypes.addressof(buf)
     assert call(children_out=base) == A.HK_ERR_SHAPE  # children over the parents
-    assert call(children_out=base + 4 * 20) == A.HK_ERR_SHAPE
+    assert call(children_out=base + 4 * 20) == A.HK_ERR_SHAPE  # the children start inside the parents' span
+    assert call(parents_in=ctypes.addressof(out) + 4 * 20) == A.HK_ERR_SHAPE  # the parents inside the children's span
+    assert call(children_out=base + 4 * 20, in_stride=40, out_stride=40) == A.HK_ERR_SHAPE  # interleaved records
+    assert call(children_out=base, out_stride=20) == A.HK_ERR_SHAPE  # the same pointer, different strides
+    assert call(in_stride=14, flags=0, out_stride=15) == A.HK_ERR_SHAPE
+    assert call(out_stride=17, children_out=base + 4 * 2048) == A.HK_ERR_SHAPE  # a stride below m*d + d with the zero tail
     iaddr = ctypes.addressof(ints)
     for bad in (dict(parents_in=base + 2), dict(children_out=ctypes.addressof(out) + 2), dict(class_id=iaddr + 2),
                 dict(child_offset=iaddr + 4), dict(child_axis=iaddr + 1), dict(status=iaddr + 3),
-                dict(dtype=A.HK_F64, parents_in=base + 4)):
+                dict(dtype=A.HK_F64, parents_in=base + 4), dict(dtype=A.HK_F64, children_out=ctypes.addressof(out) + 4)):
         assert call(**bad) == A.HK_ERR_ALIGN, bad
 
 

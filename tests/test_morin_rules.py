@@ -206,7 +206,12 @@ def test_argument_validation_without_gpu():
     for off in (8, 24 * 4 * 4 - 4):  # other than in place, the records of points_in and points_out do not overlap
         assert _call(L, offset=off, offset_of=("points_out",)) == A.HK_ERR_SHAPE
         assert _call(L, offset=off, offset_of=("points_in",)) == A.HK_ERR_SHAPE
+    # strided records that interleave without sharing an element
+    assert _call(L, offset=24 * 4, offset_of=("points_out",), in_stride=48, out_stride=48) == A.HK_ERR_SHAPE
+    assert _call(L, offset=24 * 4, offset_of=("points_in",), in_stride=48, out_stride=48) == A.HK_ERR_SHAPE
+    assert _call(L, out_stride=25) == A.HK_ERR_SHAPE  # the same pointer, different strides
     assert _call(L, offset=2) == A.HK_ERR_ALIGN
+    assert _call(L, offset=2, offset_of=("points_in", "points_out")) == A.HK_ERR_ALIGN
     assert _call(L, dtype=A.HK_F64, offset=4, offset_of=("points_in", "points_out")) == A.HK_ERR_ALIGN
     assert _call(L, offset=2, offset_of=("axis_out",)) == A.HK_ERR_ALIGN
     assert _call(L, batch=0, null=REQUIRED + OPTIONAL) == A.HK_OK

@@ -227,8 +227,10 @@ def test_argument_validation_without_gpu():
         assert call(**bad) == A.HK_ERR_NULL, bad
     base = ctypes.addressof(buf)
     # records that overlap without being the same buffer
-    assert call(points_out=base + 4 * 15) == A.HK_ERR_SHAPE
+    assert call(points_out=base + 4 * 15) == A.HK_ERR_SHAPE  # the output starts inside the input's span
+    assert call(points_in=base + 4 * 15) == A.HK_ERR_SHAPE  # the input starts inside the output's span
     assert call(points_out=base + 4 * 8, in_stride=16, out_stride=16) == A.HK_ERR_SHAPE
+    assert call(points_out=base + 4 * 15, in_stride=30, out_stride=30) == A.HK_ERR_SHAPE  # interleaved, no element shared
     for bad in (dict(points_in=base + 2, points_out=base + 2), dict(length_out=ctypes.addressof(ints) + 2),
                 dict(class_in=ctypes.addressof(ints) + 1), dict(axis_out=ctypes.addressof(ints) + 3),
                 dict(dtype=A.HK_F64, points_in=base + 4, points_out=base + 4)):
