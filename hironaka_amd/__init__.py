@@ -2,7 +2,8 @@
 __version__ = "0.1.0"
 
 _VEC_ENVS = ("HironakaHostVecEnv", "HironakaAgentVecEnv")
-__all__ = list(_VEC_ENVS) + ["ReplayBuffer"]
+_DQN = ("fit_network", "td_loss", "td_target", "update_target_net", "polyak_update", "zip_equal")
+__all__ = list(_VEC_ENVS) + ["ReplayBuffer"] + list(_DQN)
 
 
 def __getattr__(name):
@@ -13,4 +14,7 @@ def __getattr__(name):
     if name == "ReplayBuffer":
         from .replay_buffer import ReplayBuffer
         return ReplayBuffer
+    if name in _DQN:
+        from . import dqn
+        return getattr(dqn, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -85,6 +85,11 @@ HK_REPLAY_SAMPLES_DRAWN, HK_REPLAY_TICKET = 4, 5
 HK_REPLAY_STREAM = 4
 HK_REPLAY_TILE_ROWS = 128
 
+# hk_dqn_td / hk_polyak_update: rows per workgroup, the action limit, the bit of the status word; tensors per launch,
+# the bytes of one tensor a workgroup owns
+HK_DQN_TILE_ROWS, HK_DQN_MAX_ACTIONS, HK_DQN_BAD_ACTION = 256, 65536, 1
+HK_POLYAK_MAX_TENSORS, HK_POLYAK_CHUNK_BYTES = 64, 16384
+
 SEMANTICS = {"jax": HK_SEM_JAX, "torch": HK_SEM_TORCH, "list": HK_SEM_LIST}
 
 
@@ -309,6 +314,47 @@ class hk_replay_desc(C.Structure):
     ]
 
 
+class hk_dqn_td_desc(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p),
+        ("next_q", C.c_void_p),
+        ("actions", C.c_void_p),
+        ("rewards", C.c_void_p),
+        ("dones", C.c_void_p),
+        ("target", C.c_void_p),
+        ("row_loss", C.c_void_p),
+        ("dq", C.c_void_p),
+        ("loss", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("status", C.c_void_p),
+        ("q_stride", C.c_int64),
+        ("next_q_stride", C.c_int64),
+        ("dq_stride", C.c_int64),
+        ("gamma", C.c_double),
+        ("batch", C.c_int32),
+        ("num_actions", C.c_int32),
+        ("dtype", C.c_int32),
+        ("reserved_", C.c_int32),
+    ]
+
+
+class hk_polyak_tensor(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p),
+        ("dst", C.c_void_p),
+        ("numel", C.c_int64),
+    ]
+
+
+class hk_polyak_desc(C.Structure):
+    _fields_ = [
+        ("tensor", hk_polyak_tensor * HK_POLYAK_MAX_TENSORS),
+        ("tau", C.c_double),
+        ("ntensors", C.c_int32),
+        ("dtype", C.c_int32),
+    ]
+
+
 _vp, _i, _i64, _u32, _u64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
 
 # name -> (restype, argtypes) of every symbol the header declares.  `stream` is the trailing
@@ -396,13 +442,20 @@ REPLAY_PROTOTYPES = {
     "hk_replay_sample": (C.c_int, [C.POINTER(hk_replay_desc), _i, _u64, _vp, _vp]),
 }
 
+# the entry points of include/hironaka_hip_dqn.h: the device library's only, as above
+DQN_PROTOTYPES = {
+    "hk_dqn_td_workspace_bytes": (C.c_uint64, [_i]),
+    "hk_dqn_td": (C.c_int, [C.POINTER(hk_dqn_td_desc), _vp]),
+    "hk_polyak_update": (C.c_int, [C.POINTER(hk_polyak_desc), _vp]),
+}
+
 
 def bind(lib: C.CDLL, prototypes=None) -> None:
-    """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES, TREE_PROTOTYPES, ENV_PROTOTYPES
-    and REPLAY_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
+    """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES, TREE_PROTOTYPES, ENV_PROTOTYPES,
+    REPLAY_PROTOTYPES and DQN_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
     if prototypes is None:
         prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES, **TREE_PROTOTYPES, **ENV_PROTOTYPES,
-                      **REPLAY_PROTOTYPES}
+                      **REPLAY_PROTOTYPES, **DQN_PROTOTYPES}
     for name, (res, args) in prototypes.items():
         fn = getattr(lib, name)
         fn.restype = res

@@ -1216,6 +1216,184 @@ def replay_sample(ring_cols: Sequence[torch.Tensor], cursor: torch.Tensor, batch
     return list(out), index
 
 
+# ---- the DQN fit step: TD target + Huber loss + dQ in one launch, Polyak update of a parameter list in one ----------
+
+DQN_TILE_ROWS = A.HK_DQN_TILE_ROWS
+DqnTdResult = collections.namedtuple("DqnTdResult", "loss dq target row_loss status")
+_DQN_WORKSPACES: Dict[Tuple[torch.device, int], torch.Tensor] = {}
+_DQN_RETIRED_WORKSPACES: list = []  # outgrown buffers: a hipGraph captured earlier may still hold their address
+
+
+def dqn_td_workspace(batch: int, device) -> torch.Tensor:
+    """a zeroed workspace of the caller's own for dqn_td launches of up to `batch` rows (uint8; the ticket and one slot
+    per workgroup).  Launches that share one belong on one stream."""
+    need = int(lib().hk_dqn_td_workspace_bytes(int(batch)))
+    if need == 0:
+        raise ValueError(f"batch must be in [0, 2^31). Got {batch}.")
+    return torch.zeros(need, dtype=torch.uint8, device=device)
+
+
+def _dqn_workspace(dev: torch.device, batch: int) -> torch.Tensor:
+    """the per-(device, stream) workspace of dqn_td calls that bring none: launches on one stream follow each other, and
+    every launch leaves the ticket zero.  Inside a stream capture that has no workspace yet a fresh one is drawn from the
+    capture's own pool (its zero fill is captured with it) and not kept."""
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+    need = int(lib().hk_dqn_td_workspace_bytes(batch))
+    ws = _DQN_WORKSPACES.get(key)
+    if ws is None or ws.numel() < need:
+        if torch.cuda.is_current_stream_capturing():
+            return torch.zeros(need, dtype=torch.uint8, device=dev)
+        if ws is not None:
+            _DQN_RETIRED_WORKSPACES.append(ws)
+        ws = torch.zeros(max(need, 1 << 12), dtype=torch.uint8, device=dev)
+        _DQN_WORKSPACES[key] = ws
+    return ws
+
+
+def _dqn_rows(t: torch.Tensor, name: str, dtype=None) -> torch.Tensor:
+    """a [B, A] float32 / float64 block whose rows are contiguous (the rows themselves may be strided)"""
+    _require_device(t, name)
+    if t.dim() != 2 or t.dtype not in (torch.float32, torch.float64) or (dtype is not None and t.dtype != dtype):
+        raise TypeError(f"{name} must be a [B, A] {dtype or 'float32 or float64'} tensor. Got {t.dtype} "
+                        f"{tuple(t.shape)}.")
+    ok = (t.shape[1] == 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])
+    return t if ok else t.contiguous()
+
+
+def _dqn_stride(t: torch.Tensor) -> int:
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def _dqn_column(t: torch.Tensor, name: str, like: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """[B] or [B, 1], as ReplayBuffer.sample returns it, forced into the kernel's type"""
+    _require_device(t, name)
+    if t.device != like.device:
+        raise ValueError(f"{name} is on {t.device}, q on {like.device}")
+    if t.numel() != like.shape[0] or t.dim() not in (1, 2):
+        raise ValueError(f"{name} must be [B] or [B, 1] with B = {like.shape[0]}. Got {tuple(t.shape)}.")
+    t = t.reshape(-1)
+    if dtype == torch.uint8:
+        t = t.view(torch.uint8) if t.dtype == torch.bool else (t if t.dtype == torch.uint8 else (t != 0).view(torch.uint8))
+    elif t.dtype != dtype:
+        t = t.to(dtype)
+    return t.contiguous()
+
+
+def dqn_td(q: torch.Tensor, next_q: torch.Tensor, actions: torch.Tensor, rewards: torch.Tensor, dones: torch.Tensor,
+           gamma: float, *, workspace: Optional[torch.Tensor] = None, out: Optional[dict] = None,
+           want: Sequence[str] = ("target", "row_loss")) -> DqnTdResult:
+    """The 1-step TD target, the Huber loss and its gradient with respect to q in one launch (hk_dqn_td,
+    include/hironaka_hip_dqn.h; dqn_trainer.py:68-88 and the backward pass of its loss).
+
+    q, next_q: [B, A] float32 or float64, rows possibly strided; actions int32, rewards float32, dones bool, each [B] or
+    [B, 1] (other types are converted).  Returns DqnTdResult(loss [] , dq [B, A], target [B] or None, row_loss [B] or
+    None, status int32 [1]): `want` names the optional outputs, `out` may bring tensors for any of "loss", "dq",
+    "target", "row_loss", "status" (a status brought along is OR-ed into, not cleared).  An action outside [0, A) gives a
+    zero row and sets HK_DQN_BAD_ACTION in status.  workspace: dqn_td_workspace(...) of the caller's own; None: one per
+    device and stream.  Nothing here synchronises."""
+    q = _dqn_rows(q, "q")
+    next_q = _dqn_rows(next_q, "next_q", q.dtype)
+    if next_q.shape != q.shape or next_q.device != q.device:
+        raise ValueError(f"q and next_q must have one shape and device. Got {tuple(q.shape)} on {q.device} and "
+                         f"{tuple(next_q.shape)} on {next_q.device}.")
+    batch, nact = q.shape
+    if not (1 <= nact <= A.HK_DQN_MAX_ACTIONS and batch < 2 ** 31):
+        raise ValueError(f"A must be in [1, {A.HK_DQN_MAX_ACTIONS}] and B below 2^31. Got B = {batch}, A = {nact}.")
+    actions = _dqn_column(actions, "actions", q, torch.int32)
+    rewards = _dqn_column(rewards, "rewards", q, torch.float32)
+    dones = _dqn_column(dones, "dones", q, torch.uint8)
+    out = dict(out or {})
+    unknown = (set(out) | set(want)) - set(DqnTdResult._fields)
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    dev = q.device
+
+    def given(name, shape, dtype):
+        t = out.get(name)
+        if t is None:
+            return None
+        _require_device(t, name)
+        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev:
+            raise ValueError(f"out[{name!r}] must be {dtype} {shape} on {dev}. Got {t.dtype} {tuple(t.shape)}.")
+        return t
+
+    dq = given("dq", (batch, nact), q.dtype)
+    if dq is None:
+        dq = torch.empty((batch, nact), dtype=q.dtype, device=dev)
+    elif not ((nact == 1 or dq.stride(1) == 1) and (batch <= 1 or dq.stride(0) >= nact)):
+        raise ValueError(f"the rows of out['dq'] must each be contiguous. Got strides {dq.stride()}.")
+    loss = given("loss", (), q.dtype)
+    if loss is None:
+        loss = torch.full((), float("nan"), dtype=q.dtype, device=dev) if batch == 0 else \
+            torch.empty((), dtype=q.dtype, device=dev)
+    status = given("status", (1,), torch.int32)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    extra = {}
+    for name in ("target", "row_loss"):
+        t = given(name, (batch,), q.dtype)
+        if t is None and name in want:
+            t = torch.empty(batch, dtype=q.dtype, device=dev)
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"out[{name!r}] must be contiguous.")
+        extra[name] = t
+    if workspace is None:
+        workspace = _dqn_workspace(dev, batch)
+    else:
+        _require_device(workspace, "workspace")
+        if (workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != dev
+                or workspace.numel() < lib().hk_dqn_td_workspace_bytes(batch)):
+            raise ValueError("workspace must be what dqn_td_workspace(batch, device) returns (or a larger one).")
+    d = A.hk_dqn_td_desc()
+    d.q, d.next_q, d.actions, d.rewards, d.dones = (q.data_ptr(), next_q.data_ptr(), actions.data_ptr(),
+                                                    rewards.data_ptr(), dones.data_ptr())
+    d.target = extra["target"].data_ptr() if extra["target"] is not None else None
+    d.row_loss = extra["row_loss"].data_ptr() if extra["row_loss"] is not None else None
+    d.dq, d.loss, d.workspace, d.status = dq.data_ptr(), loss.data_ptr(), workspace.data_ptr(), status.data_ptr()
+    d.q_stride, d.next_q_stride, d.dq_stride = _dqn_stride(q), _dqn_stride(next_q), _dqn_stride(dq)
+    d.gamma, d.batch, d.num_actions, d.dtype = float(gamma), batch, nact, _TORCH2HK[q.dtype]
+    with torch.cuda.device(dev):
+        check(lib().hk_dqn_td(C.byref(d), _stream(q)), "hk_dqn_td")
+    return DqnTdResult(loss, dq, extra["target"], extra["row_loss"], status)
+
+
+def polyak_update(srcs: Sequence[torch.Tensor], dsts: Sequence[torch.Tensor], tau: float) -> None:
+    """dst = tau * src + (1 - tau) * dst for every pair, in place, HK_POLYAK_MAX_TENSORS pairs per launch
+    (hk_polyak_update: the reference's polyak_update, _borrowed_fn.py:25-49, to the bit: a rounded multiply, then a fused
+    multiply-add).  Every tensor is a contiguous float32 or float64 tensor on one HIP device, all of one dtype (anything
+    else is a TypeError); a pair has one number of elements.  Nothing here synchronises."""
+    srcs, dsts = list(srcs), list(dsts)
+    if len(srcs) != len(dsts):
+        raise ValueError(f"{len(srcs)} sources but {len(dsts)} destinations.")
+    if not srcs:
+        return
+    first = dsts[0]
+    _require_device(first, "dsts[0]")
+    dtype, dev = first.dtype, first.device
+    flat = []  # src, dst, numel of every pair: the descriptor's entries as they lie in memory
+    for k, (s, t) in enumerate(zip(srcs, dsts)):
+        for name, x in (("srcs", s), ("dsts", t)):
+            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dtype and x.device == dev
+                    and x.is_contiguous() and dtype in (torch.float32, torch.float64)):
+                _require_device(x, f"{name}[{k}]")
+                raise TypeError(f"every tensor must be a contiguous float32 or float64 tensor of one dtype on one "
+                                f"device ({dtype} on {dev}). {name}[{k}] is {x.dtype} on {x.device} with strides "
+                                f"{x.stride()}.")
+        n = s.numel()
+        if n != t.numel():
+            raise ValueError(f"pair {k}: {n} source elements but {t.numel()} destination elements.")
+        flat += (s.data_ptr(), t.data_ptr(), n)
+    per = 3 * A.HK_POLYAK_MAX_TENSORS
+    with torch.cuda.device(dev):
+        stream = _stream(first)
+        for at in range(0, len(flat), per):
+            part = flat[at:at + per]
+            d = A.hk_polyak_desc()
+            (C.c_int64 * len(part)).from_address(C.addressof(d))[:] = part  # d.tensor[k] = {src, dst, numel}
+            d.tau, d.ntensors, d.dtype = float(tau), len(part) // 3, _TORCH2HK[dtype]
+            check(lib().hk_polyak_update(C.byref(d), stream), "hk_polyak_update")
+
+
 # ---- one level of a game tree under any host (hk_tree_expand) -------------------------------------------------------
 
 TreeExpandResult = collections.namedtuple(

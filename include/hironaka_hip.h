@@ -629,5 +629,7 @@ int hk_search_morin_play(const hk_morin_play_desc* desc, void* stream);
 #include "hironaka_hip_env.h"
 /* within ABI 6: hk_replay_push / hk_replay_sample, likewise */
 #include "hironaka_hip_replay.h"
+/* within ABI 6: hk_dqn_td / hk_polyak_update, likewise */
+#include "hironaka_hip_dqn.h"
 
 #endif /* HIRONAKA_HIP_H */
