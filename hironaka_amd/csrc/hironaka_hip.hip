@@ -1,15 +1,8 @@
 // C ABI of libhironaka_hip.so (include/hironaka_hip.h): argument validation, kernel selection
 // and launch.  No allocation, no synchronisation, no exceptions; every entry point returns a
 // status code.  gfx950 only.
-#include "hk_fast_kernel.h"
-#include "hk_duo_kernel.h"
-#include "hk_quad_kernel.h"
-#include "hk_quadroll_kernel.h"
-#include "hk_quadgen_kernel.h"
-#include "hk_quadbin_kernel.h"
-#include "hk_team_kernel.h"
+#include "hk_select.h"
 #include "hk_search.h"
-#include "hk_generic_kernel.h"
 
 using namespace hk;
 
@@ -19,20 +12,6 @@ int check_spec(int batch, int m, int d, int dtype) {
   if (batch < 0 || m < 1 || d < 1 || d > kMaxDim) return HK_ERR_SHAPE;
   if ((int64_t)m * d > (1 << 20)) return HK_ERR_SHAPE;
   if (dtype != HK_F32 && dtype != HK_F64) return HK_ERR_UNSUPPORTED;
-  return HK_OK;
-}
-
-// LDS geometry of the generic kernel: odd per-game stride, as many games per wave as fit
-int plan_generic(Params& prm, int dtype) {
-  const int n = prm.m * prm.d;
-  int stride = n + prm.d;
-  stride |= 1;
-  const int64_t per_game = (int64_t)stride * (int64_t)elem_size(dtype);
-  int gpb = kWave;
-  while (gpb > 1 && per_game * gpb > kMaxLdsBytes) gpb >>= 1;
-  if (per_game * gpb > kMaxLdsBytes) return HK_ERR_UNSUPPORTED;
-  prm.lds_stride = stride;
-  prm.games_per_block = gpb;
   return HK_OK;
 }
 
@@ -47,10 +26,7 @@ int launch_generic_t(const Params& prm, hipStream_t stream) {
       return HK_ERR_LAUNCH;
     }
   }
-  const unsigned grid = (unsigned)(((int64_t)prm.batch + prm.games_per_block - 1) / prm.games_per_block);
-  launch_prepare();
-  hipLaunchKernelGGL(generic_kernel<T>, dim3(grid), dim3(kWave), lds, stream, prm);
-  return launch_status();
+  return launch_kernel(generic_kernel<T>, workgroups(prm.batch, prm.games_per_block), kWave, lds, stream, prm);
 }
 
 int launch_generic(Params& prm, int dtype, hipStream_t stream) {
@@ -60,132 +36,9 @@ int launch_generic(Params& prm, int dtype, hipStream_t stream) {
   return dtype == HK_F32 ? launch_generic_t<float>(prm, stream) : launch_generic_t<double>(prm, stream);
 }
 
-// ---- kernel selection -------------------------------------------------------------------------------------------------
-// `pick` alone decides which kernel serves a request (DESIGN.md §5 has the table).  The *_supported predicates of the
-// family headers say what a kernel CAN serve (shapes, alignment, semantics, mode, records); pick adds the testing flags
-// and the measured crossovers, and everything that launches or sizes a launch asks it.
-enum class Kernel { None, Quad, QuadRoll, QuadRollFused, QuadGen, QuadZeil, Duo, Fast, Team, Generic };
-
-constexpr unsigned kForceFlags = HK_FLAG_FORCE_GENERIC | HK_FLAG_FORCE_TEAM | HK_FLAG_FORCE_ONE_LANE |
-                                 HK_FLAG_FORCE_TWO_LANES | HK_FLAG_FORCE_FOUR_LANES;
-// read by pick only: cleared before a launcher sees the request (the compiled rollout configurations compare flags)
-constexpr unsigned kHostSideFlags = HK_FLAG_FORCE_ONE_LANE | HK_FLAG_FORCE_TWO_LANES | HK_FLAG_FORCE_FOUR_LANES;
-
-inline int64_t workgroups(int batch, int games_per_block) { return ((int64_t)batch + games_per_block - 1) / games_per_block; }
-
-// a generated / multi-episode rollout the fused kernel declines runs as hk_generate_points into `out` + one plain
-// rollout per episode from there
-Params plain_rollout(Params prm) {
-  prm.max_value = 0;
-  prm.episodes = 1;
-  if (!prm.in) prm.in = prm.out;
-  return prm;
-}
-
-// hk_zeillinger on the register-resident / team kernels: a step launch without stages and without a state output, whose
-// only product is class_out (both variants: the semantics code travels in the flags)
-Params zeillinger_step(Params prm) {
-  prm.mode = kModeStep;
-  prm.pad = -1.0;
-  return prm;
-}
-
-// The testing flags (HK_FLAG_FORCE_*) choose among the kernels that can serve a request, never change its result.
-// Precedence:
-//   GENERIC   the generic kernel, for every request;
-//   TEAM      the team kernel where it applies, else the generic kernel;
-//   then, on requests a kernel with a per-shape specialisation can serve:
-//   steps     FOUR_LANES: the four-lane kernel wherever it applies (over ONE_LANE / TWO_LANES); else ONE_LANE or TWO_LANES
-//             keep it out; then ONE_LANE: one lane per game (over TWO_LANES), TWO_LANES: two lanes wherever they apply;
-//   rollouts  ONE_LANE or TWO_LANES keep every four-lane kernel out (over FOUR_LANES), then as steps; FOUR_LANES: the
-//             four-lane kernel wherever it applies, the fused one without its residency rule;
-//   generator ONE_LANE or TWO_LANES keep the four-lane kernel out; FOUR_LANES changes nothing;
-//   hk_zeillinger: TEAM, ONE_LANE or TWO_LANES keep the four-lane kernel out; FOUR_LANES changes nothing.
-// Kernel::None: no kernel serves the request.
-Kernel pick(const Params& prm, int dtype) {
-  const unsigned f = prm.flags;
-  const bool generic = f & HK_FLAG_FORCE_GENERIC;
-  const bool shaped = !(f & (HK_FLAG_FORCE_GENERIC | HK_FLAG_FORCE_TEAM));  // the kernels with per-shape specialisations
-  const bool lanes = f & (HK_FLAG_FORCE_ONE_LANE | HK_FLAG_FORCE_TWO_LANES);
-  const bool four = f & HK_FLAG_FORCE_FOUR_LANES;
-  const int64_t quad_waves = workgroups(prm.batch, kQuadGames);
-  // measured (scripts/probe_duo.py): two lanes per game are ahead while the one-lane kernel (64 games per wave) leaves
-  // SIMDs short of a second wave -- up to 1.5 waves per SIMD, 98 304 games on the 1024 SIMDs of an MI355X -- and at any
-  // size for the shapes whose one-lane kernel runs one wave per SIMD
-  const auto duo_preferred = [&] {
-    return (int64_t)prm.batch * 2 <= (int64_t)3 * kWave * device_simds() || prm.m * prm.d > 64;
-  };
-
-  if (prm.mode == kModeZeillinger) {
-    if (generic) return Kernel::Generic;
-    // four lanes per game (the rollout kernel's prologue + its balanced pair loop) wherever that kernel exists: the JAX
-    // variant over contiguous 16-B aligned records ((20,3) x 65 536: 21.4 us on one lane per game, (20,4): 37.4)
-    if (shaped && !lanes && quadzeil_supported(prm, dtype)) return Kernel::QuadZeil;
-    const Params step = zeillinger_step(prm);
-    if (shaped && fast_supported(step, dtype)) return Kernel::Fast;
-    return team_supported(step, dtype) ? Kernel::Team : Kernel::Generic;
-  }
-
-  if (prm.mode == kModeRollout && (prm.max_value > 0 || prm.episodes > 1)) {
-    // generated initial states and / or several episodes as ONE launch (hk_quadroll_kernel.h: GEN, EPI)
-    if (shaped && !lanes) {
-      if (prm.max_value > 0) {
-        if (quadroll_gen_supported(prm, dtype)) return Kernel::QuadRollFused;
-      } else if (quadroll_episodes_supported(prm, dtype)) {
-        // episodes from the states in memory: where the waves of the launch are resident all at once (four per SIMD), a
-        // wave that starts its next episode early fills what the launch boundary left idle -- (20,3) x 65 536: 16.5 -
-        // 17.0 us per episode against 20.8 one launch each; beyond (131 072 games: 37 against 30 us; (50,4) x 262 144:
-        // 205 against 172 us, scripts/probe_persistent.py) the per-episode launches of the default kernels stay ahead
-        if (four || (prm.m <= 32 && quad_waves <= (int64_t)4 * device_simds())) return Kernel::QuadRollFused;
-      }
-    }
-    return pick(plain_rollout(prm), dtype);
-  }
-
-  // hk_step on four lanes per game: everywhere it applies (scripts/probe_crossover.py: ahead of the one-lane kernel
-  // from 32 768 to 524 288 games on (10,3), (20,3), (20,4) -- e.g. (20,3): 6.0 vs 11.3 us at 32 768, 44.9 vs 52.7 us at
-  // 524 288 -- and of the team kernel on (50,4): 94 vs 113 us at 262 144)
-  if (shaped && (four || !lanes) && quad_supported(prm, dtype)) return Kernel::Quad;
-  // hk_generate_points on four lanes per game: everywhere it applies
-  if (shaped && !lanes && quadgen_supported(prm, dtype)) return Kernel::QuadGen;
-  if (shaped && !lanes && quadroll_supported(prm, dtype)) {
-    // plain rollouts on four lanes per game: the shapes without a two-lane kernel ((50,4): hk::team_kernel's rollouts
-    // before) ... and, on the small shapes, batches of up to two of its waves per SIMD (32 768 games on an MI355X):
-    // measured (scripts/probe_rollout_families.py, (20,3)): 14.0 / 15.0 / 17.4 us per 20-step episode at 4 096 / 16 384 /
-    // 32 768 games against 16.9 / 18.3 / 18.8 on two lanes per game, 24.5 against 22.2 at 65 536
-    if (four || prm.m > 32) return Kernel::QuadRoll;
-    // Zeillinger's host: the two-lane kernel is ahead at every size it serves (scripts/probe_zeillinger.py, (20,3):
-    // 40.9 against 44.3 us at 32 768 games, 37.4 against 38.5 at 8 192, 44.2 against 57.0 at 65 536)
-    if (prm.host_policy != HK_HOST_ZEILLINGER) {
-      // Recording rollouts: at every size (scripts/probe_records.py, (20,3), per 20-step episode incl. the counter
-      // reduce: 39.8 against 48.6 us with the small records and 69.5 against 82.1 us with the observations at 65 536
-      // games, 90.6 / 240 against 114 / 279 us at 262 144) -- except that the small records without observations ride
-      // on the two-lane plain rollout too (hk_duo_kernel.h: flush_records): where that is the faster plain kernel it
-      // takes them (28.8 -> ~23 us at (20,3) x 65 536)
-      if (prm.obs_out) return Kernel::QuadRoll;
-      if (small_records(prm) && !(duo_supported(prm, dtype) && duo_preferred())) return Kernel::QuadRoll;
-      // short rollouts (measured at (20,3) x 65 536, scripts/probe_short_rollouts.py: 1 / 2 / 4 / 6 steps 8.2 / 10.0 /
-      // 12.3 / 14.4 us against the two-lane kernel's 9.6 / 11.5 / 13.6 / 15.0; level at 8 steps): the wave's shorter
-      // chain counts while the wide first steps are most of the launch
-      const int64_t simds = device_simds();
-      if (prm.steps <= 6 && quad_waves <= 4 * simds) return Kernel::QuadRoll;
-      if (quad_waves <= 2 * simds) return Kernel::QuadRoll;
-    }
-  }
-  // (the step's observation features, and the agent's move as an argmax of its logits, come from the four-lane kernel only)
-  if (prm.feat_out || ((prm.stages & HK_STAGE_SHIFT) && prm.axis_dtype == HK_AXIS_MASKED_LOGITS)) return Kernel::None;
-  if (shaped && fast_supported(prm, dtype)) {
-    const bool two = !(f & HK_FLAG_FORCE_ONE_LANE) && duo_supported(prm, dtype) &&
-                     ((f & HK_FLAG_FORCE_TWO_LANES) || duo_preferred());
-    return two ? Kernel::Duo : Kernel::Fast;
-  }
-  // the team kernel: f32, dim 2..6, <= 64 rows; the generic kernel: anything else (f64, dim > 6, > 64 rows, and the few
-  // mode / semantics combinations fast_supported / team_supported decline)
-  return !generic && team_supported(prm, dtype) ? Kernel::Team : Kernel::Generic;
-}
-
+// ---- kernel selection: hk_select.h ----------------------------------------------------------------------------------------
 int run(Kernel k, Params prm, int dtype, hipStream_t stream) {
-  prm.flags &= ~kHostSideFlags;
+  prm = as_launched(prm);
   switch (k) {
     case Kernel::Quad: return launch_quad(prm, stream);
     case Kernel::QuadRoll: return launch_quadroll(prm, stream);
@@ -204,32 +57,6 @@ int run(Kernel k, Params prm, int dtype, hipStream_t stream) {
 int launch(const Params& prm, int dtype, hipStream_t stream) {
   if (prm.batch == 0) return HK_OK;
   return run(pick(prm, dtype), prm, dtype, stream);
-}
-
-// workgroups of the launch that serves this rollout request (0: not launchable)
-int64_t planned_grid(Params prm, int dtype) {
-  if (prm.batch == 0) return 0;
-  switch (pick(prm, dtype)) {
-    case Kernel::QuadRoll:
-    case Kernel::QuadRollFused: return quadroll_grid(prm);
-    case Kernel::Duo: return workgroups(prm.batch, kDuoGames);
-    case Kernel::Fast: return workgroups(prm.batch, kWave);
-    case Kernel::Team: return workgroups(prm.batch, kTeamGames);
-    case Kernel::Generic: return plan_generic(prm, dtype) == HK_OK ? workgroups(prm.batch, prm.games_per_block) : 0;
-    default: return 0;
-  }
-}
-
-// row length of the finished-game workspace for a geometry: an upper bound of the grids of all the kernel
-// variants that may serve it (records, policies and semantics choose among them per launch)
-int64_t count_slots(Params prm, int dtype) {
-  if (prm.batch == 0) return 0;
-  int64_t slots = planned_grid(prm, dtype);
-  if (dtype == HK_F32 && prm.d >= 2 && prm.d <= 6 && prm.m <= kTeam * kTeamSlots)
-    slots = std::max<int64_t>(slots, workgroups(prm.batch, kTeamGames));
-  if (has_fast_path(prm.m, prm.d, dtype)) slots = std::max<int64_t>(slots, workgroups(prm.batch, kDuoGames));
-  if (plan_generic(prm, dtype) == HK_OK) slots = std::max<int64_t>(slots, workgroups(prm.batch, prm.games_per_block));
-  return slots;
 }
 
 int valid_coords_kind(int kind) {
@@ -401,26 +228,46 @@ int hk_rescale(const void* points_in, void* points_out, int batch, int max_point
   return hk_step(&s, stream);
 }
 
-int hk_get_dones(const void* points, int64_t stride, uint8_t* done_out, int batch, int max_points,
-                 int dim, int dtype, void* stream) {
+// hk_get_dones / hk_get_num_points: one of the two outputs each
+static int counts_entry(const void* points, int64_t stride, uint8_t* done_out, int32_t* num_points_out, int batch,
+                        int max_points, int dim, int dtype, void* stream) {
   int st = check_spec(batch, max_points, dim, dtype);
   if (st != HK_OK) return st;
   if (batch == 0) return HK_OK;
-  if (!points || !done_out) return HK_ERR_NULL;
+  if (!points || (!done_out && !num_points_out)) return HK_ERR_NULL;
   if (stride < (int64_t)max_points * dim) return HK_ERR_SHAPE;
-  if (!aligned(points, elem_size(dtype))) return HK_ERR_ALIGN;
-  return launch_counts(points, stride, done_out, nullptr, batch, max_points, dim, dtype, (hipStream_t)stream);
+  if (!aligned(points, elem_size(dtype)) || !aligned(num_points_out, 4)) return HK_ERR_ALIGN;
+  return launch_counts(points, stride, done_out, num_points_out, batch, max_points, dim, dtype, (hipStream_t)stream);
+}
+
+int hk_get_dones(const void* points, int64_t stride, uint8_t* done_out, int batch, int max_points,
+                 int dim, int dtype, void* stream) {
+  return counts_entry(points, stride, done_out, nullptr, batch, max_points, dim, dtype, stream);
 }
 
 int hk_get_num_points(const void* points, int64_t stride, int32_t* num_points_out, int batch,
                       int max_points, int dim, int dtype, void* stream) {
-  int st = check_spec(batch, max_points, dim, dtype);
-  if (st != HK_OK) return st;
-  if (batch == 0) return HK_OK;
-  if (!points || !num_points_out) return HK_ERR_NULL;
-  if (stride < (int64_t)max_points * dim) return HK_ERR_SHAPE;
-  if (!aligned(points, elem_size(dtype)) || !aligned(num_points_out, 4)) return HK_ERR_ALIGN;
-  return launch_counts(points, stride, nullptr, num_points_out, batch, max_points, dim, dtype, (hipStream_t)stream);
+  return counts_entry(points, stride, nullptr, num_points_out, batch, max_points, dim, dtype, stream);
+}
+
+// the request of hk_generate_points / hk_generate_points_binned
+static Params generate_params(void* points_out, int batch, int max_points, int dim, int max_value, uint64_t seed,
+                              uint64_t game_offset, uint32_t stages, double padding_value, uint32_t flags) {
+  Params prm{};
+  prm.out = points_out;
+  prm.out_stride = prm.in_stride = (int64_t)max_points * dim;
+  prm.coords_kind = HK_COORDS_NONE;
+  prm.seed = seed;
+  prm.game_offset = game_offset;
+  prm.max_value = max_value;
+  prm.pad = padding_value;
+  prm.batch = batch;
+  prm.m = max_points;
+  prm.d = dim;
+  prm.stages = stages;
+  prm.flags = flags;
+  prm.mode = kModeGenerate;
+  return prm;
 }
 
 int hk_generate_points(void* points_out, int batch, int max_points, int dim, int dtype,
@@ -434,22 +281,8 @@ int hk_generate_points(void* points_out, int batch, int max_points, int dim, int
   if (!aligned(points_out, elem_size(dtype))) return HK_ERR_ALIGN;
   if (stages & ~(HK_STAGE_REPOSITION | HK_STAGE_NEWTON | HK_STAGE_RESCALE)) return HK_ERR_UNSUPPORTED;
   if ((flags & HK_SEM_MASK) == HK_SEM_MASK) return HK_ERR_UNSUPPORTED;
-  Params prm{};
-  prm.out = points_out;
-  prm.out_stride = (int64_t)max_points * dim;
-  prm.in_stride = prm.out_stride;
-  prm.coords_kind = HK_COORDS_NONE;
-  prm.seed = seed;
-  prm.game_offset = game_offset;
-  prm.max_value = max_value;
-  prm.pad = padding_value;
-  prm.batch = batch;
-  prm.m = max_points;
-  prm.d = dim;
-  prm.stages = stages;
-  prm.flags = flags;
-  prm.mode = kModeGenerate;
-  return launch(prm, dtype, (hipStream_t)stream);
+  return launch(generate_params(points_out, batch, max_points, dim, max_value, seed, game_offset, stages, padding_value, flags),
+                dtype, (hipStream_t)stream);
 }
 
 // ---- games binned by live rows (hk_quadbin_kernel.h) -------------------------------------------------------------------
@@ -476,23 +309,9 @@ int hk_generate_points_binned(void* points_out, int32_t* game_ids_out, int32_t* 
   if (st != HK_OK || batch == 0) return st;
   if (max_value < 1) return HK_ERR_SHAPE;
   if (stages & ~(HK_STAGE_REPOSITION | HK_STAGE_NEWTON | HK_STAGE_RESCALE)) return HK_ERR_UNSUPPORTED;
-  Params prm{};
-  prm.out = points_out;
-  prm.out_stride = prm.in_stride = (int64_t)max_points * dim;
-  prm.coords_kind = HK_COORDS_NONE;
-  prm.seed = seed;
-  prm.game_offset = game_offset;
-  prm.max_value = max_value;
-  prm.pad = padding_value;
-  prm.batch = batch;
-  prm.m = max_points;
-  prm.d = dim;
-  prm.stages = stages;
-  prm.flags = flags;
-  prm.mode = kModeGenerate;
+  const Params prm = generate_params(points_out, batch, max_points, dim, max_value, seed, game_offset, stages, padding_value, flags);
   if (pick(prm, dtype) != Kernel::QuadGen) return HK_ERR_UNSUPPORTED;  // (the four-lane generator bins the games)
-  prm.flags &= ~kHostSideFlags;
-  return launch_quadbin(prm, nullptr, game_ids_out, num_points_out, (hipStream_t)stream);
+  return launch_quadbin(as_launched(prm), nullptr, game_ids_out, num_points_out, (hipStream_t)stream);
 }
 
 int hk_bin_by_live_rows(const void* points_in, void* points_out, int32_t* game_ids_out, int32_t* num_points_out, int batch,
@@ -718,9 +537,7 @@ int hk_search_expand_gather(const void* embeddings, const void* features, const 
   const int64_t node_stride = node_major ? (int64_t)batch * E64 : E64;
   if (batch == 0) return HK_OK;
   if (!embeddings || !features || !parent || !action || !obs_out || !agent_feat_out) return HK_ERR_NULL;
-  if (!aligned(embeddings, 4) || !aligned(features, 4) || !aligned(parent, 4) || !aligned(action, 4) ||
-      !aligned(obs_out, 4) || !aligned(agent_feat_out, 4))
-    return HK_ERR_ALIGN;
+  if (!all_aligned({embeddings, features, parent, action, obs_out, agent_feat_out}, 4)) return HK_ERR_ALIGN;
   return launch_expand_gather((const float*)embeddings, (const float*)features, parent, action, (float*)obs_out,
                               (float*)agent_feat_out, batch, num_nodes, max_points * dim, dim, game_stride, node_stride,
                               (hipStream_t)stream);
@@ -731,7 +548,7 @@ int hk_search_masked_argmax(const void* logits, const int32_t* action, int32_t* 
   if (batch < 0 || dim < 2 || dim > kMaxDim) return HK_ERR_SHAPE;
   if (batch == 0) return HK_OK;
   if (!logits || !action || !axis_out) return HK_ERR_NULL;
-  if (!aligned(logits, 4) || !aligned(action, 4) || !aligned(axis_out, 4)) return HK_ERR_ALIGN;
+  if (!all_aligned({logits, action, axis_out}, 4)) return HK_ERR_ALIGN;
   return launch_masked_argmax((const float*)logits, action, axis_out, batch, dim, (hipStream_t)stream);
 }
 
@@ -741,8 +558,7 @@ int hk_search_expand_scatter(const void* obs, const void* feat, const int32_t* n
   if (st != HK_OK) return st;
   if (batch == 0) return HK_OK;
   if (!obs || !feat || !node || !embeddings || !features) return HK_ERR_NULL;
-  if (!aligned(obs, 4) || !aligned(feat, 4) || !aligned(node, 4) || !aligned(embeddings, 4) || !aligned(features, 4))
-    return HK_ERR_ALIGN;
+  if (!all_aligned({obs, feat, node, embeddings, features}, 4)) return HK_ERR_ALIGN;
   return launch_expand_scatter((const float*)obs, (const float*)feat, node, (float*)embeddings, (float*)features,
                                batch, num_nodes, max_points * dim, (hipStream_t)stream);
 }
@@ -753,8 +569,7 @@ int hk_search_expand_gather_agent(const void* embeddings, const int32_t* parent,
   if (st != HK_OK) return st;
   if (batch == 0) return HK_OK;
   if (!embeddings || !parent || !points_out || !coords_out) return HK_ERR_NULL;
-  if (!aligned(embeddings, 4) || !aligned(parent, 4) || !aligned(points_out, 4) || !aligned(coords_out, 4))
-    return HK_ERR_ALIGN;
+  if (!all_aligned({embeddings, parent, points_out, coords_out}, 4)) return HK_ERR_ALIGN;
   return launch_expand_gather_agent((const float*)embeddings, parent, (float*)points_out, (float*)coords_out, batch,
                                     num_nodes, max_points * dim, dim, (hipStream_t)stream);
 }
@@ -768,8 +583,7 @@ int hk_search_expand_scatter_agent(const void* points, const void* feat, const v
   if (num_classes < 1 || (int64_t)num_classes > ((int64_t)1 << dim) - dim - 1) return HK_ERR_SHAPE;
   if (batch == 0) return HK_OK;
   if (!points || !feat || !host_logits || !node || !embeddings || !agent_feat_out) return HK_ERR_NULL;
-  if (!aligned(points, 4) || !aligned(feat, 4) || !aligned(host_logits, 4) || !aligned(node, 4) ||
-      !aligned(embeddings, 4) || !aligned(features, 4) || !aligned(agent_feat_out, 4) || !aligned(class_out, 4))
+  if (!all_aligned({points, feat, host_logits, node, embeddings, features, agent_feat_out, class_out}, 4))
     return HK_ERR_ALIGN;
   return launch_expand_scatter_agent((const float*)points, (const float*)feat, (const float*)host_logits, node,
                                      (float*)embeddings, (float*)features, (float*)agent_feat_out, class_out, batch,
@@ -780,7 +594,7 @@ int hk_search_mask_logits(const void* logits, const int32_t* class_id, void* out
   if (batch < 0 || dim < 2 || dim > kMaxDim) return HK_ERR_SHAPE;
   if (batch == 0) return HK_OK;
   if (!logits || !class_id || !out) return HK_ERR_NULL;
-  if (!aligned(logits, 4) || !aligned(class_id, 4) || !aligned(out, 4)) return HK_ERR_ALIGN;
+  if (!all_aligned({logits, class_id, out}, 4)) return HK_ERR_ALIGN;
   return launch_mask_logits((const float*)logits, class_id, (float*)out, batch, dim, (hipStream_t)stream);
 }
 
@@ -821,29 +635,28 @@ int hk_zeillinger(const void* points, int64_t stride, int32_t* class_out, int ba
   return run(k, (k == Kernel::Fast || k == Kernel::Team) ? zeillinger_step(prm) : prm, dtype, (hipStream_t)stream);
 }
 
-int hk_get_features(const void* points_in, int64_t in_stride, void* features_out,
-                    int64_t out_stride, int batch, int max_points, int dim, int dtype,
-                    int scale_observation, double padding_value, void* stream) {
-  hk_step_desc s = plain_desc(points_in, features_out, batch, max_points, dim, dtype, padding_value,
-                              (scale_observation ? HK_STAGE_RESCALE : 0u), HK_SEM_JAX);
+// hk_get_features / hk_get_features_torch: a step of at most the rescale whose output is the rows in feature order
+static int features_entry(hk_step_desc s, int64_t in_stride, int64_t out_stride, unsigned sort, void* stream) {
   s.in_stride = in_stride;
   s.out_stride = out_stride;
   Params prm{};
-  const int st = params_from_step(&s, prm, kStageFeatureSort);
+  const int st = params_from_step(&s, prm, sort);
   if (st != HK_OK) return st;
-  return launch(prm, dtype, (hipStream_t)stream);
+  return launch(prm, s.dtype, (hipStream_t)stream);
+}
+
+int hk_get_features(const void* points_in, int64_t in_stride, void* features_out,
+                    int64_t out_stride, int batch, int max_points, int dim, int dtype,
+                    int scale_observation, double padding_value, void* stream) {
+  return features_entry(plain_desc(points_in, features_out, batch, max_points, dim, dtype, padding_value,
+                                   (scale_observation ? HK_STAGE_RESCALE : 0u), HK_SEM_JAX),
+                        in_stride, out_stride, kStageFeatureSort, stream);
 }
 
 int hk_get_features_torch(const void* points_in, int64_t in_stride, void* features_out, int64_t out_stride,
                           int batch, int max_points, int dim, int dtype, double padding_value, void* stream) {
-  hk_step_desc s = plain_desc(points_in, features_out, batch, max_points, dim, dtype, padding_value,
-                              0u, HK_SEM_TORCH);
-  s.in_stride = in_stride;
-  s.out_stride = out_stride;
-  Params prm{};
-  const int st = params_from_step(&s, prm, kStageFeatureSort0);
-  if (st != HK_OK) return st;
-  return launch(prm, dtype, (hipStream_t)stream);
+  return features_entry(plain_desc(points_in, features_out, batch, max_points, dim, dtype, padding_value, 0u, HK_SEM_TORCH),
+                        in_stride, out_stride, kStageFeatureSort0, stream);
 }
 
 int hk_decode_host_class(const int32_t* class_in, void* mask_out, int mask_dtype, int batch,

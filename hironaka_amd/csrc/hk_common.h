@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "../../include/hironaka_hip.h"
 
 namespace hk {
@@ -111,15 +113,64 @@ inline bool small_records(const Params& prm) {
 }
 inline bool any_records(const Params& prm) { return prm.obs_out || small_records(prm); }
 inline bool small_records_only(const Params& prm) { return !prm.obs_out && small_records(prm); }
+// a step whose product is not the next state alone (class, sorted features, sorted output): kModeStepAux of the
+// one-lane and the team kernel
+inline bool step_aux(const Params& prm) {
+  return prm.class_out || (prm.stages & kStageFeatureSorts) || sorted_output(prm);
+}
+// the MODE template argument of the one-lane and the team kernel for a request (-1: none; hk_zeillinger comes as a step)
+inline int kernel_mode(const Params& prm) {
+  if (prm.mode == kModeStep) return step_aux(prm) ? kModeStepAux : (int)kModeStep;
+  return prm.mode == kModeRollout || prm.mode == kModeGenerate ? prm.mode : -1;
+}
 
 // hipGetLastError() is sticky per host thread and other users of the runtime in this process
 // (torch) leave benign errors behind: clear it right before a launch, read it right after.
 inline void launch_prepare() { (void)hipGetLastError(); }
 inline int launch_status() { return hipGetLastError() == hipSuccess ? HK_OK : HK_ERR_LAUNCH; }
+// every launch of the library: the kernel, its grid and block, dynamic LDS, the stream, the kernel's arguments
+template <typename... KArgs, typename... Args>
+int launch_kernel(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
+  launch_prepare();
+  hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+  return launch_status();
+}
+
+// workgroups of `games_per_block` games each that hold `batch` games
+inline int64_t workgroups(int64_t batch, int64_t games_per_block) { return (batch + games_per_block - 1) / games_per_block; }
+
+// SIMDs of the current device (4 per CU); queried once per device
+inline int device_simds() {
+  static int cached[16] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
+  if (!cached[dev]) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    (void)hipGetLastError();
+    cached[dev] = 4 * cus;
+  }
+  return cached[dev];
+}
+
+// ---- the tables of per-shape specialisations (HK_FAST_SPECS, HK_QUAD_SPECS: X-macros of (max_points, dim)) ------------
+// Every run-time (m, d) -> compile-time <M, D> step goes through a table's for_*_spec(m, d, none, f): f(Shape<M, D>())
+// of the entry (m, d), `none` where the table has none.
+template <int M_, int D_>
+struct Shape {
+  static constexpr int M = M_, D = D_;
+};
+#define HK_SHAPE_CASE(M_, D_) \
+  if (m == M_ && d == D_) return f(Shape<M_, D_>());
 
 // ---- argument checks of the C ABI entry points ---------------------------------------------------------------------
 inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 inline size_t elem_size(int dtype) { return dtype == HK_F64 ? 8 : 4; }
+inline bool all_aligned(std::initializer_list<const void*> ptrs, size_t a) {
+  for (const void* p : ptrs)
+    if (!aligned(p, a)) return false;
+  return true;
+}
 // a * b, 0 when that overflows 64 bits (workspace sizes: 0 means "too large")
 inline uint64_t checked_mul(uint64_t a, uint64_t b) { return b > 0 && a > UINT64_MAX / b ? 0 : a * b; }
 

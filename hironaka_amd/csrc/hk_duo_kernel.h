@@ -1361,24 +1361,36 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------
-// SIMDs of the current device (4 per CU); queried once per device
-inline int device_simds() {
-  static int cached[16] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-  if (!cached[dev]) {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    (void)hipGetLastError();
-    cached[dev] = 4 * cus;
+// The instantiation duo_kernel<M, D, mode, hot, acts, zeil> that serves a request (mode < 0: none)
+struct DuoVariant {
+  int mode = -1;
+  int hot = kHotNone;
+  bool acts = false;  // the small records ride on the plain rollout (flush_records)
+  bool zeil = false;
+  bool none() const { return mode < 0; }
+  constexpr int key() const { return mode < 0 ? -1 : ((mode * 8 + hot) * 2 + acts) * 2 + zeil; }
+};
+inline DuoVariant duo_variant(const Params& prm) {
+  if (prm.mode == kModeStep) {
+    // take_actions as the JAX trainer configures it (jax/util.py:83-125 with reposition, without rescale)
+    const bool hot = prm.flags == HK_SEM_JAX && prm.stages == (HK_STAGE_SHIFT | HK_STAGE_REPOSITION | HK_STAGE_NEWTON);
+    return {kModeStep, hot ? kHotJax : kHotNone};
   }
-  return cached[dev];
+  if (prm.mode != kModeRollout) return {};
+  if (prm.obs_out) return {kModeRolloutRec};
+  if (prm.host_policy == HK_HOST_ZEILLINGER) return {kModeRollout, kHotNone, false, true};
+  const int hot = fast_hot_config(prm);
+  // (the small records alone ride on the plain rollout kernels: ACTS)
+  if (small_records(prm)) return {kModeRollout, hot == kHotJax ? kHotJax : kHotNone, true};
+  return {kModeRollout, hot};
 }
+
+inline int64_t duo_grid(const Params& prm) { return workgroups(prm.batch, kDuoGames); }
 
 // steps and rollouts the two-lane kernel serves: those of a register-resident specialisation (fast_supported) of up to
 // 32 rows, without class / feature outputs
 inline bool duo_supported(const Params& prm, int dtype) {
-  if ((prm.mode != kModeRollout && prm.mode != kModeStep) || prm.m > 32) return false;
+  if (duo_variant(prm).none() || prm.m > 32) return false;
   if (prm.mode == kModeStep && (prm.class_out || (prm.stages & kStageFeatureSorts))) return false;
   // Zeillinger's host: plain rollouts (duo_kernel<..., ZEIL>); with records the one-lane kernel
   if (prm.mode == kModeRollout && prm.host_policy == HK_HOST_ZEILLINGER && any_records(prm)) return false;
@@ -1389,43 +1401,25 @@ inline bool duo_supported(const Params& prm, int dtype) {
 
 template <int M, int D>
 int launch_duo_t(Params prm, hipStream_t stream) {
-  const unsigned grid = (unsigned)(((int64_t)prm.batch + kDuoGames - 1) / kDuoGames);
   prm.games_per_block = kDuoGames;
-  launch_prepare();
-  // (the small records alone ride on the plain rollout kernels: ACTS)
-  const bool records = prm.obs_out != nullptr;
-  const bool acts = small_records_only(prm);
-  const int hot = (prm.mode == kModeRollout && !records) ? fast_hot_config(prm) : kHotNone;
-  if (prm.mode == kModeRollout && records)
-    hipLaunchKernelGGL((duo_kernel<M, D, kModeRolloutRec>), dim3(grid), dim3(kWave), 0, stream, (const float*)prm.in,
-                       prm.in_stride, prm.batch, prm);
-  else if (prm.mode == kModeRollout && prm.host_policy == HK_HOST_ZEILLINGER)
-    hipLaunchKernelGGL((duo_kernel<M, D, kModeRollout, kHotNone, false, true>), dim3(grid), dim3(kWave), 0, stream,
-                       (const float*)prm.in, prm.in_stride, prm.batch, prm);
-  else if (prm.mode == kModeRollout && acts && hot == kHotJax)
-    hipLaunchKernelGGL((duo_kernel<M, D, kModeRollout, kHotJax, true>), dim3(grid), dim3(kWave), 0, stream,
-                       (const float*)prm.in, prm.in_stride, prm.batch, prm);
-  else if (prm.mode == kModeRollout && acts)
-    hipLaunchKernelGGL((duo_kernel<M, D, kModeRollout, kHotNone, true>), dim3(grid), dim3(kWave), 0, stream,
-                       (const float*)prm.in, prm.in_stride, prm.batch, prm);
-  else if (prm.mode == kModeStep && prm.flags == HK_SEM_JAX &&
-           prm.stages == (HK_STAGE_SHIFT | HK_STAGE_REPOSITION | HK_STAGE_NEWTON))
-    // take_actions as the JAX trainer configures it (jax/util.py:83-125 with reposition, without rescale)
-    hipLaunchKernelGGL((duo_kernel<M, D, kModeStep, kHotJax>), dim3(grid), dim3(kWave), 0, stream,
-                       (const float*)prm.in, prm.in_stride, prm.batch, prm);
-  else if (prm.mode == kModeStep)
-    hipLaunchKernelGGL((duo_kernel<M, D, kModeStep>), dim3(grid), dim3(kWave), 0, stream, (const float*)prm.in,
-                       prm.in_stride, prm.batch, prm);
-  else if (hot == kHotJax)
-    hipLaunchKernelGGL((duo_kernel<M, D, kModeRollout, kHotJax>), dim3(grid), dim3(kWave), 0, stream,
-                       (const float*)prm.in, prm.in_stride, prm.batch, prm);
-  else if (hot == kHotTorch)
-    hipLaunchKernelGGL((duo_kernel<M, D, kModeRollout, kHotTorch>), dim3(grid), dim3(kWave), 0, stream,
-                       (const float*)prm.in, prm.in_stride, prm.batch, prm);
-  else
-    hipLaunchKernelGGL((duo_kernel<M, D, kModeRollout>), dim3(grid), dim3(kWave), 0, stream, (const float*)prm.in,
-                       prm.in_stride, prm.batch, prm);
-  return launch_status();
+  const auto go = [&](auto kernel) {
+    return launch_kernel(kernel, duo_grid(prm), kWave, 0, stream, (const float*)prm.in, prm.in_stride, prm.batch, prm);
+  };
+  constexpr auto key = [](int mode, int hot = kHotNone, bool acts = false, bool zeil = false) {
+    return DuoVariant{mode, hot, acts, zeil}.key();
+  };
+  switch (duo_variant(prm).key()) {  // one line per compiled instantiation
+    case key(kModeRolloutRec): return go(duo_kernel<M, D, kModeRolloutRec>);
+    case key(kModeRollout, kHotNone, false, true): return go(duo_kernel<M, D, kModeRollout, kHotNone, false, true>);
+    case key(kModeRollout, kHotJax, true): return go(duo_kernel<M, D, kModeRollout, kHotJax, true>);
+    case key(kModeRollout, kHotNone, true): return go(duo_kernel<M, D, kModeRollout, kHotNone, true>);
+    case key(kModeStep, kHotJax): return go(duo_kernel<M, D, kModeStep, kHotJax>);
+    case key(kModeStep): return go(duo_kernel<M, D, kModeStep>);
+    case key(kModeRollout, kHotJax): return go(duo_kernel<M, D, kModeRollout, kHotJax>);
+    case key(kModeRollout, kHotTorch): return go(duo_kernel<M, D, kModeRollout, kHotTorch>);
+    case key(kModeRollout): return go(duo_kernel<M, D, kModeRollout>);
+  }
+  return HK_ERR_UNSUPPORTED;  // (duo_variant names no other)
 }
 
 // instantiated next to the one-lane specialisations (hk_fast_spec.hip); the dispatcher lives in the main unit
@@ -1435,10 +1429,7 @@ HK_FAST_SPECS(HK_X)
 #undef HK_X
 
 inline int launch_duo(const Params& prm, hipStream_t stream) {
-#define HK_X(M_, D_) if (prm.m == M_ && prm.d == D_) return launch_duo_t<M_, D_>(prm, stream);
-  HK_FAST_SPECS(HK_X)
-#undef HK_X
-  return HK_ERR_UNSUPPORTED;
+  return for_fast_spec(prm.m, prm.d, (int)HK_ERR_UNSUPPORTED, [&](auto s) { return launch_duo_t<s.M, s.D>(prm, stream); });
 }
 #endif
 

@@ -760,12 +760,15 @@ __global__ __launch_bounds__(kWave, ((MODE == kModeRolloutRec || M * D > 64) ? 1
 #define HK_FAST_SPECS(X) X(4, 3) X(5, 3) X(10, 3) X(16, 3) X(20, 3) X(8, 4) X(20, 4)
 #endif
 
+// f(Shape<M, D>()) of the table's entry (m, d), `none` where it has none
+template <typename R, typename F>
+R for_fast_spec(int m, int d, R none, F&& f) {
+  HK_FAST_SPECS(HK_SHAPE_CASE)
+  return none;
+}
+
 inline int has_fast_path(int m, int d, int dtype) {
-  if (dtype != HK_F32) return 0;
-#define HK_X(M_, D_) if (m == M_ && d == D_) return 1;
-  HK_FAST_SPECS(HK_X)
-#undef HK_X
-  return 0;
+  return dtype == HK_F32 && for_fast_spec(m, d, false, [](auto) { return true; });
 }
 
 // vector slab I/O needs W-aligned records
@@ -789,29 +792,17 @@ inline int fast_hot_config(const Params& prm) {
   return kHotNone;
 }
 
-// The plain rollouts of a shape (three kernels: run-time configured, kHotJax, kHotTorch -- the staircase makes them the
-// longest to compile) live in a translation unit of their own (hk_fast_roll_spec.hip), the other modes in
-// hk_fast_spec.hip: the build's critical path halves.
-template <int M, int D>
-int launch_fast_roll_t(const Params& prm, unsigned grid, hipStream_t stream) {
-  const int hot = fast_hot_config(prm);
-  if (hot == kHotJax)
-    hipLaunchKernelGGL((fast_kernel<M, D, kModeRollout, kHotJax>), dim3(grid), dim3(kWave), 0, stream, (const float*)prm.in,
-                       prm.in_stride, prm.batch, prm.games_per_block, prm);
-  else if (hot == kHotTorch)
-    hipLaunchKernelGGL((fast_kernel<M, D, kModeRollout, kHotTorch>), dim3(grid), dim3(kWave), 0, stream, (const float*)prm.in,
-                       prm.in_stride, prm.batch, prm.games_per_block, prm);
-  else
-    hipLaunchKernelGGL((fast_kernel<M, D, kModeRollout>), dim3(grid), dim3(kWave), 0, stream, (const float*)prm.in,
-                       prm.in_stride, prm.batch, prm.games_per_block, prm);
-  return launch_status();
+// The instantiation fast_kernel<M, D, mode, hot> that serves a request (mode < 0: none).  fast_supported, the launchers
+// and the selection's grid all read this.
+struct FastVariant {
+  int mode = -1;
+  int hot = kHotNone;
+  bool none() const { return mode < 0; }
+};
+inline FastVariant fast_variant(const Params& prm) {
+  if (prm.mode != kModeRollout) return {kernel_mode(prm)};
+  return any_records(prm) ? FastVariant{kModeRolloutRec} : FastVariant{kModeRollout, fast_hot_config(prm)};
 }
-
-#ifndef HK_FAST_ROLL_TU
-#define HK_X(M_, D_) extern template int launch_fast_roll_t<M_, D_>(const Params&, unsigned, hipStream_t);
-HK_FAST_SPECS(HK_X)
-#undef HK_X
-#endif
 
 // One lane per game means one INSTRUCTION STREAM per 64 games; a wave's stream is latency-bound on its
 // own (~7.7 cycles per instruction measured, whether or not it shares its SIMD), so 65 536 games = 1024
@@ -819,42 +810,55 @@ HK_FAST_SPECS(HK_X)
 // games.  Putting fewer games in a wave (idle lanes, more waves) does not buy that back: measured at
 // 65 536 games, 64/32/16 games per wave give 50.4/50.7/84.8 us per 20-step rollout and 11.6/12.3/18.5 us
 // per hk_step, so a wave always takes 64 games.
+inline int64_t fast_grid(const Params& prm) { return workgroups(prm.batch, kWave); }
+
+template <int M, int D, int MODE, int HOT = kHotNone>
+int launch_fast_k(const Params& prm, hipStream_t stream) {
+  return launch_kernel(fast_kernel<M, D, MODE, HOT>, fast_grid(prm), kWave, 0, stream, (const float*)prm.in, prm.in_stride,
+                       prm.batch, prm.games_per_block, prm);
+}
+
+// The plain rollouts of a shape (three kernels: run-time configured, kHotJax, kHotTorch -- the staircase makes them the
+// longest to compile) live in a translation unit of their own (hk_fast_roll_spec.hip), the other modes in
+// hk_fast_spec.hip: the build's critical path halves.
+template <int M, int D>
+int launch_fast_roll_t(const Params& prm, int hot, hipStream_t stream) {
+  switch (hot) {  // one line per compiled instantiation
+    case kHotJax: return launch_fast_k<M, D, kModeRollout, kHotJax>(prm, stream);
+    case kHotTorch: return launch_fast_k<M, D, kModeRollout, kHotTorch>(prm, stream);
+    default: return launch_fast_k<M, D, kModeRollout>(prm, stream);
+  }
+}
+
+#ifndef HK_FAST_ROLL_TU
+#define HK_X(M_, D_) extern template int launch_fast_roll_t<M_, D_>(const Params&, int, hipStream_t);
+HK_FAST_SPECS(HK_X)
+#undef HK_X
+#endif
+
 template <int M, int D>
 int launch_fast_t(Params prm, hipStream_t stream) {
   prm.games_per_block = kWave;
-  const unsigned grid = (unsigned)(((int64_t)prm.batch + kWave - 1) / kWave);
-  launch_prepare();
-  if (prm.mode == kModeStep && (prm.class_out || (prm.stages & kStageFeatureSorts) || sorted_output(prm)))
-    hipLaunchKernelGGL((fast_kernel<M, D, kModeStepAux>), dim3(grid), dim3(kWave), 0, stream, (const float*)prm.in,
-                       prm.in_stride, prm.batch, prm.games_per_block, prm);
-  else if (prm.mode == kModeStep)
-    hipLaunchKernelGGL((fast_kernel<M, D, kModeStep>), dim3(grid), dim3(kWave), 0, stream, (const float*)prm.in,
-                       prm.in_stride, prm.batch, prm.games_per_block, prm);
-  else if (prm.mode == kModeRollout && any_records(prm))
-    hipLaunchKernelGGL((fast_kernel<M, D, kModeRolloutRec>), dim3(grid), dim3(kWave), 0, stream, (const float*)prm.in,
-                       prm.in_stride, prm.batch, prm.games_per_block, prm);
-  else if (prm.mode == kModeRollout)
-    return launch_fast_roll_t<M, D>(prm, grid, stream);
-  else
-    hipLaunchKernelGGL((fast_kernel<M, D, kModeGenerate>), dim3(grid), dim3(kWave), 0, stream, (const float*)prm.in,
-                       prm.in_stride, prm.batch, prm.games_per_block, prm);
-  return launch_status();
+  const FastVariant v = fast_variant(prm);
+  switch (v.mode) {  // one line per compiled instantiation
+    case kModeStepAux: return launch_fast_k<M, D, kModeStepAux>(prm, stream);
+    case kModeStep: return launch_fast_k<M, D, kModeStep>(prm, stream);
+    case kModeRolloutRec: return launch_fast_k<M, D, kModeRolloutRec>(prm, stream);
+    case kModeRollout: return launch_fast_roll_t<M, D>(prm, v.hot, stream);
+    default: return launch_fast_k<M, D, kModeGenerate>(prm, stream);
+  }
 }
 
 // can a register-resident specialisation serve this request?
 inline bool fast_supported(const Params& prm, int dtype) {
-  if (dtype != HK_F32) return false;
+  if (dtype != HK_F32 || fast_variant(prm).none()) return false;
   // sorted + compacted output (list semantics): not from the generator, and not under Zeillinger's host,
   // whose tie-breaks follow the physical row order
   if (sorted_output(prm) && (prm.mode == kModeGenerate ||
                              (prm.mode == kModeRollout && prm.host_policy == HK_HOST_ZEILLINGER)))
     return false;
   if ((prm.stages & kStageFeatureSorts) && prm.mode != kModeStep) return false;
-  if (prm.mode == kModeZeillinger) return false;
-#define HK_X(M_, D_) if (prm.m == M_ && prm.d == D_) return fast_aligned_t<M_, D_>(prm);
-  HK_FAST_SPECS(HK_X)
-#undef HK_X
-  return false;
+  return for_fast_spec(prm.m, prm.d, false, [&](auto s) { return fast_aligned_t<s.M, s.D>(prm); });
 }
 
 // Each (max_points, dim) specialisation is compiled in its own translation unit (hk_fast_spec.hip, built
@@ -866,10 +870,7 @@ HK_FAST_SPECS(HK_X)
 #undef HK_X
 
 inline int launch_fast(const Params& prm, hipStream_t stream) {
-#define HK_X(M_, D_) if (prm.m == M_ && prm.d == D_) return launch_fast_t<M_, D_>(prm, stream);
-  HK_FAST_SPECS(HK_X)
-#undef HK_X
-  return HK_ERR_UNSUPPORTED;
+  return for_fast_spec(prm.m, prm.d, (int)HK_ERR_UNSUPPORTED, [&](auto s) { return launch_fast_t<s.M, s.D>(prm, stream); });
 }
 #endif
 
@@ -919,10 +920,8 @@ __global__ __launch_bounds__(256) void count_reduce_kernel(uint32_t* ws, int nbl
 
 inline int launch_count_reduce(uint32_t* ws, int nblocks, int steps, unsigned long long* done_count,
                                hipStream_t stream) {
-  launch_prepare();
-  hipLaunchKernelGGL(count_reduce_kernel, dim3(steps + 1, (nblocks + kCountSeg - 1) / kCountSeg), dim3(256), 0,
+  return launch_kernel(count_reduce_kernel, dim3(steps + 1, (nblocks + kCountSeg - 1) / kCountSeg), dim3(256), 0,
                      stream, ws, nblocks, done_count);
-  return launch_status();
 }
 
 // ---- small utility kernels ------------------------------------------------------------------------
@@ -941,15 +940,10 @@ __global__ void counts_kernel(const T* points, int64_t stride, uint8_t* done_out
 
 inline int launch_counts(const void* points, int64_t stride, uint8_t* done_out, int32_t* num_out,
                          int batch, int m, int d, int dtype, hipStream_t stream) {
-  const unsigned grid = (unsigned)((batch + 255) / 256);
-  launch_prepare();
+  const int64_t grid = workgroups(batch, 256);
   if (dtype == HK_F32)
-    hipLaunchKernelGGL(counts_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)points,
-                       stride, done_out, num_out, batch, m, d);
-  else
-    hipLaunchKernelGGL(counts_kernel<double>, dim3(grid), dim3(256), 0, stream, (const double*)points,
-                       stride, done_out, num_out, batch, m, d);
-  return launch_status();
+    return launch_kernel(counts_kernel<float>, grid, 256, 0, stream, (const float*)points, stride, done_out, num_out, batch, m, d);
+  return launch_kernel(counts_kernel<double>, grid, 256, 0, stream, (const double*)points, stride, done_out, num_out, batch, m, d);
 }
 
 __global__ void decode_kernel(const int32_t* cls, void* mask_out, int mask_dtype, int batch, int d) {
@@ -971,11 +965,7 @@ __global__ void decode_kernel(const int32_t* cls, void* mask_out, int mask_dtype
 
 inline int launch_decode(const int32_t* cls, void* mask_out, int mask_dtype, int batch, int d,
                          hipStream_t stream) {
-  const int64_t total = (int64_t)batch * d;
-  const unsigned grid = (unsigned)((total + 255) / 256);
-  launch_prepare();
-  hipLaunchKernelGGL(decode_kernel, dim3(grid), dim3(256), 0, stream, cls, mask_out, mask_dtype, batch, d);
-  return launch_status();
+  return launch_kernel(decode_kernel, workgroups((int64_t)batch * d, 256), 256, 0, stream, cls, mask_out, mask_dtype, batch, d);
 }
 
 #endif  // HK_SPEC_TU

@@ -6,5 +6,5 @@
 
 namespace hk {
 static_assert(HK_SPEC_M * HK_SPEC_D > 0, "build with -DHK_SPEC_M=<max_points> -DHK_SPEC_D=<dim>");
-template int launch_fast_roll_t<HK_SPEC_M, HK_SPEC_D>(const Params&, unsigned, hipStream_t);
+template int launch_fast_roll_t<HK_SPEC_M, HK_SPEC_D>(const Params&, int, hipStream_t);
 }  // namespace hk

@@ -15,8 +15,6 @@
 // leaves (hk_game_play and hk_search_morin_play), and the argument checks the C entries share.
 #pragma once
 
-#include <initializer_list>
-
 #include "hk_generic_kernel.h"
 #include "hk_hosts.h"
 #include "hk_search_wave.h"
@@ -183,12 +181,6 @@ inline bool records_overlap(const void* in, int64_t in_stride, int64_t in_count,
   const uint64_t in_bytes = ((uint64_t)(in_count - 1) * (uint64_t)in_stride + (uint64_t)in_len) * elem_size;
   const uint64_t out_bytes = ((uint64_t)(out_count - 1) * (uint64_t)out_stride + (uint64_t)out_len) * elem_size;
   return i0 < o0 + out_bytes && o0 < i0 + in_bytes;
-}
-
-inline bool all_aligned(std::initializer_list<const void*> ptrs, size_t a) {
-  for (const void* p : ptrs)
-    if (!aligned(p, a)) return false;
-  return true;
 }
 
 // with_fixed_host for "a fixed host, or this one extra code": f(T(), other) when host is other's value

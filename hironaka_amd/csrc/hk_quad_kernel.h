@@ -1521,82 +1521,121 @@ constexpr int quad_waves_per_block() {
   return (G::kRegion * 4 * 4 + 4 * kQuadGames * D * 4 <= 64 * 1024) ? 4 : 1;
 }
 
-template <int M, int D, int WPB, int HOT, int ACT, bool FEAT = false>
-void launch_quad_k(const Params& prm, unsigned grid, hipStream_t stream) {
+// (max_points, dim) with a four-lane step kernel
+#ifndef HK_QUAD_SPECS
+#define HK_QUAD_SPECS(X) X(10, 3) X(20, 3) X(20, 4) X(50, 4)
+#endif
+
+// f(Shape<M, D>()) of the table's entry (m, d), `none` where it has none
+template <typename R, typename F>
+R for_quad_spec(int m, int d, R none, F&& f) {
+  HK_QUAD_SPECS(HK_SHAPE_CASE)
+  return none;
+}
+
+// the agent's logits and the features beside the state exist for the small games of at most four coordinates
+template <int M, int D>
+constexpr bool quad_small() {
+  return D <= kQuad && !QuadGeom<M, D>::kBig;
+}
+
+// what the host side knows of a shape of the table (known = false: not in it)
+struct QuadShape {
+  bool known = false;
+  int n = 0, w = 0;  // floats of a record, of a slab chunk
+  bool big = false, small = false;
+  bool tall = false;  // more than 32 rows: no one- or two-lane kernel, the rollout kernel plays Zeillinger's host too
+  int wpb = 0;        // waves per workgroup of the step kernel and the generator
+};
+inline QuadShape quad_shape(int m, int d) {
+  return for_quad_spec(m, d, QuadShape{}, [](auto s) {
+    using G = QuadGeom<s.M, s.D>;
+    return QuadShape{true, G::N, G::W, G::kBig, quad_small<s.M, s.D>(), (s.M > 32), quad_waves_per_block<s.M, s.D>()};
+  });
+}
+
+// float32, contiguous W-aligned records; the slabs stored beside the state (a step's features, a rollout's
+// observations) go out in the same W-wide chunks
+inline bool quad_layout_ok(const Params& prm, const QuadShape& q) {
+  if (!q.known) return false;
+  const size_t vec_bytes = q.w * 4;
+  return prm.in_stride == q.n && prm.out_stride == q.n && reinterpret_cast<uintptr_t>(prm.in) % vec_bytes == 0 &&
+         reinterpret_cast<uintptr_t>(prm.out) % vec_bytes == 0 &&
+         reinterpret_cast<uintptr_t>(prm.feat_out) % vec_bytes == 0 &&
+         reinterpret_cast<uintptr_t>(prm.obs_out) % vec_bytes == 0;
+}
+
+// The instantiation quad_kernel<M, D, hot, WPB, act, feat> that serves a step request (hot < 0: none)
+struct QuadVariant {
+  int hot = -1;
+  int act = kActAny;
+  bool feat = false;
+  bool none() const { return hot < 0; }
+  constexpr int key() const { return hot < 0 ? -1 : (hot * 8 + act) * 2 + feat; }
+};
+inline QuadVariant quad_variant(const Params& prm, const QuadShape& q) {
+  if (!q.known) return {};
+  const bool hot = prm.flags == HK_SEM_JAX && prm.stages == (HK_STAGE_SHIFT | HK_STAGE_REPOSITION | HK_STAGE_NEWTON);
+  const int act = quad_act_of(prm);
+  if (act == kActClassI32Logits && !q.small) return {};
+  if (prm.feat_out) {
+    // the step + features launch of the search's expansion: class-id subsets with an int32 axis or the agent's logits
+    // (or, in the JAX trainer's configuration, a float mask with an int32 axis), no sorted output, small games
+    const bool plain = !(prm.stages & kStageFeatureSorts) && (prm.flags & HK_SEM_MASK) != HK_SEM_LIST &&
+                       !(prm.flags & HK_FLAG_COMPACT_SORTED);
+    if (!q.small || !plain) return {};
+    if (act == kActClassI32Logits || act == kActClassI32AxisI32) return {hot ? kHotJax : kHotNone, act, true};
+    if (act == kActMaskF32AxisI32 && hot) return {kHotJax, act, true};  // (the agent-role tree: float mask from the embedding)
+    return {};
+  }
+  // the sorted observation features of the large games: the instantiation without the step stages (three waves per SIMD)
+  if (q.big && (prm.stages & kStageFeatureSorts) && !(prm.stages & (HK_STAGE_SHIFT | HK_STAGE_REPOSITION | HK_STAGE_NEWTON)))
+    return {kHotSort, kActAny};
+  // the JAX trainer's take_actions, with the trainers' action layouts compiled in
+  if (hot) return {kHotJax, act};
+  if (act == kActClassI32Logits || act == kActClassI32AxisI32 || act == kActMaskF32AxisI64) return {kHotNone, act};
+  return {kHotNone, kActAny};
+}
+
+inline int64_t quad_grid(const Params& prm) {
+  return workgroups(workgroups(prm.batch, kQuadGames), quad_shape(prm.m, prm.d).wpb);
+}
+
+template <int M, int D, int WPB>
+int launch_quad_w(Params prm, hipStream_t stream) {
+  const int64_t grid = workgroups(workgroups(prm.batch, kQuadGames), WPB);  // (a probe build chooses WPB)
+  prm.games_per_block = kQuadGames * WPB;
+  prm.pad_f32 = (float)prm.pad;
   size_t dynamic_lds = 0;
 #ifdef HK_QUAD_PROBE  // unused dynamic LDS: caps the workgroups per CU (how much does a second round of waves buy?)
   const char* e = getenv("HK_QUAD_DLDS");
   dynamic_lds = e ? (size_t)atoi(e) : 0;
 #endif
-  hipLaunchKernelGGL((quad_kernel<M, D, HOT, WPB, ACT, FEAT>), dim3(grid), dim3(kWave * WPB), dynamic_lds, stream,
-                     (const float*)prm.in, prm.in_stride, prm.batch, prm);
-}
-
-template <int M, int D, int WPB>
-int launch_quad_w(Params prm, hipStream_t stream) {
-  const int64_t waves = ((int64_t)prm.batch + kQuadGames - 1) / kQuadGames;
-  const unsigned grid = (unsigned)((waves + WPB - 1) / WPB);
-  prm.games_per_block = kQuadGames * WPB;
-  prm.pad_f32 = (float)prm.pad;
-  launch_prepare();
-  const bool hot = prm.flags == HK_SEM_JAX && prm.stages == (HK_STAGE_SHIFT | HK_STAGE_REPOSITION | HK_STAGE_NEWTON);
-  const int act = quad_act_of(prm);
-  if (prm.feat_out) {
-    // the step + features launch of the search's expansion: class-id subsets with an int32 axis or the agent's logits
-    // (or, in the JAX trainer's configuration, a float mask with an int32 axis), no sorted output, small games
-    if constexpr (D <= kQuad && !QuadGeom<M, D>::kBig) {
-      const bool plain = !(prm.stages & kStageFeatureSorts) && (prm.flags & HK_SEM_MASK) != HK_SEM_LIST &&
-                         !(prm.flags & HK_FLAG_COMPACT_SORTED);
-      if (!plain) return HK_ERR_UNSUPPORTED;
-      if (act == kActClassI32Logits) {
-        if (hot) launch_quad_k<M, D, WPB, kHotJax, kActClassI32Logits, true>(prm, grid, stream);
-        else launch_quad_k<M, D, WPB, kHotNone, kActClassI32Logits, true>(prm, grid, stream);
-      } else if (act == kActClassI32AxisI32) {
-        if (hot) launch_quad_k<M, D, WPB, kHotJax, kActClassI32AxisI32, true>(prm, grid, stream);
-        else launch_quad_k<M, D, WPB, kHotNone, kActClassI32AxisI32, true>(prm, grid, stream);
-      } else if (act == kActMaskF32AxisI32 && hot) {  // (the agent-role tree: float mask from the embedding)
-        launch_quad_k<M, D, WPB, kHotJax, kActMaskF32AxisI32, true>(prm, grid, stream);
-      } else {
-        return HK_ERR_UNSUPPORTED;
-      }
-      return launch_status();
-    } else {
-      return HK_ERR_UNSUPPORTED;
-    }
-  }
-  if constexpr (QuadGeom<M, D>::kBig) {
-    // the sorted observation features of the large games: the instantiation without the step stages (three waves per SIMD)
-    if ((prm.stages & kStageFeatureSorts) && !(prm.stages & (HK_STAGE_SHIFT | HK_STAGE_REPOSITION | HK_STAGE_NEWTON))) {
-      launch_quad_k<M, D, WPB, kHotSort, kActAny>(prm, grid, stream);
-      return launch_status();
-    }
-  }
-  if (hot) {  // the JAX trainer's take_actions, with the trainers' action layouts compiled in
-    switch (act) {
-      case kActMaskF32AxisI32: launch_quad_k<M, D, WPB, kHotJax, kActMaskF32AxisI32>(prm, grid, stream); break;
-      case kActMaskF32AxisI64: launch_quad_k<M, D, WPB, kHotJax, kActMaskF32AxisI64>(prm, grid, stream); break;
-      case kActMaskF32AxisF32: launch_quad_k<M, D, WPB, kHotJax, kActMaskF32AxisF32>(prm, grid, stream); break;
-      case kActClassI32AxisI32: launch_quad_k<M, D, WPB, kHotJax, kActClassI32AxisI32>(prm, grid, stream); break;
-      case kActClassI32Logits:
-        if constexpr (D <= kQuad && !QuadGeom<M, D>::kBig) {
-          launch_quad_k<M, D, WPB, kHotJax, kActClassI32Logits>(prm, grid, stream);
-          break;
-        } else {
-          return HK_ERR_UNSUPPORTED;
-        }
-      default: launch_quad_k<M, D, WPB, kHotJax, kActAny>(prm, grid, stream);
-    }
-  } else if (act == kActClassI32Logits) {
-    if constexpr (D <= kQuad && !QuadGeom<M, D>::kBig) launch_quad_k<M, D, WPB, kHotNone, kActClassI32Logits>(prm, grid, stream);
-    else return HK_ERR_UNSUPPORTED;
-  } else if (act == kActClassI32AxisI32) {
-    launch_quad_k<M, D, WPB, kHotNone, kActClassI32AxisI32>(prm, grid, stream);
-  } else if (act == kActMaskF32AxisI64) {
-    launch_quad_k<M, D, WPB, kHotNone, kActMaskF32AxisI64>(prm, grid, stream);
-  } else {
-    launch_quad_k<M, D, WPB, kHotNone, kActAny>(prm, grid, stream);
-  }
-  return launch_status();
+  const int k = quad_variant(prm, quad_shape(M, D)).key();
+  int status = HK_ERR_UNSUPPORTED;  // (stays where quad_variant names none: quad_supported has declined those)
+  const auto on = [&](int hot, int act, bool feat, auto kernel) {
+    if (k == QuadVariant{hot, act, feat}.key())
+      status = launch_kernel(kernel, grid, kWave * WPB, dynamic_lds, stream, (const float*)prm.in, prm.in_stride, prm.batch, prm);
+  };
+  constexpr bool small = quad_small<M, D>();
+  // one line per compiled instantiation
+  if constexpr (small) on(kHotJax, kActClassI32Logits, true, quad_kernel<M, D, kHotJax, WPB, kActClassI32Logits, true>);
+  if constexpr (small) on(kHotNone, kActClassI32Logits, true, quad_kernel<M, D, kHotNone, WPB, kActClassI32Logits, true>);
+  if constexpr (small) on(kHotJax, kActClassI32AxisI32, true, quad_kernel<M, D, kHotJax, WPB, kActClassI32AxisI32, true>);
+  if constexpr (small) on(kHotNone, kActClassI32AxisI32, true, quad_kernel<M, D, kHotNone, WPB, kActClassI32AxisI32, true>);
+  if constexpr (small) on(kHotJax, kActMaskF32AxisI32, true, quad_kernel<M, D, kHotJax, WPB, kActMaskF32AxisI32, true>);
+  if constexpr (QuadGeom<M, D>::kBig) on(kHotSort, kActAny, false, quad_kernel<M, D, kHotSort, WPB, kActAny>);
+  on(kHotJax, kActMaskF32AxisI32, false, quad_kernel<M, D, kHotJax, WPB, kActMaskF32AxisI32>);
+  on(kHotJax, kActMaskF32AxisI64, false, quad_kernel<M, D, kHotJax, WPB, kActMaskF32AxisI64>);
+  on(kHotJax, kActMaskF32AxisF32, false, quad_kernel<M, D, kHotJax, WPB, kActMaskF32AxisF32>);
+  on(kHotJax, kActClassI32AxisI32, false, quad_kernel<M, D, kHotJax, WPB, kActClassI32AxisI32>);
+  if constexpr (small) on(kHotJax, kActClassI32Logits, false, quad_kernel<M, D, kHotJax, WPB, kActClassI32Logits>);
+  on(kHotJax, kActAny, false, quad_kernel<M, D, kHotJax, WPB, kActAny>);
+  if constexpr (small) on(kHotNone, kActClassI32Logits, false, quad_kernel<M, D, kHotNone, WPB, kActClassI32Logits>);
+  on(kHotNone, kActClassI32AxisI32, false, quad_kernel<M, D, kHotNone, WPB, kActClassI32AxisI32>);
+  on(kHotNone, kActMaskF32AxisI64, false, quad_kernel<M, D, kHotNone, WPB, kActMaskF32AxisI64>);
+  on(kHotNone, kActAny, false, quad_kernel<M, D, kHotNone, WPB, kActAny>);
+  return status;
 }
 
 template <int M, int D>
@@ -1615,33 +1654,15 @@ int launch_quad_t(Params prm, hipStream_t stream) {
   return launch_quad_w<M, D, quad_waves_per_block<M, D>()>(prm, stream);
 }
 
-// (max_points, dim) with a four-lane step kernel
-#ifndef HK_QUAD_SPECS
-#define HK_QUAD_SPECS(X) X(10, 3) X(20, 3) X(20, 4) X(50, 4)
-#endif
-
-// hk_step requests this kernel serves: plain steps (no class / feature outputs), JAX or torch semantics (the sorted
-// output of the list semantics stays with the other kernels), float32, contiguous W-aligned records; the slabs stored
-// beside the state (a step's features, a rollout's observations) go out in the same W-wide chunks
-template <int M, int D>
-bool quad_ok_t(const Params& prm) {
-  using G = QuadGeom<M, D>;
-  const size_t vec_bytes = G::W * 4;
-  return prm.in_stride == G::N && prm.out_stride == G::N && reinterpret_cast<uintptr_t>(prm.in) % vec_bytes == 0 &&
-         reinterpret_cast<uintptr_t>(prm.out) % vec_bytes == 0 &&
-         reinterpret_cast<uintptr_t>(prm.feat_out) % vec_bytes == 0 &&
-         reinterpret_cast<uintptr_t>(prm.obs_out) % vec_bytes == 0;
-}
-
+// hk_step requests this kernel serves: plain steps (no class output), JAX or torch semantics (the sorted output of the
+// list semantics stays with the other kernels), the layout of quad_layout_ok, and what quad_variant has a kernel for
 inline bool quad_supported(const Params& prm, int dtype) {
   if (dtype != HK_F32 || prm.mode != kModeStep) return false;
   if (prm.class_out) return false;
   if (prm.coords_kind == HK_COORDS_IN_RECORD) return false;
   if (sorted_output(prm) && prm.m * prm.d > 128) return false;  // (the large games' sorted output stays with the team kernel)
-#define HK_X(M_, D_) if (prm.m == M_ && prm.d == D_) return quad_ok_t<M_, D_>(prm);
-  HK_QUAD_SPECS(HK_X)
-#undef HK_X
-  return false;
+  const QuadShape q = quad_shape(prm.m, prm.d);
+  return quad_layout_ok(prm, q) && !quad_variant(prm, q).none();
 }
 
 #ifndef HK_SPEC_TU
@@ -1650,10 +1671,7 @@ HK_QUAD_SPECS(HK_X)
 #undef HK_X
 
 inline int launch_quad(const Params& prm, hipStream_t stream) {
-#define HK_X(M_, D_) if (prm.m == M_ && prm.d == D_) return launch_quad_t<M_, D_>(prm, stream);
-  HK_QUAD_SPECS(HK_X)
-#undef HK_X
-  return HK_ERR_UNSUPPORTED;
+  return for_quad_spec(prm.m, prm.d, (int)HK_ERR_UNSUPPORTED, [&](auto s) { return launch_quad_t<s.M, s.D>(prm, stream); });
 }
 #endif
 

@@ -165,37 +165,32 @@ __global__ __launch_bounds__((kWave * QuadBinGeom<M, D>::kWaves)) void quadbin_k
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
-template <int M, int D>
-int launch_quadbin_t(Params prm, const float* in, int32_t* ids_out, int32_t* np_out, hipStream_t stream) {
+// games per group of a shape (0: the shape has no binning kernel)
+inline int quadbin_group_games(int m, int d, int dtype) {
+  return dtype == HK_F32 ? for_quad_spec(m, d, 0, [](auto s) { return QuadBinGeom<s.M, s.D>::kGames; }) : 0;
+}
+
+// the two instantiations of a shape: the games come from memory (`in`), or are drawn here (GEN)
+template <int M, int D, bool GEN>
+int launch_quadbin_k(const Params& prm, const float* in, int32_t* ids_out, int32_t* np_out, hipStream_t stream) {
   using BG = QuadBinGeom<M, D>;
-  const unsigned grid = (unsigned)(((int64_t)prm.batch + BG::kGames - 1) / BG::kGames);
   constexpr size_t lds = (size_t)BG::kWaves * QuadGenGeom<M, D>::kRegion * sizeof(float);
-  prm.pad_f32 = (float)prm.pad;
   if (lds > 48 * 1024) {  // (static + dynamic LDS beyond 64 KiB is a per-function opt-in: idempotent, cheap)
-    const void* fn = in ? reinterpret_cast<const void*>(&quadbin_kernel<M, D, false>)
-                        : reinterpret_cast<const void*>(&quadbin_kernel<M, D, true>);
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&quadbin_kernel<M, D, GEN>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
       (void)hipGetLastError();
       return HK_ERR_LAUNCH;
     }
   }
-  launch_prepare();
-  if (in)
-    hipLaunchKernelGGL((quadbin_kernel<M, D, false>), dim3(grid), dim3(kWave * BG::kWaves), lds, stream, in, (float*)prm.out,
-                       ids_out, np_out, prm.batch, prm);
-  else
-    hipLaunchKernelGGL((quadbin_kernel<M, D, true>), dim3(grid), dim3(kWave * BG::kWaves), lds, stream, (const float*)nullptr,
+  return launch_kernel(quadbin_kernel<M, D, GEN>, workgroups(prm.batch, BG::kGames), kWave * BG::kWaves, lds, stream, in,
                        (float*)prm.out, ids_out, np_out, prm.batch, prm);
-  return launch_status();
 }
 
-// games per group of a shape (0: the shape has no binning kernel)
-inline int quadbin_group_games(int m, int d, int dtype) {
-  if (dtype != HK_F32) return 0;
-#define HK_X(M_, D_) if (m == M_ && d == D_) return QuadBinGeom<M_, D_>::kGames;
-  HK_QUAD_SPECS(HK_X)
-#undef HK_X
-  return 0;
+template <int M, int D>
+int launch_quadbin_t(Params prm, const float* in, int32_t* ids_out, int32_t* np_out, hipStream_t stream) {
+  prm.pad_f32 = (float)prm.pad;
+  if (in) return launch_quadbin_k<M, D, false>(prm, in, ids_out, np_out, stream);
+  return launch_quadbin_k<M, D, true>(prm, nullptr, ids_out, np_out, stream);
 }
 
 #ifndef HK_SPEC_TU
@@ -204,10 +199,8 @@ HK_QUAD_SPECS(HK_X)
 #undef HK_X
 
 inline int launch_quadbin(const Params& prm, const float* in, int32_t* ids_out, int32_t* np_out, hipStream_t stream) {
-#define HK_X(M_, D_) if (prm.m == M_ && prm.d == D_) return launch_quadbin_t<M_, D_>(prm, in, ids_out, np_out, stream);
-  HK_QUAD_SPECS(HK_X)
-#undef HK_X
-  return HK_ERR_UNSUPPORTED;
+  return for_quad_spec(prm.m, prm.d, (int)HK_ERR_UNSUPPORTED,
+                       [&](auto s) { return launch_quadbin_t<s.M, s.D>(prm, in, ids_out, np_out, stream); });
 }
 #endif
 

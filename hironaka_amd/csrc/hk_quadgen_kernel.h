@@ -173,16 +173,12 @@ __global__ __launch_bounds__(kWave * WPB, (QuadGeom<M, D>::kWavesPerSimd)) void 
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
+// (one instantiation per shape, on the step kernel's grid: quad_grid)
 template <int M, int D>
 int launch_quadgen_t(Params prm, hipStream_t stream) {
   constexpr int WPB = quad_waves_per_block<M, D>();
-  const int64_t waves = ((int64_t)prm.batch + kQuadGames - 1) / kQuadGames;
-  const unsigned grid = (unsigned)((waves + WPB - 1) / WPB);
   prm.pad_f32 = (float)prm.pad;
-  launch_prepare();
-  hipLaunchKernelGGL((quadgen_kernel<M, D, WPB>), dim3(grid), dim3(kWave * WPB), 0, stream, (float*)prm.out, prm.batch,
-                     prm);
-  return launch_status();
+  return launch_kernel(quadgen_kernel<M, D, WPB>, quad_grid(prm), kWave * WPB, 0, stream, (float*)prm.out, prm.batch, prm);
 }
 
 // hk_generate_points requests this kernel serves: float32, contiguous W-aligned records, in-place order, a duplicate
@@ -193,11 +189,8 @@ inline bool quadgen_supported(const Params& prm, int dtype) {
   if ((prm.flags & HK_SEM_MASK) == HK_SEM_JAX && (prm.stages & HK_STAGE_NEWTON) && (float)prm.pad != -1.0f) return false;
   if (!((float)prm.pad < 0.0f)) return false;  // (a removed row must read as padding)
   if (prm.out_stride != (int64_t)prm.m * prm.d) return false;
-#define HK_X(M_, D_) \
-  if (prm.m == M_ && prm.d == D_) return reinterpret_cast<uintptr_t>(prm.out) % (QuadGeom<M_, D_>::W * 4) == 0;
-  HK_QUAD_SPECS(HK_X)
-#undef HK_X
-  return false;
+  const QuadShape q = quad_shape(prm.m, prm.d);
+  return q.known && reinterpret_cast<uintptr_t>(prm.out) % (q.w * 4) == 0;
 }
 
 #ifndef HK_SPEC_TU
@@ -206,10 +199,7 @@ HK_QUAD_SPECS(HK_X)
 #undef HK_X
 
 inline int launch_quadgen(const Params& prm, hipStream_t stream) {
-#define HK_X(M_, D_) if (prm.m == M_ && prm.d == D_) return launch_quadgen_t<M_, D_>(prm, stream);
-  HK_QUAD_SPECS(HK_X)
-#undef HK_X
-  return HK_ERR_UNSUPPORTED;
+  return for_quad_spec(prm.m, prm.d, (int)HK_ERR_UNSUPPORTED, [&](auto s) { return launch_quadgen_t<s.M, s.D>(prm, stream); });
 }
 #endif
 

@@ -826,63 +826,78 @@ __global__ __launch_bounds__(kWave * WPB, (QuadRollGeom<M, D>::kWavesPerSimd)) v
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
+// The instantiation quadroll_kernel<M, D, hot, WPB, rec, zeil, gen, epi> that serves a rollout request (hot < 0: none)
+struct QuadRollVariant {
+  int hot = -1;
+  bool rec = false, zeil = false, gen = false, epi = false;
+  bool none() const { return hot < 0; }
+  constexpr int key() const { return hot < 0 ? -1 : (((hot * 2 + rec) * 2 + zeil) * 2 + gen) * 2 + epi; }
+};
+inline QuadRollVariant quadroll_variant(const Params& prm, const QuadShape& q) {
+  if (!q.known) return {};
+  const bool zeil = prm.host_policy == HK_HOST_ZEILLINGER;  // plain rollouts (quadroll_kernel<..., ZEIL>)
+  const int hot = fast_hot_config(prm);
+  if (prm.max_value > 0 || prm.episodes > 1) {
+    // initial states drawn inside the launch (GEN), or episodes back to back from the states in memory (EPI): plain
+    // rollouts; Zeillinger's host where this kernel is its rollout kernel anyway (the large games), with GEN
+    const bool gen = prm.max_value > 0;
+    if (any_records(prm) || (zeil && !(gen && q.tall))) return {};
+    return {hot, false, zeil, gen, !gen};
+  }
+  if (any_records(prm)) return zeil ? QuadRollVariant{} : QuadRollVariant{hot == kHotJax ? kHotJax : kHotNone, true};
+  if (zeil) return {kHotNone, false, true};
+  if (hot == kHotNone && sorted_output(prm)) return {kHotList};
+  return {hot};
+}
+inline QuadRollVariant quadroll_variant(const Params& prm) { return quadroll_variant(prm, quad_shape(prm.m, prm.d)); }
+
+// workgroups of a launch (the finished-game workspace has one slot per workgroup and step)
+inline int64_t quadroll_grid(const Params& prm) {
+  const int wpb = for_quad_spec(prm.m, prm.d, 0, [](auto s) { return QuadRollGeom<s.M, s.D>::kWpb; });
+  return wpb ? workgroups(workgroups(prm.batch, kQuadGames), wpb) : 0;
+}
+
 // rollouts of float32, contiguous, W-aligned records
 inline bool quadroll_request_ok(const Params& prm) {
   if (prm.mode != kModeRollout || prm.m > 255) return false;
-  // Zeillinger's host: plain rollouts (quadroll_kernel<..., ZEIL>)
-  if (prm.host_policy == HK_HOST_ZEILLINGER && any_records(prm)) return false;
   // sorted + compacted output (list semantics): plain rollouts only -- ranked once, at the publish --, not under
   // Zeillinger's host, whose tie-breaks follow the physical row order
   if (sorted_output(prm) &&
       (prm.max_value > 0 || prm.episodes > 1 || prm.host_policy == HK_HOST_ZEILLINGER || any_records(prm)))
     return false;
-  return true;
+  return !quadroll_variant(prm).none();
+}
+
+template <int M, int D, typename K>
+int quadroll_launch(K kernel, Params prm, hipStream_t stream) {  // (a generated batch has no input: prm.in is NULL there)
+  constexpr int WPB = QuadRollGeom<M, D>::kWpb;
+  prm.games_per_block = kQuadGames * WPB;
+  prm.pad_f32 = (float)prm.pad;
+  return launch_kernel(kernel, quadroll_grid(prm), kWave * WPB, 0, stream, (const float*)prm.in, prm.in_stride, prm.batch, prm);
+}
+constexpr int quadroll_key(int hot, bool rec = false, bool zeil = false, bool gen = false, bool epi = false) {
+  return QuadRollVariant{hot, rec, zeil, gen, epi}.key();
 }
 
 template <int M, int D>
 int launch_quadroll_t(Params prm, hipStream_t stream) {
+  const auto go = [&](auto kernel) { return quadroll_launch<M, D>(kernel, prm, stream); };
   constexpr int WPB = QuadRollGeom<M, D>::kWpb;
-  const int64_t waves = ((int64_t)prm.batch + kQuadGames - 1) / kQuadGames;
-  const unsigned grid = (unsigned)((waves + WPB - 1) / WPB);
-  prm.games_per_block = kQuadGames * WPB;
-  prm.pad_f32 = (float)prm.pad;
-  launch_prepare();
-  const int hot = fast_hot_config(prm);
-  if (any_records(prm)) {  // (quadroll_supported has checked obs_out: W-aligned like the state)
-    if (hot == kHotJax)
-      hipLaunchKernelGGL((quadroll_kernel<M, D, kHotJax, WPB, true>), dim3(grid), dim3(kWave * WPB), 0, stream,
-                         (const float*)prm.in, prm.in_stride, prm.batch, prm);
-    else
-      hipLaunchKernelGGL((quadroll_kernel<M, D, kHotNone, WPB, true>), dim3(grid), dim3(kWave * WPB), 0, stream,
-                         (const float*)prm.in, prm.in_stride, prm.batch, prm);
-    return launch_status();
+  switch (quadroll_variant(prm, quad_shape(M, D)).key()) {  // one line per compiled instantiation
+    case quadroll_key(kHotJax, true): return go(quadroll_kernel<M, D, kHotJax, WPB, true>);
+    case quadroll_key(kHotNone, true): return go(quadroll_kernel<M, D, kHotNone, WPB, true>);
+    case quadroll_key(kHotNone, false, true): return go(quadroll_kernel<M, D, kHotNone, WPB, false, true>);
+    case quadroll_key(kHotJax): return go(quadroll_kernel<M, D, kHotJax, WPB>);
+    case quadroll_key(kHotTorch): return go(quadroll_kernel<M, D, kHotTorch, WPB>);
+    case quadroll_key(kHotList): return go(quadroll_kernel<M, D, kHotList, WPB>);
+    case quadroll_key(kHotNone): return go(quadroll_kernel<M, D, kHotNone, WPB>);
   }
-  if (prm.host_policy == HK_HOST_ZEILLINGER)
-    hipLaunchKernelGGL((quadroll_kernel<M, D, kHotNone, WPB, false, true>), dim3(grid), dim3(kWave * WPB), 0, stream,
-                       (const float*)prm.in, prm.in_stride, prm.batch, prm);
-  else if (hot == kHotJax)
-    hipLaunchKernelGGL((quadroll_kernel<M, D, kHotJax, WPB>), dim3(grid), dim3(kWave * WPB), 0, stream,
-                       (const float*)prm.in, prm.in_stride, prm.batch, prm);
-  else if (hot == kHotTorch)
-    hipLaunchKernelGGL((quadroll_kernel<M, D, kHotTorch, WPB>), dim3(grid), dim3(kWave * WPB), 0, stream,
-                       (const float*)prm.in, prm.in_stride, prm.batch, prm);
-  else if (sorted_output(prm))
-    hipLaunchKernelGGL((quadroll_kernel<M, D, kHotList, WPB>), dim3(grid), dim3(kWave * WPB), 0, stream,
-                       (const float*)prm.in, prm.in_stride, prm.batch, prm);
-  else
-    hipLaunchKernelGGL((quadroll_kernel<M, D, kHotNone, WPB>), dim3(grid), dim3(kWave * WPB), 0, stream,
-                       (const float*)prm.in, prm.in_stride, prm.batch, prm);
-  return launch_status();
+  return HK_ERR_UNSUPPORTED;  // (quadroll_variant names no other for a plain rollout)
 }
 
 // hk_zeillinger on the rollout kernel's prologue + pair loop (JAX variant, contiguous records, the large games: the
-// small shapes' one-lane kernel is ahead there)
-template <int M, int D>
-int launch_quadzeil_t(Params prm, hipStream_t stream) {
-  constexpr int WPB = QuadRollGeom<M, D>::kWpb;
-  const int64_t waves = ((int64_t)prm.batch + kQuadGames - 1) / kQuadGames;
-  const unsigned grid = (unsigned)((waves + WPB - 1) / WPB);
-  prm.pad_f32 = -1.0f;
+// small shapes' one-lane kernel is ahead there): a plain rollout of no steps under Zeillinger's host
+inline Params quadzeil_rollout(Params prm) {
   prm.pad = -1.0;
   prm.mode = kModeRollout;
   prm.steps = 0;
@@ -891,106 +906,56 @@ int launch_quadzeil_t(Params prm, hipStream_t stream) {
   prm.stages = 0;
   prm.count_ws = nullptr;
   prm.episodes = 1;
-  launch_prepare();
-  hipLaunchKernelGGL((quadroll_kernel<M, D, kHotNone, WPB, false, true>), dim3(grid), dim3(kWave * WPB), 0, stream,
-                     (const float*)prm.in, prm.in_stride, prm.batch, prm);
-  return launch_status();
+  return prm;
+}
+template <int M, int D>
+int launch_quadzeil_t(Params prm, hipStream_t stream) {
+  return launch_quadroll_t<M, D>(quadzeil_rollout(prm), stream);
 }
 
 // hk_zeillinger requests it serves: the JAX variant over contiguous 16-B aligned float32 records
 inline bool quadzeil_supported(const Params& prm, int dtype) {
   if (dtype != HK_F32 || prm.mode != kModeZeillinger || (prm.flags & HK_SEM_MASK) != HK_SEM_JAX) return false;
   if (prm.in_stride != (int64_t)prm.m * prm.d || reinterpret_cast<uintptr_t>(prm.in) % 16) return false;
-#define HK_X(M_, D_) if (prm.m == M_ && prm.d == D_) return true;
-  HK_QUAD_SPECS(HK_X)
-#undef HK_X
-  return false;
+  return quad_shape(prm.m, prm.d).known;
 }
 
 inline bool quadroll_supported(const Params& prm, int dtype) {
-  if (dtype != HK_F32 || !quadroll_request_ok(prm)) return false;
-#define HK_X(M_, D_) if (prm.m == M_ && prm.d == D_) return quad_ok_t<M_, D_>(prm);
-  HK_QUAD_SPECS(HK_X)
-#undef HK_X
-  return false;
+  return dtype == HK_F32 && quadroll_request_ok(prm) && quad_layout_ok(prm, quad_shape(prm.m, prm.d));
 }
 
-// ---- rollouts from initial states drawn inside the launch (hk_rollout_desc.gen_max_value) ------------------------------
-// plain rollouts (no records), in-place order, a duplicate fill equal to the padding value (there is no exactness guard
-// to send anything else down the generic routines: the draws are canonical by construction); Zeillinger's host where
-// this kernel is its rollout kernel anyway (the large games)
+// ---- rollouts from initial states drawn inside the launch (hk_rollout_desc.gen_max_value), episodes back to back -------
 template <int M, int D>
 int launch_quadroll_gen_t(Params prm, hipStream_t stream) {
+  const auto go = [&](auto kernel) { return quadroll_launch<M, D>(kernel, prm, stream); };
   constexpr int WPB = QuadRollGeom<M, D>::kWpb;
-  const int64_t waves = ((int64_t)prm.batch + kQuadGames - 1) / kQuadGames;
-  const unsigned grid = (unsigned)((waves + WPB - 1) / WPB);
-  prm.games_per_block = kQuadGames * WPB;
-  prm.pad_f32 = (float)prm.pad;
-  launch_prepare();
-  const int hot = fast_hot_config(prm);
-  if (prm.max_value <= 0) {  // episodes back to back from the states in memory (EPI without GEN)
-    if (prm.host_policy == HK_HOST_ZEILLINGER) return HK_ERR_UNSUPPORTED;
-    if (hot == kHotJax)
-      hipLaunchKernelGGL((quadroll_kernel<M, D, kHotJax, WPB, false, false, false, true>), dim3(grid), dim3(kWave * WPB), 0,
-                         stream, (const float*)prm.in, prm.in_stride, prm.batch, prm);
-    else if (hot == kHotTorch)
-      hipLaunchKernelGGL((quadroll_kernel<M, D, kHotTorch, WPB, false, false, false, true>), dim3(grid), dim3(kWave * WPB), 0,
-                         stream, (const float*)prm.in, prm.in_stride, prm.batch, prm);
-    else
-      hipLaunchKernelGGL((quadroll_kernel<M, D, kHotNone, WPB, false, false, false, true>), dim3(grid), dim3(kWave * WPB), 0,
-                         stream, (const float*)prm.in, prm.in_stride, prm.batch, prm);
-    return launch_status();
+  switch (quadroll_variant(prm, quad_shape(M, D)).key()) {  // one line per compiled instantiation
+    case quadroll_key(kHotJax, false, false, false, true): return go(quadroll_kernel<M, D, kHotJax, WPB, false, false, false, true>);
+    case quadroll_key(kHotTorch, false, false, false, true): return go(quadroll_kernel<M, D, kHotTorch, WPB, false, false, false, true>);
+    case quadroll_key(kHotNone, false, false, false, true): return go(quadroll_kernel<M, D, kHotNone, WPB, false, false, false, true>);
+    case quadroll_key(kHotNone, false, true, true):  // (Zeillinger's host: the large games only, as quadroll_variant says)
+      if constexpr (M > 32) return go(quadroll_kernel<M, D, kHotNone, WPB, false, true, true>);
+      break;
+    case quadroll_key(kHotJax, false, false, true): return go(quadroll_kernel<M, D, kHotJax, WPB, false, false, true>);
+    case quadroll_key(kHotTorch, false, false, true): return go(quadroll_kernel<M, D, kHotTorch, WPB, false, false, true>);
+    case quadroll_key(kHotNone, false, false, true): return go(quadroll_kernel<M, D, kHotNone, WPB, false, false, true>);
   }
-  if (prm.host_policy == HK_HOST_ZEILLINGER) {
-    if constexpr (M > 32)
-      hipLaunchKernelGGL((quadroll_kernel<M, D, kHotNone, WPB, false, true, true>), dim3(grid), dim3(kWave * WPB), 0, stream,
-                         (const float*)nullptr, prm.in_stride, prm.batch, prm);
-    else
-      return HK_ERR_UNSUPPORTED;
-  } else if (hot == kHotJax) {
-    hipLaunchKernelGGL((quadroll_kernel<M, D, kHotJax, WPB, false, false, true>), dim3(grid), dim3(kWave * WPB), 0, stream,
-                       (const float*)nullptr, prm.in_stride, prm.batch, prm);
-  } else if (hot == kHotTorch) {
-    hipLaunchKernelGGL((quadroll_kernel<M, D, kHotTorch, WPB, false, false, true>), dim3(grid), dim3(kWave * WPB), 0, stream,
-                       (const float*)nullptr, prm.in_stride, prm.batch, prm);
-  } else {
-    hipLaunchKernelGGL((quadroll_kernel<M, D, kHotNone, WPB, false, false, true>), dim3(grid), dim3(kWave * WPB), 0, stream,
-                       (const float*)nullptr, prm.in_stride, prm.batch, prm);
-  }
-  return launch_status();
+  return HK_ERR_UNSUPPORTED;  // (quadroll_variant names no other for a generated / multi-episode rollout)
 }
 
 // episodes back to back from the states in memory: plain rollouts the four-lane kernel serves, not Zeillinger's host
 inline bool quadroll_episodes_supported(const Params& prm, int dtype) {
   if (prm.max_value > 0 || prm.episodes <= 1 || !prm.in || !prm.out) return false;
-  if (any_records(prm)) return false;
-  if (prm.host_policy == HK_HOST_ZEILLINGER) return false;
   return quadroll_supported(prm, dtype);
 }
 
+// plain rollouts (no records), in-place order, a duplicate fill equal to the padding value (there is no exactness guard
+// to send anything else down the generic routines: the draws are canonical by construction)
 inline bool quadroll_gen_supported(const Params& prm, int dtype) {
   if (dtype != HK_F32 || prm.max_value <= 0 || !quadroll_request_ok(prm)) return false;
-  if (any_records(prm)) return false;
-  if (prm.host_policy == HK_HOST_ZEILLINGER && prm.m <= 32) return false;
   const float pad = (float)prm.pad;
   if (!(pad < 0.0f) || ((prm.flags & HK_SEM_MASK) == HK_SEM_JAX && pad != -1.0f)) return false;
-#define HK_X(M_, D_) \
-  if (prm.m == M_ && prm.d == D_) return reinterpret_cast<uintptr_t>(prm.out) % (QuadGeom<M_, D_>::W * 4) == 0;
-  HK_QUAD_SPECS(HK_X)
-#undef HK_X
-  return false;
-}
-
-// workgroups of a launch (the finished-game workspace has one slot per workgroup and step)
-inline int64_t quadroll_grid(const Params& prm) {
-#define HK_X(M_, D_)                                                             \
-  if (prm.m == M_ && prm.d == D_) {                                               \
-    constexpr int WPB = QuadRollGeom<M_, D_>::kWpb;                               \
-    return (((int64_t)prm.batch + kQuadGames - 1) / kQuadGames + WPB - 1) / WPB;  \
-  }
-  HK_QUAD_SPECS(HK_X)
-#undef HK_X
-  return 0;
+  return reinterpret_cast<uintptr_t>(prm.out) % (quad_shape(prm.m, prm.d).w * 4) == 0;
 }
 
 #ifndef HK_SPEC_TU
@@ -1001,24 +966,15 @@ HK_QUAD_SPECS(HK_X)
 #undef HK_X
 
 inline int launch_quadzeil(const Params& prm, hipStream_t stream) {
-#define HK_X(M_, D_) if (prm.m == M_ && prm.d == D_) return launch_quadzeil_t<M_, D_>(prm, stream);
-  HK_QUAD_SPECS(HK_X)
-#undef HK_X
-  return HK_ERR_UNSUPPORTED;
+  return for_quad_spec(prm.m, prm.d, (int)HK_ERR_UNSUPPORTED, [&](auto s) { return launch_quadzeil_t<s.M, s.D>(prm, stream); });
 }
 
 inline int launch_quadroll_gen(const Params& prm, hipStream_t stream) {
-#define HK_X(M_, D_) if (prm.m == M_ && prm.d == D_) return launch_quadroll_gen_t<M_, D_>(prm, stream);
-  HK_QUAD_SPECS(HK_X)
-#undef HK_X
-  return HK_ERR_UNSUPPORTED;
+  return for_quad_spec(prm.m, prm.d, (int)HK_ERR_UNSUPPORTED, [&](auto s) { return launch_quadroll_gen_t<s.M, s.D>(prm, stream); });
 }
 
 inline int launch_quadroll(const Params& prm, hipStream_t stream) {
-#define HK_X(M_, D_) if (prm.m == M_ && prm.d == D_) return launch_quadroll_t<M_, D_>(prm, stream);
-  HK_QUAD_SPECS(HK_X)
-#undef HK_X
-  return HK_ERR_UNSUPPORTED;
+  return for_quad_spec(prm.m, prm.d, (int)HK_ERR_UNSUPPORTED, [&](auto s) { return launch_quadroll_t<s.M, s.D>(prm, stream); });
 }
 #endif
 

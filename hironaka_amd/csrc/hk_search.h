@@ -367,34 +367,28 @@ inline int launch_search_select(const SearchTree& t, const float* gumbel, const 
                                 const int32_t* table, int max_considered, int num_simulations, int max_depth,
                                 int next_free, int32_t* parent_out, int32_t* action_out, int32_t* node_out,
                                 hipStream_t stream) {
-  launch_prepare();
 #define HK_CALL(AM)                                                                                               \
-  hipLaunchKernelGGL(search_select_kernel<AM>, dim3((unsigned)(((int64_t)t.batch * AM + 255) / 256)), dim3(256), 0,  \
+  return launch_kernel(search_select_kernel<AM>, dim3((unsigned)(((int64_t)t.batch * AM + 255) / 256)), dim3(256), 0,  \
                      stream, t, gumbel, invalid, table, max_considered, num_simulations, max_depth, next_free,     \
                      parent_out, action_out, node_out)
   HK_SEARCH_DISPATCH(t.num_actions, HK_CALL);
 #undef HK_CALL
-  return launch_status();
 }
 
 inline int launch_search_backup(const SearchTree& t, const int32_t* parent, const int32_t* action, const int32_t* node,
                                 const float* prior_logits, const float* value, const float* reward,
                                 const float* discount, hipStream_t stream) {
-  launch_prepare();
-  hipLaunchKernelGGL(search_backup_kernel, dim3((t.batch + 63) / 64), dim3(64), 0, stream, t, parent, action, node,
+  return launch_kernel(search_backup_kernel, dim3((t.batch + 63) / 64), dim3(64), 0, stream, t, parent, action, node,
                      prior_logits, value, reward, discount);
-  return launch_status();
 }
 
 inline int launch_search_policy(const SearchTree& t, const float* gumbel, const uint8_t* invalid, int32_t* action_out,
                                 float* weights_out, hipStream_t stream) {
-  launch_prepare();
 #define HK_CALL(AM)                                                                                               \
-  hipLaunchKernelGGL(search_policy_kernel<AM>, dim3((t.batch + 63) / 64), dim3(64), 0, stream, t, gumbel, invalid, \
+  return launch_kernel(search_policy_kernel<AM>, dim3((t.batch + 63) / 64), dim3(64), 0, stream, t, gumbel, invalid, \
                      action_out, weights_out)
   HK_SEARCH_DISPATCH(t.num_actions, HK_CALL);
 #undef HK_CALL
-  return launch_status();
 }
 
 // ---- expansion glue of a host-role tree (hironaka/jax/recurrent_fn.py:84-104 between the search's select and its
@@ -535,54 +529,42 @@ inline dim3 expand_grid(int per, int batch) { return dim3((unsigned)batch, (unsi
 
 inline int launch_expand_gather_agent(const float* emb, const int32_t* parent, float* points_out, float* coords_out,
                                       int batch, int nodes, int E, int d, hipStream_t stream) {
-  launch_prepare();
-  hipLaunchKernelGGL(expand_gather_agent_kernel, expand_grid(E + d, batch), dim3(kExpandBlock), 0, stream, emb,
+  return launch_kernel(expand_gather_agent_kernel, expand_grid(E + d, batch), dim3(kExpandBlock), 0, stream, emb,
                      parent, points_out, coords_out, batch, nodes, E, d);
-  return launch_status();
 }
 
 inline int launch_expand_scatter_agent(const float* points, const float* feat_in, const float* host_logits,
                                        const int32_t* node, float* emb, float* feat, float* agent_feat_out,
                                        int32_t* class_out, int batch, int nodes, int E, int d, int C,
                                        hipStream_t stream) {
-  launch_prepare();
-  hipLaunchKernelGGL(expand_scatter_agent_kernel, expand_grid(2 * E + d, batch), dim3(kExpandBlock), 0, stream, points,
+  return launch_kernel(expand_scatter_agent_kernel, expand_grid(2 * E + d, batch), dim3(kExpandBlock), 0, stream, points,
                      feat_in, host_logits, node, emb, feat, agent_feat_out, class_out, batch, nodes, E, d, C);
-  return launch_status();
 }
 
 inline int launch_mask_logits(const float* logits, const int32_t* class_id, float* out, int batch, int d,
                               hipStream_t stream) {
-  launch_prepare();
   const int64_t total = (int64_t)batch * d;
-  hipLaunchKernelGGL(mask_logits_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, logits, class_id,
+  return launch_kernel(mask_logits_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, logits, class_id,
                      out, batch, d);
-  return launch_status();
 }
 
 inline int launch_expand_gather(const float* emb, const float* feat, const int32_t* parent, const int32_t* action,
                                 float* obs_out, float* agent_feat_out, int batch, int nodes, int E, int d,
                                 int64_t game_stride, int64_t node_stride, hipStream_t stream) {
-  launch_prepare();
-  hipLaunchKernelGGL(expand_gather_kernel, expand_grid(2 * E + d, batch), dim3(kExpandBlock), 0, stream, emb, feat,
+  return launch_kernel(expand_gather_kernel, expand_grid(2 * E + d, batch), dim3(kExpandBlock), 0, stream, emb, feat,
                      parent, action, obs_out, agent_feat_out, batch, nodes, E, d, game_stride, node_stride);
-  return launch_status();
 }
 
 inline int launch_masked_argmax(const float* logits, const int32_t* action, int32_t* axis_out, int batch, int d,
                                 hipStream_t stream) {
-  launch_prepare();
-  hipLaunchKernelGGL(masked_argmax_kernel, dim3((batch + 255) / 256), dim3(256), 0, stream, logits, action, axis_out,
+  return launch_kernel(masked_argmax_kernel, dim3((batch + 255) / 256), dim3(256), 0, stream, logits, action, axis_out,
                      batch, d);
-  return launch_status();
 }
 
 inline int launch_expand_scatter(const float* obs, const float* feat_in, const int32_t* node, float* emb, float* feat,
                                  int batch, int nodes, int E, hipStream_t stream) {
-  launch_prepare();
-  hipLaunchKernelGGL(expand_scatter_kernel, expand_grid(2 * E, batch), dim3(kExpandBlock), 0, stream, obs, feat_in,
+  return launch_kernel(expand_scatter_kernel, expand_grid(2 * E, batch), dim3(kExpandBlock), 0, stream, obs, feat_in,
                      node, emb, feat, batch, nodes, E);
-  return launch_status();
 }
 
 // ---- value targets of a finished self-play rollout: JAXTrainer.rollout_postprocess (jax_trainer.py:558-592) ->
@@ -622,10 +604,8 @@ __global__ __launch_bounds__(64) void rollout_values_kernel(const float* obs, fl
 
 inline int launch_rollout_values(const float* obs, float* value_out, int batch, int T, int obs_dim, int dim, int offset,
                                  float disc, float rew_sign, float est_scale, hipStream_t stream) {
-  launch_prepare();
-  hipLaunchKernelGGL(rollout_values_kernel, dim3(batch), dim3(64), 0, stream, obs, value_out, batch, T, obs_dim, dim,
+  return launch_kernel(rollout_values_kernel, dim3(batch), dim3(64), 0, stream, obs, value_out, batch, T, obs_dim, dim,
                      offset, disc, rew_sign, est_scale);
-  return launch_status();
 }
 
 }  // namespace hk

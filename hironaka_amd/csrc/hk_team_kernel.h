@@ -624,35 +624,41 @@ inline int team_lds_stride(int m, int d) {
   return stride;
 }
 
+// The instantiation team_kernel<D, mode, zeil> that serves a request (mode < 0: none)
+struct TeamVariant {
+  int mode = -1;
+  bool zeil = false;
+  bool none() const { return mode < 0; }
+};
+inline TeamVariant team_variant(const Params& prm) {
+  return {kernel_mode(prm), prm.mode == kModeRollout && prm.host_policy == HK_HOST_ZEILLINGER};
+}
+
+inline int64_t team_grid(const Params& prm) { return workgroups(prm.batch, kTeamGames); }
+
 // float32, dim 2..6, <= 64 rows: also the shapes that have a register-resident specialisation
 inline bool team_supported(const Params& prm, int dtype) {
-  if (dtype != HK_F32) return false;
+  if (dtype != HK_F32 || team_variant(prm).none()) return false;
   // sorted + compacted output (list semantics): single steps only
   if (sorted_output(prm) && prm.mode != kModeStep) return false;
   if ((prm.stages & kStageFeatureSorts) && prm.mode != kModeStep) return false;
-  if (prm.mode == kModeZeillinger) return false;
   if (prm.d < 2 || prm.d > 6 || prm.m > kTeam * kTeamSlots) return false;
   return (int64_t)(team_lds_stride(prm.m, prm.d) + prm.d) * 4 * kTeamGames <= kMaxLdsBytes;
 }
 
-template <int D, int MODE, bool ZEIL = false>
-int launch_team_t(const Params& prm, hipStream_t stream) {
-  const size_t lds = (size_t)(prm.lds_stride + prm.d) * kTeamGames * sizeof(float);
-  const unsigned grid = (unsigned)(((int64_t)prm.batch + kTeamGames - 1) / kTeamGames);
-  launch_prepare();
-  hipLaunchKernelGGL((team_kernel<D, MODE, ZEIL>), dim3(grid), dim3(kWave), lds, stream, prm);
-  return launch_status();
-}
-
 template <int D>
 int launch_team_d(const Params& prm, hipStream_t stream) {
-  if (prm.mode == kModeStep && (prm.class_out || (prm.stages & kStageFeatureSorts) || sorted_output(prm)))
-    return launch_team_t<D, kModeStepAux>(prm, stream);
-  if (prm.mode == kModeStep) return launch_team_t<D, kModeStep>(prm, stream);
-  if (prm.mode == kModeRollout && prm.host_policy == HK_HOST_ZEILLINGER)
-    return launch_team_t<D, kModeRollout, true>(prm, stream);
-  if (prm.mode == kModeRollout) return launch_team_t<D, kModeRollout>(prm, stream);
-  return launch_team_t<D, kModeGenerate>(prm, stream);
+  const size_t lds = (size_t)(prm.lds_stride + prm.d) * kTeamGames * sizeof(float);
+  const auto go = [&](auto kernel) { return launch_kernel(kernel, team_grid(prm), kWave, lds, stream, prm); };
+  const TeamVariant v = team_variant(prm);
+  switch (v.mode) {  // one line per compiled instantiation
+    case kModeStepAux: return go(team_kernel<D, kModeStepAux, false>);
+    case kModeStep: return go(team_kernel<D, kModeStep, false>);
+    case kModeRollout:
+      if (v.zeil) return go(team_kernel<D, kModeRollout, true>);
+      return go(team_kernel<D, kModeRollout, false>);
+    default:return go(team_kernel<D, kModeGenerate, false>);
+  }
 }
 
 // one translation unit per dim (hk_team_spec.hip), as for the register-resident specialisations
