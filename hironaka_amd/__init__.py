@@ -3,7 +3,8 @@ __version__ = "0.1.0"
 
 _VEC_ENVS = ("HironakaHostVecEnv", "HironakaAgentVecEnv")
 _DQN = ("fit_network", "td_loss", "td_target", "update_target_net", "polyak_update", "zip_equal")
-__all__ = list(_VEC_ENVS) + ["ReplayBuffer"] + list(_DQN)
+_OPTIM = ("Adam", "SGD", "clip_grad_norm_", "from_torch")
+__all__ = list(_VEC_ENVS) + ["ReplayBuffer"] + list(_DQN) + list(_OPTIM)
 
 
 def __getattr__(name):
@@ -17,4 +18,7 @@ def __getattr__(name):
     if name in _DQN:
         from . import dqn
         return getattr(dqn, name)
+    if name in _OPTIM:
+        from . import optim
+        return getattr(optim, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -90,6 +90,12 @@ HK_REPLAY_TILE_ROWS = 128
 HK_DQN_TILE_ROWS, HK_DQN_MAX_ACTIONS, HK_DQN_BAD_ACTION = 256, 65536, 1
 HK_POLYAK_MAX_TENSORS, HK_POLYAK_CHUNK_BYTES = 64, 16384
 
+# hk_optim_prepare / hk_optim_apply: tensors per launch, the bytes of one gradient a workgroup owns, the bytes of the
+# state block; kinds; flags
+HK_OPTIM_MAX_TENSORS, HK_OPTIM_CHUNK_BYTES, HK_OPTIM_STATE_BYTES = 64, 16384, 64
+HK_OPTIM_SCALE, HK_OPTIM_SGD, HK_OPTIM_ADAM = 0, 1, 2
+HK_OPTIM_LAST, HK_OPTIM_ADVANCE, HK_OPTIM_KEEP_GRADS, HK_OPTIM_NESTEROV, HK_OPTIM_NO_CLIP = 1, 2, 4, 8, 16
+
 SEMANTICS = {"jax": HK_SEM_JAX, "torch": HK_SEM_TORCH, "list": HK_SEM_LIST}
 
 
@@ -355,6 +361,52 @@ class hk_polyak_desc(C.Structure):
     ]
 
 
+class hk_optim_tensor(C.Structure):
+    _fields_ = [
+        ("param", C.c_void_p),
+        ("grad", C.c_void_p),
+        ("state1", C.c_void_p),
+        ("state2", C.c_void_p),
+        ("numel", C.c_int64),
+    ]
+
+
+class hk_optim_state(C.Structure):
+    _fields_ = [
+        ("step", C.c_int64),
+        ("beta1_pow", C.c_double),
+        ("beta2_pow", C.c_double),
+        ("total_norm", C.c_double),
+        ("clip_coef", C.c_double),
+        ("neg_step_size", C.c_double),
+        ("bias2_sqrt", C.c_double),
+        ("lr", C.c_double),
+    ]
+
+
+class hk_optim_desc(C.Structure):
+    _fields_ = [
+        ("tensor", hk_optim_tensor * HK_OPTIM_MAX_TENSORS),
+        ("state", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("lr_dev", C.c_void_p),
+        ("lr", C.c_double),
+        ("beta1", C.c_double),
+        ("beta2", C.c_double),
+        ("eps", C.c_double),
+        ("weight_decay", C.c_double),
+        ("momentum", C.c_double),
+        ("dampening", C.c_double),
+        ("max_norm", C.c_double),
+        ("ntensors", C.c_int32),
+        ("dtype", C.c_int32),
+        ("kind", C.c_int32),
+        ("slot_base", C.c_int32),
+        ("flags", C.c_uint32),
+        ("reserved_", C.c_int32),
+    ]
+
+
 _vp, _i, _i64, _u32, _u64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
 
 # name -> (restype, argtypes) of every symbol the header declares.  `stream` is the trailing
@@ -449,13 +501,20 @@ DQN_PROTOTYPES = {
     "hk_polyak_update": (C.c_int, [C.POINTER(hk_polyak_desc), _vp]),
 }
 
+# the entry points of include/hironaka_hip_optim.h: the device library's only, as above
+OPTIM_PROTOTYPES = {
+    "hk_optim_workspace_bytes": (C.c_uint64, [_i64]),
+    "hk_optim_prepare": (C.c_int, [C.POINTER(hk_optim_desc), _vp]),
+    "hk_optim_apply": (C.c_int, [C.POINTER(hk_optim_desc), _vp]),
+}
+
 
 def bind(lib: C.CDLL, prototypes=None) -> None:
     """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES, TREE_PROTOTYPES, ENV_PROTOTYPES,
-    REPLAY_PROTOTYPES and DQN_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
+    REPLAY_PROTOTYPES, DQN_PROTOTYPES and OPTIM_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
     if prototypes is None:
         prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES, **TREE_PROTOTYPES, **ENV_PROTOTYPES,
-                      **REPLAY_PROTOTYPES, **DQN_PROTOTYPES}
+                      **REPLAY_PROTOTYPES, **DQN_PROTOTYPES, **OPTIM_PROTOTYPES}
     for name, (res, args) in prototypes.items():
         fn = getattr(lib, name)
         fn.restype = res

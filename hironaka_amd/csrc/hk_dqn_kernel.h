@@ -12,15 +12,10 @@
 // with consecutive lanes on consecutive elements, the row's action and gradient fetched from lane i.  A > 64: a row per
 // pass, every lane on columns lane, lane + 64, ...
 //
-// The loss crosses workgroups, which nothing else in this library does: a workgroup's rows are added in double (a fixed
-// tree: lane, wave, workgroup) and ONE lane stores the sum in the workspace slot of the workgroup with an agent-scope
-// atomic store (write-through), waits for the store to have left (s_waitcnt vmcnt(0)) and only then draws the ticket
-// with an agent-scope fetch_add.  The workgroup whose ticket is the last learns so from the value the add returned: by
-// then every other workgroup's slot has drained.  Its lane 0 runs an agent-scope acquire and waits for it, the
-// workgroup passes a barrier, and every slot is read with an agent-scope atomic load (past L1, never a plain load, never
-// through the scalar cache); lane 0 adds them in index order.  A per-XCD L2 is not coherent with the others and a CU's L1
-// is never refreshed by another CU's stores, so a plain store or load anywhere on that path could be stale.  Nobody
-// waits on anybody; the last workgroup zeroes the ticket for the next launch.
+// The loss crosses workgroups: a workgroup's rows are added in double (a fixed tree: lane, wave, workgroup) and ONE lane
+// leaves the sum in the workspace slot of the workgroup and draws a ticket; the workgroup whose ticket is the last adds
+// the slots in index order (hk_ticket.h, which hk_optim_kernel.h shares: the stores, the loads and why none of them is
+// a plain one).  Nobody waits on anybody; the last workgroup zeroes the ticket for the next launch.
 //
 // polyak_kernel.  The host dealt the workgroups to (tensor, chunk) pairs; the table is the kernel's argument.  A
 // workgroup finds its tensor by bisection over the tensors' first workgroups and updates its chunk: 16 bytes per lane
@@ -29,6 +24,8 @@
 #pragma once
 
 #include "hk_common.h"
+#include "hk_table.h"
+#include "hk_ticket.h"
 
 namespace hk {
 
@@ -37,7 +34,7 @@ constexpr int kDqnTile = HK_DQN_TILE_ROWS;
 constexpr int kDqnWaves = kDqnThreads / kWave;
 constexpr int kDqnWaveRows = kDqnTile / kDqnWaves;  // rows per wave
 constexpr int kDqnFlight = 4;     // independent loads of next_q a lane has in flight
-constexpr int kDqnSlotOffset = 2;  // workspace words (8 bytes each) in front of the slots: the ticket, one spare
+constexpr int kDqnSlotOffset = kTicketSlotOffset;
 
 static_assert(kDqnTile % kDqnWaves == 0 && kDqnWaveRows <= kWave, "a lane per row of the wave's share");
 
@@ -63,13 +60,6 @@ struct DqnArgs {
 template <typename T>
 __device__ __forceinline__ T nan_max(T a, T b) {
   return (b > a || b != b) ? b : a;
-}
-
-__device__ __forceinline__ double slot_load(const unsigned long long* p) {
-  return __longlong_as_double((long long)__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-__device__ __forceinline__ void slot_store(unsigned long long* p, double v) {
-  __hip_atomic_store(p, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 template <typename T>
@@ -192,33 +182,14 @@ __global__ void __launch_bounds__(kDqnThreads) dqn_td_kernel(DqnArgs a) {
 #pragma unroll
     for (int w = 1; w < kDqnWaves; ++w) part += s_wave[w];
     slot_store(a.ws + kDqnSlotOffset + blockIdx.x, part);
-    // the slot has left this CU before the ticket says so (inline asm: the compiler may not drop or move it)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long old = __hip_atomic_fetch_add(a.ws, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = old == (unsigned long long)gridDim.x - 1ull;
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    s_last = last;
+    s_last = ticket_draw(a.ws, gridDim.x);
   }
   __syncthreads();
   if (!s_last) return;  // the same for the whole workgroup
-  double total = 0.0;
-  const unsigned slots = gridDim.x;
-  for (unsigned base = 0; base < slots; base += kDqnThreads) {
-    const unsigned i = base + (unsigned)tid;
-    s_slot[tid] = i < slots ? slot_load(a.ws + kDqnSlotOffset + i) : 0.0;
-    __syncthreads();
-    if (tid == 0) {
-      const unsigned n = slots - base < (unsigned)kDqnThreads ? slots - base : (unsigned)kDqnThreads;
-      for (unsigned k = 0; k < n; ++k) total += s_slot[k];
-    }
-    __syncthreads();
-  }
+  const double total = ticket_sum<kDqnThreads>(a.ws, gridDim.x, s_slot, tid);
   if (tid == 0) {
     *static_cast<T*>(a.loss) = (T)(total / (double)a.batch);
-    __hip_atomic_store(a.ws, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ticket_reset(a.ws);
   }
 }
 
@@ -246,17 +217,6 @@ struct PolyakArgs {
 };
 
 template <typename T>
-__device__ __forceinline__ T hk_fma(T a, T b, T c);
-template <>
-__device__ __forceinline__ float hk_fma<float>(float a, float b, float c) {
-  return fmaf(a, b, c);
-}
-template <>
-__device__ __forceinline__ double hk_fma<double>(double a, double b, double c) {
-  return fma(a, b, c);
-}
-
-template <typename T>
 __device__ __forceinline__ T polyak_one(T tau, T rest, T s, T d) {
   const T scaled = d * rest;  // rounded: -ffp-contract=off keeps it out of the fma
   return hk_fma<T>(tau, s, scaled);
@@ -267,12 +227,7 @@ __global__ void __launch_bounds__(kPolyakThreads) polyak_kernel(PolyakArgs a) {
   constexpr int VE = 16 / (int)sizeof(T);  // elements per transfer
   typedef T Vec __attribute__((ext_vector_type(VE)));
   const int tid = threadIdx.x;
-  // the last tensor whose first workgroup is <= blockIdx.x (tensors without elements have no workgroup)
-  int lo = 0, hi = a.ntensors;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (a.first[mid] <= blockIdx.x) lo = mid; else hi = mid;
-  }
+  const int lo = table_find(a.first, a.ntensors, blockIdx.x);
   const PolyakTensor t = a.t[lo];
   const int64_t chunk = (int64_t)(blockIdx.x - a.first[lo]);
   const T tau = (T)a.tau, rest = (T)a.rest;

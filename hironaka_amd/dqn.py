@@ -91,7 +91,9 @@ def td_target(next_q: torch.Tensor, rewards: torch.Tensor, dones: torch.Tensor, 
 def fit_network(q_net: nn.Module, q_net_target: nn.Module, optimizer: torch.optim.Optimizer, replay_buffer,
                 batch_size: int, gamma: float, max_grad_norm: float) -> torch.Tensor:
     """One step of ``DQNTrainer._fit_network``: sample, target net under ``no_grad``, TD loss, ``zero_grad``,
-    ``backward``, ``clip_grad_norm_``, ``step``.  Returns the loss tensor without reading it."""
+    ``backward``, ``clip_grad_norm_``, ``step`` (the last two in two launches where the optimizer is one of
+    ``hironaka_amd.optim``, whose parameters are then taken to be ``q_net``'s).  Returns the loss tensor without reading
+    it."""
     observations, actions, rewards, dones, next_observations = replay_buffer.sample(batch_size)
     with torch.no_grad():
         next_q_values = q_net_target(next_observations)
@@ -99,6 +101,9 @@ def fit_network(q_net: nn.Module, q_net_target: nn.Module, optimizer: torch.opti
     loss = td_loss(current_q_values, next_q_values, actions, rewards, dones, gamma)
     optimizer.zero_grad()
     loss.backward()
-    nn.utils.clip_grad_norm_(q_net.parameters(), max_grad_norm)
-    optimizer.step()
+    if hasattr(optimizer, "clip_and_step"):  # hironaka_amd.optim.Adam / SGD: the two lines below in two launches
+        optimizer.clip_and_step(max_grad_norm)
+    else:
+        nn.utils.clip_grad_norm_(q_net.parameters(), max_grad_norm)
+        optimizer.step()
     return loss

@@ -1394,6 +1394,198 @@ def polyak_update(srcs: Sequence[torch.Tensor], dsts: Sequence[torch.Tensor], ta
             check(lib().hk_polyak_update(C.byref(d), stream), "hk_polyak_update")
 
 
+# ---- the optimiser step: gradient clipping + Adam / SGD of a parameter list in two launches per 64 tensors ----------
+
+OPTIM_KINDS = {"scale": A.HK_OPTIM_SCALE, "sgd": A.HK_OPTIM_SGD, "adam": A.HK_OPTIM_ADAM}
+_OPTIM_WORKSPACES: Dict[Tuple[torch.device, int], torch.Tensor] = {}
+_OPTIM_RETIRED_WORKSPACES: list = []  # outgrown buffers: a hipGraph captured earlier may still hold their address
+_OPTIM_STATE_FIELDS = tuple(name for name, _ in A.hk_optim_state._fields_)
+
+
+def optim_workgroups(numels: Sequence[int], dtype: torch.dtype) -> int:
+    """the workgroups of hk_optim_prepare over gradients of these sizes: one per HK_OPTIM_CHUNK_BYTES of each"""
+    esz = 8 if dtype == torch.float64 else 4
+    return sum((int(n) * esz + A.HK_OPTIM_CHUNK_BYTES - 1) // A.HK_OPTIM_CHUNK_BYTES for n in numels)
+
+
+def optim_workspace(total_workgroups: int, device) -> torch.Tensor:
+    """a zeroed workspace of the caller's own for optim_prepare chains of up to `total_workgroups` workgroups (uint8; the
+    ticket and one slot per workgroup).  Launches that share one belong on one stream."""
+    need = int(lib().hk_optim_workspace_bytes(int(total_workgroups)))
+    if need == 0:
+        raise ValueError(f"total_workgroups must be in [0, 2^31). Got {total_workgroups}.")
+    return torch.zeros(need, dtype=torch.uint8, device=device)
+
+
+def _optim_workspace(dev: torch.device, total_workgroups: int) -> torch.Tensor:
+    """the per-(device, stream) workspace of optim_prepare calls that bring none: zeroed once, every chain leaves the
+    ticket zero; an outgrown one is retired, never freed; growing inside a stream capture is refused."""
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+    need = int(lib().hk_optim_workspace_bytes(total_workgroups))
+    ws = _OPTIM_WORKSPACES.get(key)
+    if ws is None or ws.numel() < need:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("optim_prepare needs a larger workspace than this stream has, inside a stream capture: "
+                               "run one step before capturing, or bring workspace=ops.optim_workspace(...)")
+        if ws is not None:
+            _OPTIM_RETIRED_WORKSPACES.append(ws)
+        ws = torch.zeros(max(need, 1 << 12), dtype=torch.uint8, device=dev)
+        _OPTIM_WORKSPACES[key] = ws
+    return ws
+
+
+def optim_state(device, step: int = 0, beta1_pow: float = 1.0, beta2_pow: float = 1.0) -> torch.Tensor:
+    """the 64-byte state block of one parameter group on the device (hk_optim_state as 8 float64 words; word 0 holds the
+    int64 step count)"""
+    block = torch.zeros(len(_OPTIM_STATE_FIELDS), dtype=torch.float64)
+    block[1], block[2] = beta1_pow, beta2_pow
+    block.view(torch.int64)[0] = int(step)
+    return block.to(device)
+
+
+def optim_state_read(state: torch.Tensor) -> dict:
+    """the state block's fields as Python numbers (a copy to the host: synchronises)"""
+    host = state.detach().cpu()
+    out = {name: float(host[k]) for k, name in enumerate(_OPTIM_STATE_FIELDS)}
+    out["step"] = int(host.view(torch.int64)[0])
+    return out
+
+
+class OptimChain:
+    """The descriptors of one parameter list for optim_prepare / optim_apply: HK_OPTIM_MAX_TENSORS entries per launch,
+    the launches of a chain one after the other on the current stream.  Built once per set of addresses (the optimisers
+    keep theirs while the addresses stay); it holds the tensors alive.
+
+    kind: "scale", "sgd" or "adam".  grads, and where the kind uses them params, state1 (exp_avg / momentum buffer) and
+    state2 (exp_avg_sq): contiguous float32 or float64 tensors of one dtype on one HIP device (anything else is a
+    TypeError), entry by entry of one size.  state: what optim_state(...) returns.  workspace: optim_workspace(...) of
+    the caller's own; None: one per device and stream.  hold_grads=False: the chain does not keep the gradient tensors
+    alive: bring them with set_grads(...) before every use."""
+
+    def __init__(self, kind: str, grads: Sequence[torch.Tensor], params: Optional[Sequence[torch.Tensor]] = None,
+                 state1: Optional[Sequence[torch.Tensor]] = None, state2: Optional[Sequence[torch.Tensor]] = None, *,
+                 state: torch.Tensor, workspace: Optional[torch.Tensor] = None, hold_grads: bool = True):
+        if kind not in OPTIM_KINDS:
+            raise ValueError(f"kind must be one of {sorted(OPTIM_KINDS)}. Got {kind!r}.")
+        grads = list(grads)
+        columns = [("grads", grads)]
+        for name, col in (("params", params), ("state1", state1), ("state2", state2)):
+            col = list(col) if col is not None else None
+            if col is not None and len(col) != len(grads):
+                raise ValueError(f"{len(grads)} gradients but {len(col)} {name}.")
+            columns.append((name, col))
+        _require_device(state, "state")
+        if state.dtype != torch.float64 or state.numel() != len(_OPTIM_STATE_FIELDS) or not state.is_contiguous():
+            raise ValueError("state must be what optim_state(device) returns.")
+        dev = state.device
+        dtype = grads[0].dtype if grads else torch.float32
+        for name, col in columns:
+            for k, x in enumerate(col or ()):
+                if not (isinstance(x, torch.Tensor) and x.is_cuda and x.layout == torch.strided and x.dtype == dtype
+                        and x.device == dev and x.is_contiguous() and dtype in (torch.float32, torch.float64)):
+                    _require_device(x, f"{name}[{k}]")
+                    raise TypeError(f"every tensor must be a contiguous float32 or float64 tensor of one dtype on one "
+                                    f"device ({dtype} on {dev}). {name}[{k}] is {x.dtype} on {x.device}, layout "
+                                    f"{x.layout}, strides {x.stride() if x.layout == torch.strided else None}.")
+                if x.numel() != grads[k].numel():
+                    raise ValueError(f"entry {k}: {grads[k].numel()} gradient elements but {x.numel()} in {name}.")
+        if workspace is not None:
+            _require_device(workspace, "workspace")
+            if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != dev:
+                raise ValueError("workspace must be what optim_workspace(total_workgroups, device) returns.")
+        self.kind, self.device, self.dtype, self.state, self.workspace = kind, dev, dtype, state, workspace
+        # hold_grads=False: the caller brings the gradients on every use (set_grads): backward allocates new ones after
+        # zero_grad(set_to_none=True), and held here the old ones would stay alive next to them
+        self.keep = columns if hold_grads else columns[1:]
+        self.numels = [g.numel() for g in grads]
+        self.total_workgroups = optim_workgroups([g.numel() for g in grads], dtype)
+        if workspace is not None and workspace.numel() < lib().hk_optim_workspace_bytes(self.total_workgroups):
+            raise ValueError(f"workspace is smaller than optim_workspace({self.total_workgroups}, device).")
+        self.descs = []
+        per, slot_base = A.HK_OPTIM_MAX_TENSORS, 0
+        cols = dict(columns)
+        for at in range(0, max(len(grads), 1), per):
+            d = A.hk_optim_desc()
+            flat = []  # param, grad, state1, state2, numel of every entry as they lie in memory
+            for k in range(at, min(at + per, len(grads))):
+                flat += [cols[name][k].data_ptr() if cols[name] is not None else 0
+                         for name in ("params", "grads", "state1", "state2")]
+                flat.append(grads[k].numel())
+            if flat:
+                (C.c_int64 * len(flat)).from_address(C.addressof(d))[:] = flat
+            d.ntensors, d.dtype, d.kind, d.slot_base = len(flat) // 5, _TORCH2HK[dtype], OPTIM_KINDS[kind], slot_base
+            d.state = state.data_ptr()
+            slot_base += optim_workgroups([grads[k].numel() for k in range(at, min(at + per, len(grads)))], dtype)
+            self.descs.append(d)
+        # the descriptors' tables as int64 words, five per entry: word 1 of an entry is its gradient's address
+        self._words = [(C.c_int64 * (5 * d.ntensors)).from_address(C.addressof(d)) for d in self.descs]
+        self._lr_dev = None
+
+    def set_grads(self, grads: Sequence[torch.Tensor]) -> None:
+        """point the descriptors at these gradients: the same number, sizes, dtype and device as the chain was built
+        with, each contiguous (anything else is a TypeError / ValueError); everything else of the chain stays"""
+        if len(grads) != len(self.numels):
+            raise ValueError(f"the chain has {len(self.numels)} entries. Got {len(grads)} gradients.")
+        dtype, dev = self.dtype, self.device
+        for k, g in enumerate(grads):
+            if not (g.dtype == dtype and g.device == dev and g.layout == torch.strided and g.is_contiguous()):
+                raise TypeError(f"grads[{k}] must be a contiguous {dtype} tensor on {dev}. Got {g.dtype} on {g.device}, "
+                                f"layout {g.layout}.")
+            if g.numel() != self.numels[k]:
+                raise ValueError(f"entry {k}: the chain has {self.numels[k]} elements, the gradient {g.numel()}.")
+        per = A.HK_OPTIM_MAX_TENSORS
+        for at, words in zip(range(0, len(grads), per), self._words):
+            words[1::5] = [g.data_ptr() for g in grads[at:at + per]]
+        if self.keep[0][0] == "grads":
+            self.keep[0] = ("grads", list(grads))
+
+
+def optim_prepare(chain: OptimChain, *, max_norm: float = float("inf"), lr=0.0, beta1: float = 0.0, beta2: float = 0.0,
+                  advance: bool = False, clip: bool = True) -> None:
+    """hk_optim_prepare over the chain (include/hironaka_hip_optim.h): one pass over the gradients that leaves
+    total_norm, clip_coef = min(1, max_norm / (total_norm + 1e-6)) (clip=False: 1 whatever the norm is) and, with
+    `advance`, the next step's count, running powers of the betas, -lr / (1 - beta1^step) and sqrt(1 - beta2^step) in the
+    chain's state block.  lr: a float, or a one-element tensor on the device (a learning-rate schedule under graph
+    replay): a float64 one is read where it lies, one of another dtype is converted first, which costs a launch and an
+    allocation per call.  Nothing here synchronises."""
+    dev = chain.device
+    lr_dev = None
+    if isinstance(lr, torch.Tensor):
+        _require_device(lr, "lr")
+        if lr.numel() != 1 or lr.device != dev:
+            raise ValueError(f"lr must be a float or a one-element tensor on {dev}. Got {tuple(lr.shape)} on {lr.device}.")
+        lr_dev = lr.detach().reshape(1)
+        if lr_dev.dtype != torch.float64:
+            lr_dev = lr_dev.to(torch.float64)
+        chain._lr_dev = lr_dev  # alive until the next call
+    with torch.cuda.device(dev):
+        ws = chain.workspace if chain.workspace is not None else _optim_workspace(dev, chain.total_workgroups)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        for k, d in enumerate(chain.descs):
+            d.workspace = ws.data_ptr()
+            d.lr_dev = lr_dev.data_ptr() if lr_dev is not None else None
+            d.lr = 0.0 if lr_dev is not None else float(lr)
+            d.beta1, d.beta2, d.max_norm = float(beta1), float(beta2), float(max_norm)
+            d.flags = ((A.HK_OPTIM_LAST if k == len(chain.descs) - 1 else 0) | (A.HK_OPTIM_ADVANCE if advance else 0)
+                       | (0 if clip else A.HK_OPTIM_NO_CLIP))
+            check(lib().hk_optim_prepare(C.byref(d), stream), "hk_optim_prepare")
+
+
+def optim_apply(chain: OptimChain, *, eps: float = 1e-8, weight_decay: float = 0.0, momentum: float = 0.0,
+                dampening: float = 0.0, nesterov: bool = False, beta1: float = 0.9, beta2: float = 0.999,
+                keep_grads: bool = False) -> None:
+    """hk_optim_apply over the chain with the scalars optim_prepare left in its state block: "scale" grad *= clip_coef;
+    "sgd" / "adam" clip, then torch.optim.SGD's / Adam's update (the rules: include/hironaka_hip_optim.h).  The clipped
+    gradient is written back unless keep_grads.  Nothing here synchronises."""
+    with torch.cuda.device(chain.device):
+        stream = C.c_void_p(torch.cuda.current_stream(chain.device).cuda_stream)
+        for d in chain.descs:
+            d.eps, d.weight_decay, d.momentum, d.dampening = float(eps), float(weight_decay), float(momentum), float(dampening)
+            d.beta1, d.beta2 = float(beta1), float(beta2)
+            d.flags = (A.HK_OPTIM_KEEP_GRADS if keep_grads else 0) | (A.HK_OPTIM_NESTEROV if nesterov else 0)
+            check(lib().hk_optim_apply(C.byref(d), stream), "hk_optim_apply")
+
+
 # ---- one level of a game tree under any host (hk_tree_expand) -------------------------------------------------------
 
 TreeExpandResult = collections.namedtuple(

@@ -631,5 +631,7 @@ int hk_search_morin_play(const hk_morin_play_desc* desc, void* stream);
 #include "hironaka_hip_replay.h"
 /* within ABI 6: hk_dqn_td / hk_polyak_update, likewise */
 #include "hironaka_hip_dqn.h"
+/* within ABI 6: hk_optim_prepare / hk_optim_apply, likewise */
+#include "hironaka_hip_optim.h"
 
 #endif /* HIRONAKA_HIP_H */
