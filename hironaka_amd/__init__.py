@@ -4,7 +4,9 @@ __version__ = "0.1.0"
 _VEC_ENVS = ("HironakaHostVecEnv", "HironakaAgentVecEnv")
 _DQN = ("fit_network", "td_loss", "td_target", "update_target_net", "polyak_update", "zip_equal")
 _OPTIM = ("Adam", "SGD", "clip_grad_norm_", "from_torch")
-__all__ = list(_VEC_ENVS) + ["ReplayBuffer"] + list(_DQN) + list(_OPTIM)
+_NETS = ("create_mlp", "expand_net_list", "FusedSequential", "fuse", "BaseFeaturesExtractor", "HostFeatureExtractor",
+         "AgentFeatureExtractor")
+__all__ = list(_VEC_ENVS) + ["ReplayBuffer"] + list(_DQN) + list(_OPTIM) + list(_NETS)
 
 
 def __getattr__(name):
@@ -21,4 +23,7 @@ def __getattr__(name):
     if name in _OPTIM:
         from . import optim
         return getattr(optim, name)
+    if name in _NETS:
+        from . import nets
+        return getattr(nets, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -96,6 +96,13 @@ HK_OPTIM_MAX_TENSORS, HK_OPTIM_CHUNK_BYTES, HK_OPTIM_STATE_BYTES = 64, 16384, 64
 HK_OPTIM_SCALE, HK_OPTIM_SGD, HK_OPTIM_ADAM = 0, 1, 2
 HK_OPTIM_LAST, HK_OPTIM_ADVANCE, HK_OPTIM_KEEP_GRADS, HK_OPTIM_NESTEROV, HK_OPTIM_NO_CLIP = 1, 2, 4, 8, 16
 
+# hk_mlp_forward: the table's length, the widest layer, the row tiles and the largest batch on the small one; descriptor
+# flags; the layer flag
+HK_MLP_MAX_LAYERS, HK_MLP_MAX_WIDTH = 32, 256
+HK_MLP_TILE_SMALL, HK_MLP_TILE_LARGE, HK_MLP_TILE_CROSSOVER = 16, 64, 4096
+HK_MLP_INPUT_RELU, HK_MLP_FORCE_TILE_SMALL, HK_MLP_FORCE_TILE_LARGE = 1, 2, 4
+HK_MLP_RELU = 1
+
 SEMANTICS = {"jax": HK_SEM_JAX, "torch": HK_SEM_TORCH, "list": HK_SEM_LIST}
 
 
@@ -407,6 +414,45 @@ class hk_optim_desc(C.Structure):
     ]
 
 
+class hk_mlp_layer(C.Structure):
+    _fields_ = [
+        ("weight", C.c_void_p),
+        ("bias", C.c_void_p),
+        ("bn_mean", C.c_void_p),
+        ("bn_var", C.c_void_p),
+        ("bn_weight", C.c_void_p),
+        ("bn_bias", C.c_void_p),
+        ("eps", C.c_float),
+        ("k", C.c_int32),
+        ("n", C.c_int32),
+        ("flags", C.c_uint32),
+    ]
+
+
+class hk_mlp_desc(C.Structure):
+    _fields_ = [
+        ("x0", C.c_void_p),
+        ("x1", C.c_void_p),
+        ("out", C.c_void_p),
+        ("in_bn_mean", C.c_void_p),
+        ("in_bn_var", C.c_void_p),
+        ("in_bn_weight", C.c_void_p),
+        ("in_bn_bias", C.c_void_p),
+        ("x0_stride", C.c_int64),
+        ("x1_stride", C.c_int64),
+        ("out_stride", C.c_int64),
+        ("batch", C.c_int32),
+        ("k0", C.c_int32),
+        ("k1", C.c_int32),
+        ("nlayers", C.c_int32),
+        ("dtype", C.c_int32),
+        ("flags", C.c_uint32),
+        ("in_eps", C.c_float),
+        ("reserved_", C.c_int32),
+        ("layer", hk_mlp_layer * HK_MLP_MAX_LAYERS),
+    ]
+
+
 _vp, _i, _i64, _u32, _u64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
 
 # name -> (restype, argtypes) of every symbol the header declares.  `stream` is the trailing
@@ -508,13 +554,19 @@ OPTIM_PROTOTYPES = {
     "hk_optim_apply": (C.c_int, [C.POINTER(hk_optim_desc), _vp]),
 }
 
+# the entry points of include/hironaka_hip_mlp.h: the device library's only, as above
+MLP_PROTOTYPES = {
+    "hk_mlp_row_tile": (C.c_int, [_i64]),
+    "hk_mlp_forward": (C.c_int, [C.POINTER(hk_mlp_desc), _vp]),
+}
+
 
 def bind(lib: C.CDLL, prototypes=None) -> None:
     """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES, TREE_PROTOTYPES, ENV_PROTOTYPES,
-    REPLAY_PROTOTYPES, DQN_PROTOTYPES and OPTIM_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
+    REPLAY_PROTOTYPES, DQN_PROTOTYPES, OPTIM_PROTOTYPES and MLP_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
     if prototypes is None:
         prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES, **TREE_PROTOTYPES, **ENV_PROTOTYPES,
-                      **REPLAY_PROTOTYPES, **DQN_PROTOTYPES, **OPTIM_PROTOTYPES}
+                      **REPLAY_PROTOTYPES, **DQN_PROTOTYPES, **OPTIM_PROTOTYPES, **MLP_PROTOTYPES}
     for name, (res, args) in prototypes.items():
         fn = getattr(lib, name)
         fn.restype = res

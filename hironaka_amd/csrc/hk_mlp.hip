@@ -1,0 +1,106 @@
+// C ABI of hk_mlp_forward (include/hironaka_hip_mlp.h, an addition within ABI 6): argument validation and launch of
+// hk::mlp_kernel.  No allocation, no synchronisation; every status is decided before the launch.
+#include "hk_mlp_kernel.h"
+
+using namespace hk;
+
+namespace {
+
+constexpr uint32_t kDescFlags = HK_MLP_INPUT_RELU | HK_MLP_FORCE_TILE_SMALL | HK_MLP_FORCE_TILE_LARGE;
+constexpr uint32_t kLayerFlags = HK_MLP_RELU;
+
+// [p, p + bytes) and [q, q + bytes2) share a byte
+bool overlap(const void* p, uint64_t bytes, const void* q, uint64_t bytes2) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return p && q && bytes > 0 && bytes2 > 0 && a < b + bytes2 && b < a + bytes;
+}
+
+// the bytes from the first to the last element of `batch` rows of `width` floats, `stride` elements apart
+uint64_t span(int64_t batch, int64_t stride, int64_t width) {
+  return batch > 0 ? ((uint64_t)(batch - 1) * (uint64_t)stride + (uint64_t)width) * sizeof(float) : 0;
+}
+
+// out's rows share a byte with the rows of an input.  Rows of one stride that holds both widths are records side by
+// side: they meet only where the windows meet inside a record (any two records apart: the batch is not looked at);
+// everything else is judged by the spans from the first to the last element.
+bool rows_overlap(const hk_mlp_desc* q, int64_t n, const void* x, int64_t stride, int64_t k) {
+  if (!overlap(q->out, span(q->batch, q->out_stride, n), x, span(q->batch, stride, k))) return false;
+  if (q->batch == 1 || stride != q->out_stride || stride < k) return true;
+  const int64_t diff = (int64_t)((reinterpret_cast<intptr_t>(q->out) - reinterpret_cast<intptr_t>(x)) / 4);
+  const int64_t r = ((diff % stride) + stride) % stride;  // out's window starts r elements into x's record
+  return r < k || r + n > stride;
+}
+
+bool has_bn(const hk_mlp_layer& L) { return L.bn_mean || L.bn_var || L.bn_weight || L.bn_bias; }
+bool has_in_bn(const hk_mlp_desc* q) { return q->in_bn_mean || q->in_bn_var || q->in_bn_weight || q->in_bn_bias; }
+
+int validate(const hk_mlp_desc* q) {
+  if (!q) return HK_ERR_NULL;
+  if (q->dtype != HK_F32) return HK_ERR_UNSUPPORTED;
+  if (q->flags & ~kDescFlags) return HK_ERR_UNSUPPORTED;
+  if ((q->flags & HK_MLP_FORCE_TILE_SMALL) && (q->flags & HK_MLP_FORCE_TILE_LARGE)) return HK_ERR_UNSUPPORTED;
+  if (q->nlayers < 1 || q->nlayers > HK_MLP_MAX_LAYERS) return HK_ERR_SHAPE;
+  if (q->batch < 0 || q->k0 < 1 || q->k1 < 0 || q->x0_stride < 0 || q->x1_stride < 0) return HK_ERR_SHAPE;
+  int64_t width = (int64_t)q->k0 + q->k1;
+  for (int l = 0; l < q->nlayers; ++l) {
+    const hk_mlp_layer& L = q->layer[l];
+    if (L.flags & ~kLayerFlags) return HK_ERR_UNSUPPORTED;
+    if (L.k < 1 || L.k > HK_MLP_MAX_WIDTH || L.n < 1 || L.n > HK_MLP_MAX_WIDTH || L.k != width) return HK_ERR_SHAPE;
+    width = L.n;
+  }
+  if (q->out_stride < width) return HK_ERR_SHAPE;
+  if (!q->x0 || !q->out || (q->k1 > 0 && !q->x1)) return HK_ERR_NULL;
+  if (has_in_bn(q) && (!q->in_bn_mean || !q->in_bn_var)) return HK_ERR_NULL;
+  for (int l = 0; l < q->nlayers; ++l) {
+    const hk_mlp_layer& L = q->layer[l];
+    if (!L.weight || (has_bn(L) && (!L.bn_mean || !L.bn_var))) return HK_ERR_NULL;
+  }
+  if (!all_aligned({q->x0, q->x1, q->out, q->in_bn_mean, q->in_bn_var, q->in_bn_weight, q->in_bn_bias}, 4))
+    return HK_ERR_ALIGN;
+  for (int l = 0; l < q->nlayers; ++l) {
+    const hk_mlp_layer& L = q->layer[l];
+    if (!all_aligned({L.weight, L.bias, L.bn_mean, L.bn_var, L.bn_weight, L.bn_bias}, 4)) return HK_ERR_ALIGN;
+  }
+  const uint64_t out_bytes = span(q->batch, q->out_stride, width);
+  if (rows_overlap(q, width, q->x0, q->x0_stride, q->k0)) return HK_ERR_UNSUPPORTED;
+  if (q->k1 > 0 && rows_overlap(q, width, q->x1, q->x1_stride, q->k1)) return HK_ERR_UNSUPPORTED;
+  for (const void* p : {q->in_bn_mean, q->in_bn_var, q->in_bn_weight, q->in_bn_bias})
+    if (overlap(q->out, out_bytes, p, (uint64_t)(q->k0 + q->k1) * sizeof(float))) return HK_ERR_UNSUPPORTED;
+  for (int l = 0; l < q->nlayers; ++l) {
+    const hk_mlp_layer& L = q->layer[l];
+    const uint64_t vec = (uint64_t)L.n * sizeof(float);
+    if (overlap(q->out, out_bytes, L.weight, vec * (uint64_t)L.k)) return HK_ERR_UNSUPPORTED;
+    for (const void* p : {L.bias, L.bn_mean, L.bn_var, L.bn_weight, L.bn_bias})
+      if (overlap(q->out, out_bytes, p, vec)) return HK_ERR_UNSUPPORTED;
+  }
+  return HK_OK;
+}
+
+template <int TR>
+int launch(const hk_mlp_desc& q, hipStream_t stream) {
+  constexpr size_t lds = mlp_lds_bytes(TR);
+  if (lds > 48 * 1024) {  // (static + dynamic LDS beyond 64 KiB is a per-function opt-in: idempotent, cheap)
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_kernel<TR>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds) != hipSuccess) {
+      (void)hipGetLastError();
+      return HK_ERR_LAUNCH;
+    }
+  }
+  return launch_kernel(mlp_kernel<TR>, dim3((unsigned)workgroups(q.batch, TR)), dim3(kWave * mlp_waves(TR)), lds, stream, q);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hk_mlp_row_tile(int64_t batch) { return mlp_row_tile(batch); }
+
+int hk_mlp_forward(const hk_mlp_desc* q, void* stream) {
+  const int bad = validate(q);
+  if (bad != HK_OK) return bad;
+  if (q->batch == 0) return HK_OK;
+  if (mlp_row_tile(q->batch, q->flags) == HK_MLP_TILE_LARGE) return launch<HK_MLP_TILE_LARGE>(*q, (hipStream_t)stream);
+  return launch<HK_MLP_TILE_SMALL>(*q, (hipStream_t)stream);
+}
+
+}  // extern "C"

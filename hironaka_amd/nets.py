@@ -1,0 +1,297 @@
+"""The Q-networks of the DQN trainers (the reference's ``hironaka/trainer/nets.py``): ``create_mlp`` and the two feature
+extractors under the reference's names, with the eval-mode forward of the stack in ONE launch.
+
+``create_mlp`` returns a ``FusedSequential``: an ``nn.Sequential`` with exactly the children the reference's function
+produces (``state_dict`` keys, ``deepcopy``, ``.to()``, ``parameters()``, checkpoints: all ``nn.Sequential``'s), whose
+``forward`` hands the whole stack to ``ops.mlp_forward`` (``hk_mlp_forward``, include/hironaka_hip_mlp.h) where that
+serves it and runs ``nn.Sequential.forward`` unchanged where it does not.  Training-mode forward and backward are
+torch's."""
+import abc
+from typing import Any, Dict, List, NamedTuple, Optional, Tuple, Type, Union
+
+import torch
+from torch import nn
+
+from . import _abi as A
+
+TensorDict = Dict[Union[str, int], torch.Tensor]
+
+
+def expand_net_list(net_arch: List[Any]) -> List[Any]:
+    """`net_arch` flattened: every {"repeat": n, "net_arch": [...]} entry is replaced by n copies of its own flattened
+    list, to any depth; every other entry stays where it is"""
+    flat: List[Any] = []
+    for entry in net_arch:
+        if not isinstance(entry, dict):
+            flat.append(entry)
+            continue
+        missing = {"repeat", "net_arch"} - set(entry)
+        assert not missing, f"a repeated part of net_arch needs 'repeat' and 'net_arch'; {sorted(missing)} missing in {entry}"
+        assert isinstance(entry["net_arch"], list), f"a repeated part's 'net_arch' is a list, not {type(entry['net_arch'])}"
+        flat.extend(expand_net_list(entry["net_arch"]) * entry["repeat"])
+    return flat
+
+
+class ResidualBlock(nn.Module):
+    """lin1 -> bn1 -> relu -> lin2 -> bn2, plus the input (through `down_sample` where the widths differ).  Plain torch:
+    a stack with one of these takes torch's path."""
+
+    def __init__(self, in_channels: int, out_channels: int, down_sample: Optional[nn.Module] = None):
+        super().__init__()
+        self.lin1 = nn.Linear(in_channels, out_channels)
+        self.bn1 = nn.BatchNorm1d(out_channels)
+        self.relu = nn.ReLU(inplace=True)
+        self.lin2 = nn.Linear(out_channels, out_channels)
+        self.bn2 = nn.BatchNorm1d(out_channels)
+        self.down_sample = down_sample
+
+    def forward(self, x):
+        out = self.bn2(self.lin2(self.relu(self.bn1(self.lin1(x)))))
+        out += self.down_sample(x) if self.down_sample else x
+        return out
+
+
+def make_residual(in_channels: int, out_channels: int) -> ResidualBlock:
+    if in_channels == out_channels:
+        return ResidualBlock(in_channels, out_channels)
+    return ResidualBlock(in_channels, out_channels,
+                         nn.Sequential(nn.Linear(in_channels, out_channels), nn.BatchNorm1d(out_channels)))
+
+
+class BaseFeaturesExtractor(nn.Module, abc.ABC):
+    """A head of `create_mlp`: `forward(observations)` gives [batch, feature_dim] rows."""
+
+    def __init__(self, input_dim: int):
+        super().__init__()
+        self.input_dim = input_dim
+
+    @property
+    def feature_dim(self) -> int:
+        return self.input_dim
+
+    @abc.abstractmethod
+    def forward(self, observations) -> torch.Tensor:
+        pass
+
+
+class AgentFeatureExtractor(BaseFeaturesExtractor):
+    """{"points": [B, ...], "coords": [B, ...]} -> the two flattened, side by side"""
+
+    def __init__(self, input_dim: int):
+        super().__init__(input_dim)
+        self.extractors = {"points": nn.Flatten(), "coords": nn.Flatten()}
+
+    def forward(self, observations: TensorDict) -> torch.Tensor:
+        return torch.cat([extractor(observations[key]) for key, extractor in self.extractors.items()], dim=1)
+
+
+class HostFeatureExtractor(BaseFeaturesExtractor):
+    def __init__(self, input_dim: int):
+        super().__init__(input_dim)
+        self.flatten = nn.Flatten()
+
+    def forward(self, observations: torch.Tensor) -> torch.Tensor:
+        return self.flatten(observations)
+
+
+class MlpSpec(NamedTuple):
+    """how a stack reads as hk_mlp_forward's input: the head (an extractor, an nn.Flatten or None), the batch norm and
+    the ReLU on the input, and the (Linear, BatchNorm1d or None, whether a ReLU follows) blocks"""
+    head: Optional[nn.Module]
+    input_bn: Optional[nn.BatchNorm1d]
+    input_relu: bool
+    blocks: List[Tuple[nn.Linear, Optional[nn.BatchNorm1d], bool]]
+
+
+def _bn_ok(bn: nn.BatchNorm1d, width: int) -> bool:
+    return bn.track_running_stats and bn.running_mean is not None and bn.num_features == width
+
+
+def mlp_spec(sequential: nn.Sequential) -> Union[MlpSpec, str]:
+    """the MlpSpec of a stack in create_mlp's order -- [head] [BatchNorm1d] [ReLU] (Linear [BatchNorm1d] [ReLU])+ --
+    or, as a string, why it is not one"""
+    mods = list(sequential._modules.values())  # every slot: children() would drop a module that is used twice
+    head = None
+    if mods and isinstance(mods[0], (HostFeatureExtractor, AgentFeatureExtractor, nn.Flatten)):
+        head = mods.pop(0)
+        if isinstance(head, nn.Flatten) and (head.start_dim, head.end_dim) != (1, -1):
+            return "the head flattens other dimensions than 1..-1"
+    first = next((m for m in mods if isinstance(m, nn.Linear)), None)
+    if first is None:
+        return "the stack has no Linear"
+    input_bn, input_relu, at = None, False, 0
+    if isinstance(mods[at], nn.BatchNorm1d):
+        input_bn, at = mods[at], at + 1
+        if not _bn_ok(input_bn, first.in_features):
+            return "a BatchNorm1d without running statistics, or of another width than its input"
+    if isinstance(mods[at], nn.ReLU):
+        input_relu, at = True, at + 1
+    blocks = []
+    width = first.in_features
+    while at < len(mods):
+        lin = mods[at]
+        if not isinstance(lin, nn.Linear):
+            return f"a {type(lin).__name__} where create_mlp puts a Linear"
+        if lin.in_features != width:
+            return "consecutive widths do not match"
+        width, at, bn, relu = lin.out_features, at + 1, None, False
+        if at < len(mods) and isinstance(mods[at], nn.BatchNorm1d):
+            bn, at = mods[at], at + 1
+            if not _bn_ok(bn, width):
+                return "a BatchNorm1d without running statistics, or of another width than its input"
+        if at < len(mods) and isinstance(mods[at], nn.ReLU):
+            relu, at = True, at + 1
+        blocks.append((lin, bn, relu))
+    if len(blocks) > A.HK_MLP_MAX_LAYERS:
+        return f"more than {A.HK_MLP_MAX_LAYERS} Linear"
+    if max(max(lin.in_features, lin.out_features) for lin, _, _ in blocks) > A.HK_MLP_MAX_WIDTH:
+        return f"a layer wider than {A.HK_MLP_MAX_WIDTH}"
+    if min(min(lin.in_features, lin.out_features) for lin, _, _ in blocks) < 1:
+        return "a layer of width 0"
+    return MlpSpec(head, input_bn, input_relu, blocks)
+
+
+class FusedSequential(nn.Sequential):
+    """An nn.Sequential whose eval-mode, gradient-free float32 forward on a HIP device is one hk_mlp_forward launch.
+
+    `forward` takes the kernel's path when the stack is create_mlp's shape (mlp_spec), it is in eval mode or has no
+    BatchNorm1d, gradients are off or no parameter requires one, and parameters and input are float32 on one HIP
+    device; otherwise it IS nn.Sequential.forward.  `fused_reason` says why the MODULE is not served (None: it is);
+    `fused_last_reason` says why the last CALL was not (None: it was), which adds what only a call shows: parameters
+    that are not on a HIP device, an input of another dtype, device or shape.  The two paths differ in the
+    last bits (one fma chain per output against torch's GEMM), so there is no automatic crossover between them:
+    `fused_enabled = False` pins torch's.  Nothing here synchronises."""
+
+    fused_enabled = True
+    fused_last_reason = None
+
+    def _tensors(self):
+        return [t for m in self.modules() for t in list(m._parameters.values()) + list(m._buffers.values())
+                if t is not None and t.is_floating_point()]
+
+    @property
+    def fused_reason(self) -> Optional[str]:
+        return self._reason_and_spec()[0]
+
+    def _reason_and_spec(self):
+        if not self.fused_enabled:
+            return "fused_enabled is False", None
+        spec = mlp_spec(self)
+        return (spec, None) if isinstance(spec, str) else (self._state_reason(), spec)
+
+    def _state_reason(self) -> Optional[str]:
+        tensors = self._tensors()
+        if any(t.dtype != torch.float32 for t in tensors):
+            return "parameters are not float32"
+        if len({t.device for t in tensors}) > 1:
+            return "parameters live on more than one device"
+        if self.training and any(isinstance(m, nn.BatchNorm1d) for m in self.children()):
+            return "a BatchNorm1d in training mode"
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            return "gradients are on"
+        return None
+
+    def _plan(self, spec: MlpSpec):
+        """the layer table, rebuilt when the stack no longer is what the table was built from: the tensors the modules
+        hold NOW lie elsewhere (one data_ptr() per tensor per call: a parameter or buffer that was assigned anew, a
+        state loaded with assign=True, .to()), or a batch norm, a ReLU or an eps came, went or changed.  In-place updates
+        -- optimizer.step, Polyak, load_state_dict -- change no address and need nothing."""
+        from . import ops
+        records = [(lin.weight, lin.bias) + (_bn_fields(bn) if bn is not None else (None,) * 4)
+                   + (bn.eps if bn is not None else 0.0, relu) for lin, bn, relu in spec.blocks]
+        in_bn = spec.input_bn
+        in_record = None if in_bn is None else (None, None) + _bn_fields(in_bn) + (in_bn.eps,)
+        key = (spec.input_relu,) + tuple(lin.weight.shape for lin, _, _ in spec.blocks) + tuple(
+            x.data_ptr() if isinstance(x, torch.Tensor) else x for r in records + [in_record or ()] for x in r)
+        plan = self.__dict__.get("_fused_plan")
+        if plan is None or plan.key != key:
+            plan = ops.MlpPlan([ops.MlpLayer(*r) for r in records], spec.input_relu,
+                               None if in_record is None else ops.MlpLayer(*in_record))
+            plan.key = key
+            self.__dict__["_fused_plan"] = plan
+        return plan
+
+    def forward(self, input):
+        reason, spec = self._reason_and_spec()
+        self.__dict__["fused_last_reason"] = reason
+        if reason is None:
+            x1 = None
+            if isinstance(spec.head, AgentFeatureExtractor):
+                x0, x1 = (input[key] for key in spec.head.extractors)
+            else:
+                x0 = input
+            dev = spec.blocks[0][0].weight.device
+            # (a head flattens whatever follows the batch dimension; without one the rows come as they are)
+            if dev.type == "cuda" and all(
+                    isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.device == dev
+                    and (x.dim() >= 2 if spec.head is not None else x.dim() == 2)
+                    for x in ((x0,) if x1 is None else (x0, x1))):
+                from . import ops
+                return ops.mlp_forward(x0, self._plan(spec), x1=x1)
+            self.__dict__["fused_last_reason"] = (
+                f"parameters live on {dev}, not on a HIP device" if dev.type != "cuda" else
+                f"the input is not float32 on {dev} with a batch dimension" + ("" if spec.head is not None else " and one more"))
+        return super().forward(input)
+
+    def __deepcopy__(self, memo):
+        # the copy builds its own table (this one's points at this module's tensors)
+        cls = self.__class__
+        new = cls.__new__(cls)
+        memo[id(self)] = new
+        import copy
+        for k, v in self.__dict__.items():
+            if k != "_fused_plan":
+                new.__dict__[k] = copy.deepcopy(v, memo)
+        return new
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state.pop("_fused_plan", None)
+        return state
+
+
+def _bn_fields(bn: nn.BatchNorm1d):
+    return bn.running_mean, bn.running_var, bn.weight, bn.bias
+
+
+def fuse(sequential: nn.Sequential) -> FusedSequential:
+    """a FusedSequential over the SAME modules, under the same names (nothing is copied)"""
+    fused = FusedSequential()
+    for name, module in sequential._modules.items():  # every slot: named_children() drops a module's second use
+        fused.add_module(name, module)
+    fused.train(sequential.training)
+    return fused
+
+
+def create_mlp(head: nn.Module, net_arch: List[Any], input_dim: int, output_dim: int,
+               activation_fn: Type[nn.Module] = nn.ReLU) -> nn.Module:
+    """`head`, then the layers `net_arch` describes, then a Linear to `output_dim`, as a FusedSequential.
+    `head` gives [batch, input_dim] rows.  In `net_arch` (its own input and output widths are not listed)
+        an int is a Linear of that width followed by an activation,
+        'b' puts a BatchNorm1d between the layer before it and that layer's activation (a second 'b' in a row is
+            dropped; at the very front it normalises the head's output),
+        'r<width>' is a residual block of that width followed by an activation,
+        {"repeat": n, "net_arch": [...]} repeats a part, recursively.
+    The activation after the last item is dropped."""
+    nets = [head, activation_fn()]
+    last_dim, last_type = input_dim, None
+    for item in expand_net_list(net_arch):
+        if isinstance(item, int):
+            nets += [nn.Linear(last_dim, item), activation_fn()]
+            last_dim, last_type = item, "l"
+        elif isinstance(item, str):
+            assert item[:1] in ("b", "r"), f"a string in net_arch is 'b' or 'r<width>', not {item!r}"
+            if item[0] == "b":
+                if last_type == "b":
+                    continue
+                nets.pop()  # the activation moves behind the batch norm
+                nets += [nn.BatchNorm1d(last_dim), activation_fn()]
+                last_type = "b"
+            else:
+                width = int(item[1:])
+                assert width > 0, f"a residual block is written 'r<width>' with a positive width, not {item!r}"
+                nets += [make_residual(last_dim, width), activation_fn()]
+                last_dim, last_type = width, "r"
+    nets.pop()  # no activation in front of the output layer
+    nets.append(nn.Linear(last_dim, output_dim))
+    return FusedSequential(*nets)

@@ -1695,3 +1695,134 @@ def tree_expand(parents: torch.Tensor, class_id: torch.Tensor, *, spec: Tuple[in
     with torch.cuda.device(dev):
         check(lib().hk_tree_expand(C.byref(q), _stream(parents)), "hk_tree_expand")
     return TreeExpandResult(children, c_par, c_ax, c_np, c_done, total, status)
+
+
+# ---- the eval-mode forward of a create_mlp stack in one launch ---------------------------------------------------------
+
+MlpLayer = collections.namedtuple("MlpLayer", "weight bias bn_mean bn_var bn_weight bn_bias eps relu",
+                                  defaults=(None, None, None, None, None, 1e-5, False))
+MlpLayer.__doc__ = """One `Linear [-> BatchNorm1d (eval)] [-> ReLU]` block of mlp_forward: weight [n, k] as nn.Linear
+keeps it, bias [n] or None, the batch norm's running_mean / running_var [n] (both None: no batch norm) with its weight /
+bias [n] or None (affine=False) and eps, relu: whether a ReLU follows."""
+_MLP_TILES = {None: 0, A.HK_MLP_TILE_SMALL: A.HK_MLP_FORCE_TILE_SMALL, A.HK_MLP_TILE_LARGE: A.HK_MLP_FORCE_TILE_LARGE}
+
+
+def _mlp_tensor(x, name: str, dev: Optional[torch.device], shape=None) -> Optional[int]:
+    """the address of a contiguous float32 tensor on `dev` (of `shape`, if given); None for None"""
+    if x is None:
+        return None
+    _require_device(x, name)
+    if x.dtype != torch.float32 or x.layout != torch.strided or not x.is_contiguous() or (dev is not None
+                                                                                          and x.device != dev):
+        raise TypeError(f"{name} must be a contiguous float32 tensor on {dev}. Got {x.dtype} on {x.device}, "
+                        f"strides {x.stride() if x.layout == torch.strided else None}.")
+    if shape is not None and tuple(x.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}. Got {tuple(x.shape)}.")
+    return x.data_ptr()
+
+
+class MlpPlan:
+    """The layer table of mlp_forward, built once per set of parameter addresses (it holds the tensors alive):
+    `layers` is a sequence of MlpLayer (or tuples in its order).  The table points at the tensors it was given: whoever
+    swaps a tensor for another builds a new plan (hironaka_amd.nets.FusedSequential does, by the addresses of the
+    tensors its modules hold at each call)."""
+
+    def __init__(self, layers: Sequence[MlpLayer], input_relu: bool = False, input_bn: Optional[MlpLayer] = None):
+        layers = [l if isinstance(l, MlpLayer) else MlpLayer(*l) for l in layers]
+        if not 1 <= len(layers) <= A.HK_MLP_MAX_LAYERS:
+            raise ValueError(f"1 to {A.HK_MLP_MAX_LAYERS} layers. Got {len(layers)}.")
+        _require_device(layers[0].weight, "layers[0].weight")
+        dev = layers[0].weight.device
+        d = A.hk_mlp_desc()
+        self.tensors = []
+        width = None
+        for i, l in enumerate(layers):
+            if not isinstance(l.weight, torch.Tensor) or l.weight.dim() != 2:
+                raise TypeError(f"layers[{i}].weight must be a [n, k] tensor.")
+            n, k = l.weight.shape
+            if width is not None and k != width:
+                raise ValueError(f"layers[{i}] takes {k} inputs but layers[{i - 1}] gives {width}.")
+            if not (1 <= k <= A.HK_MLP_MAX_WIDTH and 1 <= n <= A.HK_MLP_MAX_WIDTH):
+                raise ValueError(f"layers[{i}]: widths must lie in 1..{A.HK_MLP_MAX_WIDTH}. Got [{n}, {k}].")
+            if (l.bn_mean is None) != (l.bn_var is None) or (l.bn_mean is None and (l.bn_weight is not None
+                                                                                   or l.bn_bias is not None)):
+                raise ValueError(f"layers[{i}]: a batch norm needs both bn_mean and bn_var.")
+            width = n
+            e = d.layer[i]
+            e.weight = _mlp_tensor(l.weight, f"layers[{i}].weight", dev)
+            for name in ("bias", "bn_mean", "bn_var", "bn_weight", "bn_bias"):
+                setattr(e, name, _mlp_tensor(getattr(l, name), f"layers[{i}].{name}", dev, (n,)))
+            e.eps, e.k, e.n, e.flags = float(l.eps), k, n, A.HK_MLP_RELU if l.relu else 0
+            self.tensors += [t for t in l[:6] if t is not None]
+        if input_bn is not None:  # an MlpLayer whose batch-norm fields alone count: the batch norm on the input
+            k = layers[0].weight.shape[1]
+            if input_bn.bn_mean is None or input_bn.bn_var is None:
+                raise ValueError("input_bn needs both bn_mean and bn_var.")
+            for name in ("bn_mean", "bn_var", "bn_weight", "bn_bias"):
+                setattr(d, "in_" + name, _mlp_tensor(getattr(input_bn, name), f"input_bn.{name}", dev, (k,)))
+            d.in_eps = float(input_bn.eps)
+            self.tensors += [t for t in input_bn[2:6] if t is not None]
+        d.nlayers, d.dtype, d.flags = len(layers), A.HK_F32, A.HK_MLP_INPUT_RELU if input_relu else 0
+        self.desc, self.device, self.k_in, self.n_out = d, dev, layers[0].weight.shape[1], width
+
+
+def _mlp_rows(x: torch.Tensor, name: str, dev: torch.device) -> torch.Tensor:
+    """x as [B, k] float32 rows on `dev` whose elements are adjacent (the rows may lie any number of elements apart)"""
+    _require_device(x, name)
+    if x.dtype != torch.float32 or x.device != dev:
+        raise TypeError(f"{name} must be a float32 tensor on {dev}. Got {x.dtype} on {x.device}.")
+    if x.dim() < 2:
+        raise ValueError(f"{name} must have a batch dimension and at least one more. Got shape {tuple(x.shape)}.")
+    if x.dim() > 2:
+        x = x.flatten(1)
+    if x.shape[1] > 1 and x.stride(1) != 1:
+        x = x.contiguous()
+    return x
+
+
+def mlp_forward(x0: torch.Tensor, layers, x1: Optional[torch.Tensor] = None, input_relu: bool = False,
+                out: Optional[torch.Tensor] = None, tile: Optional[int] = None,
+                input_bn: Optional[MlpLayer] = None) -> torch.Tensor:
+    """The forward of `Linear [-> BatchNorm1d (eval)] [-> ReLU]` blocks in ONE launch (hk_mlp_forward; the rule, to the
+    bit, is in include/hironaka_hip_mlp.h).  Row b of the input is x0[b] flattened, followed by x1[b] flattened if x1 is
+    given; input_bn (an MlpLayer whose batch-norm fields alone count) applies an eval-mode batch norm to it first,
+    input_relu a ReLU after that.  `layers`: a sequence of MlpLayer, or an MlpPlan built from one (its own input_relu
+    and input_bn count then).  out: a [B, n] float32 tensor with adjacent elements in a row to write into (rows any
+    number of elements >= n apart); None: a new one.  tile: None, or the row tile (16 / 64) to force -- same bits.
+    Everything is float32 on one HIP device (a TypeError otherwise).  Nothing here synchronises."""
+    plan = layers if isinstance(layers, MlpPlan) else MlpPlan(layers, input_relu, input_bn)
+    if tile not in _MLP_TILES:
+        raise ValueError(f"tile must be None, {A.HK_MLP_TILE_SMALL} or {A.HK_MLP_TILE_LARGE}. Got {tile!r}.")
+    dev = plan.device
+    x0 = _mlp_rows(x0, "x0", dev)
+    batch, k0 = x0.shape
+    k1 = 0
+    if x1 is not None:
+        x1 = _mlp_rows(x1, "x1", dev)
+        k1 = x1.shape[1]
+        if x1.shape[0] != batch:
+            raise ValueError(f"x0 has {batch} rows but x1 has {x1.shape[0]}.")
+    if k0 + k1 != plan.k_in:
+        raise ValueError(f"the first layer takes {plan.k_in} inputs. Got {k0}{' + ' + str(k1) if x1 is not None else ''}.")
+    if batch >= 2 ** 31:
+        raise ValueError(f"at most 2^31 - 1 rows per call. Got {batch}.")
+    if out is None:
+        out = torch.empty((batch, plan.n_out), dtype=torch.float32, device=dev)
+    else:
+        _require_device(out, "out")
+        if out.dtype != torch.float32 or out.device != dev:
+            raise TypeError(f"out must be a float32 tensor on {dev}. Got {out.dtype} on {out.device}.")
+        if tuple(out.shape) != (batch, plan.n_out) or (plan.n_out > 1 and out.stride(1) != 1) or (
+                batch > 1 and out.stride(0) < plan.n_out):
+            raise ValueError(f"out must be [{batch}, {plan.n_out}] with adjacent elements in a row and rows that do "
+                             f"not overlap. Got shape {tuple(out.shape)}, strides {out.stride()}.")
+    if batch == 0:
+        return out
+    d = plan.desc
+    d.x0, d.x0_stride, d.k0 = x0.data_ptr(), x0.stride(0) if batch > 1 else k0, k0
+    d.x1, d.x1_stride, d.k1 = (x1.data_ptr(), x1.stride(0) if batch > 1 else k1, k1) if k1 else (None, 0, 0)
+    d.out, d.out_stride, d.batch = out.data_ptr(), out.stride(0) if batch > 1 else plan.n_out, batch
+    d.flags = (d.flags & A.HK_MLP_INPUT_RELU) | _MLP_TILES[tile]
+    with torch.cuda.device(dev):
+        check(lib().hk_mlp_forward(C.byref(d), _stream(out)), "hk_mlp_forward")
+    return out

@@ -633,5 +633,7 @@ int hk_search_morin_play(const hk_morin_play_desc* desc, void* stream);
 #include "hironaka_hip_dqn.h"
 /* within ABI 6: hk_optim_prepare / hk_optim_apply, likewise */
 #include "hironaka_hip_optim.h"
+/* within ABI 6: hk_mlp_forward, likewise */
+#include "hironaka_hip_mlp.h"
 
 #endif /* HIRONAKA_HIP_H */
