@@ -102,6 +102,9 @@ HK_MLP_MAX_LAYERS, HK_MLP_MAX_WIDTH = 32, 256
 HK_MLP_TILE_SMALL, HK_MLP_TILE_LARGE, HK_MLP_TILE_CROSSOVER = 16, 64, 4096
 HK_MLP_INPUT_RELU, HK_MLP_FORCE_TILE_SMALL, HK_MLP_FORCE_TILE_LARGE = 1, 2, 4
 HK_MLP_RELU = 1
+# hk_train_mlp_forward / hk_train_mlp_backward: the largest batch, the rows of the small instantiation, the layer flag
+HK_MLP_TRAIN_MAX_BATCH, HK_MLP_TRAIN_ROWS_SMALL = 1024, 256
+HK_MLP_TRAIN_BN = 2
 
 SEMANTICS = {"jax": HK_SEM_JAX, "torch": HK_SEM_TORCH, "list": HK_SEM_LIST}
 
@@ -453,6 +456,39 @@ class hk_mlp_desc(C.Structure):
     ]
 
 
+class hk_mlp_train_layer(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in (
+        "weight", "bias", "bn_weight", "bn_bias", "running_mean", "running_var", "num_batches_tracked", "z", "act",
+        "mean", "inv", "d_weight", "d_bias", "d_bn_weight", "d_bn_bias")] + [
+        ("eps", C.c_float),
+        ("momentum", C.c_float),
+        ("k", C.c_int32),
+        ("n", C.c_int32),
+        ("flags", C.c_uint32),
+        ("reserved_", C.c_int32),
+    ]
+
+
+class hk_mlp_train_desc(C.Structure):
+    _fields_ = [
+        ("x0", C.c_void_p),
+        ("x1", C.c_void_p),
+        ("grad_out", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("x0_stride", C.c_int64),
+        ("x1_stride", C.c_int64),
+        ("grad_stride", C.c_int64),
+        ("workspace_bytes", C.c_uint64),
+        ("batch", C.c_int32),
+        ("k0", C.c_int32),
+        ("k1", C.c_int32),
+        ("nlayers", C.c_int32),
+        ("dtype", C.c_int32),
+        ("flags", C.c_uint32),
+        ("layer", hk_mlp_train_layer * HK_MLP_MAX_LAYERS),
+    ]
+
+
 _vp, _i, _i64, _u32, _u64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
 
 # name -> (restype, argtypes) of every symbol the header declares.  `stream` is the trailing
@@ -560,13 +596,22 @@ MLP_PROTOTYPES = {
     "hk_mlp_forward": (C.c_int, [C.POINTER(hk_mlp_desc), _vp]),
 }
 
+# the entry points of include/hironaka_hip_mlp_train.h: the device library's only, as above
+MLP_TRAIN_PROTOTYPES = {
+    "hk_train_mlp_rows": (C.c_int, [_i64]),
+    "hk_train_mlp_workspace_bytes": (C.c_uint64, [C.POINTER(hk_mlp_train_desc)]),
+    "hk_train_mlp_forward": (C.c_int, [C.POINTER(hk_mlp_train_desc), _vp]),
+    "hk_train_mlp_backward": (C.c_int, [C.POINTER(hk_mlp_train_desc), _vp]),
+}
+
 
 def bind(lib: C.CDLL, prototypes=None) -> None:
     """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES, TREE_PROTOTYPES, ENV_PROTOTYPES,
-    REPLAY_PROTOTYPES, DQN_PROTOTYPES, OPTIM_PROTOTYPES and MLP_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
+    REPLAY_PROTOTYPES, DQN_PROTOTYPES, OPTIM_PROTOTYPES, MLP_PROTOTYPES and MLP_TRAIN_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
     if prototypes is None:
         prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES, **TREE_PROTOTYPES, **ENV_PROTOTYPES,
-                      **REPLAY_PROTOTYPES, **DQN_PROTOTYPES, **OPTIM_PROTOTYPES, **MLP_PROTOTYPES}
+                      **REPLAY_PROTOTYPES, **DQN_PROTOTYPES, **OPTIM_PROTOTYPES, **MLP_PROTOTYPES,
+                      **MLP_TRAIN_PROTOTYPES}
     for name, (res, args) in prototypes.items():
         fn = getattr(lib, name)
         fn.restype = res

@@ -1,0 +1,170 @@
+// C ABI of hk_train_mlp_forward / hk_train_mlp_backward (include/hironaka_hip_mlp_train.h, an addition within ABI 6):
+// argument validation and one launch per layer of hk::mlp_train_forward_kernel / hk::mlp_train_backward_kernel.  No
+// allocation, no synchronisation; every status is decided before the first launch.
+#include <vector>
+
+#include "hk_mlp_train_kernel.h"
+
+using namespace hk;
+
+namespace {
+
+constexpr uint32_t kLayerFlags = HK_MLP_RELU | HK_MLP_TRAIN_BN;
+
+struct Range {
+  uintptr_t lo, hi;  // [lo, hi)
+};
+
+void add(std::vector<Range>& v, const void* p, uint64_t bytes) {
+  if (p && bytes > 0) v.push_back(Range{reinterpret_cast<uintptr_t>(p), reinterpret_cast<uintptr_t>(p) + bytes});
+}
+bool meet(const Range& a, const Range& b) { return a.lo < b.hi && b.lo < a.hi; }
+
+// the bytes from the first to the last element of `batch` rows of `width` floats, `stride` elements apart
+uint64_t span(int64_t batch, int64_t stride, int64_t width) {
+  return batch > 0 ? ((uint64_t)(batch - 1) * (uint64_t)stride + (uint64_t)width) * sizeof(float) : 0;
+}
+
+bool is_bn(const hk_mlp_train_layer& L) { return L.flags & HK_MLP_TRAIN_BN; }
+
+uint64_t workspace_bytes(const hk_mlp_train_desc* q) {
+  if (!q || q->nlayers < 2 || q->nlayers > HK_MLP_MAX_LAYERS || q->batch <= 0) return 0;
+  int64_t widest = 0;
+  for (int l = 1; l < q->nlayers; ++l) widest = q->layer[l].n > widest ? q->layer[l].n : widest;
+  return widest > 0 ? (uint64_t)2 * (uint64_t)q->batch * (uint64_t)widest * sizeof(float) : 0;
+}
+
+int validate(const hk_mlp_train_desc* q, bool backward) {
+  if (!q) return HK_ERR_NULL;
+  if (q->dtype != HK_F32) return HK_ERR_UNSUPPORTED;
+  if (q->flags & ~HK_MLP_INPUT_RELU) return HK_ERR_UNSUPPORTED;
+  if (q->nlayers < 1 || q->nlayers > HK_MLP_MAX_LAYERS) return HK_ERR_SHAPE;
+  if (q->batch < 0 || q->batch > HK_MLP_TRAIN_MAX_BATCH) return HK_ERR_SHAPE;
+  if (q->k0 < 1 || q->k1 < 0 || q->x0_stride < 0 || q->x1_stride < 0 || (backward && q->grad_stride < 0)) return HK_ERR_SHAPE;
+  int64_t width = (int64_t)q->k0 + q->k1;
+  bool any_bn = false;
+  for (int l = 0; l < q->nlayers; ++l) {
+    const hk_mlp_train_layer& L = q->layer[l];
+    if (L.flags & ~kLayerFlags) return HK_ERR_UNSUPPORTED;
+    if (L.k < 1 || L.k > HK_MLP_MAX_WIDTH || L.n < 1 || L.n > HK_MLP_MAX_WIDTH || L.k != width) return HK_ERR_SHAPE;
+    width = L.n;
+    any_bn = any_bn || is_bn(L);
+  }
+  if (any_bn && q->batch == 1) return HK_ERR_SHAPE;
+  if (backward && q->workspace_bytes < workspace_bytes(q)) return HK_ERR_SHAPE;
+  if (!q->x0 || (q->k1 > 0 && !q->x1)) return HK_ERR_NULL;
+  if (backward && (!q->grad_out || (q->nlayers > 1 && !q->workspace))) return HK_ERR_NULL;
+  for (int l = 0; l < q->nlayers; ++l) {
+    const hk_mlp_train_layer& L = q->layer[l];
+    if (!L.weight || !L.act) return HK_ERR_NULL;
+    if (is_bn(L) && (!L.z || !L.mean || !L.inv || !L.running_mean || !L.running_var)) return HK_ERR_NULL;
+    if (backward && !L.d_weight) return HK_ERR_NULL;
+    if (!is_bn(L) && (L.bn_weight || L.bn_bias || L.running_mean || L.running_var || L.num_batches_tracked ||
+                      L.d_bn_weight || L.d_bn_bias))
+      return HK_ERR_UNSUPPORTED;
+  }
+  if (!all_aligned({q->x0, q->x1, q->grad_out, q->workspace}, 4)) return HK_ERR_ALIGN;
+  for (int l = 0; l < q->nlayers; ++l) {
+    const hk_mlp_train_layer& L = q->layer[l];
+    if (!all_aligned({L.weight, L.bias, L.bn_weight, L.bn_bias, L.running_mean, L.running_var, L.z, L.act, L.mean, L.inv,
+                      L.d_weight, L.d_bias, L.d_bn_weight, L.d_bn_bias}, 4) || !aligned(L.num_batches_tracked, 8))
+      return HK_ERR_ALIGN;
+  }
+  // what is read and what is written
+  std::vector<Range> rd, wr;
+  const uint64_t B = (uint64_t)q->batch;
+  add(rd, q->x0, span(q->batch, q->x0_stride, q->k0));
+  if (q->k1 > 0) add(rd, q->x1, span(q->batch, q->x1_stride, q->k1));
+  if (backward) {
+    add(rd, q->grad_out, span(q->batch, q->grad_stride, width));
+    add(wr, q->workspace, workspace_bytes(q));
+  }
+  for (int l = 0; l < q->nlayers; ++l) {
+    const hk_mlp_train_layer& L = q->layer[l];
+    const uint64_t vec = (uint64_t)L.n * sizeof(float);
+    add(rd, L.weight, vec * (uint64_t)L.k);
+    for (const void* p : {L.bias, L.bn_weight, L.bn_bias}) add(rd, p, vec);
+    std::vector<Range>& saved = backward ? rd : wr;
+    add(saved, L.act, vec * B);
+    if (is_bn(L)) {
+      add(saved, L.z, vec * B);
+      add(saved, L.mean, vec);
+      add(saved, L.inv, vec);
+    }
+    if (!backward) {
+      add(wr, L.running_mean, vec);
+      add(wr, L.running_var, vec);
+      add(wr, L.num_batches_tracked, 8);
+    } else {
+      add(wr, L.d_weight, vec * (uint64_t)L.k);
+      for (const void* p : {L.d_bias, L.d_bn_weight, L.d_bn_bias}) add(wr, p, vec);
+    }
+  }
+  for (size_t i = 0; i < wr.size(); ++i) {
+    for (const Range& r : rd)
+      if (meet(wr[i], r)) return HK_ERR_UNSUPPORTED;
+    for (size_t j = i + 1; j < wr.size(); ++j)
+      if (meet(wr[i], wr[j])) return HK_ERR_UNSUPPORTED;
+  }
+  return HK_OK;
+}
+
+template <int RT>
+int launch_layer(bool backward, const TrainArgs& a, hipStream_t stream) {
+  constexpr size_t lds = train_lds_bytes(RT);
+  auto kernel = backward ? &mlp_train_backward_kernel<RT> : &mlp_train_forward_kernel<RT>;
+  if (lds > 48 * 1024) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+        hipSuccess) {
+      (void)hipGetLastError();
+      return HK_ERR_LAUNCH;
+    }
+  }
+  return launch_kernel(kernel, dim3((unsigned)workgroups(a.L.n, kTrainCols)), dim3(kTrainThreads), lds, stream, a);
+}
+
+int run(const hk_mlp_train_desc* q, bool backward, hipStream_t stream) {
+  const int bad = validate(q, backward);
+  if (bad != HK_OK) return bad;
+  if (q->batch == 0) return HK_OK;
+  const bool large = train_rt(q->batch) == kTrainRtLarge;
+  int64_t widest = 0;
+  for (int l = 1; l < q->nlayers; ++l) widest = q->layer[l].n > widest ? q->layer[l].n : widest;
+  float* ws[2] = {static_cast<float*>(q->workspace), static_cast<float*>(q->workspace) + (int64_t)q->batch * widest};
+  for (int i = 0; i < q->nlayers; ++i) {
+    const int l = backward ? q->nlayers - 1 - i : i;
+    TrainArgs a = {};
+    a.L = q->layer[l];
+    a.a_in = l > 0 ? static_cast<const float*>(q->layer[l - 1].act) : nullptr;
+    a.x0 = static_cast<const float*>(q->x0), a.x1 = static_cast<const float*>(q->x1);
+    a.x0_stride = q->x0_stride, a.x1_stride = q->x1_stride;
+    a.k0 = q->k0, a.input_relu = (q->flags & HK_MLP_INPUT_RELU) ? 1 : 0, a.batch = q->batch;
+    if (backward) {
+      if (l + 1 < q->nlayers) {
+        a.n_next = q->layer[l + 1].n;
+        a.w_next = static_cast<const float*>(q->layer[l + 1].weight);
+        a.dz_next = ws[(l + 1) & 1];
+      } else {
+        a.grad = static_cast<const float*>(q->grad_out), a.grad_stride = q->grad_stride;
+      }
+      a.dz_out = l > 0 ? ws[l & 1] : nullptr;
+    }
+    const int status = large ? launch_layer<kTrainRtLarge>(backward, a, stream) : launch_layer<kTrainRtSmall>(backward, a, stream);
+    if (status != HK_OK) return status;
+  }
+  return HK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hk_train_mlp_rows(int64_t batch) { return train_rows(train_rt(batch)); }
+
+uint64_t hk_train_mlp_workspace_bytes(const hk_mlp_train_desc* q) { return workspace_bytes(q); }
+
+int hk_train_mlp_forward(const hk_mlp_train_desc* q, void* stream) { return run(q, false, (hipStream_t)stream); }
+
+int hk_train_mlp_backward(const hk_mlp_train_desc* q, void* stream) { return run(q, true, (hipStream_t)stream); }
+
+}  // extern "C"

@@ -5,7 +5,8 @@ extractors under the reference's names, with the eval-mode forward of the stack 
 produces (``state_dict`` keys, ``deepcopy``, ``.to()``, ``parameters()``, checkpoints: all ``nn.Sequential``'s), whose
 ``forward`` hands the whole stack to ``ops.mlp_forward`` (``hk_mlp_forward``, include/hironaka_hip_mlp.h) where that
 serves it and runs ``nn.Sequential.forward`` unchanged where it does not.  Training-mode forward and backward are
-torch's."""
+torch's unless ``fused_training`` is set: then they are ``ops.mlp_train_forward`` / ``ops.mlp_backward``
+(include/hironaka_hip_mlp_train.h), one launch per layer each way."""
 import abc
 from typing import Any, Dict, List, NamedTuple, Optional, Tuple, Type, Union
 
@@ -152,7 +153,8 @@ def mlp_spec(sequential: nn.Sequential) -> Union[MlpSpec, str]:
 
 
 class FusedSequential(nn.Sequential):
-    """An nn.Sequential whose eval-mode, gradient-free float32 forward on a HIP device is one hk_mlp_forward launch.
+    """An nn.Sequential whose eval-mode, gradient-free float32 forward on a HIP device is one hk_mlp_forward launch
+    and, with `fused_training`, whose training-mode forward and backward are one launch per layer each way.
 
     `forward` takes the kernel's path when the stack is create_mlp's shape (mlp_spec), it is in eval mode or has no
     BatchNorm1d, gradients are off or no parameter requires one, and parameters and input are float32 on one HIP
@@ -160,9 +162,16 @@ class FusedSequential(nn.Sequential):
     `fused_last_reason` says why the last CALL was not (None: it was), which adds what only a call shows: parameters
     that are not on a HIP device, an input of another dtype, device or shape.  The two paths differ in the
     last bits (one fma chain per output against torch's GEMM), so there is no automatic crossover between them:
-    `fused_enabled = False` pins torch's.  Nothing here synchronises."""
+    `fused_enabled = False` pins torch's.  With `fused_training = True` (off by default) a stack in training mode, or
+    one without a BatchNorm1d with gradients on, is served by ops.mlp_train_forward / ops.mlp_backward through an
+    autograd.Function: up to HK_MLP_TRAIN_MAX_BATCH rows, at least 2 with a batch norm, every batch norm with a float
+    momentum and none on the input, an input that requires no gradient.  A stack with a batch norm in eval mode keeps
+    the rule above (running statistics have no backward here).  Nothing here synchronises."""
 
     fused_enabled = True
+    # opt-in: the training-mode forward (batch statistics, running statistics updated) and the backward through
+    # ops.mlp_train_forward / ops.mlp_backward.  False: exactly the paths and reasons described above.
+    fused_training = False
     fused_last_reason = None
 
     def _tensors(self):
@@ -174,22 +183,43 @@ class FusedSequential(nn.Sequential):
         return self._reason_and_spec()[0]
 
     def _reason_and_spec(self):
-        if not self.fused_enabled:
-            return "fused_enabled is False", None
-        spec = mlp_spec(self)
-        return (spec, None) if isinstance(spec, str) else (self._state_reason(), spec)
+        return self._resolve()[:2]
 
-    def _state_reason(self) -> Optional[str]:
+    def _resolve(self):
+        """(why the module is not served or None, its MlpSpec, "eval" or "train": which kernels serve it)"""
+        if not self.fused_enabled:
+            return "fused_enabled is False", None, None
+        spec = mlp_spec(self)
+        if isinstance(spec, str):
+            return spec, None, None
+        reason, mode = self._state_reason(spec)
+        return reason, spec, mode
+
+    def _state_reason(self, spec: MlpSpec):
         tensors = self._tensors()
         if any(t.dtype != torch.float32 for t in tensors):
-            return "parameters are not float32"
+            return "parameters are not float32", None
         if len({t.device for t in tensors}) > 1:
-            return "parameters live on more than one device"
-        if self.training and any(isinstance(m, nn.BatchNorm1d) for m in self.children()):
-            return "a BatchNorm1d in training mode"
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            return "gradients are on"
-        return None
+            return "parameters live on more than one device", None
+        has_bn = any(isinstance(m, nn.BatchNorm1d) for m in self.children())
+        grads = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if not self.fused_training:
+            if self.training and has_bn:
+                return "a BatchNorm1d in training mode", None
+            return ("gradients are on", None) if grads else (None, "eval")
+        if has_bn and not self.training:  # running statistics: hk_mlp_forward's, which has no backward
+            return ("gradients are on", None) if grads else (None, "eval")
+        if not has_bn and not grads:
+            return None, "eval"
+        if spec.input_bn is not None:
+            return "a BatchNorm1d on the input in training mode", None
+        if any(bn is not None and not isinstance(bn.momentum, float) for _, bn, _ in spec.blocks):
+            return "a BatchNorm1d with momentum=None in training mode", None
+        params = [p for lin, bn, _ in spec.blocks for p in (lin.weight, lin.bias) + ((bn.weight, bn.bias) if bn else ())
+                  if p is not None]
+        if grads and len({id(p) for p in params}) < len(params):
+            return "a parameter is used twice and gradients are on", None
+        return None, "train"
 
     def _plan(self, spec: MlpSpec):
         """the layer table, rebuilt when the stack no longer is what the table was built from: the tensors the modules
@@ -211,8 +241,47 @@ class FusedSequential(nn.Sequential):
             self.__dict__["_fused_plan"] = plan
         return plan
 
+    def _train_plan(self, spec: MlpSpec):
+        """_plan's counterpart for the training kernels: the same rebuild rule, keyed by the same addresses plus the
+        batch norms' momenta and counters"""
+        from . import ops
+        records = [(lin.weight, lin.bias) + (_bn_fields(bn) + (bn.eps, relu, bn.momentum, bn.num_batches_tracked)
+                                             if bn is not None else (None,) * 4 + (0.0, relu, 0.0, None))
+                   for lin, bn, relu in spec.blocks]
+        key = (spec.input_relu,) + tuple(lin.weight.shape for lin, _, _ in spec.blocks) + tuple(
+            x.data_ptr() if isinstance(x, torch.Tensor) else x for r in records for x in r)
+        plan = self.__dict__.get("_fused_train_plan")
+        if plan is None or plan.key != key:
+            plan = ops.MlpTrainPlan([ops.MlpTrainLayer(*r) for r in records], spec.input_relu)
+            plan.key = key
+            self.__dict__["_fused_train_plan"] = plan
+        return plan
+
+    def _forward_train(self, spec: MlpSpec, x0, x1):
+        """the training kernels' forward, or None with fused_last_reason set where this CALL is torch's"""
+        from . import ops
+        batch = x0.shape[0]
+        has_bn = any(bn is not None for _, bn, _ in spec.blocks)
+        grads = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        reason = None
+        if batch > A.HK_MLP_TRAIN_MAX_BATCH:
+            reason = f"more than {A.HK_MLP_TRAIN_MAX_BATCH} rows in training mode"
+        elif batch == 0:
+            reason = "an empty batch in training mode"
+        elif batch == 1 and has_bn:
+            reason = "a batch of 1 with a BatchNorm1d in training mode"
+        elif torch.is_grad_enabled() and any(x is not None and x.requires_grad for x in (x0, x1)):
+            reason = "the input requires a gradient"
+        if reason is not None:
+            self.__dict__["fused_last_reason"] = reason
+            return None
+        plan = self._train_plan(spec)
+        if not grads:
+            return ops.mlp_train_forward(x0, plan, x1=x1)[0]
+        return _MlpTrainFunction.apply(plan, x0, x1, *plan.params)
+
     def forward(self, input):
-        reason, spec = self._reason_and_spec()
+        reason, spec, mode = self._resolve()
         self.__dict__["fused_last_reason"] = reason
         if reason is None:
             x1 = None
@@ -227,7 +296,10 @@ class FusedSequential(nn.Sequential):
                     and (x.dim() >= 2 if spec.head is not None else x.dim() == 2)
                     for x in ((x0,) if x1 is None else (x0, x1))):
                 from . import ops
-                return ops.mlp_forward(x0, self._plan(spec), x1=x1)
+                if mode == "eval":
+                    return ops.mlp_forward(x0, self._plan(spec), x1=x1)
+                out = self._forward_train(spec, x0, x1)
+                return out if out is not None else super().forward(input)
             self.__dict__["fused_last_reason"] = (
                 f"parameters live on {dev}, not on a HIP device" if dev.type != "cuda" else
                 f"the input is not float32 on {dev} with a batch dimension" + ("" if spec.head is not None else " and one more"))
@@ -240,23 +312,47 @@ class FusedSequential(nn.Sequential):
         memo[id(self)] = new
         import copy
         for k, v in self.__dict__.items():
-            if k != "_fused_plan":
+            if k not in ("_fused_plan", "_fused_train_plan"):
                 new.__dict__[k] = copy.deepcopy(v, memo)
         return new
 
     def __getstate__(self):
         state = self.__dict__.copy()
         state.pop("_fused_plan", None)
+        state.pop("_fused_train_plan", None)
         return state
+
+
+class _MlpTrainFunction(torch.autograd.Function):
+    """forward: ops.mlp_train_forward; backward: ops.mlp_backward.  The parameters are saved so that torch's version
+    check refuses a backward after one of them was changed in place; the input gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, plan, x0, x1, *params):
+        from . import ops
+        out, saved = ops.mlp_train_forward(x0, plan, x1=x1)
+        ctx.hk_saved = saved
+        ctx.save_for_backward(*params)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        ctx.saved_tensors  # the version check, before anything is launched
+        from . import ops
+        return (None, None, None) + tuple(ops.mlp_backward(ctx.hk_saved, grad_out))
 
 
 def _bn_fields(bn: nn.BatchNorm1d):
     return bn.running_mean, bn.running_var, bn.weight, bn.bias
 
 
-def fuse(sequential: nn.Sequential) -> FusedSequential:
-    """a FusedSequential over the SAME modules, under the same names (nothing is copied)"""
+def fuse(sequential: nn.Sequential, training: bool = False) -> FusedSequential:
+    """a FusedSequential over the SAME modules, under the same names (nothing is copied); training: its
+    fused_training"""
     fused = FusedSequential()
+    if training:
+        fused.fused_training = True
     for name, module in sequential._modules.items():  # every slot: named_children() drops a module's second use
         fused.add_module(name, module)
     fused.train(sequential.training)
@@ -264,7 +360,7 @@ def fuse(sequential: nn.Sequential) -> FusedSequential:
 
 
 def create_mlp(head: nn.Module, net_arch: List[Any], input_dim: int, output_dim: int,
-               activation_fn: Type[nn.Module] = nn.ReLU) -> nn.Module:
+               activation_fn: Type[nn.Module] = nn.ReLU, fused_training: bool = False) -> nn.Module:
     """`head`, then the layers `net_arch` describes, then a Linear to `output_dim`, as a FusedSequential.
     `head` gives [batch, input_dim] rows.  In `net_arch` (its own input and output widths are not listed)
         an int is a Linear of that width followed by an activation,
@@ -272,7 +368,7 @@ def create_mlp(head: nn.Module, net_arch: List[Any], input_dim: int, output_dim:
             dropped; at the very front it normalises the head's output),
         'r<width>' is a residual block of that width followed by an activation,
         {"repeat": n, "net_arch": [...]} repeats a part, recursively.
-    The activation after the last item is dropped."""
+    The activation after the last item is dropped.  fused_training: the FusedSequential's attribute of that name."""
     nets = [head, activation_fn()]
     last_dim, last_type = input_dim, None
     for item in expand_net_list(net_arch):
@@ -294,4 +390,7 @@ def create_mlp(head: nn.Module, net_arch: List[Any], input_dim: int, output_dim:
                 last_dim, last_type = width, "r"
     nets.pop()  # no activation in front of the output layer
     nets.append(nn.Linear(last_dim, output_dim))
-    return FusedSequential(*nets)
+    net = FusedSequential(*nets)
+    if fused_training:
+        net.fused_training = True
+    return net

@@ -14,6 +14,7 @@ from __future__ import annotations
 import collections
 import contextlib
 import ctypes as C
+import math
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
@@ -1826,3 +1827,203 @@ def mlp_forward(x0: torch.Tensor, layers, x1: Optional[torch.Tensor] = None, inp
     with torch.cuda.device(dev):
         check(lib().hk_mlp_forward(C.byref(d), _stream(out)), "hk_mlp_forward")
     return out
+
+
+# ---- the training-mode forward of a create_mlp stack and its backward, one launch per layer each way ---------------------
+
+MlpTrainLayer = collections.namedtuple(
+    "MlpTrainLayer", "weight bias bn_mean bn_var bn_weight bn_bias eps relu momentum num_batches_tracked",
+    defaults=(None, None, None, None, None, 1e-5, False, 0.1, None))
+MlpTrainLayer.__doc__ = """One `Linear [-> BatchNorm1d (training)] [-> ReLU]` block of mlp_train_forward: MlpLayer's
+fields, where bn_mean / bn_var are the running statistics the forward UPDATES (both None: no batch norm), then the batch
+norm's momentum (a float) and its num_batches_tracked (a 0-dim int64 tensor the forward increments, or None)."""
+
+
+def _align4(n: int) -> int:
+    return (n + 3) & ~3
+
+
+class MlpTrainPlan:
+    """The layer table of mlp_train_forward / mlp_backward, built once per set of parameter addresses (it holds the
+    tensors alive).  `params` lists the parameters in module order -- per layer weight, bias, bn_weight, bn_bias, those
+    that exist -- which is the order of mlp_backward's gradients."""
+
+    def __init__(self, layers: Sequence[MlpTrainLayer], input_relu: bool = False):
+        layers = [l if isinstance(l, MlpTrainLayer) else MlpTrainLayer(*l) for l in layers]
+        if not 1 <= len(layers) <= A.HK_MLP_MAX_LAYERS:
+            raise ValueError(f"1 to {A.HK_MLP_MAX_LAYERS} layers. Got {len(layers)}.")
+        _require_device(layers[0].weight, "layers[0].weight")
+        dev = layers[0].weight.device
+        d = A.hk_mlp_train_desc()
+        self.tensors, self.params, self.shapes, self.bn = [], [], [], []
+        width = None
+        for i, l in enumerate(layers):
+            if not isinstance(l.weight, torch.Tensor) or l.weight.dim() != 2:
+                raise TypeError(f"layers[{i}].weight must be a [n, k] tensor.")
+            n, k = l.weight.shape
+            if width is not None and k != width:
+                raise ValueError(f"layers[{i}] takes {k} inputs but layers[{i - 1}] gives {width}.")
+            if not (1 <= k <= A.HK_MLP_MAX_WIDTH and 1 <= n <= A.HK_MLP_MAX_WIDTH):
+                raise ValueError(f"layers[{i}]: widths must lie in 1..{A.HK_MLP_MAX_WIDTH}. Got [{n}, {k}].")
+            bn = l.bn_mean is not None
+            if bn != (l.bn_var is not None) or (not bn and (l.bn_weight is not None or l.bn_bias is not None
+                                                            or l.num_batches_tracked is not None)):
+                raise ValueError(f"layers[{i}]: a batch norm needs both bn_mean and bn_var.")
+            if bn and not isinstance(l.momentum, float):
+                raise TypeError(f"layers[{i}]: momentum must be a float. Got {l.momentum!r}.")
+            width = n
+            e = d.layer[i]
+            e.weight = _mlp_tensor(l.weight, f"layers[{i}].weight", dev)
+            for field, name in (("bias", "bias"), ("running_mean", "bn_mean"), ("running_var", "bn_var"),
+                                ("bn_weight", "bn_weight"), ("bn_bias", "bn_bias")):
+                setattr(e, field, _mlp_tensor(getattr(l, name), f"layers[{i}].{name}", dev, (n,)))
+            nbt = l.num_batches_tracked
+            if nbt is not None:
+                _require_device(nbt, f"layers[{i}].num_batches_tracked")
+                if nbt.dtype != torch.int64 or nbt.numel() != 1 or nbt.device != dev:
+                    raise TypeError(f"layers[{i}].num_batches_tracked must be one int64 on {dev}.")
+                e.num_batches_tracked = nbt.data_ptr()
+            e.eps, e.momentum, e.k, e.n = float(l.eps), float(l.momentum) if bn else 0.0, k, n
+            e.flags = (A.HK_MLP_RELU if l.relu else 0) | (A.HK_MLP_TRAIN_BN if bn else 0)
+            self.tensors += [t for t in l[:6] + (nbt,) if t is not None]
+            self.params += [t for t in (l.weight, l.bias, l.bn_weight, l.bn_bias) if t is not None]
+            self.shapes.append((n, k, l.bias is not None, l.bn_weight is not None, l.bn_bias is not None))
+            self.bn.append(bn)
+        d.nlayers, d.dtype, d.flags = len(layers), A.HK_F32, A.HK_MLP_INPUT_RELU if input_relu else 0
+        self.desc, self.device, self.k_in, self.n_out = d, dev, layers[0].weight.shape[1], width
+        self.widest = max([n for n, *_ in self.shapes[1:]], default=0)
+        # the gradients of one backward, in floats from the start of its buffer: (d_weight, d_bias, d_bn_weight, d_bn_bias)
+        self.grad_at, at = [], 0
+        for n, k, bias, gamma, beta in self.shapes:
+            row = [at]
+            at += _align4(n * k)
+            for present in (bias, gamma, beta):
+                row.append(at if present else None)
+                at += _align4(n) if present else 0
+            self.grad_at.append(row)
+        self.grad_floats = at
+        self._saved_at = {}
+
+    def saved_at(self, batch: int):
+        """where one forward's saved tensors lie, in floats from the start of its buffer: per layer (act, z, mean, inv),
+        and the buffer's length.  The last layer's act is a tensor of its own (the result)."""
+        got = self._saved_at.get(batch)
+        if got is None:
+            rows, at = [], 0
+            for i, ((n, *_), bn) in enumerate(zip(self.shapes, self.bn)):
+                row = [None] * 4
+                if i + 1 < len(self.shapes):
+                    row[0], at = at, at + _align4(batch * n)
+                if bn:
+                    row[1], at = at, at + _align4(batch * n)
+                    row[2], at = at, at + _align4(n)
+                    row[3], at = at, at + _align4(n)
+                rows.append(row)
+            got = self._saved_at[batch] = (rows, at)
+        return got
+
+
+class MlpTrainSaved:
+    """what mlp_backward needs of one mlp_train_forward: the plan, the inputs, the result and the buffer that holds
+    every layer's act, z, mean and inv"""
+
+    def __init__(self, plan, x0, x1, out, buf):
+        self.plan, self.x0, self.x1, self.out, self.buf = plan, x0, x1, out, buf
+
+    def layer(self, i: int):
+        """(act, z, mean, inv) of layer i as tensors (None where the layer has none)"""
+        rows, _ = self.plan.saved_at(self.out.shape[0])
+        n, batch = self.plan.shapes[i][0], self.out.shape[0]
+        act, z, mean, inv = rows[i]
+        view = lambda at, *shape: None if at is None else self.buf[at:at + math.prod(shape)].view(*shape)  # noqa: E731
+        return (self.out if act is None else view(act, batch, n), view(z, batch, n), view(mean, n), view(inv, n))
+
+
+def _mlp_train_fill(plan: MlpTrainPlan, x0, x1, out, buf):
+    """the descriptor's fields that belong to one call"""
+    d = plan.desc
+    batch, k0 = x0.shape
+    k1 = x1.shape[1] if x1 is not None else 0
+    d.x0, d.x0_stride, d.k0 = x0.data_ptr(), x0.stride(0) if batch > 1 else k0, k0
+    d.x1, d.x1_stride, d.k1 = (x1.data_ptr(), x1.stride(0) if batch > 1 else k1, k1) if k1 else (None, 0, 0)
+    d.batch, d.grad_out, d.workspace, d.workspace_bytes = batch, None, None, 0
+    rows, _ = plan.saved_at(batch)
+    base = buf.data_ptr()
+    for i, (act, z, mean, inv) in enumerate(rows):
+        e = d.layer[i]
+        e.act = out.data_ptr() if act is None else base + 4 * act
+        if z is not None:
+            e.z, e.mean, e.inv = base + 4 * z, base + 4 * mean, base + 4 * inv
+
+
+def mlp_train_forward(x0: torch.Tensor, plan, x1: Optional[torch.Tensor] = None, input_relu: bool = False):
+    """The training-mode forward of `Linear [-> BatchNorm1d] [-> ReLU]` blocks, one launch per layer
+    (hk_train_mlp_forward; the rule, to the bit, is in include/hironaka_hip_mlp_train.h): batch statistics, the running
+    statistics and num_batches_tracked updated in place.  `plan`: an MlpTrainPlan, or a sequence of MlpTrainLayer (with
+    input_relu).  Row b of the input is x0[b] flattened, followed by x1[b] flattened if x1 is given.  Returns (out [B, n],
+    saved): `saved` (an MlpTrainSaved) is what mlp_backward takes.  The buffers are new per call, so a plan may run
+    forward any number of times before a backward.  At most HK_MLP_TRAIN_MAX_BATCH rows, at least 2 with a batch norm.
+    Nothing here synchronises."""
+    if not isinstance(plan, MlpTrainPlan):
+        plan = MlpTrainPlan(plan, input_relu)
+    dev = plan.device
+    x0 = _mlp_rows(x0, "x0", dev)
+    batch, k0 = x0.shape
+    k1 = 0
+    if x1 is not None:
+        x1 = _mlp_rows(x1, "x1", dev)
+        k1 = x1.shape[1]
+        if x1.shape[0] != batch:
+            raise ValueError(f"x0 has {batch} rows but x1 has {x1.shape[0]}.")
+    if k0 + k1 != plan.k_in:
+        raise ValueError(f"the first layer takes {plan.k_in} inputs. Got {k0}{' + ' + str(k1) if x1 is not None else ''}.")
+    if batch > A.HK_MLP_TRAIN_MAX_BATCH or (batch == 1 and any(plan.bn)):
+        raise ValueError(f"2 to {A.HK_MLP_TRAIN_MAX_BATCH} rows with a batch norm, 0 to {A.HK_MLP_TRAIN_MAX_BATCH} "
+                         f"without. Got {batch}.")
+    out = torch.empty((batch, plan.n_out), dtype=torch.float32, device=dev)
+    buf = torch.empty(plan.saved_at(batch)[1], dtype=torch.float32, device=dev)
+    # (an alias without autograd's marks: where `out` becomes the result of an autograd.Function whose context holds
+    # `saved`, holding `out` itself would tie the graph into a cycle that only the garbage collector ends)
+    saved = MlpTrainSaved(plan, x0, x1, out.detach(), buf)
+    if batch == 0:
+        return out, saved
+    _mlp_train_fill(plan, x0, x1, out, buf)
+    with torch.cuda.device(dev):
+        check(lib().hk_train_mlp_forward(C.byref(plan.desc), _stream(out)), "hk_train_mlp_forward")
+    return out, saved
+
+
+def mlp_backward(saved: MlpTrainSaved, grad_out: torch.Tensor):
+    """The backward of one mlp_train_forward, one launch per layer (hk_train_mlp_backward): grad_out [B, n] is the
+    gradient with respect to the forward's result; returns the gradients of the plan's `params`, in that order (new
+    tensors, views of one buffer).  The input gets none.  The parameters must be what they were in the forward.
+    Nothing here synchronises."""
+    plan, out = saved.plan, saved.out
+    dev = plan.device
+    _require_device(grad_out, "grad_out")
+    if grad_out.dtype != torch.float32 or grad_out.device != dev or tuple(grad_out.shape) != tuple(out.shape):
+        raise TypeError(f"grad_out must be a float32 tensor of shape {tuple(out.shape)} on {dev}. "
+                        f"Got {grad_out.dtype} {tuple(grad_out.shape)} on {grad_out.device}.")
+    batch = out.shape[0]
+    if plan.n_out > 1 and grad_out.stride(1) != 1:
+        grad_out = grad_out.contiguous()
+    ws_floats = 2 * batch * plan.widest
+    buf = torch.empty(plan.grad_floats + ws_floats, dtype=torch.float32, device=dev)
+    grads = []
+    for (n, k, *_), (w, b, g, be) in zip(plan.shapes, plan.grad_at):
+        grads.append(buf[w:w + n * k].view(n, k))
+        grads += [buf[at:at + n] for at in (b, g, be) if at is not None]
+    if batch == 0:
+        buf[:plan.grad_floats].zero_()
+        return grads
+    _mlp_train_fill(plan, saved.x0, saved.x1, out, saved.buf)
+    d = plan.desc
+    base = buf.data_ptr()
+    d.grad_out, d.grad_stride = grad_out.data_ptr(), grad_out.stride(0) if batch > 1 else plan.n_out
+    d.workspace, d.workspace_bytes = (base + 4 * plan.grad_floats, 4 * ws_floats) if ws_floats else (None, 0)
+    for i, row in enumerate(plan.grad_at):
+        e = d.layer[i]
+        e.d_weight, e.d_bias, e.d_bn_weight, e.d_bn_bias = (None if at is None else base + 4 * at for at in row)
+    with torch.cuda.device(dev):
+        check(lib().hk_train_mlp_backward(C.byref(d), _stream(out)), "hk_train_mlp_backward")
+    return grads
