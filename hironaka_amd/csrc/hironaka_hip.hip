@@ -18,15 +18,7 @@ int check_spec(int batch, int m, int d, int dtype) {
 template <typename T>
 int launch_generic_t(const Params& prm, hipStream_t stream) {
   const size_t lds = (size_t)prm.lds_stride * prm.games_per_block * sizeof(T);
-  if (lds > 64 * 1024) {
-    // opting in to > 64 KiB of dynamic LDS is a per-function attribute (idempotent, cheap)
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_kernel<T>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      (void)hipGetLastError();
-      return HK_ERR_LAUNCH;
-    }
-  }
-  return launch_kernel(generic_kernel<T>, workgroups(prm.batch, prm.games_per_block), kWave, lds, stream, prm);
+  return launch_kernel_lds(generic_kernel<T>, 64 * 1024, workgroups(prm.batch, prm.games_per_block), kWave, lds, stream, prm);
 }
 
 int launch_generic(Params& prm, int dtype, hipStream_t stream) {

@@ -128,12 +128,27 @@ inline int kernel_mode(const Params& prm) {
 // (torch) leave benign errors behind: clear it right before a launch, read it right after.
 inline void launch_prepare() { (void)hipGetLastError(); }
 inline int launch_status() { return hipGetLastError() == hipSuccess ? HK_OK : HK_ERR_LAUNCH; }
-// every launch of the library: the kernel, its grid and block, dynamic LDS, the stream, the kernel's arguments
+// a launch of the library: the kernel, its grid and block, dynamic LDS, the stream, the kernel's arguments.  Every launch
+// goes through here but those of the one-game-per-lane operators and the replay buffer, which spell the same three steps
+// out: launch_search (hk_search_wave.h), hk_game_play.hip, hk_morin_play.hip, hk_env_step.hip, hk_host_select.hip,
+// hk_tree_expand.hip, hk_replay.hip
 template <typename... KArgs, typename... Args>
 int launch_kernel(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
   launch_prepare();
   hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
   return launch_status();
+}
+// launch_kernel for a kernel whose dynamic LDS may exceed `opt_in_above` bytes: beyond it (64 KiB of static + dynamic LDS)
+// the size is a per-function opt-in (idempotent, cheap), made right before the launch
+template <typename... KArgs, typename... Args>
+int launch_kernel_lds(void (*kernel)(KArgs...), size_t opt_in_above, dim3 grid, dim3 block, size_t lds, hipStream_t stream,
+                      Args... args) {
+  if (lds > opt_in_above && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return HK_ERR_LAUNCH;
+  }
+  return launch_kernel(kernel, grid, block, lds, stream, args...);
 }
 
 // workgroups of `games_per_block` games each that hold `batch` games
@@ -173,6 +188,21 @@ inline bool all_aligned(std::initializer_list<const void*> ptrs, size_t a) {
 }
 // a * b, 0 when that overflows 64 bits (workspace sizes: 0 means "too large")
 inline uint64_t checked_mul(uint64_t a, uint64_t b) { return b > 0 && a > UINT64_MAX / b ? 0 : a * b; }
+// [p, p + bytes) and [q, q + bytes2) share a byte (an absent or empty range shares none)
+inline bool overlap(const void* p, uint64_t bytes, const void* q, uint64_t bytes2) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return p && q && bytes > 0 && bytes2 > 0 && a < b + bytes2 && b < a + bytes;
+}
+// the bytes from the first to the last element of `batch` rows of `width` elements of `esz` bytes, `stride` elements
+// apart; 0: no rows, or more than fits in 63 bits (with batch > 0 and width > 0, 0 means "too large")
+inline uint64_t span_bytes(int64_t batch, int64_t stride, int64_t width, size_t esz) {
+  if (batch <= 0) return 0;
+  const uint64_t rows = checked_mul((uint64_t)(batch - 1), (uint64_t)stride);
+  if (batch > 1 && stride > 0 && rows == 0) return 0;
+  const uint64_t elems = rows + (uint64_t)width;
+  const uint64_t bytes = elems < rows ? 0 : checked_mul(elems, esz);
+  return bytes >> 63 ? 0 : bytes;
+}
 
 // ---- Philox4x32-10 ------------------------------------------------------------------------
 struct U4 {

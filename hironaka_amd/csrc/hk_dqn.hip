@@ -9,21 +9,6 @@ namespace {
 
 uint64_t dqn_tiles(int batch) { return ((uint64_t)batch + kDqnTile - 1) / kDqnTile; }
 
-// [p, p + bytes) and [q, q + bytes2) share a byte
-bool overlap(const void* p, uint64_t bytes, const void* q, uint64_t bytes2) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return bytes > 0 && bytes2 > 0 && a < b + bytes2 && b < a + bytes;
-}
-
-// the bytes from the first element of the first row to the last element of the last one; 0: more than 2^63
-uint64_t span_bytes(int batch, int64_t stride, int actions, size_t esz) {
-  const uint64_t rows = checked_mul((uint64_t)(batch - 1), (uint64_t)stride);
-  if (batch > 1 && rows == 0) return 0;
-  const uint64_t elems = rows + (uint64_t)actions;
-  const uint64_t bytes = checked_mul(elems, esz);
-  return bytes >> 63 ? 0 : bytes;
-}
-
 }  // namespace
 
 extern "C" {
@@ -77,12 +62,8 @@ int hk_dqn_td(const hk_dqn_td_desc* q, void* stream) {
   while (lg < 6 && (1 << lg) < q->num_actions) ++lg;
   a.lanes_log2 = lg;
   const dim3 grid((unsigned)dqn_tiles(q->batch)), block(kDqnThreads);
-  launch_prepare();
-  if (q->dtype == HK_F64)
-    hipLaunchKernelGGL(dqn_td_kernel<double>, grid, block, 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(dqn_td_kernel<float>, grid, block, 0, (hipStream_t)stream, a);
-  return launch_status();
+  if (q->dtype == HK_F64) return launch_kernel(dqn_td_kernel<double>, grid, block, 0, (hipStream_t)stream, a);
+  return launch_kernel(dqn_td_kernel<float>, grid, block, 0, (hipStream_t)stream, a);
 }
 
 int hk_polyak_update(const hk_polyak_desc* q, void* stream) {
@@ -111,7 +92,6 @@ int hk_polyak_update(const hk_polyak_desc* q, void* stream) {
   }
   PolyakArgs a{};
   uint64_t blocks = 0;
-  const int ve = 16 / (int)esz;
   for (int i = 0; i < q->ntensors; ++i) {
     const hk_polyak_tensor& t = q->tensor[i];
     PolyakTensor& k = a.t[i];
@@ -120,20 +100,10 @@ int hk_polyak_update(const hk_polyak_desc* q, void* stream) {
     k.numel = t.numel;
     a.first[i] = (uint32_t)blocks;
     if (t.numel == 0) continue;
-    const uintptr_t ms = reinterpret_cast<uintptr_t>(t.src) & 15u, md = reinterpret_cast<uintptr_t>(t.dst) & 15u;
-    uint64_t chunks;
-    if (ms != md) {
-      k.head = -1;
-      const uint64_t per = kPolyakChunkBytes / esz;
-      chunks = ((uint64_t)t.numel + per - 1) / per;
-    } else {
-      const int64_t head = (int64_t)(((16u - md) & 15u) / esz);
-      k.head = (int32_t)(head < t.numel ? head : t.numel);
-      const uint64_t nvec = (uint64_t)(t.numel - k.head) / (uint64_t)ve;
-      const uint64_t per = (uint64_t)kPolyakThreads * kPolyakUnroll;
-      chunks = nvec ? (nvec + per - 1) / per : 1;
-    }
-    blocks += chunks;
+    const void* const ptr[2] = {t.dst, t.src};
+    const ChunkPlan plan = chunk_plan<kPolyakThreads * kPolyakUnroll, kPolyakChunkBytes>(ptr, 2, t.numel, esz);
+    k.head = plan.head;
+    blocks += plan.chunks;
     if (blocks > 0x7FFFFFFFull) return HK_ERR_SHAPE;
   }
   for (int i = q->ntensors; i <= HK_POLYAK_MAX_TENSORS; ++i) a.first[i] = (uint32_t)blocks;
@@ -142,12 +112,8 @@ int hk_polyak_update(const hk_polyak_desc* q, void* stream) {
   a.rest = 1.0 - q->tau;
   a.ntensors = q->ntensors;
   const dim3 grid((unsigned)blocks), block(kPolyakThreads);
-  launch_prepare();
-  if (q->dtype == HK_F64)
-    hipLaunchKernelGGL(polyak_kernel<double>, grid, block, 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(polyak_kernel<float>, grid, block, 0, (hipStream_t)stream, a);
-  return launch_status();
+  if (q->dtype == HK_F64) return launch_kernel(polyak_kernel<double>, grid, block, 0, (hipStream_t)stream, a);
+  return launch_kernel(polyak_kernel<float>, grid, block, 0, (hipStream_t)stream, a);
 }
 
 }  // extern "C"

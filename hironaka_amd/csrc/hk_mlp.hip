@@ -9,22 +9,12 @@ namespace {
 constexpr uint32_t kDescFlags = HK_MLP_INPUT_RELU | HK_MLP_FORCE_TILE_SMALL | HK_MLP_FORCE_TILE_LARGE;
 constexpr uint32_t kLayerFlags = HK_MLP_RELU;
 
-// [p, p + bytes) and [q, q + bytes2) share a byte
-bool overlap(const void* p, uint64_t bytes, const void* q, uint64_t bytes2) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return p && q && bytes > 0 && bytes2 > 0 && a < b + bytes2 && b < a + bytes;
-}
-
-// the bytes from the first to the last element of `batch` rows of `width` floats, `stride` elements apart
-uint64_t span(int64_t batch, int64_t stride, int64_t width) {
-  return batch > 0 ? ((uint64_t)(batch - 1) * (uint64_t)stride + (uint64_t)width) * sizeof(float) : 0;
-}
-
-// out's rows share a byte with the rows of an input.  Rows of one stride that holds both widths are records side by
-// side: they meet only where the windows meet inside a record (any two records apart: the batch is not looked at);
-// everything else is judged by the spans from the first to the last element.
-bool rows_overlap(const hk_mlp_desc* q, int64_t n, const void* x, int64_t stride, int64_t k) {
-  if (!overlap(q->out, span(q->batch, q->out_stride, n), x, span(q->batch, stride, k))) return false;
+// out's rows (`out_bytes` from first to last, n wide) share a byte with the rows of an input (`x_bytes`, k wide).  Rows of
+// one stride that holds both widths are records side by side: they meet only where the windows meet inside a record (any
+// two records apart: the batch is not looked at); everything else is judged by the spans from the first to the last element.
+bool rows_overlap(const hk_mlp_desc* q, uint64_t out_bytes, int64_t n, const void* x, uint64_t x_bytes, int64_t stride,
+                  int64_t k) {
+  if (!overlap(q->out, out_bytes, x, x_bytes)) return false;
   if (q->batch == 1 || stride != q->out_stride || stride < k) return true;
   const int64_t diff = (int64_t)((reinterpret_cast<intptr_t>(q->out) - reinterpret_cast<intptr_t>(x)) / 4);
   const int64_t r = ((diff % stride) + stride) % stride;  // out's window starts r elements into x's record
@@ -61,9 +51,12 @@ int validate(const hk_mlp_desc* q) {
     const hk_mlp_layer& L = q->layer[l];
     if (!all_aligned({L.weight, L.bias, L.bn_mean, L.bn_var, L.bn_weight, L.bn_bias}, 4)) return HK_ERR_ALIGN;
   }
-  const uint64_t out_bytes = span(q->batch, q->out_stride, width);
-  if (rows_overlap(q, width, q->x0, q->x0_stride, q->k0)) return HK_ERR_UNSUPPORTED;
-  if (q->k1 > 0 && rows_overlap(q, width, q->x1, q->x1_stride, q->k1)) return HK_ERR_UNSUPPORTED;
+  const uint64_t out_bytes = span_bytes(q->batch, q->out_stride, width, sizeof(float));
+  const uint64_t x0_bytes = span_bytes(q->batch, q->x0_stride, q->k0, sizeof(float));
+  const uint64_t x1_bytes = q->k1 > 0 ? span_bytes(q->batch, q->x1_stride, q->k1, sizeof(float)) : 1;
+  if (q->batch > 0 && (!out_bytes || !x0_bytes || !x1_bytes)) return HK_ERR_SHAPE;  // a span beyond 2^63 bytes
+  if (rows_overlap(q, out_bytes, width, q->x0, x0_bytes, q->x0_stride, q->k0)) return HK_ERR_UNSUPPORTED;
+  if (q->k1 > 0 && rows_overlap(q, out_bytes, width, q->x1, x1_bytes, q->x1_stride, q->k1)) return HK_ERR_UNSUPPORTED;
   for (const void* p : {q->in_bn_mean, q->in_bn_var, q->in_bn_weight, q->in_bn_bias})
     if (overlap(q->out, out_bytes, p, (uint64_t)(q->k0 + q->k1) * sizeof(float))) return HK_ERR_UNSUPPORTED;
   for (int l = 0; l < q->nlayers; ++l) {
@@ -78,15 +71,8 @@ int validate(const hk_mlp_desc* q) {
 
 template <int TR>
 int launch(const hk_mlp_desc& q, hipStream_t stream) {
-  constexpr size_t lds = mlp_lds_bytes(TR);
-  if (lds > 48 * 1024) {  // (static + dynamic LDS beyond 64 KiB is a per-function opt-in: idempotent, cheap)
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_kernel<TR>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess) {
-      (void)hipGetLastError();
-      return HK_ERR_LAUNCH;
-    }
-  }
-  return launch_kernel(mlp_kernel<TR>, dim3((unsigned)workgroups(q.batch, TR)), dim3(kWave * mlp_waves(TR)), lds, stream, q);
+  return launch_kernel_lds(mlp_kernel<TR>, 48 * 1024, dim3((unsigned)workgroups(q.batch, TR)), dim3(kWave * mlp_waves(TR)),
+                           mlp_lds_bytes(TR), stream, q);
 }
 
 }  // namespace

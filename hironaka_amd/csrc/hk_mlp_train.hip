@@ -1,6 +1,7 @@
 // C ABI of hk_train_mlp_forward / hk_train_mlp_backward (include/hironaka_hip_mlp_train.h, an addition within ABI 6):
 // argument validation and one launch per layer of hk::mlp_train_forward_kernel / hk::mlp_train_backward_kernel.  No
 // allocation, no synchronisation; every status is decided before the first launch.
+#include <utility>
 #include <vector>
 
 #include "hk_mlp_train_kernel.h"
@@ -11,19 +12,8 @@ namespace {
 
 constexpr uint32_t kLayerFlags = HK_MLP_RELU | HK_MLP_TRAIN_BN;
 
-struct Range {
-  uintptr_t lo, hi;  // [lo, hi)
-};
-
-void add(std::vector<Range>& v, const void* p, uint64_t bytes) {
-  if (p && bytes > 0) v.push_back(Range{reinterpret_cast<uintptr_t>(p), reinterpret_cast<uintptr_t>(p) + bytes});
-}
-bool meet(const Range& a, const Range& b) { return a.lo < b.hi && b.lo < a.hi; }
-
-// the bytes from the first to the last element of `batch` rows of `width` floats, `stride` elements apart
-uint64_t span(int64_t batch, int64_t stride, int64_t width) {
-  return batch > 0 ? ((uint64_t)(batch - 1) * (uint64_t)stride + (uint64_t)width) * sizeof(float) : 0;
-}
+// the byte ranges (pointer, bytes) that the launches read, or write
+using Ranges = std::vector<std::pair<const void*, uint64_t>>;
 
 bool is_bn(const hk_mlp_train_layer& L) { return L.flags & HK_MLP_TRAIN_BN; }
 
@@ -71,56 +61,53 @@ int validate(const hk_mlp_train_desc* q, bool backward) {
       return HK_ERR_ALIGN;
   }
   // what is read and what is written
-  std::vector<Range> rd, wr;
+  Ranges rd, wr;
   const uint64_t B = (uint64_t)q->batch;
-  add(rd, q->x0, span(q->batch, q->x0_stride, q->k0));
-  if (q->k1 > 0) add(rd, q->x1, span(q->batch, q->x1_stride, q->k1));
+  const uint64_t x0_bytes = span_bytes(q->batch, q->x0_stride, q->k0, sizeof(float));
+  const uint64_t x1_bytes = q->k1 > 0 ? span_bytes(q->batch, q->x1_stride, q->k1, sizeof(float)) : 1;
+  const uint64_t grad_bytes = backward ? span_bytes(q->batch, q->grad_stride, width, sizeof(float)) : 1;
+  if (q->batch > 0 && (!x0_bytes || !x1_bytes || !grad_bytes)) return HK_ERR_SHAPE;  // a span beyond 2^63 bytes
+  rd.emplace_back(q->x0, x0_bytes);
+  if (q->k1 > 0) rd.emplace_back(q->x1, x1_bytes);
   if (backward) {
-    add(rd, q->grad_out, span(q->batch, q->grad_stride, width));
-    add(wr, q->workspace, workspace_bytes(q));
+    rd.emplace_back(q->grad_out, grad_bytes);
+    wr.emplace_back(q->workspace, workspace_bytes(q));
   }
   for (int l = 0; l < q->nlayers; ++l) {
     const hk_mlp_train_layer& L = q->layer[l];
     const uint64_t vec = (uint64_t)L.n * sizeof(float);
-    add(rd, L.weight, vec * (uint64_t)L.k);
-    for (const void* p : {L.bias, L.bn_weight, L.bn_bias}) add(rd, p, vec);
-    std::vector<Range>& saved = backward ? rd : wr;
-    add(saved, L.act, vec * B);
+    rd.emplace_back(L.weight, vec * (uint64_t)L.k);
+    for (const void* p : {L.bias, L.bn_weight, L.bn_bias}) rd.emplace_back(p, vec);
+    Ranges& saved = backward ? rd : wr;
+    saved.emplace_back(L.act, vec * B);
     if (is_bn(L)) {
-      add(saved, L.z, vec * B);
-      add(saved, L.mean, vec);
-      add(saved, L.inv, vec);
+      saved.emplace_back(L.z, vec * B);
+      saved.emplace_back(L.mean, vec);
+      saved.emplace_back(L.inv, vec);
     }
     if (!backward) {
-      add(wr, L.running_mean, vec);
-      add(wr, L.running_var, vec);
-      add(wr, L.num_batches_tracked, 8);
+      wr.emplace_back(L.running_mean, vec);
+      wr.emplace_back(L.running_var, vec);
+      wr.emplace_back(L.num_batches_tracked, 8);
     } else {
-      add(wr, L.d_weight, vec * (uint64_t)L.k);
-      for (const void* p : {L.d_bias, L.d_bn_weight, L.d_bn_bias}) add(wr, p, vec);
+      wr.emplace_back(L.d_weight, vec * (uint64_t)L.k);
+      for (const void* p : {L.d_bias, L.d_bn_weight, L.d_bn_bias}) wr.emplace_back(p, vec);
     }
   }
   for (size_t i = 0; i < wr.size(); ++i) {
-    for (const Range& r : rd)
-      if (meet(wr[i], r)) return HK_ERR_UNSUPPORTED;
+    for (const auto& r : rd)
+      if (overlap(wr[i].first, wr[i].second, r.first, r.second)) return HK_ERR_UNSUPPORTED;
     for (size_t j = i + 1; j < wr.size(); ++j)
-      if (meet(wr[i], wr[j])) return HK_ERR_UNSUPPORTED;
+      if (overlap(wr[i].first, wr[i].second, wr[j].first, wr[j].second)) return HK_ERR_UNSUPPORTED;
   }
   return HK_OK;
 }
 
 template <int RT>
 int launch_layer(bool backward, const TrainArgs& a, hipStream_t stream) {
-  constexpr size_t lds = train_lds_bytes(RT);
   auto kernel = backward ? &mlp_train_backward_kernel<RT> : &mlp_train_forward_kernel<RT>;
-  if (lds > 48 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess) {
-      (void)hipGetLastError();
-      return HK_ERR_LAUNCH;
-    }
-  }
-  return launch_kernel(kernel, dim3((unsigned)workgroups(a.L.n, kTrainCols)), dim3(kTrainThreads), lds, stream, a);
+  return launch_kernel_lds(kernel, 48 * 1024, dim3((unsigned)workgroups(a.L.n, kTrainCols)), dim3(kTrainThreads),
+                           train_lds_bytes(RT), stream, a);
 }
 
 int run(const hk_mlp_train_desc* q, bool backward, hipStream_t stream) {

@@ -11,12 +11,6 @@ constexpr uint32_t kPrepareFlags = HK_OPTIM_LAST | HK_OPTIM_ADVANCE | HK_OPTIM_N
 constexpr uint32_t kApplyFlags = HK_OPTIM_KEEP_GRADS | HK_OPTIM_NESTEROV;
 constexpr int kMaxUsed = 4;
 
-// [p, p + bytes) and [q, q + bytes) share a byte
-bool overlap(const void* p, const void* q, uint64_t bytes, uint64_t bytes2) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return bytes > 0 && bytes2 > 0 && a < b + bytes2 && b < a + bytes;
-}
-
 // the pointers of an entry that the launch touches: prepare the gradient alone, apply what the kind uses
 int used(const hk_optim_desc* q, const hk_optim_tensor& t, bool apply, const void* out[kMaxUsed]) {
   int n = 0;
@@ -66,7 +60,7 @@ int validate(const hk_optim_desc* q, bool apply) {
       const int n2 = used(q, u, apply, other);
       for (int k = 0; k < n; ++k)
         for (int l = (j == i ? k + 1 : 0); l < n2; ++l)
-          if (overlap(ptr[k], other[l], bytes, bytes2)) return HK_ERR_UNSUPPORTED;
+          if (overlap(ptr[k], bytes, other[l], bytes2)) return HK_ERR_UNSUPPORTED;
     }
   }
   return HK_OK;
@@ -90,18 +84,15 @@ void scalars(const hk_optim_desc* q, OptimArgs& a) {
 }
 
 template <typename T, int KIND>
-void launch_apply(const OptimArgs& a, hipStream_t stream) {
-  hipLaunchKernelGGL((optim_apply_kernel<T, KIND>), dim3(a.blocks), dim3(kOptimThreads), 0, stream, a);
+int launch_apply(const OptimArgs& a, hipStream_t stream) {
+  return launch_kernel(optim_apply_kernel<T, KIND>, dim3(a.blocks), dim3(kOptimThreads), 0, stream, a);
 }
 
 template <typename T>
-void launch_apply_kind(int kind, const OptimArgs& a, hipStream_t stream) {
-  if (kind == HK_OPTIM_ADAM)
-    launch_apply<T, HK_OPTIM_ADAM>(a, stream);
-  else if (kind == HK_OPTIM_SGD)
-    launch_apply<T, HK_OPTIM_SGD>(a, stream);
-  else
-    launch_apply<T, HK_OPTIM_SCALE>(a, stream);
+int launch_apply_kind(int kind, const OptimArgs& a, hipStream_t stream) {
+  if (kind == HK_OPTIM_ADAM) return launch_apply<T, HK_OPTIM_ADAM>(a, stream);
+  if (kind == HK_OPTIM_SGD) return launch_apply<T, HK_OPTIM_SGD>(a, stream);
+  return launch_apply<T, HK_OPTIM_SCALE>(a, stream);
 }
 
 }  // namespace
@@ -132,19 +123,14 @@ int hk_optim_prepare(const hk_optim_desc* q, void* stream) {
   scalars(q, a);
   a.blocks = (uint32_t)blocks;
   const dim3 grid(reduce_only ? 1u : (unsigned)blocks), block(kOptimThreads);
-  launch_prepare();
-  if (q->dtype == HK_F64)
-    hipLaunchKernelGGL(optim_prepare_kernel<double>, grid, block, 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(optim_prepare_kernel<float>, grid, block, 0, (hipStream_t)stream, a);
-  return launch_status();
+  if (q->dtype == HK_F64) return launch_kernel(optim_prepare_kernel<double>, grid, block, 0, (hipStream_t)stream, a);
+  return launch_kernel(optim_prepare_kernel<float>, grid, block, 0, (hipStream_t)stream, a);
 }
 
 int hk_optim_apply(const hk_optim_desc* q, void* stream) {
   const int bad = validate(q, true);
   if (bad != HK_OK) return bad;
   const size_t esz = elem_size(q->dtype);
-  const int ve = 16 / (int)esz;
   OptimArgs a{};
   uint64_t blocks = 0;
   const void* ptr[kMaxUsed];
@@ -154,34 +140,17 @@ int hk_optim_apply(const hk_optim_desc* q, void* stream) {
     a.first[i] = (uint32_t)blocks;
     if (t.numel == 0) continue;
     const int n = used(q, t, true, ptr);
-    const uintptr_t mod = reinterpret_cast<uintptr_t>(ptr[0]) & 15u;
-    bool together = true;
-    for (int k = 1; k < n; ++k) together = together && (reinterpret_cast<uintptr_t>(ptr[k]) & 15u) == mod;
-    uint64_t chunks;
-    if (!together) {
-      a.head[i] = -1;
-      const uint64_t per = kOptimChunkBytes / esz;
-      chunks = ((uint64_t)t.numel + per - 1) / per;
-    } else {
-      const int64_t head = (int64_t)(((16u - mod) & 15u) / esz);
-      a.head[i] = (int8_t)(head < t.numel ? head : t.numel);
-      const uint64_t nvec = (uint64_t)(t.numel - a.head[i]) / (uint64_t)ve;
-      const uint64_t per = (uint64_t)kOptimThreads * kOptimUnroll;
-      chunks = nvec ? (nvec + per - 1) / per : 1;
-    }
-    blocks += chunks;
+    const ChunkPlan plan = chunk_plan<kOptimThreads * kOptimUnroll, kOptimChunkBytes>(ptr, n, t.numel, esz);
+    a.head[i] = (int8_t)plan.head;
+    blocks += plan.chunks;
     if (blocks > 0x7FFFFFFFull) return HK_ERR_SHAPE;
   }
   for (int i = q->ntensors; i <= HK_OPTIM_MAX_TENSORS; ++i) a.first[i] = (uint32_t)blocks;
   if (blocks == 0) return HK_OK;
   scalars(q, a);
   a.blocks = (uint32_t)blocks;
-  launch_prepare();
-  if (q->dtype == HK_F64)
-    launch_apply_kind<double>(q->kind, a, (hipStream_t)stream);
-  else
-    launch_apply_kind<float>(q->kind, a, (hipStream_t)stream);
-  return launch_status();
+  if (q->dtype == HK_F64) return launch_apply_kind<double>(q->kind, a, (hipStream_t)stream);
+  return launch_apply_kind<float>(q->kind, a, (hipStream_t)stream);
 }
 
 }  // extern "C"

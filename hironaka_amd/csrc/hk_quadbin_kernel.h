@@ -175,15 +175,8 @@ template <int M, int D, bool GEN>
 int launch_quadbin_k(const Params& prm, const float* in, int32_t* ids_out, int32_t* np_out, hipStream_t stream) {
   using BG = QuadBinGeom<M, D>;
   constexpr size_t lds = (size_t)BG::kWaves * QuadGenGeom<M, D>::kRegion * sizeof(float);
-  if (lds > 48 * 1024) {  // (static + dynamic LDS beyond 64 KiB is a per-function opt-in: idempotent, cheap)
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&quadbin_kernel<M, D, GEN>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      (void)hipGetLastError();
-      return HK_ERR_LAUNCH;
-    }
-  }
-  return launch_kernel(quadbin_kernel<M, D, GEN>, workgroups(prm.batch, BG::kGames), kWave * BG::kWaves, lds, stream, in,
-                       (float*)prm.out, ids_out, np_out, prm.batch, prm);
+  return launch_kernel_lds(quadbin_kernel<M, D, GEN>, 48 * 1024, workgroups(prm.batch, BG::kGames), kWave * BG::kWaves, lds,
+                           stream, in, (float*)prm.out, ids_out, np_out, prm.batch, prm);
 }
 
 template <int M, int D>

@@ -368,28 +368,38 @@ def generate_points(batch: int, max_points: int, dim: int, max_value: int, seed:
     return out
 
 
-_WORKSPACES: Dict[Tuple[torch.device, int], torch.Tensor] = {}
-_RETIRED_WORKSPACES: list = []  # outgrown buffers: a hipGraph captured earlier may still hold their address
+class _WorkspaceCache:
+    """Per-(device, stream) zeroed uint8 memory for the kernels' counters and tickets, grown on demand (the C ABI never
+    allocates); the key is the device's current stream, on which launches follow each other, and every launch leaves
+    its workspace zero again.  A buffer that a larger request outgrows is retired, not freed: a hipGraph captured
+    earlier may still hold its address.  Growing DURING a capture is refused with `refuse`; where that is None the
+    request is served from the capture's own pool instead (its zero fill is captured with it): exactly `nbytes`,
+    neither kept nor retiring anything."""
+
+    def __init__(self, floor: int, refuse: Optional[str] = None):
+        self.floor, self.refuse = floor, refuse
+        self.live: Dict[Tuple[torch.device, int], torch.Tensor] = {}
+        self.retired: list = []
+
+    def get(self, dev: torch.device, nbytes: int) -> torch.Tensor:
+        key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+        ws = self.live.get(key)
+        if ws is None or ws.numel() < nbytes:
+            if torch.cuda.is_current_stream_capturing():
+                if self.refuse is not None:
+                    raise RuntimeError(self.refuse)
+                return torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+            if ws is not None:
+                self.retired.append(ws)
+            ws = self.live[key] = torch.zeros(max(nbytes, self.floor), dtype=torch.uint8, device=dev)
+        return ws
 
 
-def _workspace(dev: torch.device, nbytes: int) -> torch.Tensor:
-    """Per-(device, stream) memory for hk_rollout's per-workgroup counters, grown on demand (the C ABI
-    never allocates).  Zero when created; every reduction leaves it zero again.  A buffer that a larger
-    request outgrows is retired, not freed (a captured graph may replay launches that add to it), and growing
-    DURING a capture is refused: allocate first (one eager call of the same shape, or the caller's own
-    `rollout_workspace` + `defer_counts`)."""
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _WORKSPACES.get(key)
-    if ws is None or ws.numel() < nbytes:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("hk_rollout's counter workspace would have to be (re)allocated inside a stream "
-                               "capture: run the same rollout once eagerly on this stream first, or pass "
-                               "workspace=ops.rollout_workspace(...) with defer_counts=True")
-        if ws is not None:
-            _RETIRED_WORKSPACES.append(ws)
-        ws = torch.zeros(max(nbytes, 1 << 16), dtype=torch.uint8, device=dev)
-        _WORKSPACES[key] = ws
-    return ws
+# hk_rollout's per-workgroup counters: allocate before capturing (one eager call of the same shape, or the caller's own
+# `rollout_workspace` + `defer_counts`)
+_ROLLOUT_WORKSPACES = _WorkspaceCache(1 << 16, "hk_rollout's counter workspace would have to be (re)allocated inside a "
+                                      "stream capture: run the same rollout once eagerly on this stream first, or pass "
+                                      "workspace=ops.rollout_workspace(...) with defer_counts=True")
 
 
 def _geometry_desc(batch: int, steps: int, spec: Tuple[int, int], dtype, flags: int) -> "A.hk_rollout_desc":
@@ -458,7 +468,7 @@ def _rollout_launch(r: "A.hk_rollout_desc", dev: torch.device, defer_counts: boo
                     workspace: Optional[torch.Tensor]) -> None:
     """hk_rollout on the filled descriptor, with the caller's workspace or this stream's own"""
     with torch.cuda.device(dev):
-        ws = workspace if defer_counts else _workspace(dev, lib().hk_rollout_workspace_bytes(C.byref(r)))
+        ws = workspace if defer_counts else _ROLLOUT_WORKSPACES.get(dev, lib().hk_rollout_workspace_bytes(C.byref(r)))
         r.workspace, r.workspace_bytes = ws.data_ptr(), ws.numel()
         check(lib().hk_rollout(C.byref(r), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "hk_rollout")
 
@@ -1221,8 +1231,7 @@ def replay_sample(ring_cols: Sequence[torch.Tensor], cursor: torch.Tensor, batch
 
 DQN_TILE_ROWS = A.HK_DQN_TILE_ROWS
 DqnTdResult = collections.namedtuple("DqnTdResult", "loss dq target row_loss status")
-_DQN_WORKSPACES: Dict[Tuple[torch.device, int], torch.Tensor] = {}
-_DQN_RETIRED_WORKSPACES: list = []  # outgrown buffers: a hipGraph captured earlier may still hold their address
+_DQN_WORKSPACES = _WorkspaceCache(1 << 12)  # of dqn_td calls that bring no workspace
 
 
 def dqn_td_workspace(batch: int, device) -> torch.Tensor:
@@ -1232,23 +1241,6 @@ def dqn_td_workspace(batch: int, device) -> torch.Tensor:
     if need == 0:
         raise ValueError(f"batch must be in [0, 2^31). Got {batch}.")
     return torch.zeros(need, dtype=torch.uint8, device=device)
-
-
-def _dqn_workspace(dev: torch.device, batch: int) -> torch.Tensor:
-    """the per-(device, stream) workspace of dqn_td calls that bring none: launches on one stream follow each other, and
-    every launch leaves the ticket zero.  Inside a stream capture that has no workspace yet a fresh one is drawn from the
-    capture's own pool (its zero fill is captured with it) and not kept."""
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    need = int(lib().hk_dqn_td_workspace_bytes(batch))
-    ws = _DQN_WORKSPACES.get(key)
-    if ws is None or ws.numel() < need:
-        if torch.cuda.is_current_stream_capturing():
-            return torch.zeros(need, dtype=torch.uint8, device=dev)
-        if ws is not None:
-            _DQN_RETIRED_WORKSPACES.append(ws)
-        ws = torch.zeros(max(need, 1 << 12), dtype=torch.uint8, device=dev)
-        _DQN_WORKSPACES[key] = ws
-    return ws
 
 
 def _dqn_rows(t: torch.Tensor, name: str, dtype=None) -> torch.Tensor:
@@ -1339,7 +1331,7 @@ def dqn_td(q: torch.Tensor, next_q: torch.Tensor, actions: torch.Tensor, rewards
             raise ValueError(f"out[{name!r}] must be contiguous.")
         extra[name] = t
     if workspace is None:
-        workspace = _dqn_workspace(dev, batch)
+        workspace = _DQN_WORKSPACES.get(dev, int(lib().hk_dqn_td_workspace_bytes(batch)))
     else:
         _require_device(workspace, "workspace")
         if (workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != dev
@@ -1398,8 +1390,9 @@ def polyak_update(srcs: Sequence[torch.Tensor], dsts: Sequence[torch.Tensor], ta
 # ---- the optimiser step: gradient clipping + Adam / SGD of a parameter list in two launches per 64 tensors ----------
 
 OPTIM_KINDS = {"scale": A.HK_OPTIM_SCALE, "sgd": A.HK_OPTIM_SGD, "adam": A.HK_OPTIM_ADAM}
-_OPTIM_WORKSPACES: Dict[Tuple[torch.device, int], torch.Tensor] = {}
-_OPTIM_RETIRED_WORKSPACES: list = []  # outgrown buffers: a hipGraph captured earlier may still hold their address
+_OPTIM_WORKSPACES = _WorkspaceCache(  # of optim_prepare calls that bring no workspace
+    1 << 12, "optim_prepare needs a larger workspace than this stream has, inside a stream capture: "
+             "run one step before capturing, or bring workspace=ops.optim_workspace(...)")
 _OPTIM_STATE_FIELDS = tuple(name for name, _ in A.hk_optim_state._fields_)
 
 
@@ -1416,23 +1409,6 @@ def optim_workspace(total_workgroups: int, device) -> torch.Tensor:
     if need == 0:
         raise ValueError(f"total_workgroups must be in [0, 2^31). Got {total_workgroups}.")
     return torch.zeros(need, dtype=torch.uint8, device=device)
-
-
-def _optim_workspace(dev: torch.device, total_workgroups: int) -> torch.Tensor:
-    """the per-(device, stream) workspace of optim_prepare calls that bring none: zeroed once, every chain leaves the
-    ticket zero; an outgrown one is retired, never freed; growing inside a stream capture is refused."""
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    need = int(lib().hk_optim_workspace_bytes(total_workgroups))
-    ws = _OPTIM_WORKSPACES.get(key)
-    if ws is None or ws.numel() < need:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("optim_prepare needs a larger workspace than this stream has, inside a stream capture: "
-                               "run one step before capturing, or bring workspace=ops.optim_workspace(...)")
-        if ws is not None:
-            _OPTIM_RETIRED_WORKSPACES.append(ws)
-        ws = torch.zeros(max(need, 1 << 12), dtype=torch.uint8, device=dev)
-        _OPTIM_WORKSPACES[key] = ws
-    return ws
 
 
 def optim_state(device, step: int = 0, beta1_pow: float = 1.0, beta2_pow: float = 1.0) -> torch.Tensor:
@@ -1560,7 +1536,9 @@ def optim_prepare(chain: OptimChain, *, max_norm: float = float("inf"), lr=0.0, 
             lr_dev = lr_dev.to(torch.float64)
         chain._lr_dev = lr_dev  # alive until the next call
     with torch.cuda.device(dev):
-        ws = chain.workspace if chain.workspace is not None else _optim_workspace(dev, chain.total_workgroups)
+        ws = chain.workspace
+        if ws is None:
+            ws = _OPTIM_WORKSPACES.get(dev, int(lib().hk_optim_workspace_bytes(chain.total_workgroups)))
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         for k, d in enumerate(chain.descs):
             d.workspace = ws.data_ptr()

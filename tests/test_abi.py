@@ -7,20 +7,16 @@ import re
 
 import pytest
 
+import abi_cases
 from conftest import ROOT
 from hironaka_amd import _abi as A
 from hironaka_amd import _lib
 
 
-def _header():
-    with open(os.path.join(ROOT, "include", "hironaka_hip.h")) as f:
-        return f.read()
-
-
 def test_library_exports_every_declared_symbol():
     _lib.build()
     handle = ctypes.CDLL(_lib.LIB_PATH)
-    declared = set(re.findall(r"^(?:int|uint64_t|const char\*)\s+(hk_\w+)\(", _header(), flags=re.M))
+    declared = abi_cases.declared()
     assert declared == set(A.PROTOTYPES), declared ^ set(A.PROTOTYPES)
     for name in declared:
         assert hasattr(handle, name), name
@@ -29,35 +25,15 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_python_constants_match_header():
-    text = _header()
+    text = abi_cases.header()
     for name, value in re.findall(r"#define\s+(HK_\w+)\s+\(?(-?\d+)u?\)?\s", text):
         assert getattr(A, name) == int(value), name
 
 
-def test_descriptor_layout_matches_c():
+def test_descriptor_layout_matches_c(tmp_path):
     """sizeof/offsetof as the C compiler sees them (gcc on the header) == ctypes."""
-    import subprocess, tempfile
-    fields = {"hk_step_desc": [f[0] for f in A.hk_step_desc._fields_],
-              "hk_rollout_desc": [f[0] for f in A.hk_rollout_desc._fields_],
-              "hk_search_tree": [f[0] for f in A.hk_search_tree._fields_]}
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "hironaka_hip.h"', 'int main(){']
-    for st, fl in fields.items():
-        src.append(f'printf("{st} %zu\\n", sizeof({st}));')
-        for f in fl:
-            src.append(f'printf("{st}.{f} %zu\\n", offsetof({st}, {f}));')
-    src.append('return 0;}')
-    with tempfile.TemporaryDirectory() as td:
-        c = os.path.join(td, "layout.c")
-        open(c, "w").write("\n".join(src))
-        exe = os.path.join(td, "layout")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        out = subprocess.check_output([exe]).decode().split("\n")
-    got = dict(line.split() for line in out if line)
-    for st, cls in (("hk_step_desc", A.hk_step_desc), ("hk_rollout_desc", A.hk_rollout_desc),
-                    ("hk_search_tree", A.hk_search_tree)):
-        assert int(got[st]) == ctypes.sizeof(cls)
-        for f in fields[st]:
-            assert int(got[f"{st}.{f}"]) == getattr(cls, f).offset, (st, f)
+    abi_cases.assert_layouts_match_c({"hk_step_desc": A.hk_step_desc, "hk_rollout_desc": A.hk_rollout_desc,
+                                      "hk_search_tree": A.hk_search_tree}, tmp_path)
 
 
 def test_argument_validation_without_gpu():

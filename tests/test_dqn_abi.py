@@ -3,28 +3,26 @@ them, the python mirror of the header agrees with it, and bad arguments are refu
 import ctypes
 import os
 import re
-import subprocess
 
+import abi_cases
 from conftest import ROOT
 from hironaka_amd import _abi as A
 from hironaka_amd import _lib
 
 
 def _header():
-    with open(os.path.join(ROOT, "include", "hironaka_hip_dqn.h")) as f:
-        return f.read()
+    return abi_cases.header("hironaka_hip_dqn.h")
 
 
 def test_library_exports_the_dqn_entry_points():
     _lib.build()
     handle = ctypes.CDLL(_lib.LIB_PATH)
-    declared = set(re.findall(r"^(?:int|uint64_t|const char\*)\s+(hk_\w+)\(", _header(), flags=re.M))
+    declared = abi_cases.declared("hironaka_hip_dqn.h")
     assert declared == set(A.DQN_PROTOTYPES) == {"hk_dqn_td", "hk_dqn_td_workspace_bytes", "hk_polyak_update"}
     for name in declared:
         assert hasattr(handle, name), name
     assert not declared & set(A.PROTOTYPES)
-    with open(os.path.join(ROOT, "include", "hironaka_hip.h")) as f:
-        text = f.read()
+    text = abi_cases.header()
     assert '#include "hironaka_hip_dqn.h"' in text
     assert not re.search(r"#define\s+HK_(DQN|POLYAK)_", text)  # the feature's defines live in its own header
     assert _lib.lib().hk_abi_version() == A.HK_ABI_VERSION == 6
@@ -43,23 +41,8 @@ def test_dqn_constants_match_header():
 
 def test_dqn_descriptor_layouts_match_c(tmp_path):
     """sizeof/offsetof as the C compiler sees them (gcc on the header) == ctypes"""
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "hironaka_hip.h"', 'int main(){']
-    structs = {"hk_dqn_td_desc": A.hk_dqn_td_desc, "hk_polyak_tensor": A.hk_polyak_tensor,
-               "hk_polyak_desc": A.hk_polyak_desc}
-    for s, cls in structs.items():
-        src.append(f'printf("{s}.size %zu\\n", sizeof({s}));')
-        src += [f'printf("{s}.{f[0]} %zu\\n", offsetof({s}, {f[0]}));' for f in cls._fields_]
-    src.append('return 0;}')
-    c, exe = str(tmp_path / "layout.c"), str(tmp_path / "layout")
-    with open(c, "w") as f:
-        f.write("\n".join(src))
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-    got = dict(line.split() for line in subprocess.check_output([exe]).decode().split("\n") if line)
-    assert len(got) == sum(len(cls._fields_) + 1 for cls in structs.values())
-    for s, cls in structs.items():
-        assert int(got[f"{s}.size"]) == ctypes.sizeof(cls), s
-        for f in cls._fields_:
-            assert int(got[f"{s}.{f[0]}"]) == getattr(cls, f[0]).offset, (s, f[0])
+    abi_cases.assert_layouts_match_c({"hk_dqn_td_desc": A.hk_dqn_td_desc, "hk_polyak_tensor": A.hk_polyak_tensor,
+                                      "hk_polyak_desc": A.hk_polyak_desc}, tmp_path)
 
 
 def test_workspace_bytes():

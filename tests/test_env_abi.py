@@ -1,30 +1,26 @@
 """CPU-side checks of hk_env_step's boundary (include/hironaka_hip_env.h): the library exports it, the python mirror of
 the header agrees with it, and bad arguments are refused on the host, before any launch."""
 import ctypes
-import os
 import re
-import subprocess
 
-from conftest import ROOT
+import abi_cases
 from hironaka_amd import _abi as A
 from hironaka_amd import _lib
 
 
 def _header():
-    with open(os.path.join(ROOT, "include", "hironaka_hip_env.h")) as f:
-        return f.read()
+    return abi_cases.header("hironaka_hip_env.h")
 
 
 def test_library_exports_hk_env_step():
     _lib.build()
     handle = ctypes.CDLL(_lib.LIB_PATH)
-    declared = set(re.findall(r"^(?:int|uint64_t|const char\*)\s+(hk_\w+)\(", _header(), flags=re.M))
+    declared = abi_cases.declared("hironaka_hip_env.h")
     assert declared == set(A.ENV_PROTOTYPES) == {"hk_env_step"}
     for name in declared:
         assert hasattr(handle, name), name
     assert not declared & set(A.PROTOTYPES)
-    with open(os.path.join(ROOT, "include", "hironaka_hip.h")) as f:
-        assert '#include "hironaka_hip_env.h"' in f.read()
+    assert '#include "hironaka_hip_env.h"' in abi_cases.header()
     assert _lib.lib().hk_abi_version() == A.HK_ABI_VERSION == 6
 
 
@@ -37,20 +33,7 @@ def test_env_constants_match_header():
 
 def test_env_descriptor_layout_matches_c(tmp_path):
     """sizeof/offsetof as the C compiler sees them (gcc on the header) == ctypes"""
-    fields = [f[0] for f in A.hk_env_step_desc._fields_]
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "hironaka_hip.h"', 'int main(){',
-           'printf("size %zu\\n", sizeof(hk_env_step_desc));']
-    src += [f'printf("{f} %zu\\n", offsetof(hk_env_step_desc, {f}));' for f in fields]
-    src.append('return 0;}')
-    c, exe = str(tmp_path / "layout.c"), str(tmp_path / "layout")
-    with open(c, "w") as f:
-        f.write("\n".join(src))
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-    got = dict(line.split() for line in subprocess.check_output([exe]).decode().split("\n") if line)
-    assert int(got["size"]) == ctypes.sizeof(A.hk_env_step_desc)
-    assert len(got) == len(fields) + 1
-    for f in fields:
-        assert int(got[f]) == getattr(A.hk_env_step_desc, f).offset, f
+    abi_cases.assert_layouts_match_c({"hk_env_step_desc": A.hk_env_step_desc}, tmp_path)
 
 
 def _desc(**over):

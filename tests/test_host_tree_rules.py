@@ -4,15 +4,14 @@ boundary; and TreeNode's DOT text."""
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import abi_cases
 import host_tree_rules as H
 import search_rules as R
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
 from hironaka_amd import _abi as A
 from hironaka_amd import _lib
 from oracle import np_oracle as NO
@@ -79,34 +78,19 @@ def test_leaves_sit_one_level_below_max_depth():
     assert len(H.tree(root, lambda s: 3, max_depth=1, depth=2).parent) == 1
 
 
-def test_symbol_constants_and_descriptor_are_bound():
+def test_symbol_constants_and_descriptor_are_bound(tmp_path):
     handle = ctypes.CDLL(_lib.build())
     assert hasattr(handle, "hk_tree_expand") and set(A.TREE_PROTOTYPES) == {"hk_tree_expand"}
     assert _lib.lib().hk_tree_expand.argtypes == A.TREE_PROTOTYPES["hk_tree_expand"][1]
-    with open(os.path.join(ROOT, "include", "hironaka_hip_tree.h")) as f:
-        text = f.read()
+    text = abi_cases.header("hironaka_hip_tree.h")
     assert re.search(r"^int hk_tree_expand\(const hk_tree_expand_desc\* desc, void\* stream\);", text, flags=re.M)
-    with open(os.path.join(ROOT, "include", "hironaka_hip.h")) as f:
-        assert '#include "hironaka_hip_tree.h"' in f.read()
+    assert '#include "hironaka_hip_tree.h"' in abi_cases.header()
     found = re.findall(r"#define\s+(HK_TREE_\w+)\s+\(?(-?\d+)u?\)?\s", text)
     assert len(found) == 3
     for name, value in found:
         assert getattr(A, name) == int(value), name
     assert A.HK_ABI_VERSION == 6 and _lib.lib().hk_abi_version() == 6
-    fields = [f[0] for f in A.hk_tree_expand_desc._fields_]
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "hironaka_hip.h"', 'int main(){',
-           'printf("size %zu\\n", sizeof(hk_tree_expand_desc));']
-    src += [f'printf("{f} %zu\\n", offsetof(hk_tree_expand_desc, {f}));' for f in fields] + ['return 0;}']
-    with tempfile.TemporaryDirectory() as td:
-        c = os.path.join(td, "layout.c")
-        with open(c, "w") as f:
-            f.write("\n".join(src))
-        exe = os.path.join(td, "layout")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        got = dict(line.split() for line in subprocess.check_output([exe]).decode().split("\n") if line)
-    assert int(got["size"]) == ctypes.sizeof(A.hk_tree_expand_desc)
-    for f in fields:
-        assert int(got[f]) == getattr(A.hk_tree_expand_desc, f).offset, f
+    abi_cases.assert_layouts_match_c({"hk_tree_expand_desc": A.hk_tree_expand_desc}, tmp_path)
 
 
 def _desc(buf, out, ints, **kw):

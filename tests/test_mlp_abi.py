@@ -5,24 +5,23 @@ import os
 import re
 import subprocess
 
+import abi_cases
 from conftest import ROOT
 from hironaka_amd import _abi as A
 from hironaka_amd import _lib
 
 
 def _header():
-    with open(os.path.join(ROOT, "include", "hironaka_hip_mlp.h")) as f:
-        return f.read()
+    return abi_cases.header("hironaka_hip_mlp.h")
 
 
 def test_library_exports_the_mlp_entry_points():
     _lib.build()
-    declared = set(re.findall(r"^(?:int|uint64_t)\s+(hk_\w+)\(", _header(), flags=re.M))
+    declared = abi_cases.declared("hironaka_hip_mlp.h")
     assert declared == set(A.MLP_PROTOTYPES) == {"hk_mlp_row_tile", "hk_mlp_forward"}
     exported = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
     assert set(re.findall(r"\bT (hk_mlp_\w+)", exported)) == declared  # exactly what the header declares
-    with open(os.path.join(ROOT, "include", "hironaka_hip.h")) as f:
-        text = f.read()
+    text = abi_cases.header()
     assert text.index('#include "hironaka_hip_optim.h"') < text.index('#include "hironaka_hip_mlp.h"')
     assert not re.search(r"#define\s+HK_MLP_", text)  # the feature's defines live in its own header
     assert _lib.lib().hk_abi_version() == A.HK_ABI_VERSION == 6
@@ -46,22 +45,7 @@ def test_mlp_constants_match_header():
 
 def test_mlp_descriptor_layouts_match_c(tmp_path):
     """sizeof/offsetof as the C compiler sees them (gcc on the header) == ctypes"""
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "hironaka_hip.h"', 'int main(){']
-    structs = {"hk_mlp_layer": A.hk_mlp_layer, "hk_mlp_desc": A.hk_mlp_desc}
-    for s, cls in structs.items():
-        src.append(f'printf("{s}.size %zu\\n", sizeof({s}));')
-        src += [f'printf("{s}.{f[0]} %zu\\n", offsetof({s}, {f[0]}));' for f in cls._fields_]
-    src.append('return 0;}')
-    c, exe = str(tmp_path / "layout.c"), str(tmp_path / "layout")
-    with open(c, "w") as f:
-        f.write("\n".join(src))
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-    got = dict(line.split() for line in subprocess.check_output([exe]).decode().split("\n") if line)
-    assert len(got) == sum(len(cls._fields_) + 1 for cls in structs.values())
-    for s, cls in structs.items():
-        assert int(got[f"{s}.size"]) == ctypes.sizeof(cls), s
-        for f in cls._fields_:
-            assert int(got[f"{s}.{f[0]}"]) == getattr(cls, f[0]).offset, (s, f[0])
+    abi_cases.assert_layouts_match_c({"hk_mlp_layer": A.hk_mlp_layer, "hk_mlp_desc": A.hk_mlp_desc}, tmp_path)
 
 
 _LAYER_PTRS = ("weight", "bias", "bn_mean", "bn_var", "bn_weight", "bn_bias")
@@ -162,3 +146,14 @@ def test_mlp_validation_without_gpu():
     assert run(x0=("at", -4 * 14), **rec) == A.HK_ERR_UNSUPPORTED  # out runs into the next record's x0
     assert run(x0=("at", 4 * 2), **rec) == A.HK_ERR_UNSUPPORTED  # x0 begins on out's last element
     # (ranges that only touch are accepted: test_gpu_mlp.py runs views of one storage side by side)
+
+
+def test_mlp_row_span_beyond_63_bits_is_refused():
+    """two rows 2^62 floats apart span 2^64 bytes: refused as a shape, where the spans are first computed (after the
+    pointer and alignment checks), not wrapped into a span that passes the overlap check"""
+    L = _lib.lib()
+    run = lambda **kw: L.hk_mlp_forward(ctypes.byref(_desc(batch=2, **kw)), None)  # noqa: E731
+    assert run(x0_stride=1 << 62) == A.HK_ERR_SHAPE
+    assert run(out_stride=1 << 62) == A.HK_ERR_SHAPE
+    assert run(x0_stride=1 << 62, out_stride=1 << 62) == A.HK_ERR_SHAPE
+    assert run(x0_stride=1 << 62, out=None) == A.HK_ERR_NULL and run(x0_stride=1 << 62, x0=("shift", 2)) == A.HK_ERR_ALIGN

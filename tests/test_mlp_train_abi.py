@@ -6,6 +6,7 @@ import os
 import re
 import subprocess
 
+import abi_cases
 from conftest import ROOT
 from hironaka_amd import _abi as A
 from hironaka_amd import _lib
@@ -14,18 +15,16 @@ NAMES = {"hk_train_mlp_rows", "hk_train_mlp_workspace_bytes", "hk_train_mlp_forw
 
 
 def _header():
-    with open(os.path.join(ROOT, "include", "hironaka_hip_mlp_train.h")) as f:
-        return f.read()
+    return abi_cases.header("hironaka_hip_mlp_train.h")
 
 
 def test_library_exports_the_entry_points():
     _lib.build()
-    declared = set(re.findall(r"^(?:int|uint64_t)\s+(hk_\w+)\(", _header(), flags=re.M))
+    declared = abi_cases.declared("hironaka_hip_mlp_train.h")
     assert declared == set(A.MLP_TRAIN_PROTOTYPES) == NAMES
     exported = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
     assert set(re.findall(r"\bT (hk_train_\w+)", exported)) == declared  # exactly what the header declares
-    with open(os.path.join(ROOT, "include", "hironaka_hip.h")) as f:
-        text = f.read()
+    text = abi_cases.header()
     assert text.index('#include "hironaka_hip_mlp.h"') < text.index('#include "hironaka_hip_mlp_train.h"')
     assert _lib.lib().hk_abi_version() == A.HK_ABI_VERSION == 6
     assert _lib.lib().hk_train_mlp_backward.argtypes == A.MLP_TRAIN_PROTOTYPES["hk_train_mlp_backward"][1]  # bound by default
@@ -48,22 +47,8 @@ def test_constants_match_header():
 
 def test_descriptor_layouts_match_c(tmp_path):
     """sizeof/offsetof as the C compiler sees them (gcc on the header, as C) == ctypes"""
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "hironaka_hip.h"', 'int main(){']
-    structs = {"hk_mlp_train_layer": A.hk_mlp_train_layer, "hk_mlp_train_desc": A.hk_mlp_train_desc}
-    for s, cls in structs.items():
-        src.append(f'printf("{s}.size %zu\\n", sizeof({s}));')
-        src += [f'printf("{s}.{f[0]} %zu\\n", offsetof({s}, {f[0]}));' for f in cls._fields_]
-    src.append('return 0;}')
-    c, exe = str(tmp_path / "layout.c"), str(tmp_path / "layout")
-    with open(c, "w") as f:
-        f.write("\n".join(src))
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-    got = dict(line.split() for line in subprocess.check_output([exe]).decode().split("\n") if line)
-    assert len(got) == sum(len(cls._fields_) + 1 for cls in structs.values())
-    for s, cls in structs.items():
-        assert int(got[f"{s}.size"]) == ctypes.sizeof(cls), s
-        for f in cls._fields_:
-            assert int(got[f"{s}.{f[0]}"]) == getattr(cls, f[0]).offset, (s, f[0])
+    abi_cases.assert_layouts_match_c({"hk_mlp_train_layer": A.hk_mlp_train_layer,
+                                      "hk_mlp_train_desc": A.hk_mlp_train_desc}, tmp_path)
     assert ctypes.sizeof(A.hk_mlp_train_layer) == 144
 
 
@@ -186,3 +171,16 @@ def test_validation_without_gpu():
         else:
             assert ok(grad_out=None, workspace=None, workspace_bytes=0) == A.HK_OK  # the backward's alone
             assert ok(layer1=dict(d_weight=None)) == A.HK_OK
+
+
+def test_row_span_beyond_63_bits_is_refused():
+    """two rows 2^62 floats apart span 2^64 bytes: refused as a shape, where the spans are first computed (after the
+    pointer and alignment checks), not wrapped into a span that passes the overlap check"""
+    L = _lib.lib()
+    for entry, backward in ((L.hk_train_mlp_forward, False), (L.hk_train_mlp_backward, True)):
+        run = lambda **kw: entry(ctypes.byref(_desc(batch=2, **kw)), None)  # noqa: E731
+        assert run(x0_stride=1 << 62) == A.HK_ERR_SHAPE
+        assert run(x0_stride=1 << 62, x0=None) == A.HK_ERR_NULL and run(x0_stride=1 << 62, x0=("shift", 2)) == A.HK_ERR_ALIGN
+        if backward:
+            assert run(grad_stride=1 << 62) == A.HK_ERR_SHAPE
+            assert run(x0_stride=1 << 62, grad_stride=1 << 62) == A.HK_ERR_SHAPE

@@ -9,9 +9,10 @@ import re
 import numpy as np
 import pytest
 
+import abi_cases
 import morin_rules as M
 import search_rules as R
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
 from hironaka_amd import _abi as A
 from hironaka_amd import _lib
 
@@ -130,7 +131,7 @@ def test_symbol_descriptor_and_constants():
     assert "hk_search_morin_play" in A.PROTOTYPES
     assert L.hk_search_morin_play.argtypes == A.PROTOTYPES["hk_search_morin_play"][1]
     assert A.HK_ABI_VERSION == 6 and L.hk_abi_version() == 6
-    text = open(os.path.join(ROOT, "include", "hironaka_hip.h")).read()
+    text = abi_cases.header()
     for name in ("HK_MORIN_RUNNING", "HK_MORIN_ENDED", "HK_MORIN_NO_CONTRIBUTION", "HK_MORIN_NO_MOVE",
                  "HK_MORIN_INEXACT", "HK_MORIN_TIE_LOWEST", "HK_MORIN_TIE_HIGHEST", "HK_MORIN_TIE_RANDOM",
                  "HK_MORIN_WEIGHTS_AGENT", "HK_MORIN_WEIGHTS_SEARCH", "HK_MORIN_REDUCE_ROOT", "HK_MORIN_HOST_FORCED"):
@@ -144,19 +145,7 @@ def test_symbol_descriptor_and_constants():
 
 def test_descriptor_layout_matches_c(tmp_path):
     """sizeof/offsetof as the C compiler sees them == ctypes"""
-    import subprocess
-    fields = [f[0] for f in A.hk_morin_play_desc._fields_]
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "hironaka_hip.h"', 'int main(){',
-           'printf("size %zu\\n", sizeof(hk_morin_play_desc));']
-    src += [f'printf("{f} %zu\\n", offsetof(hk_morin_play_desc, {f}));' for f in fields]
-    src.append('return 0;}')
-    c, exe = tmp_path / "layout.c", tmp_path / "layout"
-    c.write_text("\n".join(src))
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    got = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().split("\n") if line)
-    assert int(got["size"]) == ctypes.sizeof(A.hk_morin_play_desc)
-    for f in fields:
-        assert int(got[f]) == getattr(A.hk_morin_play_desc, f).offset, f
+    abi_cases.assert_layouts_match_c({"hk_morin_play_desc": A.hk_morin_play_desc}, tmp_path)
 
 
 REQUIRED = ("points_in", "points_out", "weights_in", "weights_out", "distinguished_in", "distinguished_out", "length_out",

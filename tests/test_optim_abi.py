@@ -6,32 +6,30 @@ import os
 import re
 import subprocess
 
+import abi_cases
 from conftest import ROOT
 from hironaka_amd import _abi as A
 from hironaka_amd import _lib
 
 
 def _header():
-    with open(os.path.join(ROOT, "include", "hironaka_hip_optim.h")) as f:
-        return f.read()
+    return abi_cases.header("hironaka_hip_optim.h")
 
 
 def test_library_exports_the_optim_entry_points():
     _lib.build()
     handle = ctypes.CDLL(_lib.LIB_PATH)
-    declared = set(re.findall(r"^(?:int|uint64_t|const char\*)\s+(hk_\w+)\(", _header(), flags=re.M))
+    declared = abi_cases.declared("hironaka_hip_optim.h")
     assert declared == set(A.OPTIM_PROTOTYPES) == {"hk_optim_workspace_bytes", "hk_optim_prepare", "hk_optim_apply"}
     for name in declared:
         assert hasattr(handle, name), name
     exported = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
     assert set(re.findall(r"\bT (hk_optim_\w+)", exported)) == declared  # exactly what the header declares
     assert not declared & (set(A.PROTOTYPES) | set(A.DQN_PROTOTYPES))
-    with open(os.path.join(ROOT, "include", "hironaka_hip.h")) as f:
-        text = f.read()
+    text = abi_cases.header()
     assert text.index('#include "hironaka_hip_dqn.h"') < text.index('#include "hironaka_hip_optim.h"')
     assert not re.search(r"#define\s+HK_OPTIM_", text)  # the feature's defines live in its own header
-    with open(os.path.join(ROOT, "include", "hironaka_hip_dqn.h")) as f:
-        assert "optim" not in f.read().lower()
+    assert "optim" not in abi_cases.header("hironaka_hip_dqn.h").lower()
     assert _lib.lib().hk_abi_version() == A.HK_ABI_VERSION == 6
     assert _lib.lib().hk_optim_apply.argtypes == A.OPTIM_PROTOTYPES["hk_optim_apply"][1]  # bound by default
     with open(os.path.join(ROOT, "hironaka_amd", "csrc", "Makefile")) as f:
@@ -51,23 +49,8 @@ def test_optim_constants_match_header():
 
 def test_optim_descriptor_layouts_match_c(tmp_path):
     """sizeof/offsetof as the C compiler sees them (gcc on the header) == ctypes"""
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "hironaka_hip.h"', 'int main(){']
-    structs = {"hk_optim_tensor": A.hk_optim_tensor, "hk_optim_state": A.hk_optim_state,
-               "hk_optim_desc": A.hk_optim_desc}
-    for s, cls in structs.items():
-        src.append(f'printf("{s}.size %zu\\n", sizeof({s}));')
-        src += [f'printf("{s}.{f[0]} %zu\\n", offsetof({s}, {f[0]}));' for f in cls._fields_]
-    src.append('return 0;}')
-    c, exe = str(tmp_path / "layout.c"), str(tmp_path / "layout")
-    with open(c, "w") as f:
-        f.write("\n".join(src))
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-    got = dict(line.split() for line in subprocess.check_output([exe]).decode().split("\n") if line)
-    assert len(got) == sum(len(cls._fields_) + 1 for cls in structs.values())
-    for s, cls in structs.items():
-        assert int(got[f"{s}.size"]) == ctypes.sizeof(cls), s
-        for f in cls._fields_:
-            assert int(got[f"{s}.{f[0]}"]) == getattr(cls, f[0]).offset, (s, f[0])
+    abi_cases.assert_layouts_match_c({"hk_optim_tensor": A.hk_optim_tensor, "hk_optim_state": A.hk_optim_state,
+                                      "hk_optim_desc": A.hk_optim_desc}, tmp_path)
 
 
 def test_workspace_bytes():

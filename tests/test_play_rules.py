@@ -5,15 +5,14 @@ the symbol, the descriptor and the constants are bound; bad arguments are refuse
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import abi_cases
 import play_rules as P
 import search_rules as R
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
 from hironaka_amd import _abi as A
 from hironaka_amd import _lib
 
@@ -159,15 +158,10 @@ def test_playoff_history_refuses_games_without_a_length():
 
 # ---- the C boundary ------------------------------------------------------------------------------------------------
 
-def _play_header():
-    with open(os.path.join(ROOT, "include", "hironaka_hip_play.h")) as f:
-        return f.read()
-
-
-def test_symbol_constants_and_descriptor_are_bound():
+def test_symbol_constants_and_descriptor_are_bound(tmp_path):
     handle = ctypes.CDLL(_lib.build())
     assert hasattr(handle, "hk_game_play") and set(A.PLAY_PROTOTYPES) == {"hk_game_play"}
-    text = _play_header()
+    text = abi_cases.header("hironaka_hip_play.h")
     assert re.search(r"^int hk_game_play\(const hk_game_play_desc\* desc, void\* stream\);", text, flags=re.M)
     found = re.findall(r"#define\s+(HK_PLAY_\w+)\s+\(?(-?\d+)u?\)?\s", text)
     assert len(found) == 10
@@ -179,20 +173,7 @@ def test_symbol_constants_and_descriptor_are_bound():
         A.HK_PLAY_RUNNING, A.HK_PLAY_ENDED, A.HK_PLAY_NO_MOVE, A.HK_PLAY_INEXACT, A.HK_PLAY_VALUE_LIMIT)
     assert A.HK_ABI_VERSION == 6
     # sizeof / offsetof as the C compiler sees them
-    fields = [f[0] for f in A.hk_game_play_desc._fields_]
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "hironaka_hip.h"', 'int main(){',
-           'printf("size %zu\\n", sizeof(hk_game_play_desc));']
-    src += [f'printf("{f} %zu\\n", offsetof(hk_game_play_desc, {f}));' for f in fields] + ['return 0;}']
-    with tempfile.TemporaryDirectory() as td:
-        c = os.path.join(td, "layout.c")
-        with open(c, "w") as f:
-            f.write("\n".join(src))
-        exe = os.path.join(td, "layout")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        got = dict(line.split() for line in subprocess.check_output([exe]).decode().split("\n") if line)
-    assert int(got["size"]) == ctypes.sizeof(A.hk_game_play_desc)
-    for f in fields:
-        assert int(got[f]) == getattr(A.hk_game_play_desc, f).offset, f
+    abi_cases.assert_layouts_match_c({"hk_game_play_desc": A.hk_game_play_desc}, tmp_path)
 
 
 def _desc(buf, ints, **kw):

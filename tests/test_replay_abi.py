@@ -2,30 +2,26 @@
 exports them, the python mirror of the header agrees with it, and bad arguments are refused on the host, before any
 launch."""
 import ctypes
-import os
 import re
-import subprocess
 
-from conftest import ROOT
+import abi_cases
 from hironaka_amd import _abi as A
 from hironaka_amd import _lib
 
 
 def _header():
-    with open(os.path.join(ROOT, "include", "hironaka_hip_replay.h")) as f:
-        return f.read()
+    return abi_cases.header("hironaka_hip_replay.h")
 
 
 def test_library_exports_the_replay_entry_points():
     _lib.build()
     handle = ctypes.CDLL(_lib.LIB_PATH)
-    declared = set(re.findall(r"^(?:int|uint64_t|const char\*)\s+(hk_\w+)\(", _header(), flags=re.M))
+    declared = abi_cases.declared("hironaka_hip_replay.h")
     assert declared == set(A.REPLAY_PROTOTYPES) == {"hk_replay_push", "hk_replay_sample"}
     for name in declared:
         assert hasattr(handle, name), name
     assert not declared & set(A.PROTOTYPES)
-    with open(os.path.join(ROOT, "include", "hironaka_hip.h")) as f:
-        assert '#include "hironaka_hip_replay.h"' in f.read()
+    assert '#include "hironaka_hip_replay.h"' in abi_cases.header()
     assert _lib.lib().hk_abi_version() == A.HK_ABI_VERSION == 6
     assert _lib.lib().hk_replay_push.argtypes == A.REPLAY_PROTOTYPES["hk_replay_push"][1]  # bound by default
 
@@ -39,22 +35,7 @@ def test_replay_constants_match_header():
 
 def test_replay_descriptor_layout_matches_c(tmp_path):
     """sizeof/offsetof as the C compiler sees them (gcc on the header) == ctypes"""
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "hironaka_hip.h"', 'int main(){']
-    structs = {"hk_replay_col": A.hk_replay_col, "hk_replay_desc": A.hk_replay_desc}
-    for s, cls in structs.items():
-        src.append(f'printf("{s}.size %zu\\n", sizeof({s}));')
-        src += [f'printf("{s}.{f[0]} %zu\\n", offsetof({s}, {f[0]}));' for f in cls._fields_]
-    src.append('return 0;}')
-    c, exe = str(tmp_path / "layout.c"), str(tmp_path / "layout")
-    with open(c, "w") as f:
-        f.write("\n".join(src))
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-    got = dict(line.split() for line in subprocess.check_output([exe]).decode().split("\n") if line)
-    assert len(got) == sum(len(cls._fields_) + 1 for cls in structs.values())
-    for s, cls in structs.items():
-        assert int(got[f"{s}.size"]) == ctypes.sizeof(cls), s
-        for f in cls._fields_:
-            assert int(got[f"{s}.{f[0]}"]) == getattr(cls, f[0]).offset, (s, f[0])
+    abi_cases.assert_layouts_match_c({"hk_replay_col": A.hk_replay_col, "hk_replay_desc": A.hk_replay_desc}, tmp_path)
 
 
 def _desc(ncols=2, col=None, **over):
