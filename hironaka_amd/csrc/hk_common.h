@@ -124,19 +124,15 @@ inline int kernel_mode(const Params& prm) {
   return prm.mode == kModeRollout || prm.mode == kModeGenerate ? prm.mode : -1;
 }
 
-// hipGetLastError() is sticky per host thread and other users of the runtime in this process
-// (torch) leave benign errors behind: clear it right before a launch, read it right after.
-inline void launch_prepare() { (void)hipGetLastError(); }
-inline int launch_status() { return hipGetLastError() == hipSuccess ? HK_OK : HK_ERR_LAUNCH; }
-// a launch of the library: the kernel, its grid and block, dynamic LDS, the stream, the kernel's arguments.  Every launch
-// goes through here but those of the one-game-per-lane operators and the replay buffer, which spell the same three steps
-// out: launch_search (hk_search_wave.h), hk_game_play.hip, hk_morin_play.hip, hk_env_step.hip, hk_host_select.hip,
-// hk_tree_expand.hip, hk_replay.hip
+// A launch of the library: the kernel, its grid and block, dynamic LDS, the stream, the kernel's arguments.  Every launch
+// of the library goes through here (launch_kernel_lds and launch_search, hk_search_wave.h, end in it).
+// hipGetLastError() is sticky per host thread and other users of the runtime in this process (torch) leave benign errors
+// behind: it is cleared right before the launch and read right after.
 template <typename... KArgs, typename... Args>
 int launch_kernel(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
-  launch_prepare();
+  (void)hipGetLastError();
   hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
-  return launch_status();
+  return hipGetLastError() == hipSuccess ? HK_OK : HK_ERR_LAUNCH;
 }
 // launch_kernel for a kernel whose dynamic LDS may exceed `opt_in_above` bytes: beyond it (64 KiB of static + dynamic LDS)
 // the size is a per-function opt-in (idempotent, cheap), made right before the launch

@@ -30,9 +30,9 @@ int hk_env_step(const hk_env_step_desc* q, void* stream) {
   if (host_mode && (!q->class_io || !q->obs_coords)) return HK_ERR_NULL;
   const size_t es = elem_size(q->dtype);
   const int64_t n = (int64_t)q->max_points * q->dim;
-  if (!reset_all && q->points_in != q->points_out &&
-      records_overlap(q->points_in, n, q->batch, n, q->points_out, n, q->batch, n, es))
-    return HK_ERR_SHAPE;
+  // a workgroup's write-back must not meet another's staging read: other than in place, the two spans do not overlap
+  const uint64_t bytes = span_bytes(q->batch, n, n, es);  // dense records of the sizes accepted above: never too large
+  if (!reset_all && q->points_in != q->points_out && overlap(q->points_in, bytes, q->points_out, bytes)) return HK_ERR_SHAPE;
   if (!all_aligned({q->class_io, q->step_count, q->episode, q->action, q->obs_points, q->final_points, q->agent_axis}, 4) ||
       !all_aligned({q->reward, q->obs_coords, q->final_coords}, 8) || !all_aligned({q->points_in, q->points_out}, es))
     return HK_ERR_ALIGN;
@@ -70,9 +70,7 @@ int hk_env_step(const hk_env_step_desc* q, void* stream) {
   a.games_per_block = geo.per_block;
   // agent mode: no host, the kernel's HOST is 0
   return with_fixed_host_or(q->dtype, host_mode ? q->host : 0, std::integral_constant<int, 0>(), [&](auto t, auto h) {
-    launch_prepare();
-    hipLaunchKernelGGL((env_step_kernel<decltype(t), h>), dim3(geo.grid), dim3(kWave), geo.lds, (hipStream_t)stream, a);
-    return launch_status();
+    return launch_kernel(env_step_kernel<decltype(t), h>, dim3(geo.grid), dim3(kWave), geo.lds, (hipStream_t)stream, a);
   });
 }
 

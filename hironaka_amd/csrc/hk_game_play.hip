@@ -24,9 +24,10 @@ int hk_game_play(const hk_game_play_desc* q, void* stream) {
   if (q->in_stride < n || q->out_stride < n) return HK_ERR_SHAPE;
   if (q->points_in == q->points_out && q->in_stride != q->out_stride) return HK_ERR_SHAPE;
   const size_t es = elem_size(q->dtype);
-  if (q->points_in != q->points_out &&
-      records_overlap(q->points_in, q->in_stride, q->batch, n, q->points_out, q->out_stride, q->batch, n, es))
-    return HK_ERR_SHAPE;
+  // a workgroup's write-back must not meet another's staging read: other than in place, the two spans do not overlap
+  const uint64_t in_bytes = span_bytes(q->batch, q->in_stride, n, es), out_bytes = span_bytes(q->batch, q->out_stride, n, es);
+  if (!in_bytes || !out_bytes) return HK_ERR_SHAPE;  // a span beyond 2^63 bytes
+  if (q->points_in != q->points_out && overlap(q->points_in, in_bytes, q->points_out, out_bytes)) return HK_ERR_SHAPE;
   if (!all_aligned({q->class_in, q->axis_in, q->class_out, q->axis_out, q->length_out, q->outcome_out}, 4) ||
       !all_aligned({q->points_in, q->points_out}, es))
     return HK_ERR_ALIGN;
@@ -58,9 +59,7 @@ int hk_game_play(const hk_game_play_desc* q, void* stream) {
   const LaneGeometry geo = lane_geometry(a.lds_stride, es, a.batch);
   a.games_per_block = geo.per_block;
   return with_fixed_host_or(q->dtype, q->host, std::integral_constant<int, HK_PLAY_HOST_FORCED>(), [&](auto t, auto h) {
-    launch_prepare();
-    hipLaunchKernelGGL((game_play_kernel<decltype(t), h>), dim3(geo.grid), dim3(kWave), geo.lds, (hipStream_t)stream, a);
-    return launch_status();
+    return launch_kernel(game_play_kernel<decltype(t), h>, dim3(geo.grid), dim3(kWave), geo.lds, (hipStream_t)stream, a);
   });
 }
 

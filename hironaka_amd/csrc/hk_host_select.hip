@@ -32,9 +32,7 @@ int hk_host_select(const void* points, int64_t stride, int32_t* class_out, int b
   return with_fixed_host(dtype, host, [&](auto t, auto h) {
     using T = decltype(t);
     const size_t lds = h == HK_HOST_ALL_COORD ? 0 : (size_t)a.lds_stride * a.games_per_block * sizeof(T);
-    launch_prepare();
-    hipLaunchKernelGGL((host_select_kernel<T, h>), dim3(grid), dim3(kWave), lds, (hipStream_t)stream, a);
-    return launch_status();
+    return launch_kernel(host_select_kernel<T, h>, dim3(grid), dim3(kWave), lds, (hipStream_t)stream, a);
   });
 }
 

@@ -12,7 +12,8 @@
 // communication between workgroups; every loop of a lane is bounded by the sizes in its argument block.
 //
 // Here: the block prologue and the staging, the helpers of a move, the Morin child, the moves a game is given and
-// leaves (hk_game_play and hk_search_morin_play), and the argument checks the C entries share.
+// leaves (hk_game_play and hk_search_morin_play), and the choice of instantiation the C entries share (their record
+// buffers are judged by span_bytes and overlap, hk_common.h).
 #pragma once
 
 #include "hk_generic_kernel.h"
@@ -171,18 +172,7 @@ __device__ inline void finish_game(const MoveRecords& r, int64_t g, int len, con
     for (int e = 0; e < n; ++e) home.par[e] = s.par[e];
 }
 
-// ---- the argument checks the C entries share -------------------------------------------------------------------------
-// Whether the byte ranges meet that in_count records of in_len elements, in_stride apart, and out_count records of
-// out_len elements, out_stride apart, span: a workgroup's write-back must not meet another's staging read, so other
-// than in place, where an entry takes that, the two do not overlap.
-inline bool records_overlap(const void* in, int64_t in_stride, int64_t in_count, int64_t in_len, const void* out,
-                            int64_t out_stride, int64_t out_count, int64_t out_len, size_t elem_size) {
-  const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
-  const uint64_t in_bytes = ((uint64_t)(in_count - 1) * (uint64_t)in_stride + (uint64_t)in_len) * elem_size;
-  const uint64_t out_bytes = ((uint64_t)(out_count - 1) * (uint64_t)out_stride + (uint64_t)out_len) * elem_size;
-  return i0 < o0 + out_bytes && o0 < i0 + in_bytes;
-}
-
+// ---- the choice of instantiation the C entries share -----------------------------------------------------------------
 // with_fixed_host for "a fixed host, or this one extra code": f(T(), other) when host is other's value
 // (HK_PLAY_HOST_FORCED, HK_MORIN_HOST_FORCED, or 0 for the environments' agent mode)
 template <int OTHER, typename F>

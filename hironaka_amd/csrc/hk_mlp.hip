@@ -7,7 +7,6 @@ using namespace hk;
 namespace {
 
 constexpr uint32_t kDescFlags = HK_MLP_INPUT_RELU | HK_MLP_FORCE_TILE_SMALL | HK_MLP_FORCE_TILE_LARGE;
-constexpr uint32_t kLayerFlags = HK_MLP_RELU;
 
 // out's rows (`out_bytes` from first to last, n wide) share a byte with the rows of an input (`x_bytes`, k wide).  Rows of
 // one stride that holds both widths are records side by side: they meet only where the windows meet inside a record (any
@@ -25,21 +24,12 @@ bool has_bn(const hk_mlp_layer& L) { return L.bn_mean || L.bn_var || L.bn_weight
 bool has_in_bn(const hk_mlp_desc* q) { return q->in_bn_mean || q->in_bn_var || q->in_bn_weight || q->in_bn_bias; }
 
 int validate(const hk_mlp_desc* q) {
-  if (!q) return HK_ERR_NULL;
-  if (q->dtype != HK_F32) return HK_ERR_UNSUPPORTED;
-  if (q->flags & ~kDescFlags) return HK_ERR_UNSUPPORTED;
+  if (const int bad = mlp_check_desc(q, kDescFlags)) return bad;
   if ((q->flags & HK_MLP_FORCE_TILE_SMALL) && (q->flags & HK_MLP_FORCE_TILE_LARGE)) return HK_ERR_UNSUPPORTED;
-  if (q->nlayers < 1 || q->nlayers > HK_MLP_MAX_LAYERS) return HK_ERR_SHAPE;
-  if (q->batch < 0 || q->k0 < 1 || q->k1 < 0 || q->x0_stride < 0 || q->x1_stride < 0) return HK_ERR_SHAPE;
-  int64_t width = (int64_t)q->k0 + q->k1;
-  for (int l = 0; l < q->nlayers; ++l) {
-    const hk_mlp_layer& L = q->layer[l];
-    if (L.flags & ~kLayerFlags) return HK_ERR_UNSUPPORTED;
-    if (L.k < 1 || L.k > HK_MLP_MAX_WIDTH || L.n < 1 || L.n > HK_MLP_MAX_WIDTH || L.k != width) return HK_ERR_SHAPE;
-    width = L.n;
-  }
+  int64_t width = 0;
+  if (const int bad = mlp_check_sizes(q, HK_MLP_RELU, width)) return bad;
   if (q->out_stride < width) return HK_ERR_SHAPE;
-  if (!q->x0 || !q->out || (q->k1 > 0 && !q->x1)) return HK_ERR_NULL;
+  if (mlp_input_missing(q) || !q->out) return HK_ERR_NULL;
   if (has_in_bn(q) && (!q->in_bn_mean || !q->in_bn_var)) return HK_ERR_NULL;
   for (int l = 0; l < q->nlayers; ++l) {
     const hk_mlp_layer& L = q->layer[l];
@@ -52,9 +42,8 @@ int validate(const hk_mlp_desc* q) {
     if (!all_aligned({L.weight, L.bias, L.bn_mean, L.bn_var, L.bn_weight, L.bn_bias}, 4)) return HK_ERR_ALIGN;
   }
   const uint64_t out_bytes = span_bytes(q->batch, q->out_stride, width, sizeof(float));
-  const uint64_t x0_bytes = span_bytes(q->batch, q->x0_stride, q->k0, sizeof(float));
-  const uint64_t x1_bytes = q->k1 > 0 ? span_bytes(q->batch, q->x1_stride, q->k1, sizeof(float)) : 1;
-  if (q->batch > 0 && (!out_bytes || !x0_bytes || !x1_bytes)) return HK_ERR_SHAPE;  // a span beyond 2^63 bytes
+  uint64_t x0_bytes, x1_bytes;
+  if (!mlp_input_spans(q, x0_bytes, x1_bytes) || (q->batch > 0 && !out_bytes)) return HK_ERR_SHAPE;  // beyond 2^63 bytes
   if (rows_overlap(q, out_bytes, width, q->x0, x0_bytes, q->x0_stride, q->k0)) return HK_ERR_UNSUPPORTED;
   if (q->k1 > 0 && rows_overlap(q, out_bytes, width, q->x1, x1_bytes, q->x1_stride, q->k1)) return HK_ERR_UNSUPPORTED;
   for (const void* p : {q->in_bn_mean, q->in_bn_var, q->in_bn_weight, q->in_bn_bias})

@@ -68,6 +68,42 @@ constexpr size_t mlp_lds_bytes(int tile_rows) {
 }
 static_assert(mlp_lds_bytes(HK_MLP_TILE_LARGE) <= (size_t)kMaxLdsBytes, "two panels and the stage fit the CU's LDS");
 
+// ---- what every entry point that takes a layer table asks of it (Desc: hk_mlp_desc, hk_mlp_train_desc) ----------------
+// The checks come in the order of the headers' status rules; an entry puts its own between them.
+// The descriptor itself: there, float, no flag outside `known`.
+template <typename Desc>
+int mlp_check_desc(const Desc* q, uint32_t known) {
+  if (!q) return HK_ERR_NULL;
+  if (q->dtype != HK_F32) return HK_ERR_UNSUPPORTED;
+  return (q->flags & ~known) ? HK_ERR_UNSUPPORTED : HK_OK;
+}
+// The sizes: nlayers, the batch, the input's widths and strides, every layer's flags (within `layer_flags`) and the chain
+// of widths, whose end -- the last layer's n -- `width` receives.
+template <typename Desc>
+int mlp_check_sizes(const Desc* q, uint32_t layer_flags, int64_t& width) {
+  if (q->nlayers < 1 || q->nlayers > HK_MLP_MAX_LAYERS) return HK_ERR_SHAPE;
+  if (q->batch < 0 || q->k0 < 1 || q->k1 < 0 || q->x0_stride < 0 || q->x1_stride < 0) return HK_ERR_SHAPE;
+  width = (int64_t)q->k0 + q->k1;
+  for (int l = 0; l < q->nlayers; ++l) {
+    const auto& L = q->layer[l];
+    if (L.flags & ~layer_flags) return HK_ERR_UNSUPPORTED;
+    if (L.k < 1 || L.k > HK_MLP_MAX_WIDTH || L.n < 1 || L.n > HK_MLP_MAX_WIDTH || L.k != width) return HK_ERR_SHAPE;
+    width = L.n;
+  }
+  return HK_OK;
+}
+template <typename Desc>
+bool mlp_input_missing(const Desc* q) {
+  return !q->x0 || (q->k1 > 0 && !q->x1);
+}
+// The bytes the rows of x0 and of x1 span (1 for an absent x1); false: rows, and a span beyond 2^63 bytes.
+template <typename Desc>
+bool mlp_input_spans(const Desc* q, uint64_t& x0_bytes, uint64_t& x1_bytes) {
+  x0_bytes = span_bytes(q->batch, q->x0_stride, q->k0, sizeof(float));
+  x1_bytes = q->k1 > 0 ? span_bytes(q->batch, q->x1_stride, q->k1, sizeof(float)) : 1;
+  return q->batch == 0 || (x0_bytes && x1_bytes);
+}
+
 // where real k sits in a row of either image
 __host__ __device__ constexpr int mlp_pos(int k) { return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); }
 

@@ -17,6 +17,7 @@ using Ranges = std::vector<std::pair<const void*, uint64_t>>;
 
 bool is_bn(const hk_mlp_train_layer& L) { return L.flags & HK_MLP_TRAIN_BN; }
 
+// two dz of [batch, the widest layer after the first]
 uint64_t workspace_bytes(const hk_mlp_train_desc* q) {
   if (!q || q->nlayers < 2 || q->nlayers > HK_MLP_MAX_LAYERS || q->batch <= 0) return 0;
   int64_t widest = 0;
@@ -25,24 +26,15 @@ uint64_t workspace_bytes(const hk_mlp_train_desc* q) {
 }
 
 int validate(const hk_mlp_train_desc* q, bool backward) {
-  if (!q) return HK_ERR_NULL;
-  if (q->dtype != HK_F32) return HK_ERR_UNSUPPORTED;
-  if (q->flags & ~HK_MLP_INPUT_RELU) return HK_ERR_UNSUPPORTED;
-  if (q->nlayers < 1 || q->nlayers > HK_MLP_MAX_LAYERS) return HK_ERR_SHAPE;
-  if (q->batch < 0 || q->batch > HK_MLP_TRAIN_MAX_BATCH) return HK_ERR_SHAPE;
-  if (q->k0 < 1 || q->k1 < 0 || q->x0_stride < 0 || q->x1_stride < 0 || (backward && q->grad_stride < 0)) return HK_ERR_SHAPE;
-  int64_t width = (int64_t)q->k0 + q->k1;
+  if (const int bad = mlp_check_desc(q, HK_MLP_INPUT_RELU)) return bad;
+  if (q->batch > HK_MLP_TRAIN_MAX_BATCH || (backward && q->grad_stride < 0)) return HK_ERR_SHAPE;
+  int64_t width = 0;
+  if (const int bad = mlp_check_sizes(q, kLayerFlags, width)) return bad;
   bool any_bn = false;
-  for (int l = 0; l < q->nlayers; ++l) {
-    const hk_mlp_train_layer& L = q->layer[l];
-    if (L.flags & ~kLayerFlags) return HK_ERR_UNSUPPORTED;
-    if (L.k < 1 || L.k > HK_MLP_MAX_WIDTH || L.n < 1 || L.n > HK_MLP_MAX_WIDTH || L.k != width) return HK_ERR_SHAPE;
-    width = L.n;
-    any_bn = any_bn || is_bn(L);
-  }
+  for (int l = 0; l < q->nlayers; ++l) any_bn = any_bn || is_bn(q->layer[l]);
   if (any_bn && q->batch == 1) return HK_ERR_SHAPE;
   if (backward && q->workspace_bytes < workspace_bytes(q)) return HK_ERR_SHAPE;
-  if (!q->x0 || (q->k1 > 0 && !q->x1)) return HK_ERR_NULL;
+  if (mlp_input_missing(q)) return HK_ERR_NULL;
   if (backward && (!q->grad_out || (q->nlayers > 1 && !q->workspace))) return HK_ERR_NULL;
   for (int l = 0; l < q->nlayers; ++l) {
     const hk_mlp_train_layer& L = q->layer[l];
@@ -63,10 +55,9 @@ int validate(const hk_mlp_train_desc* q, bool backward) {
   // what is read and what is written
   Ranges rd, wr;
   const uint64_t B = (uint64_t)q->batch;
-  const uint64_t x0_bytes = span_bytes(q->batch, q->x0_stride, q->k0, sizeof(float));
-  const uint64_t x1_bytes = q->k1 > 0 ? span_bytes(q->batch, q->x1_stride, q->k1, sizeof(float)) : 1;
+  uint64_t x0_bytes, x1_bytes;
   const uint64_t grad_bytes = backward ? span_bytes(q->batch, q->grad_stride, width, sizeof(float)) : 1;
-  if (q->batch > 0 && (!x0_bytes || !x1_bytes || !grad_bytes)) return HK_ERR_SHAPE;  // a span beyond 2^63 bytes
+  if (!mlp_input_spans(q, x0_bytes, x1_bytes) || (q->batch > 0 && !grad_bytes)) return HK_ERR_SHAPE;  // beyond 2^63 bytes
   rd.emplace_back(q->x0, x0_bytes);
   if (q->k1 > 0) rd.emplace_back(q->x1, x1_bytes);
   if (backward) {
@@ -115,9 +106,8 @@ int run(const hk_mlp_train_desc* q, bool backward, hipStream_t stream) {
   if (bad != HK_OK) return bad;
   if (q->batch == 0) return HK_OK;
   const bool large = train_rt(q->batch) == kTrainRtLarge;
-  int64_t widest = 0;
-  for (int l = 1; l < q->nlayers; ++l) widest = q->layer[l].n > widest ? q->layer[l].n : widest;
-  float* ws[2] = {static_cast<float*>(q->workspace), static_cast<float*>(q->workspace) + (int64_t)q->batch * widest};
+  float* const ws0 = static_cast<float*>(q->workspace);
+  float* ws[2] = {ws0, ws0 + workspace_bytes(q) / (2 * sizeof(float))};  // the workspace's halves
   for (int i = 0; i < q->nlayers; ++i) {
     const int l = backward ? q->nlayers - 1 - i : i;
     TrainArgs a = {};

@@ -24,9 +24,10 @@ int hk_search_morin_play(const hk_morin_play_desc* q, void* stream) {
   if (q->in_stride < n || q->out_stride < n) return HK_ERR_SHAPE;
   if (q->points_in == q->points_out && q->in_stride != q->out_stride) return HK_ERR_SHAPE;
   const size_t es = elem_size(q->dtype);
-  if (q->points_in != q->points_out &&
-      records_overlap(q->points_in, q->in_stride, q->batch, n, q->points_out, q->out_stride, q->batch, n, es))
-    return HK_ERR_SHAPE;
+  // a workgroup's write-back must not meet another's staging read: other than in place, the two spans do not overlap
+  const uint64_t in_bytes = span_bytes(q->batch, q->in_stride, n, es), out_bytes = span_bytes(q->batch, q->out_stride, n, es);
+  if (!in_bytes || !out_bytes) return HK_ERR_SHAPE;  // a span beyond 2^63 bytes
+  if (q->points_in != q->points_out && overlap(q->points_in, in_bytes, q->points_out, out_bytes)) return HK_ERR_SHAPE;
   if (!all_aligned({q->weights_in, q->weights_out, q->distinguished_in, q->distinguished_out, q->class_in, q->axis_in,
                     q->class_out, q->axis_out, q->length_out, q->outcome_out}, 4) ||
       !all_aligned({q->points_in, q->points_out}, es))
@@ -60,9 +61,7 @@ int hk_search_morin_play(const hk_morin_play_desc* q, void* stream) {
   const LaneGeometry geo = lane_geometry(a.lds_stride, es, a.batch);
   a.games_per_block = geo.per_block;
   return with_fixed_host_or(q->dtype, q->host, std::integral_constant<int, HK_MORIN_HOST_FORCED>(), [&](auto t, auto h) {
-    launch_prepare();
-    hipLaunchKernelGGL((morin_play_kernel<decltype(t), h>), dim3(geo.grid), dim3(kWave), geo.lds, (hipStream_t)stream, a);
-    return launch_status();
+    return launch_kernel(morin_play_kernel<decltype(t), h>, dim3(geo.grid), dim3(kWave), geo.lds, (hipStream_t)stream, a);
   });
 }
 

@@ -58,9 +58,7 @@ int hk_replay_push(const hk_replay_desc* q, void* stream) {
   if (const int st = fill_args(q, a)) return st;
   a.keep = q->keep;
   a.batch = q->batch;
-  launch_prepare();
-  hipLaunchKernelGGL(replay_push_kernel, dim3(tiles(a.batch)), dim3(kReplayThreads), 0, (hipStream_t)stream, a);
-  return launch_status();
+  return launch_kernel(replay_push_kernel, dim3(tiles(a.batch)), dim3(kReplayThreads), 0, (hipStream_t)stream, a);
 }
 
 int hk_replay_sample(const hk_replay_desc* q, int batch_size, uint64_t seed, int64_t* index_out, void* stream) {
@@ -73,9 +71,7 @@ int hk_replay_sample(const hk_replay_desc* q, int batch_size, uint64_t seed, int
   a.index_out = index_out;
   a.seed = seed;
   a.batch_size = batch_size;
-  launch_prepare();
-  hipLaunchKernelGGL(replay_sample_kernel, dim3(tiles(batch_size)), dim3(kReplayThreads), 0, (hipStream_t)stream, a);
-  return launch_status();
+  return launch_kernel(replay_sample_kernel, dim3(tiles(batch_size)), dim3(kReplayThreads), 0, (hipStream_t)stream, a);
 }
 
 }  // extern "C"

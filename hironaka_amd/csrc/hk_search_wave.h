@@ -42,9 +42,7 @@ int launch_search(void (*kernel)(Args), Args a, int batch, hipStream_t stream, i
   a.lds_stride = search_lds_stride(a.m, a.d, extra_lds);
   const LaneGeometry geo = lane_geometry(a.lds_stride, sizeof(T), batch);
   a.lanes = geo.per_block;
-  launch_prepare();
-  hipLaunchKernelGGL(kernel, dim3((unsigned)batch), dim3(kWave), geo.lds, stream, a);
-  return launch_status();
+  return launch_kernel(kernel, dim3((unsigned)batch), dim3(kWave), geo.lds, stream, a);
 }
 
 constexpr unsigned kListFlags = HK_SEM_LIST | HK_FLAG_COMPACT_SORTED;  // the semantics every lane game is played in

@@ -26,9 +26,10 @@ int hk_tree_expand(const hk_tree_expand_desc* q, void* stream) {
   const int64_t len = n + ((q->flags & HK_TREE_ZERO_TAIL) ? q->dim : 0);
   if (q->in_stride < n || q->out_stride < len) return HK_ERR_SHAPE;
   // a workgroup writes children while others still stage parents: the two buffers do not overlap
-  if (q->capacity > 0 && records_overlap(q->parents_in, q->in_stride, q->n_parents, n, q->children_out, q->out_stride,
-                                         q->capacity, len, es))
-    return HK_ERR_SHAPE;
+  const uint64_t in_bytes = span_bytes(q->n_parents, q->in_stride, n, es);
+  const uint64_t out_bytes = span_bytes(q->capacity, q->out_stride, len, es);
+  if (!in_bytes || (q->capacity > 0 && !out_bytes)) return HK_ERR_SHAPE;  // a span beyond 2^63 bytes
+  if (overlap(q->parents_in, in_bytes, q->children_out, out_bytes)) return HK_ERR_SHAPE;
   if (!all_aligned({q->class_id, q->child_parent, q->child_axis, q->child_num_points, q->status}, 4) ||
       !aligned(q->child_offset, 8) || !all_aligned({q->parents_in, q->children_out}, es))
     return HK_ERR_ALIGN;
@@ -54,12 +55,8 @@ int hk_tree_expand(const hk_tree_expand_desc* q, void* stream) {
   a.lds_stride = search_lds_stride(a.m, a.d);
   const LaneGeometry geo = lane_geometry(a.lds_stride, es, a.n_parents);
   a.parents_per_block = geo.per_block;
-  launch_prepare();
-  if (q->dtype == HK_F32)
-    hipLaunchKernelGGL((tree_expand_kernel<float>), dim3(geo.grid), dim3(kWave), geo.lds, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((tree_expand_kernel<double>), dim3(geo.grid), dim3(kWave), geo.lds, (hipStream_t)stream, a);
-  return launch_status();
+  const auto kernel = q->dtype == HK_F32 ? tree_expand_kernel<float> : tree_expand_kernel<double>;
+  return launch_kernel(kernel, dim3(geo.grid), dim3(kWave), geo.lds, (hipStream_t)stream, a);
 }
 
 }  // extern "C"

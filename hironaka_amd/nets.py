@@ -195,14 +195,18 @@ class FusedSequential(nn.Sequential):
         reason, mode = self._state_reason(spec)
         return reason, spec, mode
 
+    def _bn_and_grads(self):
+        """whether the stack has a BatchNorm1d, and whether a call now would record a graph over its parameters"""
+        return (any(isinstance(m, nn.BatchNorm1d) for m in self.children()),
+                torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))
+
     def _state_reason(self, spec: MlpSpec):
         tensors = self._tensors()
         if any(t.dtype != torch.float32 for t in tensors):
             return "parameters are not float32", None
         if len({t.device for t in tensors}) > 1:
             return "parameters live on more than one device", None
-        has_bn = any(isinstance(m, nn.BatchNorm1d) for m in self.children())
-        grads = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        has_bn, grads = self._bn_and_grads()
         if not self.fused_training:
             if self.training and has_bn:
                 return "a BatchNorm1d in training mode", None
@@ -221,48 +225,47 @@ class FusedSequential(nn.Sequential):
             return "a parameter is used twice and gradients are on", None
         return None, "train"
 
+    def _cached_plan(self, slot: str, spec: MlpSpec, records, build):
+        """the layer table kept in `slot`, rebuilt (build()) when the stack no longer is what the table was built from:
+        the tensors of `records` that the modules hold NOW lie elsewhere (one data_ptr() per tensor per call: a parameter
+        or buffer that was assigned anew, a state loaded with assign=True, .to()), or a batch norm, a ReLU or another
+        scalar of `records` came, went or changed.  In-place updates -- optimizer.step, Polyak, load_state_dict --
+        change no address and need nothing."""
+        key = (spec.input_relu,) + tuple(lin.weight.shape for lin, _, _ in spec.blocks) + tuple(
+            x.data_ptr() if isinstance(x, torch.Tensor) else x for r in records for x in r)
+        plan = self.__dict__.get(slot)
+        if plan is None or plan.key != key:
+            plan = build()
+            plan.key = key
+            self.__dict__[slot] = plan
+        return plan
+
     def _plan(self, spec: MlpSpec):
-        """the layer table, rebuilt when the stack no longer is what the table was built from: the tensors the modules
-        hold NOW lie elsewhere (one data_ptr() per tensor per call: a parameter or buffer that was assigned anew, a
-        state loaded with assign=True, .to()), or a batch norm, a ReLU or an eps came, went or changed.  In-place updates
-        -- optimizer.step, Polyak, load_state_dict -- change no address and need nothing."""
+        """hk_mlp_forward's layer table"""
         from . import ops
         records = [(lin.weight, lin.bias) + (_bn_fields(bn) if bn is not None else (None,) * 4)
                    + (bn.eps if bn is not None else 0.0, relu) for lin, bn, relu in spec.blocks]
         in_bn = spec.input_bn
         in_record = None if in_bn is None else (None, None) + _bn_fields(in_bn) + (in_bn.eps,)
-        key = (spec.input_relu,) + tuple(lin.weight.shape for lin, _, _ in spec.blocks) + tuple(
-            x.data_ptr() if isinstance(x, torch.Tensor) else x for r in records + [in_record or ()] for x in r)
-        plan = self.__dict__.get("_fused_plan")
-        if plan is None or plan.key != key:
-            plan = ops.MlpPlan([ops.MlpLayer(*r) for r in records], spec.input_relu,
-                               None if in_record is None else ops.MlpLayer(*in_record))
-            plan.key = key
-            self.__dict__["_fused_plan"] = plan
-        return plan
+        return self._cached_plan(
+            "_fused_plan", spec, records + [in_record or ()],
+            lambda: ops.MlpPlan([ops.MlpLayer(*r) for r in records], spec.input_relu,
+                                None if in_record is None else ops.MlpLayer(*in_record)))
 
     def _train_plan(self, spec: MlpSpec):
-        """_plan's counterpart for the training kernels: the same rebuild rule, keyed by the same addresses plus the
-        batch norms' momenta and counters"""
+        """the training kernels' layer table: the batch norms' momenta and counters count too"""
         from . import ops
         records = [(lin.weight, lin.bias) + (_bn_fields(bn) + (bn.eps, relu, bn.momentum, bn.num_batches_tracked)
                                              if bn is not None else (None,) * 4 + (0.0, relu, 0.0, None))
                    for lin, bn, relu in spec.blocks]
-        key = (spec.input_relu,) + tuple(lin.weight.shape for lin, _, _ in spec.blocks) + tuple(
-            x.data_ptr() if isinstance(x, torch.Tensor) else x for r in records for x in r)
-        plan = self.__dict__.get("_fused_train_plan")
-        if plan is None or plan.key != key:
-            plan = ops.MlpTrainPlan([ops.MlpTrainLayer(*r) for r in records], spec.input_relu)
-            plan.key = key
-            self.__dict__["_fused_train_plan"] = plan
-        return plan
+        return self._cached_plan("_fused_train_plan", spec, records,
+                                 lambda: ops.MlpTrainPlan([ops.MlpTrainLayer(*r) for r in records], spec.input_relu))
 
     def _forward_train(self, spec: MlpSpec, x0, x1):
         """the training kernels' forward, or None with fused_last_reason set where this CALL is torch's"""
         from . import ops
         batch = x0.shape[0]
-        has_bn = any(bn is not None for _, bn, _ in spec.blocks)
-        grads = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        has_bn, grads = self._bn_and_grads()  # (no batch norm on the input here: _state_reason)
         reason = None
         if batch > A.HK_MLP_TRAIN_MAX_BATCH:
             reason = f"more than {A.HK_MLP_TRAIN_MAX_BATCH} rows in training mode"

@@ -1700,19 +1700,20 @@ def _mlp_tensor(x, name: str, dev: Optional[torch.device], shape=None) -> Option
     return x.data_ptr()
 
 
-class MlpPlan:
-    """The layer table of mlp_forward, built once per set of parameter addresses (it holds the tensors alive):
-    `layers` is a sequence of MlpLayer (or tuples in its order).  The table points at the tensors it was given: whoever
-    swaps a tensor for another builds a new plan (hironaka_amd.nets.FusedSequential does, by the addresses of the
-    tensors its modules hold at each call)."""
+class _MlpTable:
+    """What MlpPlan and MlpTrainPlan share: the walk over `layers` (entries of LAYER, or tuples in its order) that
+    checks them and fills the layer table of a DESC, whose fields STATS take a batch norm's running statistics.  It
+    leaves `desc`, `device`, `k_in`, `n_out` and `tensors` (what the table points at, held alive); _own adds what a
+    plan keeps of a layer besides."""
+    LAYER = DESC = STATS = None
 
-    def __init__(self, layers: Sequence[MlpLayer], input_relu: bool = False, input_bn: Optional[MlpLayer] = None):
-        layers = [l if isinstance(l, MlpLayer) else MlpLayer(*l) for l in layers]
+    def _fill(self, layers, input_relu: bool):
+        layers = [l if isinstance(l, self.LAYER) else self.LAYER(*l) for l in layers]
         if not 1 <= len(layers) <= A.HK_MLP_MAX_LAYERS:
             raise ValueError(f"1 to {A.HK_MLP_MAX_LAYERS} layers. Got {len(layers)}.")
         _require_device(layers[0].weight, "layers[0].weight")
-        dev = layers[0].weight.device
-        d = A.hk_mlp_desc()
+        self.device = dev = layers[0].weight.device
+        self.desc = d = self.DESC()
         self.tensors = []
         width = None
         for i, l in enumerate(layers):
@@ -1723,26 +1724,42 @@ class MlpPlan:
                 raise ValueError(f"layers[{i}] takes {k} inputs but layers[{i - 1}] gives {width}.")
             if not (1 <= k <= A.HK_MLP_MAX_WIDTH and 1 <= n <= A.HK_MLP_MAX_WIDTH):
                 raise ValueError(f"layers[{i}]: widths must lie in 1..{A.HK_MLP_MAX_WIDTH}. Got [{n}, {k}].")
-            if (l.bn_mean is None) != (l.bn_var is None) or (l.bn_mean is None and (l.bn_weight is not None
-                                                                                   or l.bn_bias is not None)):
+            bn = l.bn_mean is not None
+            # (bn_weight, bn_bias and, where LAYER has one, num_batches_tracked belong to a batch norm)
+            if bn != (l.bn_var is not None) or (not bn and any(t is not None for t in l[4:6] + l[9:])):
                 raise ValueError(f"layers[{i}]: a batch norm needs both bn_mean and bn_var.")
             width = n
             e = d.layer[i]
             e.weight = _mlp_tensor(l.weight, f"layers[{i}].weight", dev)
-            for name in ("bias", "bn_mean", "bn_var", "bn_weight", "bn_bias"):
-                setattr(e, name, _mlp_tensor(getattr(l, name), f"layers[{i}].{name}", dev, (n,)))
+            for field, name in zip(("bias",) + self.STATS + ("bn_weight", "bn_bias"), self.LAYER._fields[1:6]):
+                setattr(e, field, _mlp_tensor(getattr(l, name), f"layers[{i}].{name}", dev, (n,)))
             e.eps, e.k, e.n, e.flags = float(l.eps), k, n, A.HK_MLP_RELU if l.relu else 0
             self.tensors += [t for t in l[:6] if t is not None]
+            self._own(i, l, e, bn)
+        d.nlayers, d.dtype, d.flags = len(layers), A.HK_F32, A.HK_MLP_INPUT_RELU if input_relu else 0
+        self.k_in, self.n_out = layers[0].weight.shape[1], width
+
+    def _own(self, i: int, l, e, bn: bool):
+        """what a plan adds for layer i: l of LAYER, its table entry e, whether it has a batch norm"""
+
+
+class MlpPlan(_MlpTable):
+    """The layer table of mlp_forward, built once per set of parameter addresses (it holds the tensors alive):
+    `layers` is a sequence of MlpLayer (or tuples in its order).  The table points at the tensors it was given: whoever
+    swaps a tensor for another builds a new plan (hironaka_amd.nets.FusedSequential does, by the addresses of the
+    tensors its modules hold at each call)."""
+    LAYER, DESC, STATS = MlpLayer, A.hk_mlp_desc, ("bn_mean", "bn_var")
+
+    def __init__(self, layers: Sequence[MlpLayer], input_relu: bool = False, input_bn: Optional[MlpLayer] = None):
+        self._fill(layers, input_relu)
         if input_bn is not None:  # an MlpLayer whose batch-norm fields alone count: the batch norm on the input
-            k = layers[0].weight.shape[1]
             if input_bn.bn_mean is None or input_bn.bn_var is None:
                 raise ValueError("input_bn needs both bn_mean and bn_var.")
             for name in ("bn_mean", "bn_var", "bn_weight", "bn_bias"):
-                setattr(d, "in_" + name, _mlp_tensor(getattr(input_bn, name), f"input_bn.{name}", dev, (k,)))
-            d.in_eps = float(input_bn.eps)
+                setattr(self.desc, "in_" + name,
+                        _mlp_tensor(getattr(input_bn, name), f"input_bn.{name}", self.device, (self.k_in,)))
+            self.desc.in_eps = float(input_bn.eps)
             self.tensors += [t for t in input_bn[2:6] if t is not None]
-        d.nlayers, d.dtype, d.flags = len(layers), A.HK_F32, A.HK_MLP_INPUT_RELU if input_relu else 0
-        self.desc, self.device, self.k_in, self.n_out = d, dev, layers[0].weight.shape[1], width
 
 
 def _mlp_rows(x: torch.Tensor, name: str, dev: torch.device) -> torch.Tensor:
@@ -1759,6 +1776,30 @@ def _mlp_rows(x: torch.Tensor, name: str, dev: torch.device) -> torch.Tensor:
     return x
 
 
+def _mlp_inputs(plan: _MlpTable, x0: torch.Tensor, x1: Optional[torch.Tensor]):
+    """x0 and x1 (or None) as rows (_mlp_rows) that together are the plan's input"""
+    x0 = _mlp_rows(x0, "x0", plan.device)
+    batch, k0 = x0.shape
+    k1 = 0
+    if x1 is not None:
+        x1 = _mlp_rows(x1, "x1", plan.device)
+        k1 = x1.shape[1]
+        if x1.shape[0] != batch:
+            raise ValueError(f"x0 has {batch} rows but x1 has {x1.shape[0]}.")
+    if k0 + k1 != plan.k_in:
+        raise ValueError(f"the first layer takes {plan.k_in} inputs. Got {k0}{' + ' + str(k1) if x1 is not None else ''}.")
+    return x0, x1
+
+
+def _mlp_fill_inputs(d, x0: torch.Tensor, x1: Optional[torch.Tensor]) -> None:
+    """the input's fields of a descriptor: the rows of _mlp_inputs and their count"""
+    batch, k0 = x0.shape
+    k1 = x1.shape[1] if x1 is not None else 0
+    d.x0, d.x0_stride, d.k0 = x0.data_ptr(), x0.stride(0) if batch > 1 else k0, k0
+    d.x1, d.x1_stride, d.k1 = (x1.data_ptr(), x1.stride(0) if batch > 1 else k1, k1) if k1 else (None, 0, 0)
+    d.batch = batch
+
+
 def mlp_forward(x0: torch.Tensor, layers, x1: Optional[torch.Tensor] = None, input_relu: bool = False,
                 out: Optional[torch.Tensor] = None, tile: Optional[int] = None,
                 input_bn: Optional[MlpLayer] = None) -> torch.Tensor:
@@ -1773,16 +1814,8 @@ def mlp_forward(x0: torch.Tensor, layers, x1: Optional[torch.Tensor] = None, inp
     if tile not in _MLP_TILES:
         raise ValueError(f"tile must be None, {A.HK_MLP_TILE_SMALL} or {A.HK_MLP_TILE_LARGE}. Got {tile!r}.")
     dev = plan.device
-    x0 = _mlp_rows(x0, "x0", dev)
-    batch, k0 = x0.shape
-    k1 = 0
-    if x1 is not None:
-        x1 = _mlp_rows(x1, "x1", dev)
-        k1 = x1.shape[1]
-        if x1.shape[0] != batch:
-            raise ValueError(f"x0 has {batch} rows but x1 has {x1.shape[0]}.")
-    if k0 + k1 != plan.k_in:
-        raise ValueError(f"the first layer takes {plan.k_in} inputs. Got {k0}{' + ' + str(k1) if x1 is not None else ''}.")
+    x0, x1 = _mlp_inputs(plan, x0, x1)
+    batch = x0.shape[0]
     if batch >= 2 ** 31:
         raise ValueError(f"at most 2^31 - 1 rows per call. Got {batch}.")
     if out is None:
@@ -1798,9 +1831,8 @@ def mlp_forward(x0: torch.Tensor, layers, x1: Optional[torch.Tensor] = None, inp
     if batch == 0:
         return out
     d = plan.desc
-    d.x0, d.x0_stride, d.k0 = x0.data_ptr(), x0.stride(0) if batch > 1 else k0, k0
-    d.x1, d.x1_stride, d.k1 = (x1.data_ptr(), x1.stride(0) if batch > 1 else k1, k1) if k1 else (None, 0, 0)
-    d.out, d.out_stride, d.batch = out.data_ptr(), out.stride(0) if batch > 1 else plan.n_out, batch
+    _mlp_fill_inputs(d, x0, x1)
+    d.out, d.out_stride = out.data_ptr(), out.stride(0) if batch > 1 else plan.n_out
     d.flags = (d.flags & A.HK_MLP_INPUT_RELU) | _MLP_TILES[tile]
     with torch.cuda.device(dev):
         check(lib().hk_mlp_forward(C.byref(d), _stream(out)), "hk_mlp_forward")
@@ -1821,54 +1853,15 @@ def _align4(n: int) -> int:
     return (n + 3) & ~3
 
 
-class MlpTrainPlan:
+class MlpTrainPlan(_MlpTable):
     """The layer table of mlp_train_forward / mlp_backward, built once per set of parameter addresses (it holds the
     tensors alive).  `params` lists the parameters in module order -- per layer weight, bias, bn_weight, bn_bias, those
     that exist -- which is the order of mlp_backward's gradients."""
+    LAYER, DESC, STATS = MlpTrainLayer, A.hk_mlp_train_desc, ("running_mean", "running_var")
 
     def __init__(self, layers: Sequence[MlpTrainLayer], input_relu: bool = False):
-        layers = [l if isinstance(l, MlpTrainLayer) else MlpTrainLayer(*l) for l in layers]
-        if not 1 <= len(layers) <= A.HK_MLP_MAX_LAYERS:
-            raise ValueError(f"1 to {A.HK_MLP_MAX_LAYERS} layers. Got {len(layers)}.")
-        _require_device(layers[0].weight, "layers[0].weight")
-        dev = layers[0].weight.device
-        d = A.hk_mlp_train_desc()
-        self.tensors, self.params, self.shapes, self.bn = [], [], [], []
-        width = None
-        for i, l in enumerate(layers):
-            if not isinstance(l.weight, torch.Tensor) or l.weight.dim() != 2:
-                raise TypeError(f"layers[{i}].weight must be a [n, k] tensor.")
-            n, k = l.weight.shape
-            if width is not None and k != width:
-                raise ValueError(f"layers[{i}] takes {k} inputs but layers[{i - 1}] gives {width}.")
-            if not (1 <= k <= A.HK_MLP_MAX_WIDTH and 1 <= n <= A.HK_MLP_MAX_WIDTH):
-                raise ValueError(f"layers[{i}]: widths must lie in 1..{A.HK_MLP_MAX_WIDTH}. Got [{n}, {k}].")
-            bn = l.bn_mean is not None
-            if bn != (l.bn_var is not None) or (not bn and (l.bn_weight is not None or l.bn_bias is not None
-                                                            or l.num_batches_tracked is not None)):
-                raise ValueError(f"layers[{i}]: a batch norm needs both bn_mean and bn_var.")
-            if bn and not isinstance(l.momentum, float):
-                raise TypeError(f"layers[{i}]: momentum must be a float. Got {l.momentum!r}.")
-            width = n
-            e = d.layer[i]
-            e.weight = _mlp_tensor(l.weight, f"layers[{i}].weight", dev)
-            for field, name in (("bias", "bias"), ("running_mean", "bn_mean"), ("running_var", "bn_var"),
-                                ("bn_weight", "bn_weight"), ("bn_bias", "bn_bias")):
-                setattr(e, field, _mlp_tensor(getattr(l, name), f"layers[{i}].{name}", dev, (n,)))
-            nbt = l.num_batches_tracked
-            if nbt is not None:
-                _require_device(nbt, f"layers[{i}].num_batches_tracked")
-                if nbt.dtype != torch.int64 or nbt.numel() != 1 or nbt.device != dev:
-                    raise TypeError(f"layers[{i}].num_batches_tracked must be one int64 on {dev}.")
-                e.num_batches_tracked = nbt.data_ptr()
-            e.eps, e.momentum, e.k, e.n = float(l.eps), float(l.momentum) if bn else 0.0, k, n
-            e.flags = (A.HK_MLP_RELU if l.relu else 0) | (A.HK_MLP_TRAIN_BN if bn else 0)
-            self.tensors += [t for t in l[:6] + (nbt,) if t is not None]
-            self.params += [t for t in (l.weight, l.bias, l.bn_weight, l.bn_bias) if t is not None]
-            self.shapes.append((n, k, l.bias is not None, l.bn_weight is not None, l.bn_bias is not None))
-            self.bn.append(bn)
-        d.nlayers, d.dtype, d.flags = len(layers), A.HK_F32, A.HK_MLP_INPUT_RELU if input_relu else 0
-        self.desc, self.device, self.k_in, self.n_out = d, dev, layers[0].weight.shape[1], width
+        self.params, self.shapes, self.bn = [], [], []
+        self._fill(layers, input_relu)
         self.widest = max([n for n, *_ in self.shapes[1:]], default=0)
         # the gradients of one backward, in floats from the start of its buffer: (d_weight, d_bias, d_bn_weight, d_bn_bias)
         self.grad_at, at = [], 0
@@ -1881,6 +1874,23 @@ class MlpTrainPlan:
             self.grad_at.append(row)
         self.grad_floats = at
         self._saved_at = {}
+
+    def _own(self, i: int, l, e, bn: bool):
+        if bn and not isinstance(l.momentum, float):
+            raise TypeError(f"layers[{i}]: momentum must be a float. Got {l.momentum!r}.")
+        nbt = l.num_batches_tracked
+        if nbt is not None:
+            _require_device(nbt, f"layers[{i}].num_batches_tracked")
+            if nbt.dtype != torch.int64 or nbt.numel() != 1 or nbt.device != self.device:
+                raise TypeError(f"layers[{i}].num_batches_tracked must be one int64 on {self.device}.")
+            e.num_batches_tracked = nbt.data_ptr()
+            self.tensors.append(nbt)
+        e.momentum = float(l.momentum) if bn else 0.0
+        e.flags |= A.HK_MLP_TRAIN_BN if bn else 0
+        n, k = l.weight.shape
+        self.params += [t for t in (l.weight, l.bias, l.bn_weight, l.bn_bias) if t is not None]
+        self.shapes.append((n, k, l.bias is not None, l.bn_weight is not None, l.bn_bias is not None))
+        self.bn.append(bn)
 
     def saved_at(self, batch: int):
         """where one forward's saved tensors lie, in floats from the start of its buffer: per layer (act, z, mean, inv),
@@ -1920,12 +1930,9 @@ class MlpTrainSaved:
 def _mlp_train_fill(plan: MlpTrainPlan, x0, x1, out, buf):
     """the descriptor's fields that belong to one call"""
     d = plan.desc
-    batch, k0 = x0.shape
-    k1 = x1.shape[1] if x1 is not None else 0
-    d.x0, d.x0_stride, d.k0 = x0.data_ptr(), x0.stride(0) if batch > 1 else k0, k0
-    d.x1, d.x1_stride, d.k1 = (x1.data_ptr(), x1.stride(0) if batch > 1 else k1, k1) if k1 else (None, 0, 0)
-    d.batch, d.grad_out, d.workspace, d.workspace_bytes = batch, None, None, 0
-    rows, _ = plan.saved_at(batch)
+    _mlp_fill_inputs(d, x0, x1)
+    d.grad_out, d.workspace, d.workspace_bytes = None, None, 0
+    rows, _ = plan.saved_at(x0.shape[0])
     base = buf.data_ptr()
     for i, (act, z, mean, inv) in enumerate(rows):
         e = d.layer[i]
@@ -1945,16 +1952,8 @@ def mlp_train_forward(x0: torch.Tensor, plan, x1: Optional[torch.Tensor] = None,
     if not isinstance(plan, MlpTrainPlan):
         plan = MlpTrainPlan(plan, input_relu)
     dev = plan.device
-    x0 = _mlp_rows(x0, "x0", dev)
-    batch, k0 = x0.shape
-    k1 = 0
-    if x1 is not None:
-        x1 = _mlp_rows(x1, "x1", dev)
-        k1 = x1.shape[1]
-        if x1.shape[0] != batch:
-            raise ValueError(f"x0 has {batch} rows but x1 has {x1.shape[0]}.")
-    if k0 + k1 != plan.k_in:
-        raise ValueError(f"the first layer takes {plan.k_in} inputs. Got {k0}{' + ' + str(k1) if x1 is not None else ''}.")
+    x0, x1 = _mlp_inputs(plan, x0, x1)
+    batch = x0.shape[0]
     if batch > A.HK_MLP_TRAIN_MAX_BATCH or (batch == 1 and any(plan.bn)):
         raise ValueError(f"2 to {A.HK_MLP_TRAIN_MAX_BATCH} rows with a batch norm, 0 to {A.HK_MLP_TRAIN_MAX_BATCH} "
                          f"without. Got {batch}.")

@@ -540,7 +540,8 @@ int hk_search_morin_tree(const void* points, const int32_t* weights, const int32
  * lost / none; an index that addresses no point counts as -1).  They are read once and written once; points_out may
  * equal points_in (with equal strides), weights_out weights_in, distinguished_out distinguished_in.  Otherwise the
  * byte ranges the records of points_in and of points_out span must not overlap (HK_ERR_SHAPE): workgroups write back
- * while others still read.  The reference's weights start as ones and stay >= 0 under HK_MORIN_WEIGHTS_AGENT;
+ * while others still read; records that span more than 2^63 bytes are HK_ERR_SHAPE too, in place or not.
+ * The reference's weights start as ones and stay >= 0 under HK_MORIN_WEIGHTS_AGENT;
  * HK_MORIN_WEIGHTS_SEARCH can leave a negative weight (a coordinate of the subset lighter than the axis), and any
  * int32 is taken as it comes: only the comparison and the wrapping subtraction below touch them.
  *

@@ -21,6 +21,7 @@ extern "C" {
  * One game per lane, in list semantics (padding -1, rows with coordinate 0 >= 0 are the points).  The state is read once
  * and written once; points_out may equal points_in (with equal strides), otherwise the byte ranges the records of
  * points_in and of points_out span must not overlap (HK_ERR_SHAPE): workgroups write back while others still read.
+ * Records that span more than 2^63 bytes are HK_ERR_SHAPE too, in place or not.
  *
  * Root: HK_PLAY_REDUCE_ROOT runs Newton sorted + compacted before any move (Game.__init__); HK_PLAY_RESCALE_ROOT then
  * applies the list rescale (x / max over the points, skipped when max is 0).  With max_steps 0 the call is just these.

@@ -37,8 +37,8 @@ extern "C" {
  * dim 2..7, HK_F32 / HK_F64, any max_points whose parent and child fit one workgroup's 64 KiB of LDS together
  * ((2*max_points*dim + 2*dim) | 1 elements), HK_SEM_JAX / HK_SEM_LIST; in_stride >= max_points*dim, out_stride >=
  * max_points*dim (+ dim with HK_TREE_ZERO_TAIL); the byte ranges that the records of parents_in and of children_out
- * span must not overlap.  Anything else is HK_ERR_UNSUPPORTED / HK_ERR_SHAPE / HK_ERR_NULL / HK_ERR_ALIGN before any
- * launch.  n_parents 0 is HK_OK with nothing done. */
+ * span must not overlap, and neither is more than 2^63 bytes.  Anything else is HK_ERR_UNSUPPORTED / HK_ERR_SHAPE /
+ * HK_ERR_NULL / HK_ERR_ALIGN before any launch.  n_parents 0 is HK_OK with nothing done. */
 #define HK_TREE_REPOSITION 1u /* hk_tree_expand_desc.flags                                          */
 #define HK_TREE_ZERO_TAIL 2u
 #define HK_TREE_OVERFLOW 1u   /* *status: a child's slot lay outside [0, capacity)                  */

@@ -135,6 +135,14 @@ def test_argument_validation_without_gpu():
     assert call(children_out=base, out_stride=20) == A.HK_ERR_SHAPE  # the same pointer, different strides
     assert call(in_stride=14, flags=0, out_stride=15) == A.HK_ERR_SHAPE
     assert call(out_stride=17, children_out=base + 4 * 2048) == A.HK_ERR_SHAPE  # a stride below m*d + d with the zero tail
+    # records that span more than 2^63 bytes (the byte count would wrap): refused, behind the null checks
+    for bad in (dict(in_stride=1 << 62), dict(out_stride=1 << 62), dict(in_stride=1 << 62, out_stride=1 << 62),
+                dict(n_parents=5, in_stride=1 << 60),  # 4 rows x 2^60 elements x 4 bytes: exactly 2^64
+                dict(in_stride=1 << 62, capacity=0),  # the parents' span counts where no child is written
+                dict(children_out=base, in_stride=1 << 62, out_stride=1 << 62)):  # children over the parents
+        assert call(**bad) == A.HK_ERR_SHAPE, bad
+    for name in ("parents_in", "children_out", "status"):
+        assert call(in_stride=1 << 62, out_stride=1 << 62, **{name: None}) == A.HK_ERR_NULL, name
     iaddr = ctypes.addressof(ints)
     for bad in (dict(parents_in=base + 2), dict(children_out=ctypes.addressof(out) + 2), dict(class_id=iaddr + 2),
                 dict(child_offset=iaddr + 4), dict(child_axis=iaddr + 1), dict(status=iaddr + 3),

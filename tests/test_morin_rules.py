@@ -199,6 +199,14 @@ def test_argument_validation_without_gpu():
     assert _call(L, offset=24 * 4, offset_of=("points_out",), in_stride=48, out_stride=48) == A.HK_ERR_SHAPE
     assert _call(L, offset=24 * 4, offset_of=("points_in",), in_stride=48, out_stride=48) == A.HK_ERR_SHAPE
     assert _call(L, out_stride=25) == A.HK_ERR_SHAPE  # the same pointer, different strides
+    # records that span more than 2^63 bytes (the byte count would wrap): refused, in place too, behind the null checks
+    far = dict(offset=32768, offset_of=("points_out",))
+    for bad in (dict(in_stride=1 << 62), dict(out_stride=1 << 62), dict(in_stride=1 << 62, out_stride=1 << 62),
+                dict(batch=5, in_stride=1 << 60)):  # 4 rows x 2^60 elements x 4 bytes: exactly 2^64
+        assert _call(L, **far, **bad) == A.HK_ERR_SHAPE, bad
+    assert _call(L, in_stride=1 << 62, out_stride=1 << 62) == A.HK_ERR_SHAPE  # in place
+    for name in REQUIRED:
+        assert _call(L, null=(name,), in_stride=1 << 62, out_stride=1 << 62) == A.HK_ERR_NULL, name
     assert _call(L, offset=2) == A.HK_ERR_ALIGN
     assert _call(L, offset=2, offset_of=("points_in", "points_out")) == A.HK_ERR_ALIGN
     assert _call(L, dtype=A.HK_F64, offset=4, offset_of=("points_in", "points_out")) == A.HK_ERR_ALIGN

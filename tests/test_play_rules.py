@@ -212,6 +212,14 @@ def test_argument_validation_without_gpu():
     assert call(points_in=base + 4 * 15) == A.HK_ERR_SHAPE  # the input starts inside the output's span
     assert call(points_out=base + 4 * 8, in_stride=16, out_stride=16) == A.HK_ERR_SHAPE
     assert call(points_out=base + 4 * 15, in_stride=30, out_stride=30) == A.HK_ERR_SHAPE  # interleaved, no element shared
+    # records that span more than 2^63 bytes (the byte count would wrap): refused, in place too, behind the null checks
+    far = base + 16384
+    for bad in (dict(in_stride=1 << 62), dict(out_stride=1 << 62), dict(in_stride=1 << 62, out_stride=1 << 62),
+                dict(batch=5, in_stride=1 << 60)):  # 4 rows x 2^60 elements x 4 bytes: exactly 2^64
+        assert call(points_out=far, **bad) == A.HK_ERR_SHAPE, bad
+    assert call(in_stride=1 << 62, out_stride=1 << 62) == A.HK_ERR_SHAPE  # in place
+    assert call(in_stride=1 << 62, out_stride=1 << 62, points_out=None) == A.HK_ERR_NULL
+    assert call(in_stride=1 << 62, out_stride=1 << 62, length_out=None) == A.HK_ERR_NULL
     for bad in (dict(points_in=base + 2, points_out=base + 2), dict(length_out=ctypes.addressof(ints) + 2),
                 dict(class_in=ctypes.addressof(ints) + 1), dict(axis_out=ctypes.addressof(ints) + 3),
                 dict(dtype=A.HK_F64, points_in=base + 4, points_out=base + 4)):
