@@ -105,6 +105,12 @@ HK_MLP_RELU = 1
 # hk_train_mlp_forward / hk_train_mlp_backward: the largest batch, the rows of the small instantiation, the layer flag
 HK_MLP_TRAIN_MAX_BATCH, HK_MLP_TRAIN_ROWS_SMALL = 1024, 256
 HK_MLP_TRAIN_BN = 2
+# hk_pvnet_forward: the table's length, the widest layer, the block kinds and the descriptor flags (the FORCE bits are
+# hk_mlp_forward's)
+HK_PVNET_MAX_BLOCKS, HK_PVNET_MAX_WIDTH = 32, 256
+HK_PVNET_DENSE, HK_PVNET_RESIDUE = 0, 1
+HK_PVNET_RAW_VALUE, HK_PVNET_FORCE_TILE_SMALL, HK_PVNET_FORCE_TILE_LARGE = 1, 2, 4
+PVNET_NORMED_WIDTHS = (32, 64, 128, 256)  # the widths of a normed layer the kernel serves (1, 2, 4, 8 columns per group)
 
 SEMANTICS = {"jax": HK_SEM_JAX, "torch": HK_SEM_TORCH, "list": HK_SEM_LIST}
 
@@ -489,6 +495,44 @@ class hk_mlp_train_desc(C.Structure):
     ]
 
 
+class hk_pvnet_dense(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("weight", "bias", "gn_scale", "gn_bias")]
+
+
+class hk_pvnet_block(C.Structure):
+    _fields_ = [
+        ("dense1", hk_pvnet_dense),
+        ("dense2", hk_pvnet_dense),
+        ("proj", hk_pvnet_dense),
+        ("eps", C.c_float),
+        ("k", C.c_int32),
+        ("n", C.c_int32),
+        ("kind", C.c_int32),
+    ]
+
+
+class hk_pvnet_desc(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p),
+        ("policy", C.c_void_p),
+        ("value", C.c_void_p),
+        ("policy_weight", C.c_void_p),
+        ("policy_bias", C.c_void_p),
+        ("value_weight", C.c_void_p),
+        ("value_bias", C.c_void_p),
+        ("x_stride", C.c_int64),
+        ("policy_stride", C.c_int64),
+        ("value_stride", C.c_int64),
+        ("batch", C.c_int32),
+        ("k0", C.c_int32),
+        ("nblocks", C.c_int32),
+        ("actions", C.c_int32),
+        ("dtype", C.c_int32),
+        ("flags", C.c_uint32),
+        ("block", hk_pvnet_block * HK_PVNET_MAX_BLOCKS),
+    ]
+
+
 _vp, _i, _i64, _u32, _u64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
 
 # name -> (restype, argtypes) of every symbol the header declares.  `stream` is the trailing
@@ -604,14 +648,19 @@ MLP_TRAIN_PROTOTYPES = {
     "hk_train_mlp_backward": (C.c_int, [C.POINTER(hk_mlp_train_desc), _vp]),
 }
 
+# the entry point of include/hironaka_hip_pvnet.h: the device library's only, as above
+PVNET_PROTOTYPES = {
+    "hk_pvnet_forward": (C.c_int, [C.POINTER(hk_pvnet_desc), _vp]),
+}
+
 
 def bind(lib: C.CDLL, prototypes=None) -> None:
     """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES, TREE_PROTOTYPES, ENV_PROTOTYPES,
-    REPLAY_PROTOTYPES, DQN_PROTOTYPES, OPTIM_PROTOTYPES, MLP_PROTOTYPES and MLP_TRAIN_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
+    REPLAY_PROTOTYPES, DQN_PROTOTYPES, OPTIM_PROTOTYPES, MLP_PROTOTYPES, MLP_TRAIN_PROTOTYPES and PVNET_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
     if prototypes is None:
         prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES, **TREE_PROTOTYPES, **ENV_PROTOTYPES,
                       **REPLAY_PROTOTYPES, **DQN_PROTOTYPES, **OPTIM_PROTOTYPES, **MLP_PROTOTYPES,
-                      **MLP_TRAIN_PROTOTYPES}
+                      **MLP_TRAIN_PROTOTYPES, **PVNET_PROTOTYPES}
     for name, (res, args) in prototypes.items():
         fn = getattr(lib, name)
         fn.restype = res

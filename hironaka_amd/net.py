@@ -1,0 +1,315 @@
+"""The policy-value networks of the MCTS trainer -- the reference's hironaka/jax/net.py (DenseResNet, DenseNet and their
+blocks) as torch modules under the reference's names, whose gradient-free float32 forward on a HIP device is ONE
+hk_pvnet_forward launch (include/hironaka_hip_pvnet.h states the rule).
+
+    net = DenseResNet(output_size, net_arch, spec=(max_num_points, dimension), role="host")
+    policy_logits, value = net(features)            # [B, output_size], [B, 1]
+
+What differs from flax, and why:
+  * torch cannot infer the input width at the first call: `input_dim` is required, or follows from `spec` and `role`
+    (host: max_num_points * dimension, agent: that plus dimension);
+  * the module holds its parameters, so `forward(x, params=None, train=True)` accepts and ignores `params` -- which makes
+    an instance a valid `host_net` / `agent_net` of HipTrainer;
+  * a normed width that is no multiple of 32 raises at construction (flax raises at the first call);
+  * the initial values are flax's default DISTRIBUTIONS (lecun_normal kernels, zero biases, unit scales) drawn from a
+    seeded torch.Generator: jax's own draws cannot be reproduced here.
+CustomNet (one sub-network per point count) is not built."""
+import copy
+import math
+from functools import partial
+from typing import Any, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _abi as A
+from .trainer_api import get_apply_fn  # noqa: F401  (hironaka/jax/net.py:110-133)
+
+NUM_GROUPS = 32
+EPS = 1e-6  # flax's GroupNorm default
+NORMED_WIDTHS = A.PVNET_NORMED_WIDTHS
+
+
+def lecun_normal_(weight: torch.Tensor, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """flax's default kernel initialiser on a [out, in] weight: a normal of variance 1 / fan_in truncated at two
+    standard deviations (the 0.8796... restores the variance the truncation takes)"""
+    std = math.sqrt(1.0 / weight.shape[1]) / 0.87962566103423978
+    return nn.init.trunc_normal_(weight, mean=0.0, std=std, a=-2 * std, b=2 * std, generator=generator)
+
+
+def _dense(k: int, n: int, generator) -> nn.Linear:
+    lin = nn.Linear(k, n)
+    with torch.no_grad():
+        lecun_normal_(lin.weight, generator)
+        lin.bias.zero_()
+    return lin
+
+
+def _norm(n: int) -> nn.GroupNorm:
+    return nn.GroupNorm(NUM_GROUPS, n, eps=EPS)  # (ValueError where n is no multiple of 32; scale 1, bias 0)
+
+
+class DenseResidueBlock(nn.Module):
+    """relu(o + GN(Dense(relu(GN(Dense(x)))))) with o = x, or GN(Dense(x)) (res_proj / norm_proj) where the block changes
+    the width (hironaka/jax/net.py:14-33); children under flax's names"""
+
+    def __init__(self, in_features: int, features: int, generator: Optional[torch.Generator] = None):
+        super().__init__()
+        self.in_features, self.features = in_features, features
+        self.Dense_0, self.GroupNorm_0 = _dense(in_features, features, generator), _norm(features)
+        self.Dense_1, self.GroupNorm_1 = _dense(features, features, generator), _norm(features)
+        if in_features != features:
+            self.res_proj, self.norm_proj = _dense(in_features, features, generator), _norm(features)
+        else:
+            self.res_proj = self.norm_proj = None
+
+    def forward(self, x):
+        y = self.GroupNorm_1(self.Dense_1(torch.relu(self.GroupNorm_0(self.Dense_0(x)))))
+        if self.res_proj is not None:
+            x = self.norm_proj(self.res_proj(x))
+        return torch.relu(x + y)
+
+
+class DenseBlock(nn.Module):
+    """relu(Dense(x)) (hironaka/jax/net.py:36-45)"""
+
+    def __init__(self, in_features: int, features: int, generator: Optional[torch.Generator] = None):
+        super().__init__()
+        self.in_features, self.features = in_features, features
+        self.Dense_0 = _dense(in_features, features, generator)
+
+    def forward(self, x):
+        return torch.relu(self.Dense_0(x))
+
+
+def input_dim_of(spec: Sequence[int], role: str) -> int:
+    if role not in ("host", "agent"):
+        raise ValueError(f"role must be either host or agent. Got {role}.")
+    m, d = spec
+    return m * d + (d if role == "agent" else 0)
+
+
+class DenseResNet(nn.Module):
+    """A trunk of `block_cls` blocks of the widths `net_arch`, a policy head `Dense_0` of `output_size` logits and a
+    value head `Dense_1` behind a tanh (hironaka/jax/net.py:48-67).  Children: `DenseResidueBlock_i` / `DenseBlock_i`,
+    `Dense_0`, `Dense_1`.
+
+    `forward(x, params=None, train=True) -> (p [B, output_size], v [B, 1])` takes the kernel's path when gradients are
+    off or no parameter requires one, parameters and input are float32 on one HIP device, and the shapes are within the
+    kernel's limits (input and widths up to 256, normed widths 32 / 64 / 128 / 256, up to 32 blocks, up to 255
+    logits); otherwise it IS the plain composition of the children.  `fused_reason` says why the MODULE is not served
+    (None: it is), `fused_last_reason` why the last CALL was not (None: it was); `fused_enabled = False` pins torch's
+    path.  The two paths differ in the last bits.  The block table is built once and rebuilt when a parameter's
+    `data_ptr()` changed (assigned anew, `.to()`); in-place updates need nothing.  Nothing here synchronises."""
+
+    fused_enabled = True
+    fused_last_reason = None
+
+    def __init__(self, output_size: int, net_arch: List[int], spec: Optional[Tuple[int, int]] = None,
+                 input_dim: Optional[int] = None, block_cls=DenseResidueBlock, role: Optional[str] = None, seed: int = 0):
+        super().__init__()
+        if input_dim is None:
+            if spec is None or role is None:
+                raise ValueError("DenseResNet needs input_dim, or spec and role to take it from (torch cannot infer the "
+                                 "input width at the first call as flax does).")
+            input_dim = input_dim_of(spec, role)
+        self.output_size, self.net_arch, self.spec, self.input_dim = int(output_size), [int(n) for n in net_arch], spec, int(input_dim)
+        generator = torch.Generator().manual_seed(int(seed) % (1 << 63))
+        self._block_names = []
+        k = self.input_dim
+        for i, n in enumerate(self.net_arch):
+            name = f"{block_cls.__name__}_{i}"
+            self.add_module(name, block_cls(k, n, generator))
+            self._block_names.append(name)
+            k = n
+        self.Dense_0 = _dense(k, self.output_size, generator)
+        self.Dense_1 = _dense(k, 1, generator)
+
+    @property
+    def blocks(self) -> List[nn.Module]:
+        return [getattr(self, name) for name in self._block_names]
+
+    # ---- torch's path: the plain composition of the children -----------------------------------------------------
+    def plain_forward(self, x):
+        x = x.flatten(1)
+        for block in self.blocks:
+            x = block(x)
+        return self.Dense_0(x), torch.tanh(self.Dense_1(x))
+
+    # ---- the kernel's path --------------------------------------------------------------------------------------
+    @property
+    def fused_reason(self) -> Optional[str]:
+        return self._reason()
+
+    def _tensors(self):
+        return [t for m in self.modules() for t in list(m._parameters.values()) + list(m._buffers.values())
+                if t is not None and t.is_floating_point()]
+
+    def _reason(self) -> Optional[str]:
+        if not self.fused_enabled:
+            return "fused_enabled is False"
+        blocks = self.blocks
+        if not 1 <= len(blocks) <= A.HK_PVNET_MAX_BLOCKS:
+            return f"not 1 to {A.HK_PVNET_MAX_BLOCKS} blocks"
+        if any(type(b) not in (DenseResidueBlock, DenseBlock) for b in blocks):
+            return "a block that is neither a DenseResidueBlock nor a DenseBlock"
+        widths = [self.input_dim] + [b.Dense_0.out_features for b in blocks]
+        if max(widths) > A.HK_PVNET_MAX_WIDTH or min(widths) < 1:
+            return f"a width outside 1..{A.HK_PVNET_MAX_WIDTH}"
+        if any(type(b) is DenseResidueBlock and b.Dense_0.out_features not in NORMED_WIDTHS for b in blocks):
+            return f"a normed width that is none of {NORMED_WIDTHS}"
+        if any(gn.num_groups != NUM_GROUPS or not gn.affine
+               for b in blocks for gn in b.children() if isinstance(gn, nn.GroupNorm)):
+            return f"a group norm that is not GroupNorm({NUM_GROUPS}) with scale and bias"
+        if not 1 <= self.Dense_0.out_features <= A.HK_PVNET_MAX_WIDTH - 1 or self.Dense_1.out_features != 1:
+            return f"a policy head outside 1..{A.HK_PVNET_MAX_WIDTH - 1} logits, or a value head of more than one"
+        tensors = self._tensors()
+        if any(t.dtype != torch.float32 for t in tensors):
+            return "parameters are not float32"
+        if len({t.device for t in tensors}) > 1:
+            return "parameters live on more than one device"
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            return "gradients are on"
+        return None
+
+    def _records(self):
+        def dn(lin, gn=None):
+            return (lin.weight, lin.bias) + ((gn.weight, gn.bias) if gn is not None else (None, None))
+        records = []
+        for b in self.blocks:
+            if type(b) is DenseBlock:
+                records.append(("dense", dn(b.Dense_0), None, None, EPS))
+            else:
+                records.append(("residue", dn(b.Dense_0, b.GroupNorm_0), dn(b.Dense_1, b.GroupNorm_1),
+                                dn(b.res_proj, b.norm_proj) if b.res_proj is not None else None, b.GroupNorm_0.eps))
+        return records, (self.Dense_0.weight, self.Dense_0.bias), (self.Dense_1.weight, self.Dense_1.bias)
+
+    def _cached_plan(self):
+        """the block table, rebuilt when the module no longer is what the table was built from: a tensor the modules hold
+        NOW lies elsewhere (one data_ptr() per tensor per call), or a shape or an eps changed.  In-place updates change
+        no address and need nothing."""
+        from . import ops
+        records, policy, value = self._records()
+        flat = [x for r in records for part in r for x in (part if isinstance(part, tuple) else (part,))] + list(policy + value)
+        key = tuple((x.data_ptr(), tuple(x.shape)) if isinstance(x, torch.Tensor) else x for x in flat)
+        plan = self.__dict__.get("_fused_plan")
+        if plan is None or plan.key != key:
+            plan = ops.PvnetPlan([ops.PvnetBlock(*r) for r in records], policy, value)
+            plan.key = key
+            self.__dict__["_fused_plan"] = plan
+        return plan
+
+    def forward(self, x, params: Any = None, train: bool = True):
+        reason = self._reason()
+        if reason is None:
+            dev = self.Dense_0.weight.device
+            if dev.type != "cuda":
+                reason = f"parameters live on {dev}, not on a HIP device"
+            elif not (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.device == dev and x.dim() >= 2
+                      and not (torch.is_grad_enabled() and x.requires_grad)):
+                reason = f"the input is not float32 on {dev} with a batch dimension, or requires a gradient"
+            elif math.prod(x.shape[1:]) != self.input_dim:
+                reason = f"the input is not {self.input_dim} wide"
+        self.__dict__["fused_last_reason"] = reason
+        if reason is not None:
+            return self.plain_forward(x)
+        from . import ops
+        p, v = ops.pvnet_forward(x, self._cached_plan())
+        return p, v.unsqueeze(1)
+
+    def __deepcopy__(self, memo):
+        # the copy builds its own table (this one's points at this module's tensors)
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            if k != "_fused_plan":
+                new.__dict__[k] = copy.deepcopy(v, memo)
+        return new
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state.pop("_fused_plan", None)
+        return state
+
+    # ---- flax parameter trees -----------------------------------------------------------------------------------
+    def _flax_leaves(self):
+        """(scope path, kind, tensor): kind "kernel" ([in, out]: the weight transposed), "bias" or "scale" """
+        for name, block in zip(self._block_names, self.blocks):
+            for child, module in block.named_children():
+                if isinstance(module, nn.Linear):
+                    yield (name, child), "kernel", module.weight
+                    yield (name, child), "bias", module.bias
+                elif isinstance(module, nn.GroupNorm):
+                    yield (name, child), "scale", module.weight
+                    yield (name, child), "bias", module.bias
+        for child in ("Dense_0", "Dense_1"):
+            yield (child,), "kernel", getattr(self, child).weight
+            yield (child,), "bias", getattr(self, child).bias
+
+    def flax_params(self) -> Dict[str, Any]:
+        """The parameters as a flax parameter dict of numpy arrays, `{"params": {...}}`: block scopes
+        `DenseResidueBlock_i` / `DenseBlock_i` holding `Dense_0`, `GroupNorm_0`, `Dense_1`, `GroupNorm_1`, `res_proj`,
+        `norm_proj`; the heads `Dense_0` (policy) and `Dense_1` (value); every `kernel` is [in, out], the transpose of
+        the nn.Linear weight.  These scope names are flax's compact auto-naming as I know it.  flax is not on this
+        machine, so nobody here has checked them against a real checkpoint."""
+        tree: Dict[str, Any] = {}
+        for path, kind, t in self._flax_leaves():
+            node = tree
+            for scope in path:
+                node = node.setdefault(scope, {})
+            a = t.detach().cpu().numpy()
+            node[kind] = np.ascontiguousarray(a.T) if kind == "kernel" else a.copy()
+        return {"params": tree}
+
+    def load_flax_params(self, tree: Dict[str, Any]) -> "DenseResNet":
+        """Copy a flax parameter dict (flax_params' layout, with or without the outer "params") into the module, in
+        place; a missing scope, a leaf of another shape or a scope the module has no use for raises.  The same caveat
+        about the scope names as flax_params: not checked against a real checkpoint."""
+        tree = tree.get("params", tree)
+        seen = set()
+        with torch.no_grad():
+            for path, kind, t in self._flax_leaves():
+                node = tree
+                for scope in path:
+                    if scope not in node:
+                        raise KeyError(f"the tree has no scope {'/'.join(path)}")
+                    node = node[scope]
+                if kind not in node:
+                    raise KeyError(f"the tree has no {'/'.join(path)}/{kind}")
+                a = np.asarray(node[kind])
+                a = a.T if kind == "kernel" else a
+                if tuple(a.shape) != tuple(t.shape):
+                    raise ValueError(f"{'/'.join(path)}/{kind}: expected {tuple(t.shape)}"
+                                     f"{' (transposed)' if kind == 'kernel' else ''}, got {tuple(a.shape)}")
+                t.copy_(torch.from_numpy(np.ascontiguousarray(a)).to(t.dtype))
+                seen.add(path)
+
+        def scopes(node, path=()):
+            for key, sub in node.items():
+                if isinstance(sub, dict):
+                    yield from scopes(sub, path + (key,))
+            if node and not any(isinstance(sub, dict) for sub in node.values()):
+                yield path
+        extra = [p for p in scopes(tree) if p not in seen]
+        if extra:
+            raise KeyError(f"the tree has scopes this module has none for: {['/'.join(p) for p in extra]}")
+        return self
+
+
+DenseNet = partial(DenseResNet, block_cls=DenseBlock)
+DResNetMini = partial(DenseResNet, net_arch=[32] * 2)
+DResNet18 = partial(DenseResNet, net_arch=[256] * 18)
+
+NET_TYPES = {"dense_resnet": DenseResNet, "dense": DenseNet}
+
+
+def build_net(net_type: str, role: str, output_size: int, net_arch: List[int], spec: Tuple[int, int], seed: int = 0):
+    """the network JAXTrainer builds for `net_type` (jax_trainer.py:126-129, 216-218): dense_resnet -> DenseResNet,
+    dense -> DenseNet; custom / custom_dense (CustomNet) are not built"""
+    if net_type in ("custom", "custom_dense"):
+        raise ValueError(f"net_type {net_type!r} is CustomNet (one sub-network per point count, chosen per row), which is "
+                         "not built: give HipTrainer host_net / agent_net, or use net_type dense / dense_resnet.")
+    if net_type not in NET_TYPES:
+        raise ValueError(f"net_type must be one of {sorted(NET_TYPES)}. Got {net_type!r}.")
+    return NET_TYPES[net_type](output_size, net_arch, spec=spec, role=role, seed=seed)

@@ -1839,6 +1839,129 @@ def mlp_forward(x0: torch.Tensor, layers, x1: Optional[torch.Tensor] = None, inp
     return out
 
 
+# ---- the gradient-free forward of a DenseResNet / DenseNet policy-value network in one launch ------------------------------
+
+PvnetDense = collections.namedtuple("PvnetDense", "weight bias gn_scale gn_bias", defaults=(None, None, None))
+PvnetDense.__doc__ = """One `Dense [-> GroupNorm(32)]` of pvnet_forward: weight [n, k] as nn.Linear keeps it, bias [n] or
+None, the group norm's scale / bias [n] or None (a dense block has no norm: both are ignored)."""
+PvnetBlock = collections.namedtuple("PvnetBlock", "kind dense1 dense2 proj eps", defaults=(None, None, 1e-6))
+PvnetBlock.__doc__ = """One block of pvnet_forward's trunk: kind "dense" (`relu(Dense1(h))`) or "residue"
+(`relu(o + GN2(Dense2(relu(GN1(Dense1(h))))))` with o = h, or GNp(Densep(h)) where the block changes the width); dense1,
+dense2, proj: PvnetDense (or tuples in its order); eps: the group norms' (flax's default)."""
+_PVNET_KINDS = {"dense": A.HK_PVNET_DENSE, "residue": A.HK_PVNET_RESIDUE}
+PVNET_NORMED_WIDTHS = A.PVNET_NORMED_WIDTHS
+
+
+class PvnetPlan:
+    """The block table of pvnet_forward, built once per set of parameter addresses (it holds the tensors alive): `blocks`
+    is a sequence of PvnetBlock, `policy` and `value` are the heads' (weight [A, n], bias [A] or None) and (weight [1, n],
+    bias [1] or None).  The table points at the tensors it was given: whoever swaps a tensor for another builds a new plan
+    (hironaka_amd.net.DenseResNet does, by the addresses of the tensors its modules hold at each call)."""
+
+    def __init__(self, blocks: Sequence[PvnetBlock], policy, value):
+        blocks = [b if isinstance(b, PvnetBlock) else PvnetBlock(*b) for b in blocks]
+        if not 1 <= len(blocks) <= A.HK_PVNET_MAX_BLOCKS:
+            raise ValueError(f"1 to {A.HK_PVNET_MAX_BLOCKS} blocks. Got {len(blocks)}.")
+        first = PvnetDense(*blocks[0].dense1).weight
+        _require_device(first, "blocks[0].dense1.weight")
+        self.device = dev = first.device
+        self.desc = d = A.hk_pvnet_desc()
+        self.tensors = []
+        width = None
+
+        def fill(e, dense, name, n, k):
+            dense = PvnetDense(*dense)
+            if not isinstance(dense.weight, torch.Tensor) or tuple(dense.weight.shape) != (n, k):
+                raise ValueError(f"{name}.weight must be a [{n}, {k}] tensor.")
+            e.weight = _mlp_tensor(dense.weight, f"{name}.weight", dev)
+            for field in ("bias", "gn_scale", "gn_bias"):
+                setattr(e, field, _mlp_tensor(getattr(dense, field), f"{name}.{field}", dev, (n,)))
+            self.tensors += [t for t in dense if t is not None]
+
+        for i, b in enumerate(blocks):
+            if b.kind not in _PVNET_KINDS:
+                raise ValueError(f'blocks[{i}].kind must be "dense" or "residue". Got {b.kind!r}.')
+            w = PvnetDense(*b.dense1).weight
+            if not isinstance(w, torch.Tensor) or w.dim() != 2:
+                raise TypeError(f"blocks[{i}].dense1.weight must be a [n, k] tensor.")
+            n, k = w.shape
+            if width is not None and k != width:
+                raise ValueError(f"blocks[{i}] takes {k} inputs but blocks[{i - 1}] gives {width}.")
+            if not (1 <= k <= A.HK_PVNET_MAX_WIDTH and 1 <= n <= A.HK_PVNET_MAX_WIDTH):
+                raise ValueError(f"blocks[{i}]: widths must lie in 1..{A.HK_PVNET_MAX_WIDTH}. Got [{n}, {k}].")
+            width = n
+            e = d.block[i]
+            e.k, e.n, e.kind, e.eps = k, n, _PVNET_KINDS[b.kind], float(b.eps)
+            fill(e.dense1, b.dense1, f"blocks[{i}].dense1", n, k)
+            if b.kind == "residue":
+                if n not in PVNET_NORMED_WIDTHS:
+                    raise ValueError(f"blocks[{i}]: a normed width must be one of {PVNET_NORMED_WIDTHS}. Got {n}.")
+                if b.dense2 is None or (k != n and b.proj is None):
+                    raise ValueError(f"blocks[{i}]: a residue block needs dense2, and proj where it changes the width.")
+                fill(e.dense2, b.dense2, f"blocks[{i}].dense2", n, n)
+                if k != n:
+                    fill(e.proj, b.proj, f"blocks[{i}].proj", n, k)
+        actions = policy[0].shape[0] if isinstance(policy[0], torch.Tensor) and policy[0].dim() == 2 else 0
+        if not 1 <= actions <= A.HK_PVNET_MAX_WIDTH - 1:
+            raise ValueError(f"the policy head must have 1 to {A.HK_PVNET_MAX_WIDTH - 1} outputs. Got {actions}.")
+        for name, (weight, bias), n in (("policy", policy, actions), ("value", value, 1)):
+            if not isinstance(weight, torch.Tensor) or tuple(weight.shape) != (n, width):
+                raise ValueError(f"{name}[0] must be a [{n}, {width}] tensor.")
+            setattr(d, name + "_weight", _mlp_tensor(weight, f"{name}[0]", dev))
+            setattr(d, name + "_bias", _mlp_tensor(bias, f"{name}[1]", dev, (n,)))
+            self.tensors += [t for t in (weight, bias) if t is not None]
+        d.nblocks, d.actions, d.dtype = len(blocks), actions, A.HK_F32
+        self.k_in, self.actions = PvnetDense(*blocks[0].dense1).weight.shape[1], actions
+
+
+def pvnet_forward(x: torch.Tensor, plan: PvnetPlan, tile: Optional[int] = None, raw_value: bool = False,
+                  policy: Optional[torch.Tensor] = None, value: Optional[torch.Tensor] = None):
+    """The forward of a trunk of dense / residue blocks with a policy head and a tanh value head in ONE launch
+    (hk_pvnet_forward; the rule, to the bit, is in include/hironaka_hip_pvnet.h).  x: [B, ...] float32 rows (flattened
+    behind the batch dimension; the rows may lie any number of elements apart).  Returns (policy [B, A], value [B]).
+    policy / value: float32 tensors of these shapes to write into (policy with adjacent elements in a row, rows >= A
+    apart; value at any element stride >= 1); None: new ones.  tile: None, or the row tile (16 / 64) to force -- same
+    bits.  raw_value: store the value head before the tanh.  Everything is float32 on one HIP device (a TypeError
+    otherwise).  Nothing here synchronises."""
+    if not isinstance(plan, PvnetPlan):
+        raise TypeError(f"plan must be a PvnetPlan. Got {type(plan).__name__}.")
+    if tile not in _MLP_TILES:
+        raise ValueError(f"tile must be None, {A.HK_MLP_TILE_SMALL} or {A.HK_MLP_TILE_LARGE}. Got {tile!r}.")
+    dev = plan.device
+    x = _mlp_rows(x, "x", dev)
+    batch, k0 = x.shape
+    if k0 != plan.k_in:
+        raise ValueError(f"the first block takes {plan.k_in} inputs. Got {k0}.")
+    if batch >= 2 ** 31:
+        raise ValueError(f"at most 2^31 - 1 rows per call. Got {batch}.")
+    a = plan.actions
+    for name, out, shape in (("policy", policy, (batch, a)), ("value", value, (batch,))):
+        if out is None:
+            continue
+        _require_device(out, name)
+        if out.dtype != torch.float32 or out.device != dev:
+            raise TypeError(f"{name} must be a float32 tensor on {dev}. Got {out.dtype} on {out.device}.")
+        rows_apart = a if name == "policy" else 1
+        if tuple(out.shape) != shape or (batch > 1 and out.stride(0) < rows_apart) or (
+                name == "policy" and a > 1 and out.stride(1) != 1):
+            raise ValueError(f"{name} must be {list(shape)} with adjacent elements in a row and rows that do not "
+                             f"overlap. Got shape {tuple(out.shape)}, strides {out.stride()}.")
+    if policy is None:
+        policy = torch.empty((batch, a), dtype=torch.float32, device=dev)
+    if value is None:
+        value = torch.empty((batch,), dtype=torch.float32, device=dev)
+    if batch == 0:
+        return policy, value
+    d = plan.desc
+    d.x, d.x_stride, d.k0, d.batch = x.data_ptr(), x.stride(0) if batch > 1 else k0, k0, batch
+    d.policy, d.policy_stride = policy.data_ptr(), policy.stride(0) if batch > 1 else a
+    d.value, d.value_stride = value.data_ptr(), value.stride(0) if batch > 1 else 1
+    d.flags = _MLP_TILES[tile] | (A.HK_PVNET_RAW_VALUE if raw_value else 0)
+    with torch.cuda.device(dev):
+        check(lib().hk_pvnet_forward(C.byref(d), _stream(policy)), "hk_pvnet_forward")
+    return policy, value
+
+
 # ---- the training-mode forward of a create_mlp stack and its backward, one launch per layer each way ---------------------
 
 MlpTrainLayer = collections.namedtuple(

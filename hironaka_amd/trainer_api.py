@@ -7,7 +7,10 @@ points and config keys (hironaka/jax/jax_trainer.py:150-320, 398-592, 626-876):
 
 What is NOT here is the neural-network side (flax models, optax optimisers, ``train``, checkpoints, wandb) and the
 trainer's control plane around it (``validate``'s battle schedule, the ``get_* / update_*`` accessor layer of
-jax_trainer.py:626-669,735-858): out of scope.  The two networks therefore arrive as callables
+jax_trainer.py:626-669,735-858): out of scope.  The networks' FORWARD is here: where the config
+has a ``host`` / ``agent`` section with ``net_arch`` and ``net_type`` is ``dense`` or ``dense_resnet``, the trainer builds
+``hironaka_amd.net``'s modules as JAXTrainer builds flax's (jax_trainer.py:216-218; ``built_nets[role]``) and calls them
+under ``torch.no_grad()``.  Otherwise the two networks arrive as callables
 ``net(features, params) -> (policy_logits [B, A], value [B])`` together with their parameter objects
 (``host_params`` / ``agent_params``: opaque, handed back to the callables) -- the role ``model.apply`` plays in
 ``get_apply_fn`` (hironaka/jax/net.py:110-133); the feature transform in front of them (rescale + row sort,
@@ -84,6 +87,17 @@ def standin_mlp(in_dim: int, out_dim: int, seed: int, width: int = 256, device="
     return net, params
 
 
+def _without_grad(module) -> Callable:
+    """`net(features, params)` over a module HipTrainer built itself: called under torch.no_grad()"""
+    def net(features, params=None):
+        with torch.no_grad():
+            return module(features, params)
+
+    net.__name__ = f"{type(module).__name__}_without_grad"
+    net.module = module
+    return net
+
+
 class PendingRollout:
     """simulate(..., overlap_gather=True): the gathered (obs, target_policy, target_value), still travelling"""
 
@@ -120,10 +134,26 @@ class HipTrainer:
         self.device = torch.device("cuda" if device is None else device)
         if self.device.type != "cuda":
             raise TypeError("HipTrainer lives on a HIP device (there is no CPU path)")
+        m, d = self.max_num_points, self.dimension
+        # the trainer's own networks (jax_trainer.py:216-218): where a net is not given and the config has the role's
+        # section with its net_arch, net_type says which of hironaka_amd.net's modules is built; they hold their own
+        # parameters, take no gradient here and are called under torch.no_grad()
+        self.built_nets: Dict[str, Any] = {}
+        given = {"host": host_net, "agent": agent_net}
+        for i, role in enumerate(("host", "agent")):
+            section = self.config.get(role)
+            if given[role] is None and isinstance(section, dict) and "net_arch" in section:
+                from .net import build_net
+                module = build_net(self.net_type, role, 2 ** d - d - 1 if role == "host" else d, section["net_arch"],
+                                   (m, d), seed=_split(key, 2)[i]).to(self.device)
+                self.built_nets[role] = module
+                given[role] = _without_grad(module)
+        host_net, agent_net = given["host"], given["agent"]
         if host_net is None or agent_net is None:
             raise ValueError("HipTrainer needs host_net and agent_net: net(features, params) -> (logits [B, A], "
-                             "value [B]).  The reference builds flax networks here (net_type / net_arch); networks "
-                             "are outside this package (trainer_api.standin_mlp gives a fixed random stand-in).")
+                             "value [B]).  The reference builds flax networks here (net_type / net_arch): give the "
+                             "config a `host` / `agent` section with `net_arch` and hironaka_amd.net's modules are built "
+                             "the same way (trainer_api.standin_mlp gives a fixed random stand-in).")
         self.use_graph = use_graph
         # trees of the trainer's own policies expand through the fused operators (recurrent_fn.HostExpander /
         # AgentExpander) -- possible while the standard feature functions sit in front of the networks

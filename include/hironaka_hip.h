@@ -638,5 +638,7 @@ int hk_search_morin_play(const hk_morin_play_desc* desc, void* stream);
 #include "hironaka_hip_mlp.h"
 /* within ABI 6: hk_train_mlp_forward / hk_train_mlp_backward, likewise */
 #include "hironaka_hip_mlp_train.h"
+/* within ABI 6: hk_pvnet_forward, likewise */
+#include "hironaka_hip_pvnet.h"
 
 #endif /* HIRONAKA_HIP_H */
