@@ -2093,11 +2093,12 @@ def mlp_train_forward(x0: torch.Tensor, plan, x1: Optional[torch.Tensor] = None,
     return out, saved
 
 
-def mlp_backward(saved: MlpTrainSaved, grad_out: torch.Tensor):
+def mlp_backward(saved: MlpTrainSaved, grad_out: torch.Tensor, grads: Optional[Sequence[torch.Tensor]] = None):
     """The backward of one mlp_train_forward, one launch per layer (hk_train_mlp_backward): grad_out [B, n] is the
     gradient with respect to the forward's result; returns the gradients of the plan's `params`, in that order (new
-    tensors, views of one buffer).  The input gets none.  The parameters must be what they were in the forward.
-    Nothing here synchronises."""
+    tensors, views of one buffer).  grads: contiguous float32 tensors of the parameters' shapes, in that order, to write
+    the gradients into instead (views of one flat buffer, say: any 4-byte boundary will do); they are what is returned.
+    The input gets none.  The parameters must be what they were in the forward.  Nothing here synchronises."""
     plan, out = saved.plan, saved.out
     dev = plan.device
     _require_device(grad_out, "grad_out")
@@ -2108,22 +2109,33 @@ def mlp_backward(saved: MlpTrainSaved, grad_out: torch.Tensor):
     if plan.n_out > 1 and grad_out.stride(1) != 1:
         grad_out = grad_out.contiguous()
     ws_floats = 2 * batch * plan.widest
-    buf = torch.empty(plan.grad_floats + ws_floats, dtype=torch.float32, device=dev)
-    grads = []
-    for (n, k, *_), (w, b, g, be) in zip(plan.shapes, plan.grad_at):
-        grads.append(buf[w:w + n * k].view(n, k))
-        grads += [buf[at:at + n] for at in (b, g, be) if at is not None]
+    if grads is not None:
+        grads = list(grads)
+        if len(grads) != len(plan.params):
+            raise ValueError(f"grads must hold one tensor per parameter ({len(plan.params)}). Got {len(grads)}.")
+        at = [_mlp_tensor(g, f"grads[{i}]", dev, p.shape) for i, (g, p) in enumerate(zip(grads, plan.params))]
+        buf, ws_at, rows, given = torch.empty(ws_floats, dtype=torch.float32, device=dev), 0, [], iter(at)
+        for n, k, bias, gamma, beta in plan.shapes:
+            rows.append([next(given)] + [next(given) if present else None for present in (bias, gamma, beta)])
+    else:
+        buf, ws_at = torch.empty(plan.grad_floats + ws_floats, dtype=torch.float32, device=dev), plan.grad_floats
+        base = buf.data_ptr()
+        rows = [[None if at is None else base + 4 * at for at in row] for row in plan.grad_at]
+        grads = []
+        for (n, k, *_), (w, b, g, be) in zip(plan.shapes, plan.grad_at):
+            grads.append(buf[w:w + n * k].view(n, k))
+            grads += [buf[at:at + n] for at in (b, g, be) if at is not None]
     if batch == 0:
-        buf[:plan.grad_floats].zero_()
+        for g in ([buf[:plan.grad_floats]] if ws_at else grads):  # (ws_at == 0: the caller's tensors)
+            g.zero_()
         return grads
     _mlp_train_fill(plan, saved.x0, saved.x1, out, saved.buf)
     d = plan.desc
-    base = buf.data_ptr()
     d.grad_out, d.grad_stride = grad_out.data_ptr(), grad_out.stride(0) if batch > 1 else plan.n_out
-    d.workspace, d.workspace_bytes = (base + 4 * plan.grad_floats, 4 * ws_floats) if ws_floats else (None, 0)
-    for i, row in enumerate(plan.grad_at):
+    d.workspace, d.workspace_bytes = (buf.data_ptr() + 4 * ws_at, 4 * ws_floats) if ws_floats else (None, 0)
+    for i, row in enumerate(rows):
         e = d.layer[i]
-        e.d_weight, e.d_bias, e.d_bn_weight, e.d_bn_bias = (None if at is None else base + 4 * at for at in row)
+        e.d_weight, e.d_bias, e.d_bn_weight, e.d_bn_bias = row
     with torch.cuda.device(dev):
         check(lib().hk_train_mlp_backward(C.byref(d), _stream(out)), "hk_train_mlp_backward")
     return grads

@@ -136,6 +136,98 @@ class Guarded:
         return same_bits(self.store.cpu().numpy(), self.expect)
 
 
+class Packed:
+    """arrays (None: none) back to back, `gap` sentinels between neighbours, in one sentinel-filled flat buffer from element
+    `start` on with 8 sentinels behind the last: whatever 4-byte boundary that gives each.  `views` are the tensors,
+    `expect` is the buffer as a launch that only reads them must leave it (`put` says what a launch writes)."""
+
+    def __init__(self, arrays, start, gap=0):
+        self.at, at = [], start
+        for a in arrays:
+            self.at.append(None if a is None else at)
+            at += 0 if a is None else a.size + gap
+        self.expect = np.full(at + 8, SENTINEL, F32)
+        for a, p in zip(arrays, self.at):
+            if a is not None:
+                self.expect[p:p + a.size] = a.ravel()
+        self.store = dev(self.expect)
+        self.views = [None if a is None else self.store[p:p + a.size].view(*a.shape) for a, p in zip(arrays, self.at)]
+
+    def put(self, i, values):
+        self.expect[self.at[i]:self.at[i] + values.size] = values.ravel()
+
+    def holds(self):
+        return same_bits(self.store.cpu().numpy(), self.expect)
+
+
+def repoint(module, start):
+    """every parameter and floating-point buffer of `module` re-pointed at a view of ONE flat sentinel-padded tensor,
+    back to back from element `start`: (flat, [(view's first element, numel)])"""
+    tensors = list(module.parameters()) + [b for b in module.buffers() if b.is_floating_point()]
+    flat = torch.full((start + sum(t.numel() for t in tensors) + 8,), SENTINEL, dtype=torch.float32, device="cuda")
+    where, at = [], start
+    with torch.no_grad():
+        for t in tensors:
+            view = flat[at:at + t.numel()].view_as(t)
+            view.copy_(t)
+            t.data = view
+            where.append((at, t.numel()))
+            at += t.numel()
+    return flat, where
+
+
+@pytest.mark.parametrize("start", [0, 1, 2, 3])
+def test_parameters_packed_in_a_flat_buffer(start):
+    """64 -> 64 -> 4 (K % 4 == 0 everywhere: the 16-byte loads of the weights hang on the address alone) with every
+    parameter a view into one flat buffer from element `start`; 19 rows, every tile.  The rule's bits, and the buffer
+    -- sentinels and parameters -- as it was."""
+    rng = np.random.default_rng(17)
+    layers = R.random_layers(rng, (64, 64, 4), bn=True)
+    input_bn = R.random_layers(rng, (64, 64), bn=True)[0]._replace(weight=None, bias=None)
+    x = inputs(rng, 19, 64)
+    want = R.forward(x, layers, input_relu=True, input_bn=input_bn)
+    packed = Packed([a for l in [input_bn] + layers for a in l[:6]], start)
+    assert sorted({(p % 4) for p in packed.at if p is not None}) == [start % 4]  # every size is a multiple of 4 here
+    views = iter(packed.views)
+    mk = lambda l: _ops().MlpLayer(*(next(views) for _ in range(6)), l.eps, l.relu)  # noqa: E731
+    dev_in, dl = mk(input_bn), [mk(l) for l in layers]
+    assert dl[0].weight.data_ptr() % 16 == 4 * (start % 4)
+    for tile in (None,) + TILES:
+        out = Guarded(19, 4, 1, 4)
+        _ops().mlp_forward(dev(x), dl, input_relu=True, input_bn=dev_in, out=out.view, tile=tile)
+        assert out.holds(want) and packed.holds(), tile
+    # tensors of odd sizes one sentinel apart: every boundary at once, K % 4 != 0 next to K % 4 == 0
+    layers = R.random_layers(rng, (64, 17, 64, 3), bn=True)
+    packed = Packed([a for l in layers for a in l[:6]], start, gap=1)
+    assert len({p % 4 for p in packed.at}) == 4
+    views = iter(packed.views)
+    dl = [mk(l) for l in layers]
+    for tile in TILES:
+        got = _ops().mlp_forward(dev(x), dl, tile=tile)
+        assert same_bits(got.cpu().numpy(), R.forward(x, layers)) and packed.holds(), tile
+
+
+def test_a_module_whose_parameters_are_views_of_one_flat_tensor(fixture):
+    """create_mlp's net re-pointed at one flat tensor (a flattened parameter vector): the kernel's path, the rule's bits,
+    a new table (every data_ptr changed), and the flat tensor as it was"""
+    key = "test_host"  # 60 -> 16 -> 32 -> 32 -> 16 -> 4: K % 4 == 0 everywhere
+    net = fixture_net(fixture, key)
+    x = fixture_input(fixture, key)
+    want = rule_output(fixture, key, net)
+    with torch.inference_mode():
+        assert same_bits(net(x).cpu().numpy(), want) and net.fused_last_reason is None
+    for start in (1, 2, 3, 0):
+        plan = net.__dict__["_fused_plan"]
+        flat, where = repoint(net, start)
+        before = flat.clone()
+        assert next(net.parameters()).data_ptr() == flat.data_ptr() + 4 * start and where[0] == (start, 16 * 60)
+        with torch.inference_mode():
+            y = net(x)
+        assert net.fused_last_reason is None and net.__dict__["_fused_plan"] is not plan, start
+        assert same_bits(y.cpu().numpy(), want) and torch.equal(flat, before), start
+        assert bool((flat[:start] == SENTINEL).all()) and bool((flat[-8:] == SENTINEL).all())
+
+
 @pytest.mark.parametrize("tile", TILES)
 def test_layouts_and_guards(tile):
     """two segments; offset, strided and record layouts of x0, x1 and out between sentinels that must stay"""

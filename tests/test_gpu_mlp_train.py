@@ -128,6 +128,52 @@ def test_nan_and_inf_in_the_input():
         assert np.isnan(_np(sv.out)).any()
 
 
+@pytest.mark.parametrize("start", [0, 1, 2, 3])
+def test_parameters_statistics_and_gradients_packed_in_flat_buffers(start):
+    """64 -> 64 -> 4 with every parameter a view into one flat buffer from element `start`, and what the kernels write
+    -- the running statistics and every gradient -- views into a second one, one sentinel between neighbours: 19 rows
+    and 257 (both instantiations).  The rule's bits in every output; the first buffer as it was; in the second the new
+    statistics, the gradients, and every sentinel between and around them."""
+    from test_gpu_mlp import Packed
+    ops = _ops()
+    rng = np.random.default_rng(70 + start)
+    layers = T.random_layers(rng, (64, 64, 4), momentum=0.5)
+    for batch in (19, 257):
+        x = rng.standard_normal((batch, 64)).astype(F32)
+        grad = rng.standard_normal((batch, 4)).astype(F32)
+        out, saved, stats = T.forward(x, layers, True)
+        want = T.param_grads(layers, T.backward(layers, saved, grad))
+        read = Packed([a for l in layers for a in (l.weight, l.bias, l.bn_weight, l.bn_bias)], start)
+        running = [a for l in layers for a in (l.bn_mean, l.bn_var)]
+        written = Packed(running + [np.full(g.shape, R.F32(-3.5)) for g in want], (start + 1) % 4, gap=1)
+        assert read.views[0].data_ptr() % 16 == 4 * start and len({p % 4 for p in written.at}) == 4
+        r, w = iter(read.views), iter(written.views)
+        dl = []
+        for l in layers:
+            weight, bias, gamma, beta = (next(r) for _ in range(4))
+            dl.append(ops.MlpTrainLayer(weight, bias, next(w), next(w), gamma, beta, l.eps, l.relu, float(l.momentum),
+                                        torch.zeros((), dtype=torch.int64, device="cuda")))
+        grads = list(w)
+        got_out, sv = ops.mlp_train_forward(_cuda(x), ops.MlpTrainPlan(dl, True))
+        got = ops.mlp_backward(sv, _cuda(grad), grads=grads)
+        assert same_bits(_np(got_out), out)
+        assert len(got) == len(want) and all(g is t for g, t in zip(got, grads))
+        for i, g in enumerate(want):
+            assert same_bits(_np(got[i]), g), (batch, i)
+            written.put(len(running) + i, np.ascontiguousarray(g, F32))
+        for i, a in enumerate(a for st in stats for a in st):
+            written.put(i, a)
+        assert read.holds() and written.holds(), batch
+        assert [int(l.num_batches_tracked) for l in dl] == [1, 1]
+    # the front end's checks of `grads`
+    with pytest.raises(ValueError):
+        ops.mlp_backward(sv, _cuda(grad), grads=grads[:-1])
+    with pytest.raises(ValueError):
+        ops.mlp_backward(sv, _cuda(grad), grads=[grads[1]] + grads[1:])
+    with pytest.raises(TypeError):
+        ops.mlp_backward(sv, _cuda(grad), grads=[grads[0].t().contiguous().t()] + grads[1:])
+
+
 def test_ops_refuse_what_the_kernels_do_not_take():
     ops = _ops()
     rng = np.random.default_rng(10)
@@ -192,6 +238,43 @@ def test_reference_configs_end_to_end(name, head, rows):
         layers, input_relu, input_bn = R.spec_layers(nets.mlp_spec(net), lambda t: None if t is None else _np(t))
         x = points.reshape(rows, -1) if head == "host" else np.concatenate([points.reshape(rows, -1), coords], axis=1)
         assert same_bits(_np(y), R.forward(x, layers, input_relu, input_bn))
+
+
+def test_a_training_net_whose_parameters_and_buffers_are_views_of_one_flat_tensor():
+    """create_mlp's "test" net (60 -> 16 -> 32 -> 32 -> 16 -> 4: K % 4 == 0 everywhere) with every parameter and running
+    statistic re-pointed at a view of one flat tensor: the kernels' path, a new table (every data_ptr changed), the
+    rule's bits in the result, in every .grad and in the statistics, and the flat tensor's sentinels and parameters as
+    they were"""
+    from test_gpu_mlp import SENTINEL, repoint
+    net = T.seeded_net("test", "host", 71, fused_training=True).cuda()
+    points, coords = T.seeded_rows(72, 37)
+    grad = T.sparse_grad(np.random.default_rng(73), 37, R.HEADS["host"][1])
+    net(_cuda(points))  # a first call builds the table (and moves the statistics once)
+    assert net.fused_last_reason is None
+    for tracked, start in enumerate((1, 2, 3, 0), 2):
+        plan = net.__dict__["_fused_train_plan"]
+        flat, where = repoint(net, start)
+        nparams = len(list(net.parameters()))
+        before = _np(flat).copy()
+        out, grads, stats = _net_rule(net, "host", points, coords, grad)
+        net.zero_grad()
+        q = net(_cuda(points))
+        assert net.fused_last_reason is None and net.__dict__["_fused_train_plan"] is not plan, start
+        q.backward(_cuda(grad))
+        assert same_bits(_np(q), out)
+        for p, g in zip(net.parameters(), grads):
+            assert same_bits(_np(p.grad), g), start
+        bns = [m for m in net if isinstance(m, nn.BatchNorm1d)]
+        expect = before.copy()
+        buffers = iter(where[nparams:])
+        for bn, (mean, var) in zip(bns, [s for s in stats if s[0] is not None]):
+            for a in (mean, var):
+                at, size = next(buffers)
+                expect[at:at + size] = a
+            assert same_bits(_np(bn.running_mean), mean) and same_bits(_np(bn.running_var), var)
+            assert int(bn.num_batches_tracked) == tracked
+        assert same_bits(_np(flat), expect), start
+        assert (expect[:start] == SENTINEL).all() and (expect[-8:] == SENTINEL).all()
 
 
 def test_two_forwards_before_either_backward():

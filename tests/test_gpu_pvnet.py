@@ -231,6 +231,53 @@ def test_front_end_refuses():
     assert e.value.status == A.HK_ERR_UNSUPPORTED
 
 
+@pytest.mark.parametrize("start", [0, 1, 2, 3])
+def test_parameters_packed_in_a_flat_buffer(start):
+    """[64, 128] behind k0 = 64 (K % 4 == 0 in every Dense and both heads: the 16-byte loads of the weights hang on the
+    address alone) with every parameter a view into one flat buffer from element `start`; 19 rows, every tile.  The
+    rule's bits, and the buffer -- sentinels and parameters -- as it was.  Then blocks of other widths one sentinel
+    apart: every boundary at once."""
+    from test_gpu_mlp import Packed
+    ops = _ops()
+    rng = np.random.default_rng(40 + start)
+    for k0, arch, kinds, actions, gap in ((64, [64, 128], "residue", 4, 0), (60, [17, 64, 128], ["dense", "residue", "residue"], 15, 1)):
+        net = R.random_net(rng, k0, arch, actions, kinds)
+        x = inputs(rng, 19, k0)
+        want = R.forward(x, net)
+        denses = [d for b in net.blocks for d in (b.dense1, b.dense2, b.proj)]
+        packed = Packed([a for d in denses for a in (d if d is not None else (None,) * 4)] + list(net.policy + net.value),
+                        start, gap)
+        assert len({p % 4 for p in packed.at if p is not None}) == (4 if gap else 1)
+        v = iter(packed.views)
+
+        def dn(d):  # (an absent Dense has four absent views)
+            views = [next(v) for _ in range(4)]
+            return None if d is None else ops.PvnetDense(*views)
+        blocks = [ops.PvnetBlock(b.kind, dn(b.dense1), dn(b.dense2), dn(b.proj), b.eps) for b in net.blocks]
+        plan = ops.PvnetPlan(blocks, (next(v), next(v)), (next(v), next(v)))
+        assert plan.tensors[0].data_ptr() % 16 == 4 * start
+        for tile in TILES:
+            policy, value = Guarded(19, actions, 1, actions + 2), Guarded(19, 1, 3, 1)
+            ops.pvnet_forward(dev(x), plan, tile=tile, raw_value=True, policy=policy.view, value=value.view[:, 0])
+            assert policy.holds(want[0]) and value.holds(want[1]) and packed.holds(), (arch, tile)
+
+
+def test_a_module_whose_parameters_are_views_of_one_flat_tensor():
+    """a DenseResNet re-pointed at one flat tensor (a flattened parameter vector): the kernel's path, the rule's bits, a
+    new table (every data_ptr changed), and the flat tensor as it was"""
+    from test_gpu_mlp import repoint
+    net = randomised(_net().DenseResNet(4, [64, 128], input_dim=64), 41).cuda()
+    x = dev(inputs(np.random.default_rng(42), 19, 64))
+    assert served(net, x)
+    for start in (1, 2, 3, 0):
+        plan = net.__dict__["_fused_plan"]
+        flat, where = repoint(net, start)
+        before = flat.clone()
+        assert next(net.parameters()).data_ptr() == flat.data_ptr() + 4 * start
+        assert served(net, x) and net.__dict__["_fused_plan"] is not plan, start
+        assert torch.equal(flat, before) and bool((flat[:start] == SENTINEL).all()) and bool((flat[-8:] == SENTINEL).all())
+
+
 @pytest.mark.parametrize("tile", TILES[1:])
 def test_a_nan_stays_in_its_row(tile):
     rng = np.random.default_rng(29)
