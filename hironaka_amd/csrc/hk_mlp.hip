@@ -25,7 +25,7 @@ bool has_in_bn(const hk_mlp_desc* q) { return q->in_bn_mean || q->in_bn_var || q
 
 int validate(const hk_mlp_desc* q) {
   if (const int bad = mlp_check_desc(q, kDescFlags)) return bad;
-  if ((q->flags & HK_MLP_FORCE_TILE_SMALL) && (q->flags & HK_MLP_FORCE_TILE_LARGE)) return HK_ERR_UNSUPPORTED;
+  if (mlp_forces_both_tiles(q->flags)) return HK_ERR_UNSUPPORTED;
   int64_t width = 0;
   if (const int bad = mlp_check_sizes(q, HK_MLP_RELU, width)) return bad;
   if (q->out_stride < width) return HK_ERR_SHAPE;
@@ -58,12 +58,6 @@ int validate(const hk_mlp_desc* q) {
   return HK_OK;
 }
 
-template <int TR>
-int launch(const hk_mlp_desc& q, hipStream_t stream) {
-  return launch_kernel_lds(mlp_kernel<TR>, 48 * 1024, dim3((unsigned)workgroups(q.batch, TR)), dim3(kWave * mlp_waves(TR)),
-                           mlp_lds_bytes(TR), stream, q);
-}
-
 }  // namespace
 
 extern "C" {
@@ -74,8 +68,7 @@ int hk_mlp_forward(const hk_mlp_desc* q, void* stream) {
   const int bad = validate(q);
   if (bad != HK_OK) return bad;
   if (q->batch == 0) return HK_OK;
-  if (mlp_row_tile(q->batch, q->flags) == HK_MLP_TILE_LARGE) return launch<HK_MLP_TILE_LARGE>(*q, (hipStream_t)stream);
-  return launch<HK_MLP_TILE_SMALL>(*q, (hipStream_t)stream);
+  return mlp_launch(mlp_kernel<HK_MLP_TILE_SMALL>, mlp_kernel<HK_MLP_TILE_LARGE>, *q, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // hk::mlp_kernel -- the eval-mode forward of a create_mlp stack in one launch (include/hironaka_hip_mlp.h states the
 // rule).  One workgroup of 4 waves (16 rows) or 16 waves (64 rows) carries TR batch rows through every layer; the
 // activations ping-pong between two LDS panels, the weights pass through a 16-k stage of LDS, the products run on
-// v_mfma_f32_16x16x4_f32, which is bit for bit a k-ordered fmaf chain.
+// v_mfma_f32_16x16x4_f32, which is bit for bit a k-ordered fmaf chain.  The tile (MlpTile), the input load
+// (mlp_load_rows) and the Dense k-loop (mlp_dense) are hk::pvnet_kernel's too (hk_pvnet_kernel.h): its one copy is here.
 //
 // ---- who computes what ----
 // A layer's output is MT = TR / 16 row tiles x NT = ceil(n / 16) column tiles of 16 x 16.  Wave w of W owns the column
@@ -136,11 +137,128 @@ __device__ inline void mlp_load_w(mlp_f4 (&w)[PASSES], const float* W, int K, in
   }
 }
 
+// the tile of a workgroup that carries TR rows: MT row tiles, W waves of TPW column tiles each (the accumulators Acc), and
+// the PASSES of PER rows in which its threads cover the weight stage (mlp_load_w)
+template <int TR>
+struct MlpTile {
+  static constexpr int MT = TR / 16, W = mlp_waves(TR), TPW = kMlpColumnTiles / W;
+  static constexpr int PASSES = HK_MLP_MAX_WIDTH / (W * kWave / 4), PER = HK_MLP_MAX_WIDTH / PASSES;
+  typedef mlp_f4 Acc[MT][TPW];
+};
+
+// the rows a workgroup starts from: x0 | x1 per row, x1_stride apart; the batch norm (bn_mean: there is one) and the
+// ReLU come before the first layer.  Only the x0 fields count where mlp_load_rows is told so.
+struct MlpInput {
+  const float *x0, *x1;
+  int64_t x0_stride, x1_stride;
+  int k0, k1;
+  const float *bn_mean, *bn_var, *bn_weight, *bn_bias;
+  float eps;
+  bool relu;
+};
+
+// the input rows row0 .. row0 + TR - 1 into the panel `dst`: thread k of a row, zeros behind the width and below the
+// batch.  EXTRAS: the second segment, the batch norm and the ReLU of `in` (false: x0 alone, as it is)
+template <int TR, bool EXTRAS>
+__device__ __forceinline__ void mlp_load_rows(float* dst, const MlpInput& in, int64_t row0, int64_t batch, int tid) {
+  const int K = EXTRAS ? in.k0 + in.k1 : in.k0, Kp = (K + 15) & ~15;
+  if (tid < Kp) {
+    const int p = mlp_pos(tid);
+    const bool bn = EXTRAS && in.bn_mean && tid < K;
+    float mu = 0.0f, alpha = 1.0f, beta = 0.0f;
+    if (bn) {
+      mu = in.bn_mean[tid];
+      const float inv = 1.0f / sqrtf(in.bn_var[tid] + in.eps);
+      alpha = in.bn_weight ? in.bn_weight[tid] * inv : inv;
+      beta = in.bn_bias ? in.bn_bias[tid] : 0.0f;
+    }
+#pragma unroll 4
+    for (int r = 0; r < TR; ++r) {
+      const int64_t b = row0 + r;
+      float v = 0.0f;
+      if (b < batch && tid < K) {
+        v = !EXTRAS || tid < in.k0 ? in.x0[b * in.x0_stride + tid] : in.x1[b * in.x1_stride + (tid - in.k0)];
+        if (bn) v = fmaf(v - mu, alpha, beta);
+        if (EXTRAS && in.relu) v = mlp_relu(v);
+      }
+      dst[r * kMlpLda + p] = v;
+    }
+  }
+}
+
+// acc = Dense(src): N outputs over K inputs, every chain started from its bias (NULL: 0).  HEADS: the last of the N rows
+// of the weight comes from Wv (its bias from bv, NULL: 0) and the N - 1 before it from W -- hk::pvnet_kernel's two
+// heads as one layer; without HEADS all N come from W, and Wv and bv are not looked at.
+// The chunk of 16 k's a pass multiplies waits in the stage `wst`, the one behind it in the registers w: the first
+// barrier of a pass says that every wave has read the stage (and, at kc == 0, that whoever wrote the panel `src` is
+// done), the second that the stage is written.  Nothing waits behind the last pass: a caller may write the OTHER panel
+// right after the call (every wave left its last read of it before this call's barriers), but other waves may still be
+// reading `src` and the stage until the next call's first barrier.  Stage writes and ds_read_b128 reads: the bank
+// notes at the head of this file.
+template <int TR, bool HEADS>
+__device__ __forceinline__ void mlp_dense(typename MlpTile<TR>::Acc& acc, const float* src, float* wst, const float* W,
+                                          const float* bias, const float* Wv, const float* bv, int K, int N, int tid) {
+  typedef MlpTile<TR> T;
+  const int lane = tid & (kWave - 1), wave = tid >> 6, lm = lane & 15, lg = lane >> 4;
+  const int Kp = (K + 15) & ~15, NT = (N + 15) >> 4, rows = NT * 16;
+  const int NW = HEADS ? N - 1 : N;  // the rows W holds
+  const bool vec = (K & 3) == 0 && (reinterpret_cast<uintptr_t>(W) & 15u) == 0;
+#pragma unroll
+  for (int i = 0; i < T::TPW; ++i) {
+    const int j = (wave + T::W * i) * 16 + lm;
+    float b0 = bias && j < NW ? bias[j] : 0.0f;
+    if (HEADS && bv && j == NW) b0 = bv[0];
+#pragma unroll
+    for (int mt = 0; mt < T::MT; ++mt) acc[mt][i] = mlp_f4{b0, b0, b0, b0};
+  }
+  mlp_f4 w[T::PASSES];
+  auto load = [&](int kc) {
+    mlp_load_w<T::PASSES>(w, W, K, NW, rows, kc, vec, tid);
+    if (HEADS) {  // the value row, float by float: one row of the chunk
+      const int k = kc + 4 * (tid & 3);
+#pragma unroll
+      for (int i = 0; i < T::PASSES; ++i)
+        if ((tid >> 2) + T::PER * i == NW) {
+          if (k + 0 < K) w[i].x = Wv[k + 0];
+          if (k + 1 < K) w[i].y = Wv[k + 1];
+          if (k + 2 < K) w[i].z = Wv[k + 2];
+          if (k + 3 < K) w[i].w = Wv[k + 3];
+        }
+    }
+  };
+  load(0);
+  for (int kc = 0; kc < Kp; kc += kMlpKc) {
+    __syncthreads();  // the stage is free (and, at kc == 0, the panel `src` is complete)
+#pragma unroll
+    for (int i = 0; i < T::PASSES; ++i)
+      if (T::PER * i < rows) {
+        float* s = wst + ((tid >> 2) + T::PER * i) * kMlpLdw + (tid & 3);
+        s[0] = w[i].x, s[4] = w[i].y, s[8] = w[i].z, s[12] = w[i].w;
+      }
+    __syncthreads();
+    if (kc + kMlpKc < Kp) load(kc + kMlpKc);
+    mlp_f4 a[T::MT];
+#pragma unroll
+    for (int mt = 0; mt < T::MT; ++mt)
+      a[mt] = *reinterpret_cast<const mlp_f4*>(src + (mt * 16 + lm) * kMlpLda + kc + 4 * lg);
+#pragma unroll
+    for (int i = 0; i < T::TPW; ++i) {
+      const int nt = wave + T::W * i;
+      if (nt < NT) {
+        const mlp_f4 b = *reinterpret_cast<const mlp_f4*>(wst + (nt * 16 + lm) * kMlpLdw + 4 * lg);
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int mt = 0; mt < T::MT; ++mt)
+            acc[mt][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mt][t], b[t], acc[mt][i], 0, 0, 0);
+      }
+    }
+  }
+}
+
 template <int TR>
 __global__ __launch_bounds__(kWave * mlp_waves(TR)) void mlp_kernel(const hk_mlp_desc q) {
-  constexpr int MT = TR / 16;
-  constexpr int kMlpWaves = mlp_waves(TR), kMlpTilesPerWave = kMlpColumnTiles / kMlpWaves;
-  constexpr int PASSES = HK_MLP_MAX_WIDTH / (kMlpWaves * kWave / 4), PER = HK_MLP_MAX_WIDTH / PASSES;
+  typedef MlpTile<TR> T;
   extern __shared__ __align__(16) float hk_mlp_lds[];
   float* cur = hk_mlp_lds;
   float* nxt = cur + TR * kMlpLda;
@@ -148,93 +266,30 @@ __global__ __launch_bounds__(kWave * mlp_waves(TR)) void mlp_kernel(const hk_mlp
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
   const int lm = lane & 15, lg = lane >> 4;
   const int64_t row0 = (int64_t)blockIdx.x * TR;
+  auto f = [](const void* p) { return static_cast<const float*>(p); };
 
-  {  // the input rows: thread k of a row, zeros behind the width and below the batch
-    const int K = q.k0 + q.k1, Kp = (K + 15) & ~15;
-    const float* x0 = static_cast<const float*>(q.x0);
-    const float* x1 = static_cast<const float*>(q.x1);
-    const bool relu = q.flags & HK_MLP_INPUT_RELU;
-    if (tid < Kp) {
-      const int p = mlp_pos(tid);
-      const bool bn = q.in_bn_mean && tid < K;
-      float mu = 0.0f, alpha = 1.0f, beta = 0.0f;
-      if (bn) {
-        mu = static_cast<const float*>(q.in_bn_mean)[tid];
-        const float inv = 1.0f / sqrtf(static_cast<const float*>(q.in_bn_var)[tid] + q.in_eps);
-        alpha = q.in_bn_weight ? static_cast<const float*>(q.in_bn_weight)[tid] * inv : inv;
-        beta = q.in_bn_bias ? static_cast<const float*>(q.in_bn_bias)[tid] : 0.0f;
-      }
-#pragma unroll 4
-      for (int r = 0; r < TR; ++r) {
-        const int64_t b = row0 + r;
-        float v = 0.0f;
-        if (b < q.batch && tid < K) {
-          v = tid < q.k0 ? x0[b * q.x0_stride + tid] : x1[b * q.x1_stride + (tid - q.k0)];
-          if (bn) v = fmaf(v - mu, alpha, beta);
-          if (relu) v = mlp_relu(v);
-        }
-        cur[r * kMlpLda + p] = v;
-      }
-    }
-  }
+  mlp_load_rows<TR, true>(cur,
+                          MlpInput{f(q.x0), f(q.x1), q.x0_stride, q.x1_stride, q.k0, q.k1, f(q.in_bn_mean), f(q.in_bn_var),
+                                   f(q.in_bn_weight), f(q.in_bn_bias), q.in_eps, (q.flags & HK_MLP_INPUT_RELU) != 0},
+                          row0, q.batch, tid);
 
   for (int l = 0; l < q.nlayers; ++l) {
     const hk_mlp_layer& L = q.layer[l];
-    const int K = L.k, N = L.n, Kp = (K + 15) & ~15, NT = (N + 15) >> 4, rows = NT * 16;
-    const float* W = static_cast<const float*>(L.weight);
-    const float* bias = static_cast<const float*>(L.bias);
-    const bool vec = (K & 3) == 0 && (reinterpret_cast<uintptr_t>(W) & 15u) == 0;
+    const int N = L.n, NT = (N + 15) >> 4;
     const bool last = l + 1 == q.nlayers;
-
-    mlp_f4 acc[MT][kMlpTilesPerWave];
-#pragma unroll
-    for (int i = 0; i < kMlpTilesPerWave; ++i) {
-      const int j = (wave + kMlpWaves * i) * 16 + lm;
-      const float b0 = bias && j < N ? bias[j] : 0.0f;
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) acc[mt][i] = mlp_f4{b0, b0, b0, b0};
-    }
-
-    mlp_f4 w[PASSES];
-    mlp_load_w<PASSES>(w, W, K, N, rows, 0, vec, tid);
-    for (int kc = 0; kc < Kp; kc += kMlpKc) {
-      __syncthreads();  // the stage is free (and, at kc == 0, the panel `cur` is complete)
-#pragma unroll
-      for (int i = 0; i < PASSES; ++i)
-        if (PER * i < rows) {
-          float* s = wst + ((tid >> 2) + PER * i) * kMlpLdw + (tid & 3);
-          s[0] = w[i].x, s[4] = w[i].y, s[8] = w[i].z, s[12] = w[i].w;
-        }
-      __syncthreads();
-      if (kc + kMlpKc < Kp) mlp_load_w<PASSES>(w, W, K, N, rows, kc + kMlpKc, vec, tid);
-      mlp_f4 a[MT];
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-        a[mt] = *reinterpret_cast<const mlp_f4*>(cur + (mt * 16 + lm) * kMlpLda + kc + 4 * lg);
-#pragma unroll
-      for (int i = 0; i < kMlpTilesPerWave; ++i) {
-        const int nt = wave + kMlpWaves * i;
-        if (nt < NT) {
-          const mlp_f4 b = *reinterpret_cast<const mlp_f4*>(wst + (nt * 16 + lm) * kMlpLdw + 4 * lg);
-#pragma unroll
-          for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-              acc[mt][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mt][t], b[t], acc[mt][i], 0, 0, 0);
-        }
-      }
-    }
+    typename T::Acc acc;
+    mlp_dense<TR, false>(acc, cur, wst, f(L.weight), f(L.bias), nullptr, nullptr, L.k, N, tid);
 
     // epilogue: C/D has its column j on lane & 15 and its rows 4 (lane >> 4) + r in the registers
-    const float* mean = static_cast<const float*>(L.bn_mean);
-    const float* var = static_cast<const float*>(L.bn_var);
-    const float* gamma = static_cast<const float*>(L.bn_weight);
-    const float* beta_p = static_cast<const float*>(L.bn_bias);
+    const float* mean = f(L.bn_mean);
+    const float* var = f(L.bn_var);
+    const float* gamma = f(L.bn_weight);
+    const float* beta_p = f(L.bn_bias);
     const bool relu = L.flags & HK_MLP_RELU;
     float* out = static_cast<float*>(q.out);
 #pragma unroll
-    for (int i = 0; i < kMlpTilesPerWave; ++i) {
-      const int nt = wave + kMlpWaves * i;
+    for (int i = 0; i < T::TPW; ++i) {
+      const int nt = wave + T::W * i;
       if (nt < NT) {
         const int j = nt * 16 + lm;
         const bool valid = j < N;
@@ -247,7 +302,7 @@ __global__ __launch_bounds__(kWave * mlp_waves(TR)) void mlp_kernel(const hk_mlp
         }
         const int pj = mlp_pos(j);
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
+        for (int mt = 0; mt < T::MT; ++mt)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int row = mt * 16 + 4 * lg + r;
@@ -266,6 +321,20 @@ __global__ __launch_bounds__(kWave * mlp_waves(TR)) void mlp_kernel(const hk_mlp
     cur = nxt;
     nxt = swap;
   }
+}
+
+// ---- the host's side of a kernel on this tile (hk_mlp.hip, hk_pvnet.hip) -------------------------------------------------
+// a descriptor may force one row tile, not both
+inline bool mlp_forces_both_tiles(uint32_t flags) {
+  return (flags & HK_MLP_FORCE_TILE_SMALL) && (flags & HK_MLP_FORCE_TILE_LARGE);
+}
+// the launch over q.batch rows of the instantiation mlp_row_tile picks: `small` is the kernel's <HK_MLP_TILE_SMALL>,
+// `large` its <HK_MLP_TILE_LARGE>
+template <typename Desc>
+int mlp_launch(void (*small)(const Desc), void (*large)(const Desc), const Desc& q, hipStream_t stream) {
+  const int tr = mlp_row_tile(q.batch, q.flags);
+  return launch_kernel_lds(tr == HK_MLP_TILE_LARGE ? large : small, 48 * 1024, dim3((unsigned)workgroups(q.batch, tr)),
+                           dim3(kWave * mlp_waves(tr)), mlp_lds_bytes(tr), stream, q);
 }
 
 }  // namespace hk

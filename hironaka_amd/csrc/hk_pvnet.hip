@@ -20,7 +20,7 @@ int denses(const hk_pvnet_block& B, const hk_pvnet_dense* (&d)[3]) {
 
 int validate(const hk_pvnet_desc* q) {
   if (const int bad = mlp_check_desc(q, kDescFlags)) return bad;
-  if ((q->flags & HK_PVNET_FORCE_TILE_SMALL) && (q->flags & HK_PVNET_FORCE_TILE_LARGE)) return HK_ERR_UNSUPPORTED;
+  if (mlp_forces_both_tiles(q->flags)) return HK_ERR_UNSUPPORTED;
   if (q->nblocks < 1 || q->nblocks > HK_PVNET_MAX_BLOCKS) return HK_ERR_SHAPE;
   if (q->batch < 0 || q->k0 < 1 || q->x_stride < 0) return HK_ERR_SHAPE;
   if (q->actions < 1 || q->actions > HK_PVNET_MAX_WIDTH - 1) return HK_ERR_SHAPE;
@@ -68,12 +68,6 @@ int validate(const hk_pvnet_desc* q) {
   return HK_OK;
 }
 
-template <int TR>
-int launch(const hk_pvnet_desc& q, hipStream_t stream) {
-  return launch_kernel_lds(pvnet_kernel<TR>, 48 * 1024, dim3((unsigned)workgroups(q.batch, TR)), dim3(kWave * mlp_waves(TR)),
-                           mlp_lds_bytes(TR), stream, q);
-}
-
 }  // namespace
 
 extern "C" {
@@ -82,8 +76,7 @@ int hk_pvnet_forward(const hk_pvnet_desc* q, void* stream) {
   const int bad = validate(q);
   if (bad != HK_OK) return bad;
   if (q->batch == 0) return HK_OK;
-  if (mlp_row_tile(q->batch, q->flags) == HK_MLP_TILE_LARGE) return launch<HK_MLP_TILE_LARGE>(*q, (hipStream_t)stream);
-  return launch<HK_MLP_TILE_SMALL>(*q, (hipStream_t)stream);
+  return mlp_launch(pvnet_kernel<HK_MLP_TILE_SMALL>, pvnet_kernel<HK_MLP_TILE_LARGE>, *q, (hipStream_t)stream);
 }
 
 }  // extern "C"

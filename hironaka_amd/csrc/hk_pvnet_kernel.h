@@ -1,8 +1,9 @@
 // hk::pvnet_kernel -- the gradient-free forward of a DenseResNet / DenseNet policy-value network in one launch
 // (include/hironaka_hip_pvnet.h states the rule).  The scheme is hk::mlp_kernel's (hk_mlp_kernel.h: who computes what, the
-// LDS image, mlp_pos, mlp_load_w, the banks): a workgroup of 4 waves carries 16 rows, one of 16 waves 64 rows, through
-// every block and both heads; the rows live in two LDS panels, the weights pass through the 16-k stage, every Dense is
-// one k-ordered chain per output on v_mfma_f32_16x16x4_f32.  What is new here:
+// LDS image, mlp_pos, the banks) and so is the code: MlpTile, the input load mlp_load_rows and every Dense, mlp_dense.
+// A workgroup of 4 waves carries 16 rows, one of 16 waves 64 rows, through every block and both heads; the rows live in
+// two LDS panels, the weights pass through the 16-k stage, every Dense is one k-ordered chain per output on
+// v_mfma_f32_16x16x4_f32.  What is this kernel's own:
 //
 // ---- the group norm, in the registers of the MFMA's result ----
 // C/D has column j on lane & 15 and the rows 4 (lane >> 4) + r in its four registers.  A group is g = n / 32 in
@@ -49,81 +50,11 @@ __device__ __forceinline__ float pvnet_group_sum(float v, int g) {
   return v;
 }
 
-template <int TR>
-struct PvnetTile {
-  static constexpr int MT = TR / 16, W = mlp_waves(TR), TPW = kMlpColumnTiles / W;
-  static constexpr int PASSES = HK_MLP_MAX_WIDTH / (W * kWave / 4), PER = HK_MLP_MAX_WIDTH / PASSES;
-  typedef mlp_f4 Acc[MT][TPW];
-};
-
-// acc = Dense(src): N outputs over K inputs, hk::mlp_kernel's k-loop.  Wv: the last of the N rows of the weight comes
-// from Wv (its bias from bv) and the N - 1 before it from W (the heads); NULL: all N from W.
-template <int TR>
-__device__ __forceinline__ void pvnet_dense(typename PvnetTile<TR>::Acc& acc, const float* src, float* wst, const float* W,
-                                            const float* bias, const float* Wv, const float* bv, int K, int N, int tid) {
-  typedef PvnetTile<TR> T;
-  const int lane = tid & (kWave - 1), wave = tid >> 6, lm = lane & 15, lg = lane >> 4;
-  const int Kp = (K + 15) & ~15, NT = (N + 15) >> 4, rows = NT * 16;
-  const int NW = Wv ? N - 1 : N;  // the rows W holds
-  const bool vec = (K & 3) == 0 && (reinterpret_cast<uintptr_t>(W) & 15u) == 0;
-#pragma unroll
-  for (int i = 0; i < T::TPW; ++i) {
-    const int j = (wave + T::W * i) * 16 + lm;
-    float b0 = bias && j < NW ? bias[j] : 0.0f;
-    if (Wv && bv && j == NW) b0 = bv[0];
-#pragma unroll
-    for (int mt = 0; mt < T::MT; ++mt) acc[mt][i] = mlp_f4{b0, b0, b0, b0};
-  }
-  mlp_f4 w[T::PASSES];
-  auto load = [&](int kc) {
-    mlp_load_w<T::PASSES>(w, W, K, NW, rows, kc, vec, tid);
-    if (Wv) {
-      const int k = kc + 4 * (tid & 3);
-#pragma unroll
-      for (int i = 0; i < T::PASSES; ++i)
-        if ((tid >> 2) + T::PER * i == NW) {
-          if (k + 0 < K) w[i].x = Wv[k + 0];
-          if (k + 1 < K) w[i].y = Wv[k + 1];
-          if (k + 2 < K) w[i].z = Wv[k + 2];
-          if (k + 3 < K) w[i].w = Wv[k + 3];
-        }
-    }
-  };
-  load(0);
-  for (int kc = 0; kc < Kp; kc += kMlpKc) {
-    __syncthreads();  // the stage is free (and, at kc == 0, the panel `src` is complete)
-#pragma unroll
-    for (int i = 0; i < T::PASSES; ++i)
-      if (T::PER * i < rows) {
-        float* s = wst + ((tid >> 2) + T::PER * i) * kMlpLdw + (tid & 3);
-        s[0] = w[i].x, s[4] = w[i].y, s[8] = w[i].z, s[12] = w[i].w;
-      }
-    __syncthreads();
-    if (kc + kMlpKc < Kp) load(kc + kMlpKc);
-    mlp_f4 a[T::MT];
-#pragma unroll
-    for (int mt = 0; mt < T::MT; ++mt)
-      a[mt] = *reinterpret_cast<const mlp_f4*>(src + (mt * 16 + lm) * kMlpLda + kc + 4 * lg);
-#pragma unroll
-    for (int i = 0; i < T::TPW; ++i) {
-      const int nt = wave + T::W * i;
-      if (nt < NT) {
-        const mlp_f4 b = *reinterpret_cast<const mlp_f4*>(wst + (nt * 16 + lm) * kMlpLdw + 4 * lg);
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int mt = 0; mt < T::MT; ++mt)
-            acc[mt][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mt][t], b[t], acc[mt][i], 0, 0, 0);
-      }
-    }
-  }
-}
-
 // acc = GN(acc) over the N columns (a normed width: every column of a tile below N / 16 is real)
 template <int TR>
-__device__ __forceinline__ void pvnet_group_norm(typename PvnetTile<TR>::Acc& acc, const hk_pvnet_dense& D, float eps, int N,
+__device__ __forceinline__ void pvnet_group_norm(typename MlpTile<TR>::Acc& acc, const hk_pvnet_dense& D, float eps, int N,
                                                  int tid) {
-  typedef PvnetTile<TR> T;
+  typedef MlpTile<TR> T;
   const int wave = tid >> 6, lm = tid & 15;
   const int g = N >> 5;
   const float rg = 1.0f / (float)g;  // a power of two: the product with it is the rule's quotient, to the bit
@@ -151,9 +82,9 @@ __device__ __forceinline__ void pvnet_group_norm(typename PvnetTile<TR>::Acc& ac
 // dst[row][pos(j)] = relu(acc) for the columns below N, +0 behind them up to the next multiple of 16 (the next layer's
 // padding); RESIDUAL: relu(o + acc) with o from `other` (a projection's result: `projected`) or from dst itself
 template <int TR, bool RESIDUAL>
-__device__ __forceinline__ void pvnet_store(const typename PvnetTile<TR>::Acc& acc, float* dst, int N, int tid,
-                                            const typename PvnetTile<TR>::Acc& other, bool projected) {
-  typedef PvnetTile<TR> T;
+__device__ __forceinline__ void pvnet_store(const typename MlpTile<TR>::Acc& acc, float* dst, int N, int tid,
+                                            const typename MlpTile<TR>::Acc& other, bool projected) {
+  typedef MlpTile<TR> T;
   const int lane = tid & (kWave - 1), wave = tid >> 6, lm = lane & 15, lg = lane >> 4;
   const int NT = (N + 15) >> 4;
 #pragma unroll
@@ -177,7 +108,7 @@ __device__ __forceinline__ void pvnet_store(const typename PvnetTile<TR>::Acc& a
 
 template <int TR>
 __global__ __launch_bounds__(kWave * mlp_waves(TR)) void pvnet_kernel(const hk_pvnet_desc q) {
-  typedef PvnetTile<TR> T;
+  typedef MlpTile<TR> T;
   extern __shared__ __align__(16) float hk_pvnet_lds[];
   float* cur = hk_pvnet_lds;
   float* nxt = cur + TR * kMlpLda;
@@ -186,26 +117,15 @@ __global__ __launch_bounds__(kWave * mlp_waves(TR)) void pvnet_kernel(const hk_p
   const int lm = lane & 15, lg = lane >> 4;
   const int64_t row0 = (int64_t)blockIdx.x * TR;
 
-  {  // the input rows: thread k of a row, zeros behind the width and below the batch
-    const int K = q.k0, Kp = (K + 15) & ~15;
-    const float* x = static_cast<const float*>(q.x);
-    if (tid < Kp) {
-      const int p = mlp_pos(tid);
-#pragma unroll 4
-      for (int r = 0; r < TR; ++r) {
-        const int64_t b = row0 + r;
-        cur[r * kMlpLda + p] = b < q.batch && tid < K ? x[b * q.x_stride + tid] : 0.0f;
-      }
-    }
-  }
+  auto f = [](const void* p) { return static_cast<const float*>(p); };
+  mlp_load_rows<TR, false>(cur, MlpInput{f(q.x), nullptr, q.x_stride, 0, q.k0}, row0, q.batch, tid);
 
   typename T::Acc acc;
   for (int l = 0; l < q.nblocks; ++l) {
     const hk_pvnet_block& B = q.block[l];
     const int K = B.k, N = B.n;
     if (B.kind == HK_PVNET_DENSE) {
-      pvnet_dense<TR>(acc, cur, wst, static_cast<const float*>(B.dense1.weight), static_cast<const float*>(B.dense1.bias),
-                      nullptr, nullptr, K, N, tid);
+      mlp_dense<TR, false>(acc, cur, wst, f(B.dense1.weight), f(B.dense1.bias), nullptr, nullptr, K, N, tid);
       pvnet_store<TR, false>(acc, nxt, N, tid, acc, false);
       float* const swap = cur;
       cur = nxt;
@@ -215,8 +135,7 @@ __global__ __launch_bounds__(kWave * mlp_waves(TR)) void pvnet_kernel(const hk_p
     const bool proj = K != N;
     typename T::Acc o;
     if (proj) {
-      pvnet_dense<TR>(o, cur, wst, static_cast<const float*>(B.proj.weight), static_cast<const float*>(B.proj.bias), nullptr,
-                      nullptr, K, N, tid);
+      mlp_dense<TR, false>(o, cur, wst, f(B.proj.weight), f(B.proj.bias), nullptr, nullptr, K, N, tid);
       pvnet_group_norm<TR>(o, B.proj, B.eps, N, tid);
     } else {
 #pragma unroll
@@ -224,20 +143,17 @@ __global__ __launch_bounds__(kWave * mlp_waves(TR)) void pvnet_kernel(const hk_p
 #pragma unroll
         for (int mt = 0; mt < T::MT; ++mt) o[mt][i] = mlp_f4{0.0f, 0.0f, 0.0f, 0.0f};
     }
-    pvnet_dense<TR>(acc, cur, wst, static_cast<const float*>(B.dense1.weight), static_cast<const float*>(B.dense1.bias),
-                    nullptr, nullptr, K, N, tid);
+    mlp_dense<TR, false>(acc, cur, wst, f(B.dense1.weight), f(B.dense1.bias), nullptr, nullptr, K, N, tid);
     pvnet_group_norm<TR>(acc, B.dense1, B.eps, N, tid);
     pvnet_store<TR, false>(acc, nxt, N, tid, acc, false);
-    pvnet_dense<TR>(acc, nxt, wst, static_cast<const float*>(B.dense2.weight), static_cast<const float*>(B.dense2.bias),
-                    nullptr, nullptr, N, N, tid);
+    mlp_dense<TR, false>(acc, nxt, wst, f(B.dense2.weight), f(B.dense2.bias), nullptr, nullptr, N, N, tid);
     pvnet_group_norm<TR>(acc, B.dense2, B.eps, N, tid);
     pvnet_store<TR, true>(acc, cur, N, tid, o, proj);
   }
 
   // the heads: columns 0 .. actions - 1 the policy, column `actions` the value
   const int K = q.block[q.nblocks - 1].n, A = q.actions, NT = (A + 16) >> 4;
-  pvnet_dense<TR>(acc, cur, wst, static_cast<const float*>(q.policy_weight), static_cast<const float*>(q.policy_bias),
-                  static_cast<const float*>(q.value_weight), static_cast<const float*>(q.value_bias), K, A + 1, tid);
+  mlp_dense<TR, true>(acc, cur, wst, f(q.policy_weight), f(q.policy_bias), f(q.value_weight), f(q.value_bias), K, A + 1, tid);
   float* policy = static_cast<float*>(q.policy);
   float* value = static_cast<float*>(q.value);
   const bool raw = q.flags & HK_PVNET_RAW_VALUE;

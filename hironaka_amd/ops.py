@@ -1700,6 +1700,43 @@ def _mlp_tensor(x, name: str, dev: Optional[torch.device], shape=None) -> Option
     return x.data_ptr()
 
 
+def _mlp_widths(weight, table: str, i: int, field: str, width: Optional[int]):
+    """(n, k) of the weight [n, k] of entry i of a plan's `table` ("layers" / "blocks"): k is the `width` the entry before
+    gives (None: the first entry), and both lie within the limit"""
+    if not isinstance(weight, torch.Tensor) or weight.dim() != 2:
+        raise TypeError(f"{table}[{i}].{field} must be a [n, k] tensor.")
+    n, k = weight.shape
+    if width is not None and k != width:
+        raise ValueError(f"{table}[{i}] takes {k} inputs but {table}[{i - 1}] gives {width}.")
+    if not (1 <= k <= A.HK_MLP_MAX_WIDTH and 1 <= n <= A.HK_MLP_MAX_WIDTH):
+        raise ValueError(f"{table}[{i}]: widths must lie in 1..{A.HK_MLP_MAX_WIDTH}. Got [{n}, {k}].")
+    return n, k
+
+
+def _mlp_tile_flag(tile: Optional[int]) -> int:
+    """the descriptor flag that forces the row tile `tile` (None: 0, the library picks)"""
+    if tile not in _MLP_TILES:
+        raise ValueError(f"tile must be None, {A.HK_MLP_TILE_SMALL} or {A.HK_MLP_TILE_LARGE}. Got {tile!r}.")
+    return _MLP_TILES[tile]
+
+
+def _mlp_batch_limit(batch: int) -> None:
+    if batch >= 2 ** 31:
+        raise ValueError(f"at most 2^31 - 1 rows per call. Got {batch}.")
+
+
+def _mlp_given_out(out: torch.Tensor, name: str, dev: torch.device, shape) -> None:
+    """an output tensor the caller gave: float32 on `dev`, of `shape` ([B, n] or [B]), the elements of a row adjacent and
+    the rows at least a row apart"""
+    _require_device(out, name)
+    if out.dtype != torch.float32 or out.device != dev:
+        raise TypeError(f"{name} must be a float32 tensor on {dev}. Got {out.dtype} on {out.device}.")
+    n = shape[1] if len(shape) > 1 else 1
+    if tuple(out.shape) != tuple(shape) or (n > 1 and out.stride(1) != 1) or (shape[0] > 1 and out.stride(0) < n):
+        raise ValueError(f"{name} must be {list(shape)} with adjacent elements in a row and rows that do not overlap. "
+                         f"Got shape {tuple(out.shape)}, strides {out.stride()}.")
+
+
 class _MlpTable:
     """What MlpPlan and MlpTrainPlan share: the walk over `layers` (entries of LAYER, or tuples in its order) that
     checks them and fills the layer table of a DESC, whose fields STATS take a batch norm's running statistics.  It
@@ -1717,13 +1754,7 @@ class _MlpTable:
         self.tensors = []
         width = None
         for i, l in enumerate(layers):
-            if not isinstance(l.weight, torch.Tensor) or l.weight.dim() != 2:
-                raise TypeError(f"layers[{i}].weight must be a [n, k] tensor.")
-            n, k = l.weight.shape
-            if width is not None and k != width:
-                raise ValueError(f"layers[{i}] takes {k} inputs but layers[{i - 1}] gives {width}.")
-            if not (1 <= k <= A.HK_MLP_MAX_WIDTH and 1 <= n <= A.HK_MLP_MAX_WIDTH):
-                raise ValueError(f"layers[{i}]: widths must lie in 1..{A.HK_MLP_MAX_WIDTH}. Got [{n}, {k}].")
+            n, k = _mlp_widths(l.weight, "layers", i, "weight", width)
             bn = l.bn_mean is not None
             # (bn_weight, bn_bias and, where LAYER has one, num_batches_tracked belong to a batch norm)
             if bn != (l.bn_var is not None) or (not bn and any(t is not None for t in l[4:6] + l[9:])):
@@ -1811,29 +1842,21 @@ def mlp_forward(x0: torch.Tensor, layers, x1: Optional[torch.Tensor] = None, inp
     number of elements >= n apart); None: a new one.  tile: None, or the row tile (16 / 64) to force -- same bits.
     Everything is float32 on one HIP device (a TypeError otherwise).  Nothing here synchronises."""
     plan = layers if isinstance(layers, MlpPlan) else MlpPlan(layers, input_relu, input_bn)
-    if tile not in _MLP_TILES:
-        raise ValueError(f"tile must be None, {A.HK_MLP_TILE_SMALL} or {A.HK_MLP_TILE_LARGE}. Got {tile!r}.")
+    tile_flag = _mlp_tile_flag(tile)
     dev = plan.device
     x0, x1 = _mlp_inputs(plan, x0, x1)
     batch = x0.shape[0]
-    if batch >= 2 ** 31:
-        raise ValueError(f"at most 2^31 - 1 rows per call. Got {batch}.")
+    _mlp_batch_limit(batch)
     if out is None:
         out = torch.empty((batch, plan.n_out), dtype=torch.float32, device=dev)
     else:
-        _require_device(out, "out")
-        if out.dtype != torch.float32 or out.device != dev:
-            raise TypeError(f"out must be a float32 tensor on {dev}. Got {out.dtype} on {out.device}.")
-        if tuple(out.shape) != (batch, plan.n_out) or (plan.n_out > 1 and out.stride(1) != 1) or (
-                batch > 1 and out.stride(0) < plan.n_out):
-            raise ValueError(f"out must be [{batch}, {plan.n_out}] with adjacent elements in a row and rows that do "
-                             f"not overlap. Got shape {tuple(out.shape)}, strides {out.stride()}.")
+        _mlp_given_out(out, "out", dev, (batch, plan.n_out))
     if batch == 0:
         return out
     d = plan.desc
     _mlp_fill_inputs(d, x0, x1)
     d.out, d.out_stride = out.data_ptr(), out.stride(0) if batch > 1 else plan.n_out
-    d.flags = (d.flags & A.HK_MLP_INPUT_RELU) | _MLP_TILES[tile]
+    d.flags = (d.flags & A.HK_MLP_INPUT_RELU) | tile_flag
     with torch.cuda.device(dev):
         check(lib().hk_mlp_forward(C.byref(d), _stream(out)), "hk_mlp_forward")
     return out
@@ -1881,14 +1904,7 @@ class PvnetPlan:
         for i, b in enumerate(blocks):
             if b.kind not in _PVNET_KINDS:
                 raise ValueError(f'blocks[{i}].kind must be "dense" or "residue". Got {b.kind!r}.')
-            w = PvnetDense(*b.dense1).weight
-            if not isinstance(w, torch.Tensor) or w.dim() != 2:
-                raise TypeError(f"blocks[{i}].dense1.weight must be a [n, k] tensor.")
-            n, k = w.shape
-            if width is not None and k != width:
-                raise ValueError(f"blocks[{i}] takes {k} inputs but blocks[{i - 1}] gives {width}.")
-            if not (1 <= k <= A.HK_PVNET_MAX_WIDTH and 1 <= n <= A.HK_PVNET_MAX_WIDTH):
-                raise ValueError(f"blocks[{i}]: widths must lie in 1..{A.HK_PVNET_MAX_WIDTH}. Got [{n}, {k}].")
+            n, k = _mlp_widths(PvnetDense(*b.dense1).weight, "blocks", i, "dense1.weight", width)
             width = n
             e = d.block[i]
             e.k, e.n, e.kind, e.eps = k, n, _PVNET_KINDS[b.kind], float(b.eps)
@@ -1925,27 +1941,17 @@ def pvnet_forward(x: torch.Tensor, plan: PvnetPlan, tile: Optional[int] = None, 
     otherwise).  Nothing here synchronises."""
     if not isinstance(plan, PvnetPlan):
         raise TypeError(f"plan must be a PvnetPlan. Got {type(plan).__name__}.")
-    if tile not in _MLP_TILES:
-        raise ValueError(f"tile must be None, {A.HK_MLP_TILE_SMALL} or {A.HK_MLP_TILE_LARGE}. Got {tile!r}.")
+    tile_flag = _mlp_tile_flag(tile)
     dev = plan.device
     x = _mlp_rows(x, "x", dev)
     batch, k0 = x.shape
     if k0 != plan.k_in:
         raise ValueError(f"the first block takes {plan.k_in} inputs. Got {k0}.")
-    if batch >= 2 ** 31:
-        raise ValueError(f"at most 2^31 - 1 rows per call. Got {batch}.")
+    _mlp_batch_limit(batch)
     a = plan.actions
     for name, out, shape in (("policy", policy, (batch, a)), ("value", value, (batch,))):
-        if out is None:
-            continue
-        _require_device(out, name)
-        if out.dtype != torch.float32 or out.device != dev:
-            raise TypeError(f"{name} must be a float32 tensor on {dev}. Got {out.dtype} on {out.device}.")
-        rows_apart = a if name == "policy" else 1
-        if tuple(out.shape) != shape or (batch > 1 and out.stride(0) < rows_apart) or (
-                name == "policy" and a > 1 and out.stride(1) != 1):
-            raise ValueError(f"{name} must be {list(shape)} with adjacent elements in a row and rows that do not "
-                             f"overlap. Got shape {tuple(out.shape)}, strides {out.stride()}.")
+        if out is not None:
+            _mlp_given_out(out, name, dev, shape)
     if policy is None:
         policy = torch.empty((batch, a), dtype=torch.float32, device=dev)
     if value is None:
@@ -1956,7 +1962,7 @@ def pvnet_forward(x: torch.Tensor, plan: PvnetPlan, tile: Optional[int] = None, 
     d.x, d.x_stride, d.k0, d.batch = x.data_ptr(), x.stride(0) if batch > 1 else k0, k0, batch
     d.policy, d.policy_stride = policy.data_ptr(), policy.stride(0) if batch > 1 else a
     d.value, d.value_stride = value.data_ptr(), value.stride(0) if batch > 1 else 1
-    d.flags = _MLP_TILES[tile] | (A.HK_PVNET_RAW_VALUE if raw_value else 0)
+    d.flags = tile_flag | (A.HK_PVNET_RAW_VALUE if raw_value else 0)
     with torch.cuda.device(dev):
         check(lib().hk_pvnet_forward(C.byref(d), _stream(policy)), "hk_pvnet_forward")
     return policy, value

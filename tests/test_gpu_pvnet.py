@@ -93,6 +93,30 @@ def test_policy_widths():
 
 
 @pytest.mark.parametrize("tile", TILES[1:])
+def test_a_dense_trunk_is_mlp_forward(tile):
+    """a trunk of dense blocks is `Linear -> ReLU` per block and the two heads are one Linear of actions + 1 columns, so
+    pvnet_forward (raw value) and mlp_forward, with the policy and value weights stacked as its last layer, run the one
+    Dense loop with and without the value row and must give the same bits: column j < A the policy, column A the value.
+    Batches one row past a tile; k0 = 15 (weights float by float, a padded chunk) and 60 (16-byte loads, no multiple of
+    16); a width that pads and two layers; the value row inside the first column tile (3 actions), as its last column
+    (15) and alone in a second one (16)."""
+    ops = _ops()
+    rng = np.random.default_rng(20261020)
+    for batch, k0, arch, actions in itertools.product((17, 65), (15, 60), ([33], [32, 48]), (3, 15, 16)):
+        net = R.random_net(rng, k0, arch, actions, "dense")
+        x = dev(inputs(rng, batch, k0))
+        layers = [ops.MlpLayer(dev(b.dense1.weight), dev(b.dense1.bias), relu=True) for b in net.blocks]
+        layers.append(ops.MlpLayer(dev(np.concatenate([net.policy[0], net.value[0]])),
+                                   dev(np.concatenate([net.policy[1], net.value[1]]))))
+        p, v = ops.pvnet_forward(x, device_plan(net), tile=tile, raw_value=True)
+        out = ops.mlp_forward(x, layers, tile=tile).cpu().numpy()
+        assert out.shape == (batch, actions + 1) and np.abs(out).max(axis=0).min() > 0
+        where = (batch, k0, arch, actions)
+        assert same_bits(p.cpu().numpy(), out[:, :actions]), (where, "policy")
+        assert same_bits(v.cpu().numpy(), out[:, actions]), (where, "value")
+
+
+@pytest.mark.parametrize("tile", TILES[1:])
 def test_every_batch_around_the_tiles(tile):
     rng = np.random.default_rng(23)
     net = R.random_net(rng, 37, [64, 17], 5, ["residue", "dense"])
