@@ -229,9 +229,24 @@ __device__ inline void duo_store_slab(const float* lds, float* out, int64_t out_
 #endif
 }
 
-struct DuoLadder {  // slots per lane: 1..6, 8, 10, ...
-  static constexpr int next_bucket(int nb) { return nb < 6 ? nb + 1 : nb + 2; }
+// The parts of the step loops themselves, one bit each as HK_DUO_LEGS above (-DHK_DUO_STEPS=<mask>; scripts/build_probe.sh
+// passes it on; profiles/duo_levels_ab.txt holds their alternations): 1 a level of seven slots per lane in the plain
+// rollouts' staircase (DuoLadderT), 2 the domination test's verdicts as sign bits of a word per row on the narrow levels
+// (d_newton_signs).
+#ifndef HK_DUO_STEPS
+#define HK_DUO_STEPS 3
+#endif
+constexpr bool kDuoStepSeven = (HK_DUO_STEPS & 1) != 0, kDuoStepSigns = (HK_DUO_STEPS & 2) != 0;
+
+// slots per lane: 1..6, 8, 10, ...; SEVEN: 1..8, 10, ... -- a wave whose widest game has 13 or 14 rows plays its first
+// steps on 49 pair tests per lane, not 64.  The plain rollouts of ten slots per lane take the seven (duo_kernel: Ladder);
+// single steps, recording rollouts and Zeillinger's host (kDuoZeilDpp: its unrolled pair loop ends at six slots) keep the
+// ladder they had.
+template <bool SEVEN>
+struct DuoLadderT {
+  static constexpr int next_bucket(int nb) { return nb < (SEVEN ? 8 : 6) ? nb + 1 : nb + 2; }
 };
+using DuoLadder = DuoLadderT<false>;
 
 // ---- image <-> registers ----------------------------------------------------------------------------------
 // the set bits of `mask` in ascending order are the game's live rows; lane h takes the ranks h, h + 2, ...
@@ -280,13 +295,13 @@ __device__ __forceinline__ void duo_gather_level(float (&q)[CH * D], const float
   for (int e = NB * D; e < SB * D; ++e) q[e] = INFINITY;
 }
 
-// slots [0, smax) from the image.  LEVELS: the body is the smallest DuoLadder level that covers smax (wave-uniform), SB
+// slots [0, smax) from the image.  LEVELS: the body is the smallest LADDER level that covers smax (wave-uniform), SB
 // at most, and every slot up to SB is written; else slot by slot.
-template <int M, int CH, int D, bool LEVELS, int SB = CH>
+template <int M, int CH, int D, bool LEVELS, typename LADDER = DuoLadder, int SB = CH>
 __device__ __forceinline__ void duo_gather(float (&q)[CH * D], const float* mine, const float* hole, uint32_t mask,
                                            int smax, int h) {
   if constexpr (LEVELS) {
-    StagesFor<DuoLadder, SB>::run(smax, [&](auto nb) {
+    StagesFor<LADDER, SB>::run(smax, [&](auto nb) {
       duo_gather_level<CH, D, decltype(nb)::value, SB>(q, mine, hole, mask, h);
       return 0;
     });
@@ -448,8 +463,82 @@ __device__ __forceinline__ void duo_length_counts(uint32_t* hist, uint32_t* slot
 //   mine earlier:  other removed iff t <= 0;            mine removed iff u >= 0 and t > 0
 //   other earlier: other removed iff t <= 0 and u < 0;  mine removed iff u >= 0
 // acc[] <= 0 marks my row removed; oth[] <= 0 marks the partner's slot removed (sent back at the end).
+//
+// The verdicts as sign bits (kDuoStepSigns).  On this path a coordinate is a bit pattern in [+0, +inf] (the exactness
+// guard admits no sign bit; sums, x - min and quotients of such values keep it clear), so a difference is never -0 and
+// t >= u.  With T = bits(t) - 1 and U = bits(u), as integers:
+//   t <= 0           iff  T < 0   (+0 wraps to -1; a negative t keeps its sign bit: its magnitude is not zero)
+//   u >= 0 and t > 0 iff  U >= 0 and T >= 0   (u >= 0 gives t >= 0, and then t > 0 iff its bits are not zero)
+//   u < 0            iff  U < 0
+// so "the later row removed" is the sign of T, "the earlier row removed" the sign of ~(U | T), and a row's verdicts meet
+// by OR in ONE word per row: an add and two three-input bit operations per pair, where the float form was a compare, a
+// select and two minima.  Equal rows (t = u = +0: T = -1) remove the later one alone, as before.  A hole against a live
+// row gives t = u = -inf or +inf, signs as for any other value; which verdict a hole itself gets -- against a live row, or
+// against another hole, where t and u are NaN -- does not matter: removing it writes +inf over +inf.
+// The form costs two registers.  The plain rollouts without records of the lean shapes of eight slots per lane and more
+// take it (duo_kernel: kSigns): the (8,4) headline instantiation would lose its seventh wave per SIMD (71 -> 73 VGPRs),
+// (20,4) its third (168 -> 170), and so would the (20,3) run-time instantiation with the small records (168 -> 170).
+constexpr int kDuoSignsMinSlots = 8;
+// Levels of up to four slots per lane take it -- the levels every wave plays, and the one-slot level most of all.  On the
+// wide levels the pinned accumulators (below) order the pair tests more strictly than the float minima did, and the form
+// loses: at (20,3) on every level 15.10 us per launch against 14.76 on levels 1..6 and 14.48 on 1..4, the level of seven
+// alone 16.38 against 14.61 (profiles/duo_levels_ab.txt).
+constexpr int kDuoSignsMaxLevel = 4;
 template <int CH, int D, int NB>
+__device__ __forceinline__ void d_newton_signs(float (&q)[CH * D], int h) {
+  uint32_t acc[NB], oth[NB];  // sign bit set: my row / the partner's slot is removed
+#pragma unroll
+  for (int i = 0; i + 1 < NB; ++i) {
+#pragma unroll
+    for (int j = i + 1; j < NB; ++j) {
+      float t, u;
+      diff_extrema<D>(&q[i * D], &q[j * D], t, u);
+      const uint32_t T = __float_as_uint(t) - 1u, U = __float_as_uint(u);
+      acc[j] = (i == 0) ? T : (acc[j] | T);
+      acc[i] = (i == 0 && j == 1) ? ~(U | T) : (acc[i] | ~(U | T));
+      // (pinned pair by pair: integer ORs, unlike the float minima, may be regrouped across the scheduling barriers, and
+      // the regrouped form kept a row of verdicts alive per accumulator -- 24 to 70 registers more, a wave per SIMD or two)
+      asm volatile("" : "+v"(acc[i]), "+v"(acc[j]));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  const uint32_t late = 0u - (uint32_t)h;  // all ones: on the diagonal the partner's row is the earlier one
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    float o[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) o[k] = duo_other(q[b * D + k]);
+    {  // diagonal
+      float t, u;
+      diff_extrema<D>(&q[b * D], o, t, u);
+      const uint32_t T = __float_as_uint(t) - 1u, U = __float_as_uint(u);
+      const uint32_t va = ~U & (~T | late);  // mine: u >= 0 and (t > 0 or late)
+      acc[b] = (NB == 1) ? va : (acc[b] | va);
+      oth[b] = T & (U | ~late);              // the partner's: t <= 0 and (u < 0 or not late)
+    }
+#pragma unroll
+    for (int a = 0; a < b; ++a) {
+      float t, u;
+      diff_extrema<D>(&q[a * D], o, t, u);
+      const uint32_t T = __float_as_uint(t) - 1u, U = __float_as_uint(u);
+      oth[b] |= T;
+      acc[a] |= ~(U | T);
+      asm volatile("" : "+v"(oth[b]), "+v"(acc[a]));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int r = 0; r < NB; ++r) {
+    const bool removed = (int32_t)(acc[r] | (uint32_t)duo_other_i((int)oth[r])) < 0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) q[r * D + k] = removed ? INFINITY : q[r * D + k];
+  }
+}
+
+// SIGNS: the rows are those of a rollout (see d_newton_signs; a single step takes any real weights from its caller)
+template <int CH, int D, int NB, bool SIGNS = false>
 __device__ __forceinline__ void d_newton(float (&q)[CH * D], int h) {
+  if constexpr (SIGNS && kDuoStepSigns && NB <= kDuoSignsMaxLevel) return d_newton_signs<CH, D, NB>(q, h);
   // (the accumulators take their FIRST contribution by assignment -- which one that is, is known at compile time --
   // instead of starting at +inf: min(+inf, x) was an instruction per slot, two with the canonicalising v_max)
   float acc[NB], oth[NB];
@@ -527,18 +616,19 @@ __device__ __forceinline__ void d_shift_words(float (&q)[CH * D], uint32_t cmask
 }
 
 // one transition on slots [0, NB) of both lanes; returns the GAME's number of live rows
-// (WORDS: the shift of a 0/1 subset as d_shift_words)
-template <int CH, int D, int NB, bool BIN = false, bool WORDS = false>
+// (WORDS: the shift of a 0/1 subset as d_shift_words; SIGNS: the domination test as d_newton_signs)
+template <int CH, int D, int NB, bool BIN = false, bool WORDS = false, bool SIGNS = false>
 __device__ __forceinline__ int d_stages(float (&q)[CH * D], const float (&c)[D], int axis, int np, int h,
                                         unsigned flags, unsigned stages, uint32_t cmask = 0) {
   static_assert(!WORDS || BIN, "the subset as bits");
+  static_assert(!SIGNS || BIN, "the rows of a rollout");
   if (stages & HK_STAGE_SHIFT) {
     if constexpr (WORDS) d_shift_words<CH, D, NB>(q, cmask, axis, np, flags);
     else if constexpr (BIN) b_shift_mask<CH, D, NB>(q, cmask, axis, np, flags);
     else b_shift<CH, D, NB>(q, c, axis, np, flags);
   }
   if (stages & HK_STAGE_REPOSITION) reposition<2, CH, D, NB, BIN>(q, flags);
-  if (stages & HK_STAGE_NEWTON) d_newton<CH, D, NB>(q, h);
+  if (stages & HK_STAGE_NEWTON) d_newton<CH, D, NB, SIGNS>(q, h);
   if (stages & HK_STAGE_RESCALE) rescale<2, CH, D, NB>(q, flags);
   return live_rows<2, CH, D, NB>(q);
 }
@@ -797,6 +887,12 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
   // the rows that changed.  Not Zeillinger's host for the publish: it parks rows by rank in the image between two deals.
   constexpr bool kPartialPublish = MODE == kModeRollout && !ZEIL && DuoGeom<M, D>::kLean;
   constexpr bool kLevelDeal = MODE == kModeRollout && DuoGeom<M, D>::kLean;
+  // the staircase's ladder (and the level deal's, which enters it): plain rollouts of ten slots per lane have a level of
+  // seven.  Not (16,3), eight slots: with the sign-bit verdicts beside it its headline instantiation went from 85 to 111
+  // VGPRs and from five waves per SIMD to four (either part alone: 85 and 78).
+  constexpr bool kSigns = kDuoStepSigns && MODE == kModeRollout && !ACTS && DuoGeom<M, D>::kLean &&
+                          DuoGeom<M, D>::CH >= kDuoSignsMinSlots;  // (d_newton_signs)
+  using Ladder = DuoLadderT<kDuoStepSeven && MODE == kModeRollout && !ZEIL && DuoGeom<M, D>::CH >= 10>;
   using G = FastGeom<M, D>;
   constexpr int CH = DuoGeom<M, D>::CH;
   static_assert(M <= 32, "the live mask of a game travels as 32 bits");
@@ -996,7 +1092,7 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
 #pragma unroll
     for (int e = 0; e < CH * D; ++e) q[e] = INFINITY;
   }
-  duo_gather<M, CH, D, kLevelDeal>(q, mine, hole_row, gmask, smax, h);
+  duo_gather<M, CH, D, kLevelDeal, Ladder>(q, mine, hole_row, gmask, smax, h);
 #ifdef HK_DUO_PROBE
   {
     float sink = 0.0f;
@@ -1067,7 +1163,7 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
     // never grows, so the wave walks down the stairs once; each loop is straight-line for its own bucket -- no
     // per-step dispatch over the buckets, and only the slots the bucket covers are loop-carried registers (a single
     // loop over all buckets moves the whole row array at every back edge: 16 v_mov_b64 per step at (20,3)). -------
-    static_assert(CH <= 6 || CH % 2 == 0, "bucket ladder: 1..6, then even numbers");
+    static_assert(CH <= 6 || CH % 2 == 0, "bucket ladder: 1..6 or 1..8, then even numbers");
     // The wave's votes are scalar: a ballot, ANDed with the mask of the lanes that speak for a game (both lanes of a
     // pair: `amask`; its first lane: `lmask`), and a branch on the AND's own condition code.
     uint64_t amask = duo_ballot(active), lmask = duo_ballot(leader);
@@ -1098,7 +1194,7 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
     // the action byte of step t, requested one step ahead: the LDS round trip (it opened every step: ds_read, wait)
     // runs behind the previous step's arithmetic
     uint32_t a_next = ZEIL ? 0u : pol[(int)(step0 + (uint32_t)t - (pol_b0 << 2)) * kDuoGames + gi];
-    Levels<DuoLadder, CH>::run([&](auto nbc, auto loc) {
+    Levels<Ladder, CH>::run([&](auto nbc, auto loc) {
       constexpr int NB = decltype(nbc)::value, LO = decltype(loc)::value;
       if (!((smax > LO || LO == 0) && t < tw && !stop)) return;  // (a wave of empty games has smax 0: the last loop's)
 #ifndef HK_NO_SETPRIO
@@ -1133,7 +1229,7 @@ __global__ __launch_bounds__(kWave, 2) void duo_kernel(const float* in0, int64_t
           }
           const unsigned st = (end_sort && t + 1 == nsteps) ? (stages & ~(unsigned)HK_STAGE_RESCALE) : stages;
           rescale_pending = end_sort && t + 1 == nsteps && (stages & HK_STAGE_RESCALE);
-          const int np_new = d_stages<CH, D, NB, true, (NB == 1)>(q, c, axis, np, h, flags, st, mask);
+          const int np_new = d_stages<CH, D, NB, true, (NB == 1), kSigns>(q, c, axis, np, h, flags, st, mask);
 #ifdef HK_DUO_PROBE
           if (lane == 0 && t == 0) probe_buf[20] = (int32_t)wall_clock64();  // step 0: the stages are done
 #endif

@@ -19,8 +19,9 @@ done
 wait
 # the two-lane kernel's time-line probe (HK_DUO_PROBE: per-wave time stamps in a buffer of its own) at (20,3)
 # (HK_DUO_LEGS=<mask> in the environment: the parts around the step loops to build, hk_duo_kernel.h; default all.
-# HK_DUO_PRE_BLOCKS=<blocks>, HK_DUO_FILL_CHAINS=<2|3>: the action window's size and the Philox chains per lane)
-/opt/rocm/bin/hipcc ${FLAGS/-DHK_QUAD_PROBE/-DHK_DUO_PROBE} ${HK_DUO_LEGS:+-DHK_DUO_LEGS=$HK_DUO_LEGS} ${HK_DUO_PRE_BLOCKS:+-DHK_DUO_PRE_BLOCKS=$HK_DUO_PRE_BLOCKS} ${HK_DUO_FILL_CHAINS:+-DHK_DUO_FILL_CHAINS=$HK_DUO_FILL_CHAINS} -DHK_SPEC_M=20 -DHK_SPEC_D=3 -c $C/hk_duo_spec.hip -o build_probe/duo_20_3.o
+# HK_DUO_PRE_BLOCKS=<blocks>, HK_DUO_FILL_CHAINS=<2|3>: the action window's size and the Philox chains per lane;
+# HK_DUO_STEPS=<mask>: the parts of the step loops themselves, 0 is the time line "before")
+/opt/rocm/bin/hipcc ${FLAGS/-DHK_QUAD_PROBE/-DHK_DUO_PROBE} ${HK_DUO_LEGS:+-DHK_DUO_LEGS=$HK_DUO_LEGS} ${HK_DUO_STEPS:+-DHK_DUO_STEPS=$HK_DUO_STEPS} ${HK_DUO_PRE_BLOCKS:+-DHK_DUO_PRE_BLOCKS=$HK_DUO_PRE_BLOCKS} ${HK_DUO_FILL_CHAINS:+-DHK_DUO_FILL_CHAINS=$HK_DUO_FILL_CHAINS} -DHK_SPEC_M=20 -DHK_SPEC_D=3 -c $C/hk_duo_spec.hip -o build_probe/duo_20_3.o
 OTHERS=$(ls $C/build/*.o | grep -v "/quad_" | grep -v duo_20_3)
 OBJS="$OBJS build_probe/duo_20_3.o"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OTHERS $OBJS -o build_probe/libhk_probe.so
