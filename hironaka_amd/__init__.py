@@ -3,10 +3,11 @@ __version__ = "0.1.0"
 
 _VEC_ENVS = ("HironakaHostVecEnv", "HironakaAgentVecEnv")
 _DQN = ("fit_network", "td_loss", "td_target", "update_target_net", "polyak_update", "zip_equal")
-_OPTIM = ("Adam", "SGD", "clip_grad_norm_", "from_torch")
+_OPTIM = ("Adam", "AdamW", "SGD", "clip_grad_norm_", "safe_clip_grads_", "from_torch")
+_LOSS = ("policy_value_loss", "compute_loss", "clip_log")
 _NETS = ("create_mlp", "expand_net_list", "FusedSequential", "fuse", "BaseFeaturesExtractor", "HostFeatureExtractor",
          "AgentFeatureExtractor")
-__all__ = list(_VEC_ENVS) + ["ReplayBuffer"] + list(_DQN) + list(_OPTIM) + list(_NETS)
+__all__ = list(_VEC_ENVS) + ["ReplayBuffer"] + list(_DQN) + list(_OPTIM) + list(_LOSS) + list(_NETS)
 
 
 def __getattr__(name):
@@ -23,6 +24,9 @@ def __getattr__(name):
     if name in _OPTIM:
         from . import optim
         return getattr(optim, name)
+    if name in _LOSS:
+        from . import loss
+        return getattr(loss, name)
     if name in _NETS:
         from . import nets
         return getattr(nets, name)

@@ -110,6 +110,8 @@ HK_MLP_TRAIN_BN = 2
 HK_PVNET_MAX_BLOCKS, HK_PVNET_MAX_WIDTH = 32, 256
 HK_PVNET_DENSE, HK_PVNET_RESIDUE = 0, 1
 HK_PVNET_RAW_VALUE, HK_PVNET_FORCE_TILE_SMALL, HK_PVNET_FORCE_TILE_LARGE = 1, 2, 4
+# hk_pv_loss: rows per workgroup, the action limit (the policy head's), the bit of the status word
+HK_PVLOSS_TILE_ROWS, HK_PVLOSS_MAX_ACTIONS, HK_PVLOSS_BAD_INDEX = 16, 255, 1
 PVNET_NORMED_WIDTHS = (32, 64, 128, 256)  # the widths of a normed layer the kernel serves (1, 2, 4, 8 columns per group)
 
 SEMANTICS = {"jax": HK_SEM_JAX, "torch": HK_SEM_TORCH, "list": HK_SEM_LIST}
@@ -357,6 +359,33 @@ class hk_dqn_td_desc(C.Structure):
         ("num_actions", C.c_int32),
         ("dtype", C.c_int32),
         ("reserved_", C.c_int32),
+    ]
+
+
+class hk_pv_loss_desc(C.Structure):
+    _fields_ = [
+        ("logits", C.c_void_p),
+        ("value", C.c_void_p),
+        ("target_policy", C.c_void_p),
+        ("target_value", C.c_void_p),
+        ("weight", C.c_void_p),
+        ("index", C.c_void_p),
+        ("dlogits", C.c_void_p),
+        ("dvalue", C.c_void_p),
+        ("row_loss", C.c_void_p),
+        ("loss", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("status", C.c_void_p),
+        ("logits_stride", C.c_int64),
+        ("value_stride", C.c_int64),
+        ("target_policy_stride", C.c_int64),
+        ("dlogits_stride", C.c_int64),
+        ("dvalue_stride", C.c_int64),
+        ("num_samples", C.c_int64),
+        ("batch", C.c_int32),
+        ("actions", C.c_int32),
+        ("dtype", C.c_int32),
+        ("flags", C.c_int32),
     ]
 
 
@@ -653,14 +682,21 @@ PVNET_PROTOTYPES = {
     "hk_pvnet_forward": (C.c_int, [C.POINTER(hk_pvnet_desc), _vp]),
 }
 
+# the entry points of include/hironaka_hip_pvloss.h: the device library's only, as above
+PVLOSS_PROTOTYPES = {
+    "hk_pv_loss_workspace_bytes": (C.c_uint64, [_i]),
+    "hk_pv_loss": (C.c_int, [C.POINTER(hk_pv_loss_desc), _vp]),
+}
+
 
 def bind(lib: C.CDLL, prototypes=None) -> None:
     """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES, TREE_PROTOTYPES, ENV_PROTOTYPES,
-    REPLAY_PROTOTYPES, DQN_PROTOTYPES, OPTIM_PROTOTYPES, MLP_PROTOTYPES, MLP_TRAIN_PROTOTYPES and PVNET_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
+    REPLAY_PROTOTYPES, DQN_PROTOTYPES, OPTIM_PROTOTYPES, MLP_PROTOTYPES, MLP_TRAIN_PROTOTYPES, PVNET_PROTOTYPES and
+    PVLOSS_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
     if prototypes is None:
         prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES, **TREE_PROTOTYPES, **ENV_PROTOTYPES,
                       **REPLAY_PROTOTYPES, **DQN_PROTOTYPES, **OPTIM_PROTOTYPES, **MLP_PROTOTYPES,
-                      **MLP_TRAIN_PROTOTYPES, **PVNET_PROTOTYPES}
+                      **MLP_TRAIN_PROTOTYPES, **PVNET_PROTOTYPES, **PVLOSS_PROTOTYPES}
     for name, (res, args) in prototypes.items():
         fn = getattr(lib, name)
         fn.restype = res

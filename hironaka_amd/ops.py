@@ -1387,6 +1387,138 @@ def polyak_update(srcs: Sequence[torch.Tensor], dsts: Sequence[torch.Tensor], ta
             check(lib().hk_polyak_update(C.byref(d), stream), "hk_polyak_update")
 
 
+# ---- the MCTS trainer's loss: policy_value_loss with its gradient, the sampled target rows gathered, in one launch ----
+
+PVLOSS_TILE_ROWS = A.HK_PVLOSS_TILE_ROWS
+PvLossResult = collections.namedtuple("PvLossResult", "loss dlogits dvalue row_loss status")
+_PVLOSS_WORKSPACES = _WorkspaceCache(1 << 12)  # of pv_loss calls that bring no workspace
+
+
+def pv_loss_workspace(batch: int, device) -> torch.Tensor:
+    """a zeroed workspace of the caller's own for pv_loss launches of up to `batch` rows (uint8; the ticket and one slot
+    per workgroup).  Launches that share one belong on one stream."""
+    need = int(lib().hk_pv_loss_workspace_bytes(int(batch)))
+    if need == 0:
+        raise ValueError(f"batch must be in [0, 2^31). Got {batch}.")
+    return torch.zeros(need, dtype=torch.uint8, device=device)
+
+
+def _pvloss_rows(t: torch.Tensor, name: str, dev=None) -> torch.Tensor:
+    """a [rows, A] float32 block whose rows are contiguous (the rows themselves may be strided)"""
+    _require_device(t, name)
+    if t.dim() != 2 or t.dtype != torch.float32 or (dev is not None and t.device != dev):
+        raise TypeError(f"{name} must be a [rows, A] float32 tensor{f' on {dev}' if dev is not None else ''}. Got "
+                        f"{t.dtype} {tuple(t.shape)} on {t.device}.")
+    ok = (t.shape[1] == 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])
+    return t if ok else t.contiguous()
+
+
+def _pvloss_column(t: torch.Tensor, name: str, rows: int, dev, dtype=torch.float32, strided: bool = False):
+    """[rows] or [rows, 1] of `dtype` on `dev` as a 1-d view; contiguous unless `strided` (then: a positive stride)"""
+    _require_device(t, name)
+    if t.dtype != dtype or t.device != dev or t.dim() not in (1, 2) or t.numel() != rows or t.shape[0] != rows:
+        raise TypeError(f"{name} must be [{rows}] or [{rows}, 1] {dtype} on {dev}. Got {t.dtype} {tuple(t.shape)} on "
+                        f"{t.device}.")
+    t = t[:, 0] if t.dim() == 2 else t
+    if rows > 1 and (t.stride(0) < 1 or (not strided and t.stride(0) != 1)):
+        t = t.contiguous()
+    return t
+
+
+def pv_loss(logits: torch.Tensor, value: torch.Tensor, target_policy: torch.Tensor, target_value: torch.Tensor,
+            weight: Optional[torch.Tensor] = None, index: Optional[torch.Tensor] = None, *,
+            workspace: Optional[torch.Tensor] = None, out: Optional[dict] = None,
+            want: Sequence[str] = ("row_loss",)) -> PvLossResult:
+    """policy_value_loss (hironaka/jax/loss.py:12-24) and its gradient with respect to logits and value in one launch
+    (hk_pv_loss; the rule is in include/hironaka_hip_pvloss.h).
+
+    logits [B, A] and value [B] or [B, 1]: float32, the network's outputs, rows possibly strided.  target_policy [N, A],
+    target_value [N] and weight [N] (or None: 1): float32, the N samples; index [B] int64 (or None: N == B, row b takes
+    sample b) says which sample a row takes.  Returns PvLossResult(loss [], dlogits [B, A], dvalue of value's shape,
+    row_loss [B] or None, status int32 [1]): `want` names the optional output, `out` may bring tensors for any of "loss",
+    "dlogits", "dvalue", "row_loss", "status" (a status brought along is OR-ed into, not cleared).  An index outside
+    [0, N) gives a zero row and sets HK_PVLOSS_BAD_INDEX in status.  workspace: pv_loss_workspace(...) of the caller's
+    own; None: one per device and stream.  Nothing here synchronises."""
+    logits = _pvloss_rows(logits, "logits")
+    dev = logits.device
+    batch, nact = logits.shape
+    target_policy = _pvloss_rows(target_policy, "target_policy", dev)
+    samples = target_policy.shape[0]
+    if not (1 <= nact <= A.HK_PVLOSS_MAX_ACTIONS and batch < 2 ** 31) or target_policy.shape[1] != nact:
+        raise ValueError(f"A must be in [1, {A.HK_PVLOSS_MAX_ACTIONS}], the same for logits and target_policy, and B "
+                         f"below 2^31. Got logits {tuple(logits.shape)}, target_policy {tuple(target_policy.shape)}.")
+    value_shape = tuple(value.shape)
+    value = _pvloss_column(value, "value", batch, dev, strided=True)
+    target_value = _pvloss_column(target_value, "target_value", samples, dev)
+    if weight is not None:
+        weight = _pvloss_column(weight, "weight", samples, dev)
+    if index is not None:
+        index = _pvloss_column(index, "index", batch, dev, dtype=torch.int64)
+    elif samples != batch:
+        raise ValueError(f"without an index the targets have one row per batch row. Got {samples} samples, B = {batch}.")
+    out = dict(out or {})
+    unknown = (set(out) | set(want)) - set(PvLossResult._fields)
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+
+    def given(name, shape, dtype):
+        t = out.get(name)
+        if t is None:
+            return None
+        _require_device(t, name)
+        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev:
+            raise ValueError(f"out[{name!r}] must be {dtype} {shape} on {dev}. Got {t.dtype} {tuple(t.shape)}.")
+        return t
+
+    dlogits = given("dlogits", (batch, nact), torch.float32)
+    if dlogits is None:
+        dlogits = torch.empty((batch, nact), dtype=torch.float32, device=dev)
+    elif not ((nact == 1 or dlogits.stride(1) == 1) and (batch <= 1 or dlogits.stride(0) >= nact)):
+        raise ValueError(f"the rows of out['dlogits'] must each be contiguous. Got strides {dlogits.stride()}.")
+    dvalue = given("dvalue", value_shape, torch.float32)
+    if dvalue is None:
+        dvalue = torch.empty(value_shape, dtype=torch.float32, device=dev)
+    dvalue_1d = dvalue[:, 0] if dvalue.dim() == 2 else dvalue
+    if batch > 1 and dvalue_1d.stride(0) < 1:
+        raise ValueError(f"out['dvalue'] must have a positive stride. Got {dvalue.stride()}.")
+    loss = given("loss", (), torch.float32)
+    if loss is None:
+        loss = torch.full((), float("nan"), dtype=torch.float32, device=dev) if batch == 0 else \
+            torch.empty((), dtype=torch.float32, device=dev)
+    status = given("status", (1,), torch.int32)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    row_loss = given("row_loss", (batch,), torch.float32)
+    if row_loss is None and "row_loss" in want:
+        row_loss = torch.empty(batch, dtype=torch.float32, device=dev)
+    if row_loss is not None and not row_loss.is_contiguous():
+        raise ValueError("out['row_loss'] must be contiguous.")
+    need = int(lib().hk_pv_loss_workspace_bytes(batch))
+    if workspace is None:
+        workspace = _PVLOSS_WORKSPACES.get(dev, need)
+    else:
+        _require_device(workspace, "workspace")
+        if (workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != dev
+                or workspace.numel() < need):
+            raise ValueError("workspace must be what pv_loss_workspace(batch, device) returns (or a larger one).")
+    d = A.hk_pv_loss_desc()
+    d.logits, d.value, d.target_policy, d.target_value = (logits.data_ptr(), value.data_ptr(), target_policy.data_ptr(),
+                                                         target_value.data_ptr())
+    d.weight = weight.data_ptr() if weight is not None else None
+    d.index = index.data_ptr() if index is not None else None
+    d.dlogits, d.dvalue, d.loss = dlogits.data_ptr(), dvalue_1d.data_ptr(), loss.data_ptr()
+    d.row_loss = row_loss.data_ptr() if row_loss is not None else None
+    d.workspace, d.status = workspace.data_ptr(), status.data_ptr()
+    d.logits_stride, d.target_policy_stride, d.dlogits_stride = _dqn_stride(logits), _dqn_stride(target_policy), \
+        _dqn_stride(dlogits)
+    d.value_stride = value.stride(0) if batch > 1 else 1
+    d.dvalue_stride = dvalue_1d.stride(0) if batch > 1 else 1
+    d.num_samples, d.batch, d.actions, d.dtype, d.flags = samples, batch, nact, A.HK_F32, 0
+    with torch.cuda.device(dev):
+        check(lib().hk_pv_loss(C.byref(d), _stream(logits)), "hk_pv_loss")
+    return PvLossResult(loss, dlogits, dvalue, row_loss, status)
+
+
 # ---- the optimiser step: gradient clipping + Adam / SGD of a parameter list in two launches per 64 tensors ----------
 
 OPTIM_KINDS = {"scale": A.HK_OPTIM_SCALE, "sgd": A.HK_OPTIM_SGD, "adam": A.HK_OPTIM_ADAM}

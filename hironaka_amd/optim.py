@@ -10,6 +10,13 @@ step count back), so a whole fit step can be captured into a graph, with a learn
 ``Adam`` and ``SGD`` are ``torch.optim.Optimizer`` subclasses whose per-parameter state carries torch's keys, so
 ``state_dict()`` / ``load_state_dict()`` exchange with ``torch.optim.Adam`` / ``SGD`` in both directions.
 
+``AdamW`` is ``Adam`` behind torch's decoupled decay (one ``torch._foreach_mul_`` per group, then the two launches with
+``weight_decay = 0``); its ``state_dict`` exchanges with ``torch.optim.AdamW``.  ``safe_clip_grads_`` is the MCTS trainer's
+clipping rule (``hironaka/jax/util.py:426-430``), which is not torch's: the norm from ``hk_optim_prepare``'s pass, the
+coefficient on the device, one ``torch._foreach_mul_``.  Followed by ``step()`` that is a second pass over the gradients
+(``clip_and_step`` reads them once): the rule differs from the one the kernels have, whose flag and kind spaces are
+pinned.
+
 Deviations from torch: a parameter group has ONE step count and one pair of running powers ``beta ** step`` on the
 device (torch counts per parameter and evaluates the power in Python: at most ``step * 2**-53`` relative apart; a
 parameter whose ``.grad`` is None is skipped as in torch, but does not fall behind in count); Adam's last line is
@@ -59,6 +66,45 @@ def clip_grad_norm_(parameters: Union[torch.Tensor, Iterable[torch.Tensor]], max
     ops.optim_prepare(chain, max_norm=max_norm)
     ops.optim_apply(chain)
     return block[3].to(grads[0].dtype, copy=True)
+
+
+def safe_clip_grads_(parameters: Union[torch.Tensor, Iterable[torch.Tensor]], max_norm: float) -> torch.Tensor:
+    """The MCTS trainer's clipping rule, ``safe_clip_grads`` (hironaka/jax/util.py:426-430), in place: with ``norm`` the
+    2-norm of all gradients, they stay as they are where ``norm < max_norm`` and are multiplied by
+    ``max_norm / (norm + 1e-9)`` otherwise (so at ``norm == max_norm`` they shrink by a hair).  Not torch's rule, which
+    is ``min(1, max_norm / (norm + 1e-6))``.  On a HIP device the norm is ``hk_optim_prepare``'s one pass over the
+    gradients, the coefficient a one-element expression on the device (in float64, rounded to the gradients' dtype) and
+    the scaling one ``torch._foreach_mul_``; elsewhere it is torch's operators.  Returns the norm as a tensor on the
+    gradients' device (of no gradient: a zero).  Nothing here synchronises.
+
+    The reference multiplies by ``max_norm`` and then divides; here the quotient is taken first: the last bit of a
+    clipped gradient may differ."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.tensor(0.0)
+    dev = grads[0].device
+    if dev.type == "cuda":
+        key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+        block = _CLIP_STATES.get(key)
+        if block is None:
+            block = _CLIP_STATES[key] = ops.optim_state(dev)
+        ckey = (key, tuple(g.numel() for g in grads), grads[0].dtype)
+        chain = _CLIP_CHAINS.get(ckey)
+        if chain is None:
+            if len(_CLIP_CHAINS) > 64:
+                _CLIP_CHAINS.clear()
+            chain = _CLIP_CHAINS[ckey] = ops.OptimChain("scale", grads, state=block, hold_grads=False)
+        else:
+            chain.set_grads(grads)
+        ops.optim_prepare(chain, clip=False)  # the norm alone: the block's coefficient is 1 and is not used
+        norm = block[3].clone()
+    else:
+        norm = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(g.double()) for g in grads]))
+    coef = torch.where(norm < max_norm, torch.ones_like(norm), max_norm / (norm + 1e-9))
+    torch._foreach_mul_(grads, coef.to(grads[0].dtype))
+    return norm.to(grads[0].dtype)
 
 
 class _TwoLaunch(torch.optim.Optimizer):
@@ -223,6 +269,50 @@ class Adam(_TwoLaunch):
                     self.state[p]["step"] = torch.tensor(float(step))
 
 
+class AdamW(Adam):
+    """``torch.optim.AdamW``: the decoupled decay ``p *= 1 - lr * weight_decay`` of every parameter that has a gradient
+    (one ``torch._foreach_mul_`` per group), then ``Adam``'s two launches with ``weight_decay = 0`` -- torch's order and
+    torch's factor.  (optax's adamw, which the reference's configs name, subtracts ``lr * (update + weight_decay * p)``
+    in one line: the same rule, rounded differently.)  The factor is computed on the host, so a learning rate that lives
+    on the device is refused."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, *, amsgrad=False,
+                 maximize=False, capturable=False, differentiable=False):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
+                         maximize=maximize, capturable=capturable, differentiable=differentiable)
+        # torch.optim.AdamW's own mark, in the defaults and in every group, so that a state_dict loads into either class
+        self.defaults["decoupled_weight_decay"] = True
+        for group in self.param_groups:
+            group["decoupled_weight_decay"] = True
+            self._check_group(group)
+
+    def _check_group(self, group):
+        for name in _REFUSED:
+            if group.get(name):
+                raise NotImplementedError(f"{name}=True is not supported by hironaka_amd.optim.AdamW.")
+        if isinstance(group["lr"], torch.Tensor):
+            raise NotImplementedError("hironaka_amd.optim.AdamW takes the learning rate as a float: the decay factor "
+                                      "1 - lr * weight_decay is computed on the host.  (optim.Adam accepts a "
+                                      "one-element tensor on the device.)")
+
+    def _apply_args(self, group):
+        return dict(super()._apply_args(group), weight_decay=0.0)  # the decay is step()'s first line
+
+    def step(self, closure=None, *, max_grad_norm=None, keep_grads: bool = True):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        with torch.no_grad():
+            for group in self.param_groups:
+                self._check_group(group)
+                ps = [p for p in group["params"] if p.grad is not None]
+                if ps and group["weight_decay"] != 0:
+                    torch._foreach_mul_(ps, 1 - group["lr"] * group["weight_decay"])
+        super().step(max_grad_norm=max_grad_norm, keep_grads=keep_grads)
+        return loss
+
+
 class SGD(_TwoLaunch):
     """``torch.optim.SGD`` in two launches per step; see the module's text."""
     _kind = "sgd"
@@ -267,7 +357,8 @@ class SGD(_TwoLaunch):
 
 def from_torch(optimizer: torch.optim.Optimizer):
     """an ``Adam`` / ``SGD`` of this module over the parameters of a ``torch.optim.Adam`` / ``torch.optim.SGD``, with its
-    hyper-parameters and state (the state tensors are copies)"""
+    hyper-parameters and state (the state tensors are copies).  A ``torch.optim.AdamW`` is refused here: build an
+    ``AdamW`` over its parameters and ``load_state_dict`` its ``state_dict()``."""
     if type(optimizer) is torch.optim.Adam:
         cls, names = Adam, ("lr", "betas", "eps", "weight_decay")
     elif type(optimizer) is torch.optim.SGD:

@@ -5,9 +5,17 @@ points and config keys (hironaka/jax/jax_trainer.py:150-320, 398-592, 626-876):
     obs, target_policy, target_value = trainer.simulate(key, role, use_mcts_policy=False, use_unified_tree=False)
     rho, details = trainer.compute_rho(host, agent, batch_size=..., num_of_loops=10, max_length=...)
 
-What is NOT here is the neural-network side (flax models, optax optimisers, ``train``, checkpoints, wandb) and the
-trainer's control plane around it (``validate``'s battle schedule, the ``get_* / update_*`` accessor layer of
-jax_trainer.py:626-669,735-858): out of scope.  The networks' FORWARD is here: where the config
+    losses = trainer.train(key, role, gradient_steps, (obs, target_policy, target_value), mask=None, random_sampling=False)
+
+What is NOT here is flax and optax themselves, checkpoints, wandb and the trainer's control plane (``validate``'s battle
+schedule inside ``train``, the ``get_* / update_*`` accessor layer of jax_trainer.py:626-669,735-858): out of scope
+(SURVEY.md section 2).  The LEARNING side is here for the networks the trainer builds itself (jax_trainer.py:57-79,
+322-375, 727-733): ``set_optim(role, optim_config)`` maps the config's optax names onto ``hironaka_amd.optim`` (it is
+called for every built network whose section has ``optim``), ``loss_fn`` is ``hironaka_amd.loss.policy_value_loss`` and
+``train`` runs gradient steps of gather -> network with gradients on (torch autograd: the modules run their children)
+-> the fused loss with the targets gathered inside its launch -> ``backward`` -> ``safe_clip_grads_`` -> ``step``,
+updating the parameters in place; ``train_step`` is one such step, which can be captured into a graph.  More than one
+rank is refused (the mean of the gradients over the ranks is not built).  The networks' FORWARD is here: where the config
 has a ``host`` / ``agent`` section with ``net_arch`` and ``net_type`` is ``dense`` or ``dense_resnet``, the trainer builds
 ``hironaka_amd.net``'s modules as JAXTrainer builds flax's (jax_trainer.py:216-218; ``built_nets[role]``) and calls them
 under ``torch.no_grad()``.  Otherwise the two networks arrive as callables
@@ -87,6 +95,51 @@ def standin_mlp(in_dim: int, out_dim: int, seed: int, width: int = 256, device="
     return net, params
 
 
+# jax_trainer.py:125 optim_dict -- optax's argument names onto hironaka_amd.optim's; an argument at the value that means
+# "nothing" for optax is accepted, anything else is refused by name
+_OPTIM_ARGS = {
+    "adam": {"learning_rate": "lr", "b1": "b1", "b2": "b2", "eps": "eps"},
+    "adamw": {"learning_rate": "lr", "b1": "b1", "b2": "b2", "eps": "eps", "weight_decay": "weight_decay"},
+    "sgd": {"learning_rate": "lr", "momentum": "momentum", "nesterov": "nesterov"},
+}
+_OPTIM_NOTHING = {"eps_root": 0.0, "mu_dtype": None, "mask": None, "accumulator_dtype": None}
+
+
+def optim_from_config(optim_config: dict) -> Tuple[str, Dict[str, Any]]:
+    """``{"name": "adam" | "adamw" | "sgd", "args": {...optax's arguments...}}`` -> the name of the class of
+    ``hironaka_amd.optim`` ("Adam", "AdamW", "SGD") and its keyword arguments: ``learning_rate -> lr``, ``b1, b2 ->
+    betas``, ``eps``, ``weight_decay`` (adamw: optax's default 1e-4), ``momentum`` (None -> 0), ``nesterov``.  An
+    argument this module has no counterpart for (``eps_root != 0``, ``mu_dtype``, ...) and a missing ``learning_rate``
+    raise ValueError naming the key."""
+    name = optim_config["name"]
+    if name not in _OPTIM_ARGS:
+        raise ValueError(f"optim name must be one of {sorted(_OPTIM_ARGS)}. Got {name!r}.")
+    args = dict(optim_config.get("args") or {})
+    for key, value in args.items():
+        if key in _OPTIM_ARGS[name]:
+            continue
+        if key in _OPTIM_NOTHING and (value is None or (_OPTIM_NOTHING[key] is not None and value == _OPTIM_NOTHING[key])):
+            continue
+        raise ValueError(f"optim argument {key!r} = {value!r} of {name!r} has no counterpart in hironaka_amd.optim "
+                         f"(served: {sorted(_OPTIM_ARGS[name])}).")
+    if "learning_rate" not in args:
+        raise ValueError(f"optim argument 'learning_rate' of {name!r} is missing.")
+    if not isinstance(args["learning_rate"], (int, float)):
+        raise ValueError(f"optim argument 'learning_rate' must be a number (optax schedules are not served). Got "
+                         f"{args['learning_rate']!r}.")
+    kwargs: Dict[str, Any] = {"lr": float(args["learning_rate"])}
+    if name in ("adam", "adamw"):
+        kwargs["betas"] = (float(args.get("b1", 0.9)), float(args.get("b2", 0.999)))
+        kwargs["eps"] = float(args.get("eps", 1e-8))
+        if name == "adamw":
+            kwargs["weight_decay"] = float(args.get("weight_decay", 1e-4))
+        return ("Adam" if name == "adam" else "AdamW"), kwargs
+    momentum = args.get("momentum")
+    kwargs["momentum"] = 0.0 if momentum is None else float(momentum)
+    kwargs["nesterov"] = bool(args.get("nesterov", False))
+    return "SGD", kwargs
+
+
 def _without_grad(module) -> Callable:
     """`net(features, params)` over a module HipTrainer built itself: called under torch.no_grad()"""
     def net(features, params=None):
@@ -116,7 +169,7 @@ class HipTrainer:
                  host_net: Optional[Callable] = None, agent_net: Optional[Callable] = None,
                  host_params: Any = None, agent_params: Any = None,
                  host_feature_fn=None, agent_feature_fn=None, device=None, use_graph: bool = False,
-                 fused_expand: bool = True):
+                 fused_expand: bool = True, loss_fn: Optional[Callable] = None):
         if isinstance(config, str):
             import yaml
             with open(config, "r") as stream:
@@ -168,10 +221,13 @@ class HipTrainer:
         self.host_params, self.agent_params = host_params, agent_params
         feature_fns = {"host": host_feature_fn, "agent": agent_feature_fn}
         self.policy_fns: Dict[str, Callable] = {}
+        self._train_apply_fns: Dict[str, Callable] = {}  # the built networks with gradients on: get_apply_fn(role)
         for role in ("host", "agent"):
             feature_fn = feature_fns[role] if feature_fns[role] is not None else \
                 get_feature_fn(role, self.spec, scale_observation=self.scale_observation)
             fn = get_apply_fn(role, self.models[role], self.spec, feature_fn=feature_fn)
+            if role in self.built_nets:
+                self._train_apply_fns[role] = get_apply_fn(role, self.built_nets[role], self.spec, feature_fn=feature_fn)
             # (the agent's logits go through its action mask, jax_trainer.py:836-855, in its NaN-free form: the
             # reference's `policy * mask - inf * (~mask)`, jax/util.py:302, is inf * 0 = NaN on the allowed logits)
             self.policy_fns[role] = apply_agent_action_mask(fn, d, nan_free=True) if role == "agent" else fn
@@ -180,6 +236,15 @@ class HipTrainer:
         self._fn_args: Dict[Any, Any] = {}        # (role, unified tree) -> (params objects, argument tuples)
         self._gather_pipes = None                 # simulate(overlap_gather=True): one GatherPipeline per output tensor
         self.log: Dict[str, Any] = {}
+        # the learning side (jax_trainer.py:155, 193, 219-222): the loss, and an optimiser for every network built here
+        # whose section of the config names one
+        if loss_fn is None:
+            from .loss import policy_value_loss as loss_fn
+        self.loss_fn = loss_fn
+        self.optimizers: Dict[str, torch.optim.Optimizer] = {}
+        for role in self.built_nets:
+            if "optim" in self.config[role]:
+                self.set_optim(role, self.config[role]["optim"])
 
     @staticmethod
     def _opponent(role: str) -> str:
@@ -293,6 +358,94 @@ class HipTrainer:
                                   for _ in range(3)]
         tickets = [pipe.submit(x.contiguous()) for pipe, x in zip(self._gather_pipes, out)]
         return PendingRollout(self._gather_pipes, tickets)
+
+    # ---- jax_trainer.py:727-733 ----------------------------------------------------------------------------------
+    def set_optim(self, role: str, optim_config: dict):
+        """Set up / reset the optimiser of a network this trainer built: `optim_from_config` says which class of
+        hironaka_amd.optim, over the module's parameters (``optimizers[role]``, and ``host_optim`` / ``agent_optim`` as in
+        the reference)."""
+        self._opponent(role)
+        if role not in self.built_nets:
+            raise ValueError(f"set_optim needs a network this trainer built (a `{role}` section with `net_arch` in the "
+                             f"config): the {role} network was given as a callable, whose parameters are opaque here.")
+        from . import optim
+        name, kwargs = optim_from_config(optim_config)
+        optimizer = getattr(optim, name)(self.built_nets[role].parameters(), **kwargs)
+        self.optimizers[role] = optimizer
+        setattr(self, f"{role}_optim", optimizer)
+        return optimizer
+
+    def get_apply_fn(self, role: str) -> Callable:
+        """`apply_fn(obs, params) -> (policy_logits [B, A], value [B])` over the network built for `role`, with
+        gradients as the caller has them (`policy_fns[role]` is the same network under ``no_grad``, with the agent's
+        action mask); ``params`` is ignored: the module holds its own."""
+        if role not in self._train_apply_fns:
+            self._opponent(role)
+            raise ValueError(f"the {role} network was given as a callable: there is no module to differentiate.")
+        return self._train_apply_fns[role]
+
+    # ---- jax_trainer.py:57-79, 322-375 ---------------------------------------------------------------------------
+    def train_step(self, role: str, rollouts, rows: torch.Tensor) -> torch.Tensor:
+        """One gradient step on the rows `rows` ([batch_size] int64 on the device) of `rollouts` (p_train_loop,
+        jax_trainer.py:57-79): gather the observations, the network with gradients on, the loss with the targets
+        gathered inside its launch, ``backward``, ``safe_clip_grads_(parameters, max_grad_norm)``, ``step()``.  Returns
+        the loss tensor without reading it; nothing synchronises, so the step can be captured into a graph."""
+        from .optim import safe_clip_grads_
+        obs, target_policy, target_value = rollouts
+        optimizer = self.optimizers[role]
+        policy_logits, value = self.get_apply_fn(role)(obs[rows], None)
+        loss = self.loss_fn(policy_logits, value, target_policy, target_value, weight=None, index=rows)
+        optimizer.zero_grad()
+        loss.backward()
+        safe_clip_grads_(list(self.built_nets[role].parameters()), self.max_grad_norm)
+        optimizer.step()
+        return loss.detach()
+
+    def train(self, key: int, role: str, gradient_steps: int, rollouts, mask: Optional[torch.Tensor] = None,
+              random_sampling: bool = False, verbose=0, save_best: bool = True) -> torch.Tensor:
+        """`gradient_steps` steps of regression of the `role` network on `rollouts`, what `simulate` returns: flat
+        (obs [N, input_dim], target_policy [N, A], target_value [N]) -- there is no device axis here.  Every step takes
+        ``config[role]["batch_size"]`` rows: step i of a call the rows ``(i * batch_size + arange(batch_size)) % N``,
+        or with `random_sampling` the rows ``torch.multinomial(mask, batch_size, replacement=True)`` drawn from
+        ``torch.Generator(device).manual_seed(key)`` (`mask`: [N], bool or weights; None: all rows alike; not jax's
+        stream).  As in the reference the mask only weights the draw: the loss weight is None.  The parameters are
+        updated in place, so the fused forward's table and a captured search stay valid.  Returns the losses as a
+        [gradient_steps] tensor on the device, unread; `verbose` prints them, which synchronises.  The reference's
+        logging, validation schedule and checkpoints (jax_trainer.py:377-396) are not here: `save_best` is accepted and
+        unused."""
+        self._opponent(role)
+        if role not in self.built_nets:
+            raise ValueError(f"train needs a network this trainer built (a `{role}` section with `net_arch` in the "
+                             f"config): the {role} network was given as a callable, whose parameters are opaque here.")
+        if role not in self.optimizers:
+            raise ValueError(f"the {role} network has no optimiser: give config[{role!r}] an `optim` section or call "
+                             "set_optim(role, optim_config).")
+        if hkdist.world() > 1:
+            raise NotImplementedError("train on more than one rank needs the mean of the gradients over the ranks, "
+                                      "which is not built.")
+        batch_size = int(self.config[role]["batch_size"])
+        obs, target_policy, target_value = rollouts
+        sample_size = obs.shape[0]
+        if not (sample_size > 0 and target_policy.shape[0] == sample_size and target_value.numel() == sample_size):
+            raise ValueError(f"rollouts must be (obs [N, ...], target_policy [N, A], target_value [N]) with N > 0. Got "
+                             f"{tuple(obs.shape)}, {tuple(target_policy.shape)}, {tuple(target_value.shape)}.")
+        rollouts = (obs, target_policy, target_value.reshape(sample_size))
+        losses = torch.empty(gradient_steps, dtype=torch.float32, device=self.device)
+        offsets = torch.arange(batch_size, device=self.device)
+        if random_sampling:
+            generator = torch.Generator(device=self.device).manual_seed(int(key) % (1 << 63))
+            draw_weight = torch.ones(sample_size, dtype=torch.float32, device=self.device) if mask is None else \
+                mask.to(device=self.device, dtype=torch.float32).reshape(sample_size)
+        for i in range(gradient_steps):
+            if random_sampling:
+                rows = torch.multinomial(draw_weight, batch_size, replacement=True, generator=generator)
+            else:
+                rows = (i * batch_size + offsets) % sample_size
+            losses[i] = self.train_step(role, rollouts, rows)
+        if verbose:
+            for i, loss in enumerate(losses.tolist()):
+                print(f"{role} gradient step {i}: loss {loss}")
+        return losses
 
     # ---- jax_trainer.py:398-465 ----------------------------------------------------------------------------------
     def validate(self, metric_fn: Optional[Callable] = None, verbose=0, batch_size=50, num_of_loops=10, max_length=None,

@@ -640,5 +640,7 @@ int hk_search_morin_play(const hk_morin_play_desc* desc, void* stream);
 #include "hironaka_hip_mlp_train.h"
 /* within ABI 6: hk_pvnet_forward, likewise */
 #include "hironaka_hip_pvnet.h"
+/* within ABI 6: hk_pv_loss, likewise */
+#include "hironaka_hip_pvloss.h"
 
 #endif /* HIRONAKA_HIP_H */
