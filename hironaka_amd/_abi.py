@@ -112,6 +112,8 @@ HK_PVNET_DENSE, HK_PVNET_RESIDUE = 0, 1
 HK_PVNET_RAW_VALUE, HK_PVNET_FORCE_TILE_SMALL, HK_PVNET_FORCE_TILE_LARGE = 1, 2, 4
 # hk_pv_loss: rows per workgroup, the action limit (the policy head's), the bit of the status word
 HK_PVLOSS_TILE_ROWS, HK_PVLOSS_MAX_ACTIONS, HK_PVLOSS_BAD_INDEX = 16, 255, 1
+# hk_pvgrad_forward / hk_pvgrad_backward: the largest batch (the 16-row tile's range), Denses per parameter-gradient launch
+HK_PVGRAD_MAX_BATCH, HK_PVGRAD_TABLE = 4096, 40
 PVNET_NORMED_WIDTHS = (32, 64, 128, 256)  # the widths of a normed layer the kernel serves (1, 2, 4, 8 columns per group)
 
 SEMANTICS = {"jax": HK_SEM_JAX, "torch": HK_SEM_TORCH, "list": HK_SEM_LIST}
@@ -562,6 +564,29 @@ class hk_pvnet_desc(C.Structure):
     ]
 
 
+class hk_pvgrad_dense(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("d_weight", "d_bias", "d_gn_scale", "d_gn_bias")]
+
+
+class hk_pvgrad_block(C.Structure):
+    _fields_ = [("dense1", hk_pvgrad_dense), ("dense2", hk_pvgrad_dense), ("proj", hk_pvgrad_dense)]
+
+
+class hk_pvgrad_desc(C.Structure):
+    _fields_ = [
+        ("net", hk_pvnet_desc),
+        ("grad_policy", C.c_void_p),
+        ("grad_value", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("grad_policy_stride", C.c_int64),
+        ("grad_value_stride", C.c_int64),
+        ("workspace_bytes", C.c_uint64),
+        ("policy", hk_pvgrad_dense),
+        ("value", hk_pvgrad_dense),
+        ("block", hk_pvgrad_block * HK_PVNET_MAX_BLOCKS),
+    ]
+
+
 _vp, _i, _i64, _u32, _u64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
 
 # name -> (restype, argtypes) of every symbol the header declares.  `stream` is the trailing
@@ -688,15 +713,23 @@ PVLOSS_PROTOTYPES = {
     "hk_pv_loss": (C.c_int, [C.POINTER(hk_pv_loss_desc), _vp]),
 }
 
+# the entry points of include/hironaka_hip_pvgrad.h: the device library's only, as above
+PVGRAD_PROTOTYPES = {
+    "hk_pvgrad_workspace_bytes": (C.c_uint64, [C.POINTER(hk_pvgrad_desc)]),
+    "hk_pvgrad_forward": (C.c_int, [C.POINTER(hk_pvgrad_desc), _vp]),
+    "hk_pvgrad_backward": (C.c_int, [C.POINTER(hk_pvgrad_desc), _vp]),
+}
+
 
 def bind(lib: C.CDLL, prototypes=None) -> None:
     """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES, TREE_PROTOTYPES, ENV_PROTOTYPES,
-    REPLAY_PROTOTYPES, DQN_PROTOTYPES, OPTIM_PROTOTYPES, MLP_PROTOTYPES, MLP_TRAIN_PROTOTYPES, PVNET_PROTOTYPES and
-    PVLOSS_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
+    REPLAY_PROTOTYPES, DQN_PROTOTYPES, OPTIM_PROTOTYPES, MLP_PROTOTYPES, MLP_TRAIN_PROTOTYPES, PVNET_PROTOTYPES,
+    PVLOSS_PROTOTYPES and PVGRAD_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
     if prototypes is None:
         prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES, **TREE_PROTOTYPES, **ENV_PROTOTYPES,
                       **REPLAY_PROTOTYPES, **DQN_PROTOTYPES, **OPTIM_PROTOTYPES, **MLP_PROTOTYPES,
-                      **MLP_TRAIN_PROTOTYPES, **PVNET_PROTOTYPES, **PVLOSS_PROTOTYPES}
+                      **MLP_TRAIN_PROTOTYPES, **PVNET_PROTOTYPES, **PVLOSS_PROTOTYPES,
+                      **PVGRAD_PROTOTYPES}
     for name, (res, args) in prototypes.items():
         fn = getattr(lib, name)
         fn.restype = res

@@ -101,9 +101,16 @@ class DenseResNet(nn.Module):
     logits); otherwise it IS the plain composition of the children.  `fused_reason` says why the MODULE is not served
     (None: it is), `fused_last_reason` why the last CALL was not (None: it was); `fused_enabled = False` pins torch's
     path.  The two paths differ in the last bits.  The block table is built once and rebuilt when a parameter's
-    `data_ptr()` changed (assigned anew, `.to()`); in-place updates need nothing.  Nothing here synchronises."""
+    `data_ptr()` changed (assigned anew, `.to()`); in-place updates need nothing.  Nothing here synchronises.
+
+    With `fused_training = True` (off by default) a call with gradients on is served too: the forward and backward are a
+    once-differentiable autograd.Function over ops.pvnet_train_forward / ops.pvnet_backward (include/hironaka_hip_pvgrad.h
+    states the rule) where the module is servable apart from "gradients are on" and the input is float32 on the device,
+    requires no gradient and has at most HK_PVGRAD_MAX_BATCH rows; parameters that require no gradient get None.  Anything
+    else is torch's path, with `fused_last_reason` saying why."""
 
     fused_enabled = True
+    fused_training = False
     fused_last_reason = None
 
     def __init__(self, output_size: int, net_arch: List[int], spec: Optional[Tuple[int, int]] = None,
@@ -169,9 +176,13 @@ class DenseResNet(nn.Module):
             return "parameters are not float32"
         if len({t.device for t in tensors}) > 1:
             return "parameters live on more than one device"
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if not self.fused_training and self._records_graph():
             return "gradients are on"
         return None
+
+    def _records_graph(self) -> bool:
+        """whether a call now would record a graph over the parameters"""
+        return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
 
     def _records(self):
         def dn(lin, gn=None):
@@ -211,11 +222,24 @@ class DenseResNet(nn.Module):
                 reason = f"the input is not float32 on {dev} with a batch dimension, or requires a gradient"
             elif math.prod(x.shape[1:]) != self.input_dim:
                 reason = f"the input is not {self.input_dim} wide"
+        grads = reason is None and self._records_graph()  # (only with fused_training: _reason)
+        if grads:
+            records, policy, value = self._records()
+            params = [t for r in records for part in r[1:4] if part is not None for t in part if t is not None]
+            params += list(policy + value)
+            if x.shape[0] > A.HK_PVGRAD_MAX_BATCH:
+                reason = f"more than {A.HK_PVGRAD_MAX_BATCH} rows with gradients on"
+            elif len({id(p) for p in params}) < len(params):
+                reason = "a parameter is used twice and gradients are on"
         self.__dict__["fused_last_reason"] = reason
         if reason is not None:
             return self.plain_forward(x)
         from . import ops
-        p, v = ops.pvnet_forward(x, self._cached_plan())
+        plan = self._cached_plan()
+        if grads:
+            p, v = _PvnetTrainFunction.apply(plan, x, *plan.params)
+        else:
+            p, v = ops.pvnet_forward(x, plan)
         return p, v.unsqueeze(1)
 
     def __deepcopy__(self, memo):
@@ -295,6 +319,28 @@ class DenseResNet(nn.Module):
         if extra:
             raise KeyError(f"the tree has scopes this module has none for: {['/'.join(p) for p in extra]}")
         return self
+
+
+class _PvnetTrainFunction(torch.autograd.Function):
+    """forward: ops.pvnet_train_forward; backward: ops.pvnet_backward.  The parameters are saved so that torch's version
+    check refuses a backward after one of them was changed in place; the input gets no gradient, a parameter that requires
+    none gets None."""
+
+    @staticmethod
+    def forward(ctx, plan, x, *params):
+        from . import ops
+        policy, value, saved = ops.pvnet_train_forward(x, plan)
+        ctx.hk_saved = saved
+        ctx.save_for_backward(*params)
+        return policy, value
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_policy, grad_value):
+        ctx.saved_tensors  # the version check, before anything is launched
+        from . import ops
+        grads = ops.pvnet_backward(ctx.hk_saved, grad_policy, grad_value)
+        return (None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))
 
 
 DenseNet = partial(DenseResNet, block_cls=DenseBlock)

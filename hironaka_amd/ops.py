@@ -2022,9 +2022,14 @@ class PvnetPlan:
         self.device = dev = first.device
         self.desc = d = A.hk_pvnet_desc()
         self.tensors = []
+        # the parameters in module order -- per block dense1, dense2, proj (those it has), per Dense weight, bias, gn_scale,
+        # gn_bias (those that exist), then the policy head's and the value head's: the order of pvnet_backward's gradients;
+        # grad_fields says where each one's gradient goes in an hk_pvgrad_desc: (block or "policy" / "value", Dense, field)
+        self.params, self.grad_fields = [], []
         width = None
 
-        def fill(e, dense, name, n, k):
+        def fill(i, which, dense, n, k, normed=True):
+            e, name = getattr(d.block[i], which), f"blocks[{i}].{which}"
             dense = PvnetDense(*dense)
             if not isinstance(dense.weight, torch.Tensor) or tuple(dense.weight.shape) != (n, k):
                 raise ValueError(f"{name}.weight must be a [{n}, {k}] tensor.")
@@ -2032,6 +2037,10 @@ class PvnetPlan:
             for field in ("bias", "gn_scale", "gn_bias"):
                 setattr(e, field, _mlp_tensor(getattr(dense, field), f"{name}.{field}", dev, (n,)))
             self.tensors += [t for t in dense if t is not None]
+            for field, t in zip(("d_weight", "d_bias", "d_gn_scale", "d_gn_bias"), dense if normed else dense[:2]):
+                if t is not None:
+                    self.params.append(t)
+                    self.grad_fields.append((i, which, field))
 
         for i, b in enumerate(blocks):
             if b.kind not in _PVNET_KINDS:
@@ -2040,15 +2049,15 @@ class PvnetPlan:
             width = n
             e = d.block[i]
             e.k, e.n, e.kind, e.eps = k, n, _PVNET_KINDS[b.kind], float(b.eps)
-            fill(e.dense1, b.dense1, f"blocks[{i}].dense1", n, k)
+            fill(i, "dense1", b.dense1, n, k, b.kind == "residue")
             if b.kind == "residue":
                 if n not in PVNET_NORMED_WIDTHS:
                     raise ValueError(f"blocks[{i}]: a normed width must be one of {PVNET_NORMED_WIDTHS}. Got {n}.")
                 if b.dense2 is None or (k != n and b.proj is None):
                     raise ValueError(f"blocks[{i}]: a residue block needs dense2, and proj where it changes the width.")
-                fill(e.dense2, b.dense2, f"blocks[{i}].dense2", n, n)
+                fill(i, "dense2", b.dense2, n, n)
                 if k != n:
-                    fill(e.proj, b.proj, f"blocks[{i}].proj", n, k)
+                    fill(i, "proj", b.proj, n, k)
         actions = policy[0].shape[0] if isinstance(policy[0], torch.Tensor) and policy[0].dim() == 2 else 0
         if not 1 <= actions <= A.HK_PVNET_MAX_WIDTH - 1:
             raise ValueError(f"the policy head must have 1 to {A.HK_PVNET_MAX_WIDTH - 1} outputs. Got {actions}.")
@@ -2058,6 +2067,10 @@ class PvnetPlan:
             setattr(d, name + "_weight", _mlp_tensor(weight, f"{name}[0]", dev))
             setattr(d, name + "_bias", _mlp_tensor(bias, f"{name}[1]", dev, (n,)))
             self.tensors += [t for t in (weight, bias) if t is not None]
+            for field, t in (("d_weight", weight), ("d_bias", bias)):
+                if t is not None:
+                    self.params.append(t)
+                    self.grad_fields.append((name, None, field))
         d.nblocks, d.actions, d.dtype = len(blocks), actions, A.HK_F32
         self.k_in, self.actions = PvnetDense(*blocks[0].dense1).weight.shape[1], actions
 
@@ -2276,4 +2289,108 @@ def mlp_backward(saved: MlpTrainSaved, grad_out: torch.Tensor, grads: Optional[S
         e.d_weight, e.d_bias, e.d_bn_weight, e.d_bn_bias = row
     with torch.cuda.device(dev):
         check(lib().hk_train_mlp_backward(C.byref(d), _stream(out)), "hk_train_mlp_backward")
+    return grads
+
+
+# ---- the training-mode forward of a DenseResNet / DenseNet policy-value network and its backward -------------------------
+
+class PvnetSaved:
+    """what pvnet_backward needs of one pvnet_train_forward: the plan, the input rows, the results (value as the kernel
+    stored it) and the workspace that holds every block's saved arrays"""
+
+    def __init__(self, plan, x, policy, value, workspace, raw_value):
+        self.plan, self.x, self.policy, self.value, self.workspace, self.raw_value = plan, x, policy, value, workspace, raw_value
+
+
+def _pvgrad_desc(plan: PvnetPlan, x, policy, value, workspace, raw_value: bool):
+    """the plan's hk_pvgrad_desc with the fields of one call filled in"""
+    g = plan.__dict__.get("_grad_desc")
+    if g is None:
+        g = plan.__dict__["_grad_desc"] = A.hk_pvgrad_desc()
+    batch, k0, a = x.shape[0], x.shape[1], plan.actions
+    g.net = plan.desc
+    d = g.net
+    d.x, d.x_stride, d.k0, d.batch = x.data_ptr(), x.stride(0) if batch > 1 else k0, k0, batch
+    d.policy, d.policy_stride = policy.data_ptr(), policy.stride(0) if batch > 1 else a
+    d.value, d.value_stride = value.data_ptr(), value.stride(0) if batch > 1 else 1
+    d.flags = A.HK_PVNET_RAW_VALUE if raw_value else 0
+    g.workspace, g.workspace_bytes = workspace.data_ptr(), 4 * workspace.numel()
+    g.grad_policy = g.grad_value = None
+    return g
+
+
+def pvnet_train_forward(x: torch.Tensor, plan: PvnetPlan, raw_value: bool = False):
+    """pvnet_forward with what the backward needs saved, in one launch (hk_pvgrad_forward; the rule is in
+    include/hironaka_hip_pvgrad.h).  Returns (policy [B, A], value [B], saved): policy and value have pvnet_forward's bits,
+    `saved` (a PvnetSaved) is what pvnet_backward takes.  The buffers are new per call.  At most HK_PVGRAD_MAX_BATCH rows.
+    Nothing here synchronises."""
+    if not isinstance(plan, PvnetPlan):
+        raise TypeError(f"plan must be a PvnetPlan. Got {type(plan).__name__}.")
+    dev = plan.device
+    x = _mlp_rows(x, "x", dev)
+    batch, k0 = x.shape
+    if k0 != plan.k_in:
+        raise ValueError(f"the first block takes {plan.k_in} inputs. Got {k0}.")
+    if batch > A.HK_PVGRAD_MAX_BATCH:
+        raise ValueError(f"at most {A.HK_PVGRAD_MAX_BATCH} rows. Got {batch}.")
+    policy = torch.empty((batch, plan.actions), dtype=torch.float32, device=dev)
+    value = torch.empty((batch,), dtype=torch.float32, device=dev)
+    g = _pvgrad_desc(plan, x, policy, value, policy, raw_value)
+    g.workspace, g.workspace_bytes = None, 0
+    floats = lib().hk_pvgrad_workspace_bytes(C.byref(g)) // 4 if batch else 0
+    workspace = torch.empty(max(floats, 1), dtype=torch.float32, device=dev)
+    # (aliases without autograd's marks: see mlp_train_forward)
+    saved = PvnetSaved(plan, x, policy.detach(), value.detach(), workspace, bool(raw_value))
+    if batch == 0:
+        return policy, value, saved
+    g.workspace, g.workspace_bytes = workspace.data_ptr(), 4 * workspace.numel()
+    with torch.cuda.device(dev):
+        check(lib().hk_pvgrad_forward(C.byref(g), _stream(policy)), "hk_pvgrad_forward")
+    return policy, value, saved
+
+
+def pvnet_backward(saved: PvnetSaved, grad_policy: torch.Tensor, grad_value: torch.Tensor,
+                   grads: Optional[Sequence[torch.Tensor]] = None):
+    """The backward of one pvnet_train_forward (hk_pvgrad_backward: one launch for the rows, one per HK_PVGRAD_TABLE Denses
+    for the parameters): grad_policy [B, A] and grad_value [B] or [B, 1] are the gradients with respect to the forward's
+    policy and value (the tanh's result, or the raw value where the forward ran with raw_value); their rows may lie any
+    number of elements apart.  Returns the gradients of the plan's `params`, in that order (new tensors, views of one
+    buffer).  grads: contiguous float32 tensors of the parameters' shapes, in that order, to write into instead.  The input
+    gets none.  The parameters must be what they were in the forward.  Nothing here synchronises."""
+    plan = saved.plan
+    dev = plan.device
+    batch, a = saved.policy.shape
+    for name, t, shapes in (("grad_policy", grad_policy, ((batch, a),)), ("grad_value", grad_value, ((batch,), (batch, 1)))):
+        _require_device(t, name)
+        if t.dtype != torch.float32 or t.device != dev or tuple(t.shape) not in shapes:
+            raise TypeError(f"{name} must be a float32 tensor of shape {' or '.join(map(str, shapes))} on {dev}. "
+                            f"Got {t.dtype} {tuple(t.shape)} on {t.device}.")
+    if (a > 1 and grad_policy.stride(1) != 1) or (batch > 1 and grad_policy.stride(0) < a):
+        grad_policy = grad_policy.contiguous()
+    if batch > 1 and grad_value.stride(0) < 1:
+        grad_value = grad_value.contiguous()
+    if grads is not None:
+        grads = list(grads)
+        if len(grads) != len(plan.params):
+            raise ValueError(f"grads must hold one tensor per parameter ({len(plan.params)}). Got {len(grads)}.")
+        at = [_mlp_tensor(t, f"grads[{i}]", dev, p.shape) for i, (t, p) in enumerate(zip(grads, plan.params))]
+    else:
+        starts, floats = [], 0
+        for p in plan.params:
+            starts.append(floats)
+            floats += _align4(p.numel())
+        buf = torch.empty(floats, dtype=torch.float32, device=dev)
+        grads = [buf[s:s + p.numel()].view(p.shape) for s, p in zip(starts, plan.params)]
+        at = [buf.data_ptr() + 4 * s for s in starts]
+    if batch == 0:
+        for t in grads:
+            t.zero_()
+        return grads
+    g = _pvgrad_desc(plan, saved.x, saved.policy, saved.value, saved.workspace, saved.raw_value)
+    g.grad_policy, g.grad_policy_stride = grad_policy.data_ptr(), grad_policy.stride(0) if batch > 1 else a
+    g.grad_value, g.grad_value_stride = grad_value.data_ptr(), grad_value.stride(0) if batch > 1 else 1
+    for (block, which, field), ptr in zip(plan.grad_fields, at):
+        setattr(getattr(g, block) if which is None else getattr(g.block[block], which), field, ptr)
+    with torch.cuda.device(dev):
+        check(lib().hk_pvgrad_backward(C.byref(g), _stream(saved.policy)), "hk_pvgrad_backward")
     return grads

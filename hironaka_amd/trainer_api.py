@@ -14,7 +14,9 @@ schedule inside ``train``, the ``get_* / update_*`` accessor layer of jax_traine
 called for every built network whose section has ``optim``), ``loss_fn`` is ``hironaka_amd.loss.policy_value_loss`` and
 ``train`` runs gradient steps of gather -> network with gradients on (torch autograd: the modules run their children)
 -> the fused loss with the targets gathered inside its launch -> ``backward`` -> ``safe_clip_grads_`` -> ``step``,
-updating the parameters in place; ``train_step`` is one such step, which can be captured into a graph.  More than one
+updating the parameters in place; ``train_step`` is one such step, which can be captured into a graph.  With
+``HipTrainer(..., fused_training=True)`` the built networks carry ``DenseResNet.fused_training``: the forward and backward
+through the network are then ``hk_pvgrad_forward`` / ``hk_pvgrad_backward`` instead of torch autograd (off by default).  More than one
 rank is refused (the mean of the gradients over the ranks is not built).  The networks' FORWARD is here: where the config
 has a ``host`` / ``agent`` section with ``net_arch`` and ``net_type`` is ``dense`` or ``dense_resnet``, the trainer builds
 ``hironaka_amd.net``'s modules as JAXTrainer builds flax's (jax_trainer.py:216-218; ``built_nets[role]``) and calls them
@@ -169,7 +171,7 @@ class HipTrainer:
                  host_net: Optional[Callable] = None, agent_net: Optional[Callable] = None,
                  host_params: Any = None, agent_params: Any = None,
                  host_feature_fn=None, agent_feature_fn=None, device=None, use_graph: bool = False,
-                 fused_expand: bool = True, loss_fn: Optional[Callable] = None):
+                 fused_expand: bool = True, loss_fn: Optional[Callable] = None, fused_training: bool = False):
         if isinstance(config, str):
             import yaml
             with open(config, "r") as stream:
@@ -199,6 +201,9 @@ class HipTrainer:
                 from .net import build_net
                 module = build_net(self.net_type, role, 2 ** d - d - 1 if role == "host" else d, section["net_arch"],
                                    (m, d), seed=_split(key, 2)[i]).to(self.device)
+                # fused_training: the gradient step's forward and backward through the network are the library's
+                # (hironaka_amd.net.DenseResNet.fused_training; off by default)
+                module.fused_training = bool(fused_training)
                 self.built_nets[role] = module
                 given[role] = _without_grad(module)
         host_net, agent_net = given["host"], given["agent"]

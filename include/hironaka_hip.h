@@ -642,5 +642,7 @@ int hk_search_morin_play(const hk_morin_play_desc* desc, void* stream);
 #include "hironaka_hip_pvnet.h"
 /* within ABI 6: hk_pv_loss, likewise */
 #include "hironaka_hip_pvloss.h"
+/* within ABI 6: hk_pvgrad_forward / hk_pvgrad_backward, likewise */
+#include "hironaka_hip_pvgrad.h"
 
 #endif /* HIRONAKA_HIP_H */
