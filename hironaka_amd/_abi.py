@@ -587,6 +587,32 @@ class hk_pvgrad_desc(C.Structure):
     ]
 
 
+# include/hironaka_hip_unified.h
+HK_UNIFIED_REPOSITION, HK_UNIFIED_SCALE_OBSERVATION = 1, 2
+HK_UNIFIED_MAX_DIM = 5  # the search takes at most 32 actions
+
+
+class hk_unified_expand_desc(C.Structure):
+    _fields_ = [
+        ("embeddings", C.c_void_p),
+        ("parent", C.c_void_p),
+        ("action", C.c_void_p),
+        ("node", C.c_void_p),
+        ("kind", C.c_void_p),
+        ("net_in", C.c_void_p),
+        ("subset", C.c_void_p),
+        ("reward", C.c_void_p),
+        ("discount_out", C.c_void_p),
+        ("discount", C.c_float),
+        ("batch", C.c_int32),
+        ("num_nodes", C.c_int32),
+        ("max_points", C.c_int32),
+        ("dim", C.c_int32),
+        ("dtype", C.c_int32),
+        ("flags", C.c_uint32),
+    ]
+
+
 _vp, _i, _i64, _u32, _u64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
 
 # name -> (restype, argtypes) of every symbol the header declares.  `stream` is the trailing
@@ -720,16 +746,23 @@ PVGRAD_PROTOTYPES = {
     "hk_pvgrad_backward": (C.c_int, [C.POINTER(hk_pvgrad_desc), _vp]),
 }
 
+# the entry points of include/hironaka_hip_unified.h: the device library's only, as above
+UNIFIED_PROTOTYPES = {
+    "hk_unified_expand": (C.c_int, [C.POINTER(hk_unified_expand_desc), _vp]),
+    "hk_unified_prior": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "hk_unified_pvnet_forward": (C.c_int, [C.POINTER(hk_pvnet_desc), _vp, C.c_int32, _vp]),
+}
+
 
 def bind(lib: C.CDLL, prototypes=None) -> None:
     """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES, TREE_PROTOTYPES, ENV_PROTOTYPES,
     REPLAY_PROTOTYPES, DQN_PROTOTYPES, OPTIM_PROTOTYPES, MLP_PROTOTYPES, MLP_TRAIN_PROTOTYPES, PVNET_PROTOTYPES,
-    PVLOSS_PROTOTYPES and PVGRAD_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
+    PVLOSS_PROTOTYPES, PVGRAD_PROTOTYPES and UNIFIED_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
     if prototypes is None:
         prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES, **TREE_PROTOTYPES, **ENV_PROTOTYPES,
                       **REPLAY_PROTOTYPES, **DQN_PROTOTYPES, **OPTIM_PROTOTYPES, **MLP_PROTOTYPES,
                       **MLP_TRAIN_PROTOTYPES, **PVNET_PROTOTYPES, **PVLOSS_PROTOTYPES,
-                      **PVGRAD_PROTOTYPES}
+                      **PVGRAD_PROTOTYPES, **UNIFIED_PROTOTYPES}
     for name, (res, args) in prototypes.items():
         fn = getattr(lib, name)
         fn.restype = res

@@ -79,4 +79,17 @@ int hk_pvnet_forward(const hk_pvnet_desc* q, void* stream) {
   return mlp_launch(pvnet_kernel<HK_MLP_TILE_SMALL>, pvnet_kernel<HK_MLP_TILE_LARGE>, *q, (hipStream_t)stream);
 }
 
+// include/hironaka_hip_unified.h: hk_pvnet_forward's checks and launch shape (mlp_launch's), behind the gate
+int hk_unified_pvnet_forward(const hk_pvnet_desc* q, const int32_t* gate, int32_t want, void* stream) {
+  const int bad = validate(q);
+  if (bad != HK_OK) return bad;
+  if (!gate) return HK_ERR_NULL;
+  if (!aligned(gate, 4)) return HK_ERR_ALIGN;
+  if (q->batch == 0) return HK_OK;
+  const int tr = mlp_row_tile(q->batch, q->flags);
+  const auto kernel = tr == HK_MLP_TILE_LARGE ? pvnet_gated_kernel<HK_MLP_TILE_LARGE> : pvnet_gated_kernel<HK_MLP_TILE_SMALL>;
+  return launch_kernel_lds(kernel, 48 * 1024, dim3((unsigned)workgroups(q->batch, tr)), dim3(kWave * mlp_waves(tr)),
+                           mlp_lds_bytes(tr), (hipStream_t)stream, *q, gate, want);
+}
+
 }  // extern "C"

@@ -106,8 +106,9 @@ __device__ __forceinline__ void pvnet_store(const typename MlpTile<TR>::Acc& acc
   }
 }
 
+// the whole forward of a workgroup's row tile: the body of pvnet_kernel and of pvnet_gated_kernel
 template <int TR>
-__global__ __launch_bounds__(kWave * mlp_waves(TR)) void pvnet_kernel(const hk_pvnet_desc q) {
+__device__ __forceinline__ void pvnet_tile(const hk_pvnet_desc& q) {
   typedef MlpTile<TR> T;
   extern __shared__ __align__(16) float hk_pvnet_lds[];
   float* cur = hk_pvnet_lds;
@@ -175,6 +176,21 @@ __global__ __launch_bounds__(kWave * mlp_waves(TR)) void pvnet_kernel(const hk_p
         }
     }
   }
+}
+
+template <int TR>
+__global__ __launch_bounds__(kWave * mlp_waves(TR)) void pvnet_kernel(const hk_pvnet_desc q) {
+  pvnet_tile<TR>(q);
+}
+
+// hk_unified_pvnet_forward (include/hironaka_hip_unified.h): the same forward where *gate == want; otherwise every
+// workgroup returns before it touches anything but the gate, and the outputs stay as they were.  The gate is uniform
+// over the launch, so a workgroup either runs whole or not at all: no barrier is ever left half attended.
+template <int TR>
+__global__ __launch_bounds__(kWave * mlp_waves(TR)) void pvnet_gated_kernel(const hk_pvnet_desc q, const int32_t* gate,
+                                                                            int32_t want) {
+  if (*gate != want) return;
+  pvnet_tile<TR>(q);
 }
 
 }  // namespace hk

@@ -2076,16 +2076,31 @@ class PvnetPlan:
 
 
 def pvnet_forward(x: torch.Tensor, plan: PvnetPlan, tile: Optional[int] = None, raw_value: bool = False,
-                  policy: Optional[torch.Tensor] = None, value: Optional[torch.Tensor] = None):
+                  policy: Optional[torch.Tensor] = None, value: Optional[torch.Tensor] = None, *,
+                  gate: Optional[Tuple[torch.Tensor, int]] = None,
+                  out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
     """The forward of a trunk of dense / residue blocks with a policy head and a tanh value head in ONE launch
     (hk_pvnet_forward; the rule, to the bit, is in include/hironaka_hip_pvnet.h).  x: [B, ...] float32 rows (flattened
     behind the batch dimension; the rows may lie any number of elements apart).  Returns (policy [B, A], value [B]).
     policy / value: float32 tensors of these shapes to write into (policy with adjacent elements in a row, rows >= A
-    apart; value at any element stride >= 1); None: new ones.  tile: None, or the row tile (16 / 64) to force -- same
-    bits.  raw_value: store the value head before the tanh.  Everything is float32 on one HIP device (a TypeError
+    apart; value at any element stride >= 1); None: new ones.  out: the two as a pair.  tile: None, or the row tile
+    (16 / 64) to force -- same bits.  raw_value: store the value head before the tanh.  gate: (word, want) -- an int32
+    tensor of one element on the device and an int: the launch computes only where the word holds `want` when the
+    kernel runs (hk_unified_pvnet_forward, include/hironaka_hip_unified.h), otherwise it leaves policy and value as they
+    are; the decision is the device's, nothing is read back.  Everything is float32 on one HIP device (a TypeError
     otherwise).  Nothing here synchronises."""
     if not isinstance(plan, PvnetPlan):
         raise TypeError(f"plan must be a PvnetPlan. Got {type(plan).__name__}.")
+    if out is not None:
+        if policy is not None or value is not None:
+            raise ValueError("give the outputs as out=(policy, value) or as policy= / value=, not both.")
+        policy, value = out
+    if gate is not None:
+        word, want = gate
+        _require_device(word, "gate[0]")
+        if word.dtype != torch.int32 or word.numel() != 1 or word.device != plan.device:
+            raise TypeError(f"gate[0] must be an int32 tensor of one element on {plan.device}. "
+                            f"Got {word.dtype} {tuple(word.shape)} on {word.device}.")
     tile_flag = _mlp_tile_flag(tile)
     dev = plan.device
     x = _mlp_rows(x, "x", dev)
@@ -2109,8 +2124,88 @@ def pvnet_forward(x: torch.Tensor, plan: PvnetPlan, tile: Optional[int] = None, 
     d.value, d.value_stride = value.data_ptr(), value.stride(0) if batch > 1 else 1
     d.flags = tile_flag | (A.HK_PVNET_RAW_VALUE if raw_value else 0)
     with torch.cuda.device(dev):
-        check(lib().hk_pvnet_forward(C.byref(d), _stream(policy)), "hk_pvnet_forward")
+        if gate is None:
+            check(lib().hk_pvnet_forward(C.byref(d), _stream(policy)), "hk_pvnet_forward")
+        else:
+            check(lib().hk_unified_pvnet_forward(C.byref(d), word.data_ptr(), int(want), _stream(policy)),
+                  "hk_unified_pvnet_forward")
     return policy, value
+
+
+# ---- one expansion of the role-agnostic search tree: kind of the batch, expansion, prior (hironaka_hip_unified.h) ----------
+
+def _unified_array(t: torch.Tensor, name: str, dtype, shape, dev) -> int:
+    _require_device(t, name)
+    if t.dtype != dtype or t.device != dev or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}. "
+                         f"Got {t.dtype} {tuple(t.shape)} on {t.device}.")
+    return t.data_ptr()
+
+
+def unified_expand(embeddings: torch.Tensor, parent: torch.Tensor, action: torch.Tensor, node: torch.Tensor,
+                   kind: torch.Tensor, *, spec: Tuple[int, int], discount: float, scale_observation: bool = True,
+                   reposition: bool = False, net_in: Optional[torch.Tensor] = None,
+                   subset: Optional[torch.Tensor] = None, reward: Optional[torch.Tensor] = None,
+                   discount_out: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """One expansion of a role-agnostic tree (hk_unified_expand; include/hironaka_hip_unified.h states the rule).
+    embeddings: the contiguous float32 table [B, N, m*d + d], read at `parent` and written at `node` (both [B] int32);
+    action: [B] int32; kind: an int32 tensor of one element that holds 0 -- it receives 1 when a parent is a host
+    state.  Returns {"net_in": [B, m*d + d], "subset": [B] int32, "reward": [B], "discount": [B]} (the tensors given, or
+    new ones).  Nothing here synchronises."""
+    _require_device(embeddings, "embeddings")
+    m, d = spec
+    dev = embeddings.device
+    if embeddings.dim() != 3 or embeddings.shape[2] != m * d + d:
+        raise ValueError(f"embeddings must be [B, N, {m * d + d}]. Got {tuple(embeddings.shape)}.")
+    b, n, w = embeddings.shape
+    q = A.hk_unified_expand_desc()
+    q.embeddings = _unified_array(embeddings, "embeddings", torch.float32, (b, n, w), dev)
+    for name, t in (("parent", parent), ("action", action), ("node", node)):
+        setattr(q, name, _unified_array(t, name, torch.int32, (b,), dev))
+    _require_device(kind, "kind")
+    if kind.dtype != torch.int32 or kind.numel() != 1 or kind.device != dev:
+        raise ValueError(f"kind must be an int32 tensor of one element on {dev}.")
+    q.kind = kind.data_ptr()
+    res = {}
+    for name, t, dtype, shape in (("net_in", net_in, torch.float32, (b, w)), ("subset", subset, torch.int32, (b,)),
+                                  ("reward", reward, torch.float32, (b,)), ("discount", discount_out, torch.float32, (b,))):
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        setattr(q, "discount_out" if name == "discount" else name, _unified_array(t, name, dtype, shape, dev))
+        res[name] = t
+    q.discount = float(discount)
+    q.batch, q.num_nodes, q.max_points, q.dim, q.dtype = b, n, m, d, A.HK_F32
+    q.flags = (A.HK_UNIFIED_REPOSITION if reposition else 0) | (A.HK_UNIFIED_SCALE_OBSERVATION if scale_observation else 0)
+    with torch.cuda.device(dev):
+        check(lib().hk_unified_expand(C.byref(q), _stream(embeddings)), "hk_unified_expand")
+    return res
+
+
+def unified_prior(kind: torch.Tensor, agent_logits: torch.Tensor, agent_value: torch.Tensor, host_logits: torch.Tensor,
+                  host_value: torch.Tensor, subset: torch.Tensor, *, dim: int, prior: Optional[torch.Tensor] = None,
+                  value: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(prior [B, 2^dim - dim - 1], value [B]) of the node a role-agnostic expansion made (hk_unified_prior): where `kind`
+    holds 1 the agent's logits behind the bits of `subset`, padded with -inf, and the agent's value; where it holds 0
+    the host's.  The side that is not selected is not read.  Nothing here synchronises."""
+    _require_device(agent_logits, "agent_logits")
+    dev = agent_logits.device
+    b = agent_logits.shape[0]
+    a = 2 ** dim - dim - 1
+    if prior is None:
+        prior = torch.empty((b, a), dtype=torch.float32, device=dev)
+    if value is None:
+        value = torch.empty((b,), dtype=torch.float32, device=dev)
+    _require_device(kind, "kind")
+    if kind.dtype != torch.int32 or kind.numel() != 1 or kind.device != dev:
+        raise ValueError(f"kind must be an int32 tensor of one element on {dev}.")
+    ptrs = [_unified_array(t, name, dtype, shape, dev) for name, t, dtype, shape in (
+        ("agent_logits", agent_logits, torch.float32, (b, dim)), ("agent_value", agent_value, torch.float32, (b,)),
+        ("host_logits", host_logits, torch.float32, (b, a)), ("host_value", host_value, torch.float32, (b,)),
+        ("subset", subset, torch.int32, (b,)), ("prior", prior, torch.float32, (b, a)),
+        ("value", value, torch.float32, (b,)))]
+    with torch.cuda.device(dev):
+        check(lib().hk_unified_prior(kind.data_ptr(), *ptrs, b, dim, _stream(prior)), "hk_unified_prior")
+    return prior, value
 
 
 # ---- the training-mode forward of a create_mlp stack and its backward, one launch per layer each way ---------------------

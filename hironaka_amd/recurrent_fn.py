@@ -6,8 +6,10 @@ around the step (recurrent_fn.py:84-121, 161-197):
     -> role_fn(next_observations)
 
 The search driver that calls it in the reference (third-party ``mctx``) is out of scope; any search
-loop over torch tensors can call these functions.  ``mctx.RecurrentFnOutput`` is replaced by a
-NamedTuple with the same fields.
+loop over torch tensors can call these functions.  ``HostExpander`` / ``AgentExpander`` / ``UnifiedExpander`` (not in the
+reference) are the same expansions as fused device work for a search loop that knows about them (``hironaka_amd.search``):
+the last one is what makes a role-agnostic tree free of host decisions, and so capturable into a graph.
+``mctx.RecurrentFnOutput`` is replaced by a NamedTuple with the same fields.
 """
 from __future__ import annotations
 
@@ -223,6 +225,89 @@ class AgentExpander:
                                  value=value.reshape(b))
 
 
+class UnifiedExpander:
+    """The same for a ROLE-AGNOSTIC tree (recurrent_fn.py:126-199): embeddings are [m*d + d] states, a host state has a
+    zero tail, an agent state carries the host's subset; whether an expansion treats its batch as host states or as
+    agent states is decided once per batch -- on the device, so that nothing waits for the host and the search can be
+    captured into a graph:
+
+        hk_unified_expand (kind of the batch; next state into the tree; features ++ tail; subset; reward; -discount)
+        -> agent network where the kind is 1, host network where it is 0 -> hk_unified_prior (masked, padded selection)
+
+    A model is GATEABLE when it is one of HipTrainer's wrappers of a network it built itself (``model.module`` is a
+    ``net.DenseResNet``) whose ``fused_reason`` is None: its launch is hk_unified_pvnet_forward, which returns at once
+    where the kind is the other one, so an expansion costs one network, not two.  Any other callable
+    (``trainer_api.standin_mlp`` among them) is opaque: BOTH networks run on every expansion and hk_unified_prior takes
+    the one the kind names.  Results are identical to the generic path (tests/test_gpu_unified_search.py)."""
+
+    def __init__(self, host_model: Callable, agent_model: Callable, spec: Tuple[int, int], discount: float,
+                 scale_observation: bool, reposition: bool):
+        self.host_model, self.agent_model = host_model, agent_model
+        self.m, self.d = spec
+        self.discount = discount
+        self.scale_observation = scale_observation
+        self.reposition = reposition
+
+    def accepts(self, root_embedding: torch.Tensor) -> bool:
+        m, d = self.m, self.d
+        return (root_embedding.is_cuda and root_embedding.dtype == torch.float32 and root_embedding.dim() == 2
+                and root_embedding.shape[1] == (m + 1) * d and 2 <= d <= A.HK_UNIFIED_MAX_DIM
+                and ((2 * m * d + 2 * d) | 1) * 4 <= 64 * 1024)  # the lane frame's slice (hk_unified_expand)
+
+    @staticmethod
+    def _plan(model):
+        """the block table of a gateable model, None for any other callable"""
+        from .net import DenseResNet
+        module = getattr(model, "module", None)
+        if not isinstance(module, DenseResNet):
+            return None
+        with torch.no_grad():  # as the wrapper calls it
+            if module.fused_reason is not None or module.Dense_0.weight.device.type != "cuda":
+                return None
+            return module._cached_plan()
+
+    def begin(self, tree, root_embedding: torch.Tensor):
+        """per search: one kind word per simulation (zeroed here: inside a capture the memset is replayed with the
+        graph, and no word is ever reset) and the arrays of an expansion"""
+        b, n, w = tree.embeddings.shape
+        d = self.d
+        dev = tree.embeddings.device
+        a = num_classes(d)
+        f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)  # noqa: E731
+        return {"sim": 0, "kind": torch.zeros(n - 1, dtype=torch.int32, device=dev),
+                "net_in": f32(b, w), "subset": torch.empty(b, dtype=torch.int32, device=dev),
+                "reward": f32(b), "discount": f32(b),
+                "agent_logits": f32(b, d), "agent_value": f32(b), "host_logits": f32(b, a), "host_value": f32(b),
+                "prior": f32(b, a), "value": f32(b)}
+
+    def expand(self, params, key, tree, state, parent: torch.Tensor, action: torch.Tensor, node: torch.Tensor):
+        from . import ops
+        (host_params, *_), (agent_params, *_) = params
+        m, d = self.m, self.d
+        b = parent.shape[0]
+        kind = state["kind"][state["sim"]: state["sim"] + 1]
+        state["sim"] += 1
+        net_in = state["net_in"]
+        ops.unified_expand(tree.embeddings, parent, action, node, kind, spec=(m, d), discount=self.discount,
+                           scale_observation=self.scale_observation, reposition=self.reposition, net_in=net_in,
+                           subset=state["subset"], reward=state["reward"], discount_out=state["discount"])
+        outs = {}
+        for name, model, model_params, x, want in (("agent", self.agent_model, agent_params, net_in, 1),
+                                                   ("host", self.host_model, host_params, net_in[:, : m * d], 0)):
+            logits, value = state[name + "_logits"], state[name + "_value"]
+            plan = self._plan(model)
+            if plan is not None:
+                ops.pvnet_forward(x, plan, gate=(kind, want), out=(logits, value))
+            else:  # an opaque callable: it runs whatever the kind is
+                logits, value = model(x.contiguous(), model_params)
+                logits = logits.to(torch.float32).contiguous()
+                value = value.to(torch.float32).reshape(b).contiguous()
+            outs[name] = (logits, value)
+        prior, value = ops.unified_prior(kind, *outs["agent"], *outs["host"], state["subset"], dim=d,
+                                         prior=state["prior"], value=state["value"])
+        return RecurrentFnOutput(reward=state["reward"], discount=state["discount"], prior_logits=prior, value=value)
+
+
 def get_recurrent_fn_for_role(role: str, role_fn: Callable, opponent_action_fn: Callable, reward_fn: Callable,
                               spec: Tuple[int, int], discount: float = 0.99, dtype=torch.float32,
                               rescale_points: bool = False, reposition: bool = False,
@@ -293,10 +378,12 @@ def get_recurrent_fn_for_role(role: str, role_fn: Callable, opponent_action_fn: 
 
 def get_unified_recurrent_fn(host_fn: Callable, agent_fn: Callable, reward_fn: Callable, spec: Tuple[int, int],
                              discount: float = 0.99, dtype=torch.float32, rescale_points: bool = False,
-                             reposition: bool = False) -> Callable:
+                             reposition: bool = False, expander: "UnifiedExpander | None" = None) -> Callable:
     """recurrent_fn.py:126-199 -- one tree for both players: states are [B, m*d + d]; a host state has
     a zero tail, an agent state carries the subset mask; the discount is negated; agent logits are
-    padded with -inf to the host's action count."""
+    padded with -inf to the host's action count.  The function below decides the kind of a batch on the host (one
+    synchronisation per call); `expander` (not in the reference) rides along as `.expander` for a search loop that
+    knows about it: the same expansion as fused device work, decided on the device."""
     m, d = spec
     obs_preprocess, coords_preprocess = get_preprocess_fns("agent", spec)
     batch_decode = get_batch_decode(d)
@@ -330,4 +417,7 @@ def get_unified_recurrent_fn(host_fn: Callable, agent_fn: Callable, reward_fn: C
                                 prior_logits=policy_prior, value=value_prior)
         return out, next_state
 
+    if expander is not None and not isinstance(expander, UnifiedExpander):
+        raise TypeError(f"a role-agnostic tree cannot expand through {type(expander).__name__}")
+    recurrent_fn.expander = expander
     return recurrent_fn

@@ -9,8 +9,9 @@ itself is UNPINNED; the kernels are pinned to oracle/search_oracle.py (tests/tes
 
 Per simulation the device runs: hk_search_select (one lane per ACTION walks the game's tree) -> gather of the parent embeddings -> `recurrent_fn` (opponent
 policy + HIP environment step + the player's network) -> scatter of the new embeddings -> hk_search_backup; a recurrent_fn with an
-`expander` (recurrent_fn.HostExpander / AgentExpander) runs gather / step / scatter as fused operators.  No host
-synchronisation anywhere in the loop.
+`expander` (recurrent_fn.HostExpander / AgentExpander, and UnifiedExpander for the role-agnostic tree, whose host / agent
+decision per batch it makes on the device) runs gather / step / scatter as fused operators.  No host synchronisation
+anywhere in the loop.
 """
 from __future__ import annotations
 
@@ -152,7 +153,7 @@ def _run_search(params, rng_key, root: RootFnOutput, gumbel: torch.Tensor, inval
     rows = torch.arange(b, device=dev)
     inv_ptr = None if invalid_u8 is None else invalid_u8.data_ptr()
     L = lib()
-    # a recurrent_fn built by recurrent_fn.get_recurrent_fn_for_role may offer its expansion as fused operators
+    # a recurrent_fn built by recurrent_fn.get_recurrent_fn_for_role / get_unified_recurrent_fn may offer its expansion as fused operators
     # (recurrent_fn.HostExpander: gather / opponent argmax / step / features / scatter without the tensor-library glue)
     expander = getattr(recurrent_fn, "expander", None)
     if expander is not None and not expander.accepts(root.embedding):

@@ -31,14 +31,17 @@ def get_evaluation_loop(role: str, policy_fn: Callable, opponent_fn: Callable, r
     """simulation_fn.py:16-122.  policy_fn(observations, *args, key=) -> (policy_prior, value_prior);
     opponent_fn(observations, *args, key=) -> one-hot actions; reward_fn(dones, prev_dones) -> rewards.
     use_graph (not in the reference): capture the search of each distinct batch shape into a hipGraph
-    (search.CapturedSearch: its requirements apply -- role-specific trees only, callables without host
-    synchronisation, randomness from torch's default generator, same argument objects on every call).
-    expander (not in the reference): a recurrent_fn.HostExpander -- the expansions of a host-role tree through the
-    fused operators."""
+    (search.CapturedSearch: its requirements apply -- callables without host synchronisation, randomness from
+    torch's default generator, same argument objects on every call; a role-agnostic tree only with an expander: its
+    generic recurrent function asks the host for the kind of every batch).
+    expander (not in the reference): a recurrent_fn.HostExpander / AgentExpander / UnifiedExpander -- the expansions
+    of a host-role, agent-role or role-agnostic tree through the fused operators.  (The root's policy of a
+    role-agnostic tree still decides on the host, once per search and outside the captured region.)"""
     if role_agnostic:
         policy_fn_on_root = get_dynamic_policy_fn(spec, policy_fn, opponent_fn)
         recurrent_fn = get_unified_recurrent_fn(policy_fn, opponent_fn, reward_fn, spec, discount=discount,
-                                                dtype=dtype, rescale_points=rescale_points, reposition=reposition)
+                                                dtype=dtype, rescale_points=rescale_points, reposition=reposition,
+                                                expander=expander)
     else:
         def policy_fn_on_root(state, role_and_opponent_params, *args, **kwargs):
             params, _ = role_and_opponent_params
@@ -48,8 +51,9 @@ def get_evaluation_loop(role: str, policy_fn: Callable, opponent_fn: Callable, r
                                                  dtype=dtype, rescale_points=rescale_points, reposition=reposition,
                                                  expander=expander)
 
-    if use_graph and role_agnostic:
-        raise ValueError("the role-agnostic tree decides host/agent on the host per call: not capturable")
+    if use_graph and role_agnostic and expander is None:
+        raise ValueError("the role-agnostic tree decides host/agent on the host per call: not capturable without a "
+                         "recurrent_fn.UnifiedExpander, which decides on the device")
     captured = {}
 
     def evaluation_loop(key: int, root_states: torch.Tensor, role_fn_args=(), opponent_fn_args=(),

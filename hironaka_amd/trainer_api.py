@@ -48,7 +48,7 @@ from .functional import (action_wrapper, apply_agent_action_mask, flatten, gener
 from .host_action_preprocess import get_batch_decode_from_one_hot
 from .players import get_host_with_flattened_obs
 from .rollout import compute_rho as _compute_rho
-from .recurrent_fn import AgentExpander, HostExpander
+from .recurrent_fn import AgentExpander, HostExpander, UnifiedExpander
 from .rollout import rollout_postprocess as _rollout_postprocess
 from .simulation_fn import get_evaluation_loop, get_simulation
 
@@ -214,7 +214,8 @@ class HipTrainer:
                              "the same way (trainer_api.standin_mlp gives a fixed random stand-in).")
         self.use_graph = use_graph
         # trees of the trainer's own policies expand through the fused operators (recurrent_fn.HostExpander /
-        # AgentExpander) -- possible while the standard feature functions sit in front of the networks
+        # AgentExpander, UnifiedExpander for the tree of both players) -- possible while the standard feature functions
+        # sit in front of the networks
         self.fused_expand = bool(fused_expand) and host_feature_fn is None and agent_feature_fn is None
         self.key = int(key)
         self.spec = (self.max_num_points, self.dimension)
@@ -269,7 +270,14 @@ class HipTrainer:
                       reposition=self.reposition, dtype=self.dtype, gumbel_scale=gumbel_scale)
         if unified:  # one tree for both players: host policy on the points, agent policy below it; the agent's reward
             host_on_points = lambda pts, *a, dtype=None, **k: self.policy_fns["host"](pts.reshape(pts.shape[0], -1), *a, **k)
-            return get_evaluation_loop(role="host", role_agnostic=True, use_graph=False, expander=None,
+            # the expansions as fused device work, kind of the batch included (recurrent_fn.UnifiedExpander), under the
+            # same condition as the role-specific trees; only then is the search free of host decisions and capturable
+            expander = None
+            if self.fused_expand and self.dtype == torch.float32:
+                expander = UnifiedExpander(self.models["host"], self.models["agent"], self.spec, self.discount,
+                                           self.scale_observation, self.reposition)
+            return get_evaluation_loop(role="host", role_agnostic=True,
+                                       use_graph=self.use_graph and expander is not None, expander=expander,
                                        policy_fn=get_host_with_flattened_obs(self.spec, host_on_points, truncate_input=True),
                                        opponent_fn=self.policy_fns["agent"],
                                        **{**common, "reward_fn": self.reward_fns["agent"]})
@@ -316,7 +324,9 @@ class HipTrainer:
 
         A search captured into a hipGraph (``use_graph``) replays with the parameter OBJECTS it was captured with:
         update ``host_params`` / ``agent_params`` in place (``tensor.copy_``) to keep the capture; assigning new
-        objects drops it and captures again on the next call (one capture per role and kind of tree is kept).
+        objects drops it and captures again on the next call (one capture per role and kind of tree is kept).  The
+        unified tree is captured too where it expands through ``recurrent_fn.UnifiedExpander`` (``fused_expand``, float32,
+        standard feature functions); on the generic path it asks the host for the kind of every batch and runs eagerly.
 
         overlap_gather (more than one rank): return a `PendingRollout` instead -- the all-gather of the three tensors
         runs on a side stream behind the next simulate's searches; `.result()` is the tuple above (valid until two

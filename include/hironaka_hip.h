@@ -644,5 +644,7 @@ int hk_search_morin_play(const hk_morin_play_desc* desc, void* stream);
 #include "hironaka_hip_pvloss.h"
 /* within ABI 6: hk_pvgrad_forward / hk_pvgrad_backward, likewise */
 #include "hironaka_hip_pvgrad.h"
+/* within ABI 6: hk_unified_expand / hk_unified_prior / hk_unified_pvnet_forward, likewise */
+#include "hironaka_hip_unified.h"
 
 #endif /* HIRONAKA_HIP_H */
