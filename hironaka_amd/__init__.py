@@ -7,7 +7,8 @@ _OPTIM = ("Adam", "AdamW", "SGD", "clip_grad_norm_", "safe_clip_grads_", "from_t
 _LOSS = ("policy_value_loss", "compute_loss", "clip_log")
 _NETS = ("create_mlp", "expand_net_list", "FusedSequential", "fuse", "BaseFeaturesExtractor", "HostFeatureExtractor",
          "AgentFeatureExtractor")
-__all__ = list(_VEC_ENVS) + ["ReplayBuffer"] + list(_DQN) + list(_OPTIM) + list(_LOSS) + list(_NETS)
+_HOSTS = ("Spivakovsky", "RandomSpivakovsky")
+__all__ = list(_VEC_ENVS) + ["ReplayBuffer"] + list(_DQN) + list(_OPTIM) + list(_LOSS) + list(_NETS) + list(_HOSTS)
 
 
 def __getattr__(name):
@@ -30,4 +31,7 @@ def __getattr__(name):
     if name in _NETS:
         from . import nets
         return getattr(nets, name)
+    if name in _HOSTS:
+        from . import host
+        return getattr(host, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -47,6 +47,7 @@ HK_FLAG_FORCE_FOUR_LANES = 1024
 # fused policies
 HK_HOST_RANDOM, HK_HOST_ALL_COORD, HK_HOST_ZEILLINGER = 0, 1, 2
 HK_HOST_ZEILLINGER_LEX, HK_HOST_WEAK_SPIVAKOVSKY, HK_HOST_MIN_HITTING = 3, 4, 5  # hk_host_select / hk_search_depth
+HK_HOST_SPIVAKOVSKY, HK_HOST_RANDOM_SPIVAKOVSKY = 6, 7  # hk_spivakovsky_select only (hironaka_hip_spivakovsky.h)
 HK_AGENT_RANDOM, HK_AGENT_RANDOM_LEGAL, HK_AGENT_CHOOSE_FIRST, HK_AGENT_CHOOSE_LAST = 0, 1, 2, 3
 
 # hk_search_depth / hk_search_game_tree status bits
@@ -753,16 +754,22 @@ UNIFIED_PROTOTYPES = {
     "hk_unified_pvnet_forward": (C.c_int, [C.POINTER(hk_pvnet_desc), _vp, C.c_int32, _vp]),
 }
 
+# the entry point of include/hironaka_hip_spivakovsky.h: the device library's only, as above
+SPIVAKOVSKY_PROTOTYPES = {
+    "hk_spivakovsky_select": (C.c_int, [_vp, _i64, _vp, _i, _i, _i, _i, _i, _u64, _u64, _u32, _vp]),
+}
+
 
 def bind(lib: C.CDLL, prototypes=None) -> None:
     """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES, TREE_PROTOTYPES, ENV_PROTOTYPES,
     REPLAY_PROTOTYPES, DQN_PROTOTYPES, OPTIM_PROTOTYPES, MLP_PROTOTYPES, MLP_TRAIN_PROTOTYPES, PVNET_PROTOTYPES,
-    PVLOSS_PROTOTYPES, PVGRAD_PROTOTYPES and UNIFIED_PROTOTYPES); raises AttributeError for a symbol the library lacks."""
+    PVLOSS_PROTOTYPES, PVGRAD_PROTOTYPES, UNIFIED_PROTOTYPES and SPIVAKOVSKY_PROTOTYPES); raises AttributeError for a
+    symbol the library lacks."""
     if prototypes is None:
         prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES, **TREE_PROTOTYPES, **ENV_PROTOTYPES,
                       **REPLAY_PROTOTYPES, **DQN_PROTOTYPES, **OPTIM_PROTOTYPES, **MLP_PROTOTYPES,
                       **MLP_TRAIN_PROTOTYPES, **PVNET_PROTOTYPES, **PVLOSS_PROTOTYPES,
-                      **PVGRAD_PROTOTYPES, **UNIFIED_PROTOTYPES}
+                      **PVGRAD_PROTOTYPES, **UNIFIED_PROTOTYPES, **SPIVAKOVSKY_PROTOTYPES}
     for name, (res, args) in prototypes.items():
         fn = getattr(lib, name)
         fn.restype = res

@@ -43,6 +43,7 @@ constexpr uint32_t kStreamGenerate = 1u;
 constexpr uint32_t kStreamMorinTie = 2u;               // hk_search_morin_play: the agent's random tie-break
 constexpr uint32_t kStreamPlayAgent = 3u;              // hk_game_play, hk_env_step: the random-legal agent
 constexpr uint32_t kStreamReplay = HK_REPLAY_STREAM;  // hk_replay_sample: the sample indices
+constexpr uint32_t kStreamRandomSpivakovsky = 5u;     // hk_spivakovsky_select: RandomSpivakovsky's pick
 
 // Kernel argument block (passed by value).  Union of what the modes need.
 struct Params {

@@ -1,6 +1,6 @@
 """Fixed hosts for the gym / game surfaces, vectorised over a batch of games -- the counterparts of
 ``hironaka/host.py`` (`Host.select_coord`, `RandomHost`, `AllCoordHost`, `Zeillinger`, `ZeillingerLex`,
-`WeakSpivakovsky`, `WeakSpivakovskyMinHitting`).
+`WeakSpivakovsky`, `WeakSpivakovskyMinHitting`, `Spivakovsky`, `RandomSpivakovsky`).
 
 ``select_coord(points)`` takes the padded state ``[B, m, d]`` (device tensor or a container with a
 ``.points`` attribute) and returns the chosen coordinate subsets as a multi-binary mask ``[B, d]``
@@ -8,6 +8,7 @@
 the reference's ``[]`` (host.py:78-80).
 """
 import abc
+import random
 from typing import Optional, Union
 
 import torch
@@ -114,6 +115,46 @@ class WeakSpivakovskyMinHitting(Host):
 
     def _select_coord(self, points: torch.Tensor) -> torch.Tensor:
         return _hk_host(points, "weak_spivakovsky_min_hitting")
+
+
+def _hk_mask_host(points: torch.Tensor, host: str, **draw) -> torch.Tensor:
+    """select_coord of a host of hk_spivakovsky_select (list semantics): its bit masks as a multi-binary mask"""
+    d = points.shape[2]
+    if d > MAX_HOST_DIM:
+        raise ValueError(f"{host} runs on the GPU for dimensions up to {MAX_HOST_DIM} (hk_spivakovsky_select). Got {d}.")
+    bits = ops.spivakovsky_select(points, host, **draw)
+    return (bits.unsqueeze(1) >> torch.arange(d, dtype=torch.int32, device=bits.device)) & 1
+
+
+class Spivakovsky(Host):
+    """host.py:130-290 -- Spivakovsky's host, the one the game was solved with (hk_spivakovsky_select): levels of
+    "move to the origin, take the coordinates of the nearest points, project", then a minimal permissible set.  The
+    subset may hold 0 or 1 coordinates, as the reference's does.  ``dim`` is accepted and ignored."""
+
+    def __init__(self, dim=16):
+        self.dim = dim
+
+    def _select_coord(self, points: torch.Tensor) -> torch.Tensor:
+        return _hk_mask_host(points, "spivakovsky")
+
+
+class RandomSpivakovsky(Host):
+    """host.py:293-354 -- one of the smallest hitting sets (>= 2 coordinates) of the points' supports, uniformly
+    (hk_spivakovsky_select).  The draws come from Philox keyed by ``seed`` (a fresh key when None), the game's number
+    ``game_offset + g`` and the number of the call, ``moves``, which every ``select_coord`` advances.  ``dim`` (the
+    width of the reference's subset table) is accepted and ignored: the candidates lie within the game's coordinates."""
+
+    def __init__(self, dim=16, seed: Optional[int] = None, game_offset: int = 0):
+        self.dim = dim
+        self.seed = (random.getrandbits(63) if seed is None else int(seed)) % 2 ** 64
+        self.game_offset = game_offset
+        self.moves = 0  # calls made: the move number in the host's counter
+
+    def _select_coord(self, points: torch.Tensor) -> torch.Tensor:
+        mask = _hk_mask_host(points, "random_spivakovsky", seed=self.seed, game_offset=self.game_offset,
+                             step=self.moves)
+        self.moves += 1
+        return mask
 
 
 class PolicyHost(Host):

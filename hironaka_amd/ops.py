@@ -315,6 +315,32 @@ def host_select(points: torch.Tensor, host: str, spec=None) -> torch.Tensor:
     return out
 
 
+# the hosts of hk_spivakovsky_select, which answers with bit masks: their subsets may hold fewer than 2 coordinates
+SPIVAKOVSKY_HOSTS = {"spivakovsky": A.HK_HOST_SPIVAKOVSKY, "random_spivakovsky": A.HK_HOST_RANDOM_SPIVAKOVSKY}
+
+
+def spivakovsky_select(points: torch.Tensor, host: str, spec=None, seed: int = 0, game_offset: int = 0,
+                       step: int = 0) -> torch.Tensor:
+    """The subset Spivakovsky's host (hironaka/host.py:130-290) or RandomSpivakovsky (host.py:293-354) picks per game,
+    in list semantics (hk_spivakovsky_select), as an int32 bit mask [B] (bit k <-> coordinate k).  "spivakovsky" may
+    give 0 or 1 coordinates, as the reference does; fewer than 2 points give 0, and so does "random_spivakovsky" on a
+    zero row.  "random_spivakovsky" draws candidate number (word * n) >> 32, word = the first word of the Philox block
+    (game_offset + g, step, stream 5) under seed; "spivakovsky" ignores the three.  dim 2..6, up to 64 points.
+    points: [B, m, d], or [B, stride] records with spec=(m, d)."""
+    if host not in SPIVAKOVSKY_HOSTS:
+        raise ValueError(f"host must be one of {sorted(SPIVAKOVSKY_HOSTS)}. Got {host!r}.")
+    if not (0 <= seed < 2 ** 64 and 0 <= game_offset < 2 ** 64 and 0 <= step < 2 ** 32):
+        raise ValueError(f"seed and game_offset must fit 64 bits, step 32. Got {seed}, {game_offset}, {step}.")
+    pts, _ = _state(points)
+    b, m, d, stride = _batch_spec(pts, spec)
+    out = torch.empty(b, dtype=torch.int32, device=pts.device)
+    with torch.cuda.device(pts.device):
+        check(lib().hk_spivakovsky_select(pts.data_ptr(), stride, out.data_ptr(), b, m, d, _TORCH2HK[pts.dtype],
+                                          SPIVAKOVSKY_HOSTS[host], seed, game_offset, step, _stream(pts)),
+              "hk_spivakovsky_select")
+    return out
+
+
 def get_features(points: torch.Tensor, scale_observation: bool = True, padding_value: float = -1.0,
                  spec=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """order_and_rescale (jax/util.py:186-197): [B, m*d] rows sorted descending, last coordinate

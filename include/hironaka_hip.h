@@ -646,5 +646,7 @@ int hk_search_morin_play(const hk_morin_play_desc* desc, void* stream);
 #include "hironaka_hip_pvgrad.h"
 /* within ABI 6: hk_unified_expand / hk_unified_prior / hk_unified_pvnet_forward, likewise */
 #include "hironaka_hip_unified.h"
+/* within ABI 6: hk_spivakovsky_select, likewise */
+#include "hironaka_hip_spivakovsky.h"
 
 #endif /* HIRONAKA_HIP_H */
