@@ -8,7 +8,9 @@ _LOSS = ("policy_value_loss", "compute_loss", "clip_log")
 _NETS = ("create_mlp", "expand_net_list", "FusedSequential", "fuse", "BaseFeaturesExtractor", "HostFeatureExtractor",
          "AgentFeatureExtractor")
 _HOSTS = ("Spivakovsky", "RandomSpivakovsky")
-__all__ = list(_VEC_ENVS) + ["ReplayBuffer"] + list(_DQN) + list(_OPTIM) + list(_LOSS) + list(_NETS) + list(_HOSTS)
+_TRAINERS = {"Trainer": "trainer", "DQNTrainer": "dqn_trainer"}
+__all__ = (list(_VEC_ENVS) + ["ReplayBuffer"] + list(_DQN) + list(_OPTIM) + list(_LOSS) + list(_NETS) + list(_HOSTS)
+           + list(_TRAINERS))
 
 
 def __getattr__(name):
@@ -34,4 +36,7 @@ def __getattr__(name):
     if name in _HOSTS:
         from . import host
         return getattr(host, name)
+    if name in _TRAINERS:
+        import importlib
+        return getattr(importlib.import_module(f".{_TRAINERS[name]}", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

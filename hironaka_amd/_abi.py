@@ -75,6 +75,9 @@ HK_ENV_MODE_HOST, HK_ENV_MODE_AGENT = 0, 1
 HK_ENV_SCALE_OBSERVATION, HK_ENV_STOP_AFTER_INVALID, HK_ENV_STOP_AT_THRESHOLD, HK_ENV_POINT_REDUCTION_REWARD = 1, 2, 4, 8
 HK_ENV_IMPROVE_EFFICIENCY, HK_ENV_AGENT_REPOSITION, HK_ENV_AUTO_RESET, HK_ENV_RESET_ALL = 16, 32, 64, 128
 
+# hk_dqn_agent_move: descriptor flags
+HK_DQN_MOVE_MASKED, HK_DQN_MOVE_RESCALE = 1, 2
+
 # hk_tree_expand: descriptor flags, the bit of its status word
 HK_TREE_REPOSITION, HK_TREE_ZERO_TAIL = 1, 2
 HK_TREE_OVERFLOW = 1
@@ -292,6 +295,42 @@ class hk_env_step_desc(C.Structure):
         ("agent", C.c_int32),
         ("max_value", C.c_int32),
         ("step_threshold", C.c_int32),
+        ("flags", C.c_uint32),
+    ]
+
+
+class hk_dqn_host_move_desc(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p),
+        ("q_stride", C.c_int64),
+        ("class_out", C.c_void_p),
+        ("coords_out", C.c_void_p),
+        ("prev_done", C.c_void_p),
+        ("counts", C.c_void_p),
+        ("batch", C.c_int32),
+        ("dim", C.c_int32),
+        ("q_dtype", C.c_int32),
+        ("coords_dtype", C.c_int32),
+    ]
+
+
+class hk_dqn_agent_move_desc(C.Structure):
+    _fields_ = [
+        ("points", C.c_void_p),
+        ("q", C.c_void_p),
+        ("q_stride", C.c_int64),
+        ("class_id", C.c_void_p),
+        ("axis_out", C.c_void_p),
+        ("features_out", C.c_void_p),
+        ("done_out", C.c_void_p),
+        ("lengths", C.c_void_p),
+        ("counts", C.c_void_p),
+        ("padding_value", C.c_double),
+        ("batch", C.c_int32),
+        ("max_points", C.c_int32),
+        ("dim", C.c_int32),
+        ("dtype", C.c_int32),
+        ("q_dtype", C.c_int32),
         ("flags", C.c_uint32),
     ]
 
@@ -759,17 +798,24 @@ SPIVAKOVSKY_PROTOTYPES = {
     "hk_spivakovsky_select": (C.c_int, [_vp, _i64, _vp, _i, _i, _i, _i, _i, _u64, _u64, _u32, _vp]),
 }
 
+# the entry points of include/hironaka_hip_dqn_move.h: the device library's only, as above
+DQN_MOVE_PROTOTYPES = {
+    "hk_dqn_host_move": (C.c_int, [C.POINTER(hk_dqn_host_move_desc), _vp]),
+    "hk_dqn_agent_move": (C.c_int, [C.POINTER(hk_dqn_agent_move_desc), _vp]),
+}
+
 
 def bind(lib: C.CDLL, prototypes=None) -> None:
     """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES, TREE_PROTOTYPES, ENV_PROTOTYPES,
     REPLAY_PROTOTYPES, DQN_PROTOTYPES, OPTIM_PROTOTYPES, MLP_PROTOTYPES, MLP_TRAIN_PROTOTYPES, PVNET_PROTOTYPES,
-    PVLOSS_PROTOTYPES, PVGRAD_PROTOTYPES, UNIFIED_PROTOTYPES and SPIVAKOVSKY_PROTOTYPES); raises AttributeError for a
-    symbol the library lacks."""
+    PVLOSS_PROTOTYPES, PVGRAD_PROTOTYPES, UNIFIED_PROTOTYPES, SPIVAKOVSKY_PROTOTYPES and DQN_MOVE_PROTOTYPES); raises
+    AttributeError for a symbol the library lacks."""
     if prototypes is None:
         prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES, **TREE_PROTOTYPES, **ENV_PROTOTYPES,
                       **REPLAY_PROTOTYPES, **DQN_PROTOTYPES, **OPTIM_PROTOTYPES, **MLP_PROTOTYPES,
                       **MLP_TRAIN_PROTOTYPES, **PVNET_PROTOTYPES, **PVLOSS_PROTOTYPES,
-                      **PVGRAD_PROTOTYPES, **UNIFIED_PROTOTYPES, **SPIVAKOVSKY_PROTOTYPES}
+                      **PVGRAD_PROTOTYPES, **UNIFIED_PROTOTYPES, **SPIVAKOVSKY_PROTOTYPES,
+                      **DQN_MOVE_PROTOTYPES}
     for name, (res, args) in prototypes.items():
         fn = getattr(lib, name)
         fn.restype = res

@@ -13,6 +13,7 @@ from typing import Callable, Optional, Tuple, Type, Union
 
 import torch
 
+from . import ops
 from .core import HipPoints
 from .host_action_preprocess import HostActionEncoder
 
@@ -35,6 +36,40 @@ class Timer:
             if self._cuda:
                 torch.cuda.current_stream().synchronize()
             self._log[self.name] += (time.perf_counter() - self._start) * 1000
+
+
+class GreedyBuffers:
+    """The caller-owned buffers of `FusedGame.greedy_move` for B games of [m, d] points: the host's class and subset,
+    the agent's axis, the features of the current state (`features`) and of the next (`next_features`; with
+    `double=False` the two are one tensor, which a captured move needs: it reads and writes fixed addresses), the done
+    flags, the lengths and -- `count_for` "host" / "agent" -- the action counts."""
+
+    def __init__(self, batch: int, max_num_points: int, dimension: int, dtype: torch.dtype, device,
+                 count_for: Optional[str] = None, double: bool = True):
+        assert count_for in (None, "host", "agent"), f"count_for must be None, 'host' or 'agent'. Got {count_for}."
+        new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)  # noqa: E731
+        self.class_id = new((batch,), torch.int32)
+        self.coords = new((batch, dimension), dtype)
+        self.axis = new((batch,), torch.int32)
+        self.features = new((batch, max_num_points, dimension), dtype)
+        self.next_features = new((batch, max_num_points, dimension), dtype) if double else self.features
+        self.done = new((batch,), torch.uint8)
+        self.lengths = new((batch,), torch.int32)
+        self.count_for = count_for
+        self.counts = None
+        if count_for is not None:
+            self.counts = new((2 ** dimension - dimension - 1 if count_for == "host" else dimension,), torch.int32)
+
+
+class EvalResult:
+    """What `FusedGame.evaluate` returns: lengths int32 [B] (moves played by each game: 0 for one that was over at the
+    start, `max_steps` for one that never ended), initial_done bool [B], counts int32 (the actions of the role
+    `count_for` over the moves of unfinished games) or None, and rho = (B - initial_done.sum()) / lengths.sum(), a 0-d
+    tensor (NaN for 0 / 0), the reference's `get_rho_for_pair`.  `fused`: whether the two kernels played."""
+
+    def __init__(self, lengths, initial_done, counts, fused: bool):
+        self.lengths, self.initial_done, self.counts, self.fused = lengths, initial_done, counts, fused
+        self.rho = (lengths.shape[0] - initial_done.sum()) / lengths.sum()
 
 
 class FusedGame:
@@ -181,6 +216,125 @@ class FusedGame:
             if inplace:
                 points.step(host_moves, actions, rescale=bool(scale_observation))
         return actions
+
+    # ---- greedy play: exploration off, nothing drawn, nothing read back ------------------------------------------------
+    def fused_eval_reason(self, points: HipPoints) -> Optional[str]:
+        """why `evaluate` cannot play `points` with hk_dqn_host_move / hk_dqn_agent_move (None: it can)"""
+        t = points.points
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            return f"the points live on {getattr(t, 'device', None)}, not on a HIP device"
+        if points.semantics != "torch":
+            return f"the points are in {points.semantics!r} semantics"
+        if t.dtype not in (torch.float32, torch.float64):
+            return f"the points are {t.dtype}"
+        if not 2 <= points.dimension <= ops.DQN_MOVE_MAX_DIM:
+            return f"dimension {points.dimension} is outside 2..{ops.DQN_MOVE_MAX_DIM}"
+        if not 1 <= t.shape[1] <= ops.DQN_MOVE_MAX_POINTS:
+            return f"{t.shape[1]} points per game are outside 1..{ops.DQN_MOVE_MAX_POINTS}"
+        if not points.padding_value < 0:
+            return f"the padding value {points.padding_value} is not negative"
+        return None
+
+    @staticmethod
+    def _q_values(q: torch.Tensor) -> torch.Tensor:
+        """a net's output as the kernels read it: float32 / float64 rows of unit stride"""
+        if q.dtype not in (torch.float32, torch.float64):
+            q = q.float()
+        return q if q.dim() == 2 and q.stride(1) == 1 and (q.shape[0] < 2 or q.stride(0) >= q.shape[1]) \
+            else q.contiguous()
+
+    def greedy_move(self, points: HipPoints, features: torch.Tensor, buffers: GreedyBuffers, *, masked=True,
+                    scale_observation=True, count_for: Optional[str] = None) -> torch.Tensor:
+        """One move of both players without exploration, in four launches when both nets are FusedSequential: the host
+        net on `features`, hk_dqn_host_move (class and subset into `buffers`), the agent net on
+        {"points": features, "coords": subset}, hk_dqn_agent_move (the move on `points` in place, the next features,
+        done flags, lengths and counts into `buffers`).  Any other nn.Module runs as it is between the same two
+        kernels.  `buffers.done` must hold the done flags of `points` (`evaluate` fills it before the first move).
+        `features` is normally `buffers.features`; the next state's land in `buffers.next_features`, the two swap, and
+        the new `buffers.features` is returned.  Needs `fused_eval_reason(points)` to be None."""
+        assert count_for == buffers.count_for, f"the buffers count for {buffers.count_for}, the call for {count_for}."
+        with torch.inference_mode():
+            host_q = self._q_values(self.host_net(features))
+            counting = count_for == "host"
+            ops.dqn_host_move(host_q, buffers.class_id, buffers.coords, prev_done=buffers.done if counting else None,
+                              counts=buffers.counts if counting else None)
+            agent_q = self._q_values(self.agent_net({"points": features, "coords": buffers.coords}))
+            ops.dqn_agent_move(points.points, agent_q, buffers.class_id, axis_out=buffers.axis,
+                               features_out=buffers.next_features, done_out=buffers.done, lengths=buffers.lengths,
+                               counts=buffers.counts if count_for == "agent" else None, masked=bool(masked),
+                               rescale=bool(scale_observation), padding_value=points.padding_value)
+        buffers.features, buffers.next_features = buffers.next_features, buffers.features
+        return buffers.features
+
+    def evaluate(self, points: HipPoints, max_steps: int, *, masked=True, scale_observation=True,
+                 count_for: Optional[str] = None, use_graph=False, force_torch=False) -> EvalResult:
+        """`max_steps` greedy moves of every game of `points` (moved in place), with the accounting of the reference's
+        `Trainer.get_rho_for_pair` kept on the device: see EvalResult.  count_for "host" / "agent": also count that
+        role's actions over the moves of unfinished games.  use_graph: one move is captured (a linear chain) and
+        replayed `max_steps` times.  Where `fused_eval_reason(points)` names a reason, or with `force_torch`, the moves
+        are `host_move` / `agent_move` with exploration_rate=0.0 -- which still draw `rand().le(0.0)` and so explore
+        with probability 2^-24 per row, while the kernels' path is exactly greedy.  Nothing here synchronises (the capture
+        of `use_graph` apart, which torch brackets with a synchronisation): no timer runs, whatever `log_time` says."""
+        assert count_for in (None, "host", "agent"), f"count_for must be None, 'host' or 'agent'. Got {count_for}."
+        if points.dtype != self.dtype:
+            points.type(self.dtype)
+        self.fused_eval_last_reason = "force_torch" if force_torch else self.fused_eval_reason(points)
+        log_time, self.log_time = self.log_time, False  # a running timer synchronises the stream
+        try:
+            if self.fused_eval_last_reason is not None:
+                return self._evaluate_torch(points, max_steps, masked, scale_observation, count_for)
+            b, m, d = points.points.shape
+            if not points.points.is_contiguous():
+                points.points = points.points.contiguous()
+            buf = GreedyBuffers(b, m, d, points.points.dtype, points.points.device, count_for, double=not use_graph)
+            initial_done = ops.get_dones(points.points)
+            buf.done.copy_(initial_done)
+            buf.features.copy_(points.get_features())
+            move = lambda: self.greedy_move(points, buf.features, buf, masked=masked,  # noqa: E731
+                                            scale_observation=scale_observation, count_for=count_for)
+            if use_graph and max_steps > 0:
+                # the first move runs eagerly on a side stream (the nets build their tables, the allocator warms up);
+                # the capture of the second plays nothing itself: it is replayed for every move that remains
+                side = torch.cuda.Stream(device=points.points.device)
+                side.wait_stream(torch.cuda.current_stream(points.points.device))
+                with torch.cuda.stream(side):
+                    move()
+                torch.cuda.current_stream(points.points.device).wait_stream(side)
+                if max_steps > 1:
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph):
+                        move()
+                    for _ in range(max_steps - 1):
+                        graph.replay()
+            else:
+                for _ in range(max_steps):
+                    move()
+            return EvalResult(buf.lengths, initial_done, buf.counts, True)
+        finally:
+            self.log_time = log_time
+
+    def _evaluate_torch(self, points: HipPoints, max_steps: int, masked, scale_observation, count_for) -> EvalResult:
+        """`evaluate` through `host_move` / `agent_move`, the features computed once per state"""
+        dev = points.points.device
+        b, d = points.batch_size, points.dimension
+        done = points.ended_batch_in_tensor
+        initial_done = done.clone()
+        lengths = torch.zeros(b, dtype=torch.int32, device=dev)
+        counts = None
+        if count_for is not None:
+            counts = torch.zeros(2 ** d - d - 1 if count_for == "host" else d, dtype=torch.int32, device=dev)
+        features = points.get_features()
+        for _ in range(max_steps):
+            host_move, classes = self.host_move(points, exploration_rate=0.0, features=features)
+            axes = self.agent_move(points, host_move, masked=masked, scale_observation=scale_observation, inplace=True,
+                                   exploration_rate=0.0, features=features)
+            playing = (~done).to(torch.int32)
+            lengths += playing
+            if counts is not None:
+                counts.index_add_(0, (classes if count_for == "host" else axes).to(torch.int64), playing)
+            done = points.ended_batch_in_tensor
+            features = points.get_features()
+        return EvalResult(lengths, initial_done, counts, False)
 
     def _make_type_for_nets(self, dtype: torch.dtype):
         """a net whose parameters have another dtype is copied and recast (the caller's stays untouched)"""

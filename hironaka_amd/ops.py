@@ -1141,6 +1141,127 @@ def env_step(points: torch.Tensor, *, mode: str, step_count: torch.Tensor, episo
         check(lib().hk_env_step(C.byref(q), _stream(points)), "hk_env_step")
 
 
+# ---- one greedy move of the DQN evaluation (hk_dqn_host_move / hk_dqn_agent_move) -------------------------------------
+
+DQN_MOVE_MAX_DIM, DQN_MOVE_MAX_POINTS = 7, 64
+
+
+def _q_rows(q: torch.Tensor, name: str, rows: int, width: int, dev) -> int:
+    """the row stride of the Q-values [rows, width] of a network: float32/float64, rows of unit stride any distance
+    apart (a slice of a wider output is read in place)"""
+    _require_device(q, name)
+    if q.dtype not in (torch.float32, torch.float64) or tuple(q.shape) != (rows, width) or q.device != dev:
+        raise ValueError(f"{name} must be a float32/float64 tensor of shape ({rows}, {width}) on {dev}. Got {q.dtype} "
+                         f"{tuple(q.shape)} on {q.device}.")
+    if q.stride(1) != 1 or (rows > 1 and q.stride(0) < width):
+        raise ValueError(f"{name} must have rows of unit stride that do not overlap. Got strides {q.stride()}.")
+    return q.stride(0) if rows > 1 else width
+
+
+def _shares_memory(x: Optional[torch.Tensor], y: Optional[torch.Tensor]) -> bool:
+    """whether the byte ranges from the first to the last element of two tensors meet"""
+    def span(t):
+        last = sum((n - 1) * s for n, s in zip(t.shape, t.stride()))
+        return t.data_ptr(), t.data_ptr() + (last + 1) * t.element_size()
+    if x is None or y is None or not x.numel() or not y.numel():
+        return False
+    (x0, x1), (y0, y1) = span(x), span(y)
+    return x0 < y1 and y0 < x1
+
+
+def _no_shared_memory(written: Dict[str, Optional[torch.Tensor]], read: Dict[str, Optional[torch.Tensor]]) -> None:
+    names = list(written)
+    for i, a in enumerate(names):
+        for b in names[i + 1:]:
+            if _shares_memory(written[a], written[b]):
+                raise ValueError(f"{a} and {b} are both written and must not share memory.")
+        for b, t in read.items():
+            if _shares_memory(written[a], t):
+                raise ValueError(f"{a} is written and must not share memory with {b}.")
+
+
+def dqn_host_move(q: torch.Tensor, class_out: torch.Tensor, coords_out: torch.Tensor, *,
+                  prev_done: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None) -> None:
+    """The host's greedy move from its Q-values in one launch (hk_dqn_host_move, include/hironaka_hip_dqn_move.h):
+    class_out[b] = torch.argmax(q[b]) (the first maximum; the first NaN wins) and coords_out[b] = the class's subset as
+    0/1 values, what FusedGame.host_move returns with exploration off.  Every tensor is a buffer the caller owns, used in
+    place; nothing is allocated.
+
+    q [B, 2^d - d - 1] float32/float64, rows of unit stride at any distance; class_out int32 [B]; coords_out [B, d]
+    float32/float64, contiguous; d in 2..7.  prev_done uint8 [B] and counts int32 [2^d - d - 1], both or neither:
+    counts[class_out[b]] += 1 for every b with prev_done[b] == 0."""
+    _require_device(coords_out, "coords_out")
+    if coords_out.dim() != 2 or coords_out.dtype not in (torch.float32, torch.float64) or not coords_out.is_contiguous():
+        raise ValueError(f"coords_out must be a contiguous float32/float64 [B, dim] tensor. Got {coords_out.dtype} "
+                         f"{tuple(coords_out.shape)}, contiguous: {coords_out.is_contiguous()}.")
+    b, d = coords_out.shape
+    dev = coords_out.device
+    if not (2 <= d <= DQN_MOVE_MAX_DIM and b < 2 ** 31):
+        raise ValueError(f"hk_dqn_host_move serves dim 2..{DQN_MOVE_MAX_DIM} and fewer than 2^31 games. Got {(b, d)}.")
+    classes = 2 ** d - d - 1
+    if (prev_done is None) != (counts is None):
+        raise ValueError("prev_done and counts go together: pass both or neither.")
+    s = A.hk_dqn_host_move_desc()
+    s.q_stride = _q_rows(q, "q", b, classes, dev)
+    s.q = q.data_ptr()
+    s.class_out = _env_buffer(class_out, "class_out", torch.int32, (b,), dev)
+    s.coords_out = coords_out.data_ptr()
+    s.prev_done = _env_buffer(prev_done, "prev_done", torch.uint8, (b,), dev, optional=True)
+    s.counts = _env_buffer(counts, "counts", torch.int32, (classes,), dev, optional=True)
+    _no_shared_memory({"class_out": class_out, "coords_out": coords_out, "counts": counts},
+                      {"q": q, "prev_done": prev_done})
+    s.batch, s.dim, s.q_dtype, s.coords_dtype = b, d, _TORCH2HK[q.dtype], _TORCH2HK[coords_out.dtype]
+    with torch.cuda.device(dev):
+        check(lib().hk_dqn_host_move(C.byref(s), _stream(coords_out)), "hk_dqn_host_move")
+
+
+def dqn_agent_move(points: torch.Tensor, q: torch.Tensor, class_id: torch.Tensor, *, axis_out: torch.Tensor,
+                   features_out: torch.Tensor, done_out: torch.Tensor, lengths: torch.Tensor,
+                   counts: Optional[torch.Tensor] = None, masked: bool = True, rescale: bool = True,
+                   padding_value: float = -1.0) -> None:
+    """The agent's greedy move from its Q-values, the move itself and the next observation in one launch
+    (hk_dqn_agent_move, include/hironaka_hip_dqn_move.h): what FusedGame.agent_move does with exploration off
+    (``masked``: the argmax over the host's subset by fused_game's expression), then ``get_features`` and ``get_dones``
+    of the new state.  Every tensor is a buffer the caller owns, used in place; nothing is allocated.
+
+    points [B, m, d] float32/float64, contiguous, moved in place (torch semantics: shift unless the axis lies outside the
+    subset or the game is over, Newton polytope, ``rescale``); q [B, d] float32/float64, rows of unit stride at any
+    distance; class_id int32 [B], the host's class; axis_out int32 [B]; features_out [B, m, d] of the points' dtype;
+    done_out uint8 [B]; lengths int32 [B], += 1 for every game that was not over before the move; counts int32 [d]
+    (optional), += 1 at the axis of each such game.  d in 2..7, m <= 64, padding_value negative."""
+    _require_device(points, "points")
+    if points.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"points must be float32 or float64. Got {points.dtype}.")
+    if points.dim() != 3 or not points.is_contiguous():
+        raise ValueError(f"points must be a contiguous [B, max_points, dim]. Got shape {tuple(points.shape)}, "
+                         f"strides {points.stride()}.")
+    b, m, d = points.shape
+    dev = points.device
+    if not (2 <= d <= DQN_MOVE_MAX_DIM and 1 <= m <= DQN_MOVE_MAX_POINTS and b < 2 ** 31):
+        raise ValueError(f"hk_dqn_agent_move serves dim 2..{DQN_MOVE_MAX_DIM}, max_points 1..{DQN_MOVE_MAX_POINTS} and "
+                         f"fewer than 2^31 games. Got {(b, m, d)}.")
+    if not padding_value < 0:
+        raise ValueError(f"padding_value must be negative. Got {padding_value}.")
+    s = A.hk_dqn_agent_move_desc()
+    s.points = points.data_ptr()
+    s.q_stride = _q_rows(q, "q", b, d, dev)
+    s.q = q.data_ptr()
+    s.class_id = _env_buffer(class_id, "class_id", torch.int32, (b,), dev)
+    s.axis_out = _env_buffer(axis_out, "axis_out", torch.int32, (b,), dev)
+    s.features_out = _env_buffer(features_out, "features_out", points.dtype, (b, m, d), dev)
+    s.done_out = _env_buffer(done_out, "done_out", torch.uint8, (b,), dev)
+    s.lengths = _env_buffer(lengths, "lengths", torch.int32, (b,), dev)
+    s.counts = _env_buffer(counts, "counts", torch.int32, (d,), dev, optional=True)
+    _no_shared_memory({"points": points, "features_out": features_out, "axis_out": axis_out, "done_out": done_out,
+                       "lengths": lengths, "counts": counts}, {"q": q, "class_id": class_id})
+    s.padding_value = float(padding_value)
+    s.batch, s.max_points, s.dim = b, m, d
+    s.dtype, s.q_dtype = _TORCH2HK[points.dtype], _TORCH2HK[q.dtype]
+    s.flags = (A.HK_DQN_MOVE_MASKED if masked else 0) | (A.HK_DQN_MOVE_RESCALE if rescale else 0)
+    with torch.cuda.device(dev):
+        check(lib().hk_dqn_agent_move(C.byref(s), _stream(points)), "hk_dqn_agent_move")
+
+
 # ---- the replay buffer as a ring on the device (hk_replay_push / hk_replay_sample) ---------------------------------
 
 REPLAY_TILE_ROWS = A.HK_REPLAY_TILE_ROWS

@@ -648,5 +648,7 @@ int hk_search_morin_play(const hk_morin_play_desc* desc, void* stream);
 #include "hironaka_hip_unified.h"
 /* within ABI 6: hk_spivakovsky_select, likewise */
 #include "hironaka_hip_spivakovsky.h"
+/* within ABI 6: hk_dqn_host_move / hk_dqn_agent_move, likewise */
+#include "hironaka_hip_dqn_move.h"
 
 #endif /* HIRONAKA_HIP_H */
