@@ -118,6 +118,9 @@ HK_PVNET_RAW_VALUE, HK_PVNET_FORCE_TILE_SMALL, HK_PVNET_FORCE_TILE_LARGE = 1, 2,
 HK_PVLOSS_TILE_ROWS, HK_PVLOSS_MAX_ACTIONS, HK_PVLOSS_BAD_INDEX = 16, 255, 1
 # hk_pvgrad_forward / hk_pvgrad_backward: the largest batch (the 16-row tile's range), Denses per parameter-gradient launch
 HK_PVGRAD_MAX_BATCH, HK_PVGRAD_TABLE = 4096, 40
+# hk_customnet_forward: the most points, and the descriptor flags (hk_pvnet_forward's)
+HK_CUSTOMNET_MAX_POINTS = 64
+HK_CUSTOMNET_RAW_VALUE, HK_CUSTOMNET_FORCE_TILE_SMALL, HK_CUSTOMNET_FORCE_TILE_LARGE = 1, 2, 4
 PVNET_NORMED_WIDTHS = (32, 64, 128, 256)  # the widths of a normed layer the kernel serves (1, 2, 4, 8 columns per group)
 
 SEMANTICS = {"jax": HK_SEM_JAX, "torch": HK_SEM_TORCH, "list": HK_SEM_LIST}
@@ -604,6 +607,35 @@ class hk_pvnet_desc(C.Structure):
     ]
 
 
+class hk_customnet_desc(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p),
+        ("policy", C.c_void_p),
+        ("value", C.c_void_p),
+        ("towers", C.c_void_p),
+        ("policy_weight", C.c_void_p),
+        ("policy_bias", C.c_void_p),
+        ("value_weight", C.c_void_p),
+        ("value_bias", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("gate", C.c_void_p),
+        ("workspace_bytes", C.c_uint64),
+        ("x_stride", C.c_int64),
+        ("policy_stride", C.c_int64),
+        ("value_stride", C.c_int64),
+        ("batch", C.c_int32),
+        ("m", C.c_int32),
+        ("d", C.c_int32),
+        ("e", C.c_int32),
+        ("nblocks", C.c_int32),
+        ("n_last", C.c_int32),
+        ("actions", C.c_int32),
+        ("want", C.c_int32),
+        ("dtype", C.c_int32),
+        ("flags", C.c_uint32),
+    ]
+
+
 class hk_pvgrad_dense(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("d_weight", "d_bias", "d_gn_scale", "d_gn_bias")]
 
@@ -773,6 +805,12 @@ PVNET_PROTOTYPES = {
     "hk_pvnet_forward": (C.c_int, [C.POINTER(hk_pvnet_desc), _vp]),
 }
 
+# the entry points of include/hironaka_hip_customnet.h: the device library's only, as above
+CUSTOMNET_PROTOTYPES = {
+    "hk_customnet_workspace_bytes": (C.c_uint64, [_i64, C.c_int32]),
+    "hk_customnet_forward": (C.c_int, [C.POINTER(hk_customnet_desc), _vp]),
+}
+
 # the entry points of include/hironaka_hip_pvloss.h: the device library's only, as above
 PVLOSS_PROTOTYPES = {
     "hk_pv_loss_workspace_bytes": (C.c_uint64, [_i]),
@@ -808,12 +846,12 @@ DQN_MOVE_PROTOTYPES = {
 def bind(lib: C.CDLL, prototypes=None) -> None:
     """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES, TREE_PROTOTYPES, ENV_PROTOTYPES,
     REPLAY_PROTOTYPES, DQN_PROTOTYPES, OPTIM_PROTOTYPES, MLP_PROTOTYPES, MLP_TRAIN_PROTOTYPES, PVNET_PROTOTYPES,
-    PVLOSS_PROTOTYPES, PVGRAD_PROTOTYPES, UNIFIED_PROTOTYPES, SPIVAKOVSKY_PROTOTYPES and DQN_MOVE_PROTOTYPES); raises
+    CUSTOMNET_PROTOTYPES, PVLOSS_PROTOTYPES, PVGRAD_PROTOTYPES, UNIFIED_PROTOTYPES, SPIVAKOVSKY_PROTOTYPES and DQN_MOVE_PROTOTYPES); raises
     AttributeError for a symbol the library lacks."""
     if prototypes is None:
         prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES, **TREE_PROTOTYPES, **ENV_PROTOTYPES,
                       **REPLAY_PROTOTYPES, **DQN_PROTOTYPES, **OPTIM_PROTOTYPES, **MLP_PROTOTYPES,
-                      **MLP_TRAIN_PROTOTYPES, **PVNET_PROTOTYPES, **PVLOSS_PROTOTYPES,
+                      **MLP_TRAIN_PROTOTYPES, **PVNET_PROTOTYPES, **CUSTOMNET_PROTOTYPES, **PVLOSS_PROTOTYPES,
                       **PVGRAD_PROTOTYPES, **UNIFIED_PROTOTYPES, **SPIVAKOVSKY_PROTOTYPES,
                       **DQN_MOVE_PROTOTYPES}
     for name, (res, args) in prototypes.items():

@@ -106,24 +106,16 @@ __device__ __forceinline__ void pvnet_store(const typename MlpTile<TR>::Acc& acc
   }
 }
 
-// the whole forward of a workgroup's row tile: the body of pvnet_kernel and of pvnet_gated_kernel
+// the trunk on a workgroup's row tile: the `nblocks` blocks of `blocks` (a kernel argument's table or one in device
+// memory) on the rows in `cur`; the result is in `cur` when it returns (a dense block swaps the panels).  The one copy of
+// the block loop: pvnet_tile's and hk::customnet_kernel's (hk_customnet_kernel.h)
 template <int TR>
-__device__ __forceinline__ void pvnet_tile(const hk_pvnet_desc& q) {
+__device__ __forceinline__ void pvnet_trunk(const hk_pvnet_block* blocks, int nblocks, float*& cur, float*& nxt,
+                                            float* const wst, typename MlpTile<TR>::Acc& acc, int tid) {
   typedef MlpTile<TR> T;
-  extern __shared__ __align__(16) float hk_pvnet_lds[];
-  float* cur = hk_pvnet_lds;
-  float* nxt = cur + TR * kMlpLda;
-  float* const wst = nxt + TR * kMlpLda;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
-  const int lm = lane & 15, lg = lane >> 4;
-  const int64_t row0 = (int64_t)blockIdx.x * TR;
-
   auto f = [](const void* p) { return static_cast<const float*>(p); };
-  mlp_load_rows<TR, false>(cur, MlpInput{f(q.x), nullptr, q.x_stride, 0, q.k0}, row0, q.batch, tid);
-
-  typename T::Acc acc;
-  for (int l = 0; l < q.nblocks; ++l) {
-    const hk_pvnet_block& B = q.block[l];
+  for (int l = 0; l < nblocks; ++l) {
+    const hk_pvnet_block& B = blocks[l];
     const int K = B.k, N = B.n;
     if (B.kind == HK_PVNET_DENSE) {
       mlp_dense<TR, false>(acc, cur, wst, f(B.dense1.weight), f(B.dense1.bias), nullptr, nullptr, K, N, tid);
@@ -151,6 +143,25 @@ __device__ __forceinline__ void pvnet_tile(const hk_pvnet_desc& q) {
     pvnet_group_norm<TR>(acc, B.dense2, B.eps, N, tid);
     pvnet_store<TR, true>(acc, cur, N, tid, o, proj);
   }
+}
+
+// the whole forward of a workgroup's row tile: the body of pvnet_kernel and of pvnet_gated_kernel
+template <int TR>
+__device__ __forceinline__ void pvnet_tile(const hk_pvnet_desc& q) {
+  typedef MlpTile<TR> T;
+  extern __shared__ __align__(16) float hk_pvnet_lds[];
+  float* cur = hk_pvnet_lds;
+  float* nxt = cur + TR * kMlpLda;
+  float* const wst = nxt + TR * kMlpLda;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+  const int lm = lane & 15, lg = lane >> 4;
+  const int64_t row0 = (int64_t)blockIdx.x * TR;
+
+  auto f = [](const void* p) { return static_cast<const float*>(p); };
+  mlp_load_rows<TR, false>(cur, MlpInput{f(q.x), nullptr, q.x_stride, 0, q.k0}, row0, q.batch, tid);
+
+  typename T::Acc acc;
+  pvnet_trunk<TR>(q.block, q.nblocks, cur, nxt, wst, acc, tid);
 
   // the heads: columns 0 .. actions - 1 the policy, column `actions` the value
   const int K = q.block[q.nblocks - 1].n, A = q.actions, NT = (A + 16) >> 4;

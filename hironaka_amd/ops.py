@@ -2160,7 +2160,8 @@ class PvnetPlan:
     bias [1] or None).  The table points at the tensors it was given: whoever swaps a tensor for another builds a new plan
     (hironaka_amd.net.DenseResNet does, by the addresses of the tensors its modules hold at each call)."""
 
-    def __init__(self, blocks: Sequence[PvnetBlock], policy, value):
+    def __init__(self, blocks: Sequence[PvnetBlock], policy, value, *, _head_extra: int = 0):
+        # (_head_extra: CustomnetPlan's heads, which read that many features behind the trunk's result)
         blocks = [b if isinstance(b, PvnetBlock) else PvnetBlock(*b) for b in blocks]
         if not 1 <= len(blocks) <= A.HK_PVNET_MAX_BLOCKS:
             raise ValueError(f"1 to {A.HK_PVNET_MAX_BLOCKS} blocks. Got {len(blocks)}.")
@@ -2208,6 +2209,7 @@ class PvnetPlan:
         actions = policy[0].shape[0] if isinstance(policy[0], torch.Tensor) and policy[0].dim() == 2 else 0
         if not 1 <= actions <= A.HK_PVNET_MAX_WIDTH - 1:
             raise ValueError(f"the policy head must have 1 to {A.HK_PVNET_MAX_WIDTH - 1} outputs. Got {actions}.")
+        self.n_last, width = width, width + int(_head_extra)
         for name, (weight, bias), n in (("policy", policy, actions), ("value", value, 1)):
             if not isinstance(weight, torch.Tensor) or tuple(weight.shape) != (n, width):
                 raise ValueError(f"{name}[0] must be a [{n}, {width}] tensor.")
@@ -2276,6 +2278,121 @@ def pvnet_forward(x: torch.Tensor, plan: PvnetPlan, tile: Optional[int] = None, 
         else:
             check(lib().hk_unified_pvnet_forward(C.byref(d), word.data_ptr(), int(want), _stream(policy)),
                   "hk_unified_pvnet_forward")
+    return policy, value
+
+
+# ---- the gradient-free forward of CustomNet: one tower per row, chosen by its point count (hironaka_hip_customnet.h) --------
+
+class CustomnetPlan:
+    """The tower table of customnet_forward in device memory, the heads and the workspace, built once per set of parameter
+    addresses (it holds the tensors alive).  `towers`: m sequences of PvnetBlock, tower t for the rows with t points -- its
+    first block takes (t + 1) * d + e inputs, every tower has the same number of blocks, kinds and output widths; `policy`
+    / `value`: the heads' (weight [A, n_last + e], bias or None) and (weight [1, n_last + e], bias or None); `spec`:
+    (m, d); `extra_dim`: e.  Every record is checked against pvnet_forward's rules here, once: the library cannot read
+    the table (include/hironaka_hip_customnet.h).  The workspace grows with the batches the plan is called on."""
+
+    def __init__(self, towers, policy, value, spec: Tuple[int, int], extra_dim: int):
+        m, d = (int(v) for v in spec)
+        e = int(extra_dim)
+        towers = [list(t) for t in towers]
+        if not 1 <= m <= A.HK_CUSTOMNET_MAX_POINTS or d < 2 or e < 0 or m * d + e > A.HK_PVNET_MAX_WIDTH:
+            raise ValueError(f"1 to {A.HK_CUSTOMNET_MAX_POINTS} points of at least 2 coordinates and m * d + e <= "
+                             f"{A.HK_PVNET_MAX_WIDTH}. Got m={m}, d={d}, e={e}.")
+        if len(towers) != m:
+            raise ValueError(f"one tower per point count: {m}. Got {len(towers)}.")
+        plans = [PvnetPlan(t, policy, value, _head_extra=e) for t in towers]
+        shapes = [[(b.kind, b.n) for b in p.desc.block[: p.desc.nblocks]] for p in plans]
+        if any(s != shapes[0] for s in shapes):
+            raise ValueError("every tower must have the same blocks: kinds and output widths.")
+        for t, p in enumerate(plans):
+            if p.k_in != (t + 1) * d + e:
+                raise ValueError(f"towers[{t}] must take {(t + 1) * d + e} inputs. Got {p.k_in}.")
+        first = plans[0]
+        if first.n_last + e > A.HK_PVNET_MAX_WIDTH:
+            raise ValueError(f"n_last + e must be at most {A.HK_PVNET_MAX_WIDTH}. Got {first.n_last} + {e}.")
+        self.device = dev = first.device
+        self.tensors = [t for p in plans for t in p.tensors]
+        self.m, self.d, self.e, self.k_in, self.actions = m, d, e, m * d + e, first.actions
+        nblocks = first.desc.nblocks
+        table = (A.hk_pvnet_block * (m * nblocks))()
+        for t, p in enumerate(plans):
+            for l in range(nblocks):
+                table[t * nblocks + l] = p.desc.block[l]
+        # (the copy is ordered with the stream that is current now, as every later launch on it is)
+        self.table = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+        self.desc = q = A.hk_customnet_desc()
+        q.towers = self.table.data_ptr()
+        for name in ("policy_weight", "policy_bias", "value_weight", "value_bias"):
+            setattr(q, name, getattr(first.desc, name))
+        q.m, q.d, q.e, q.nblocks, q.n_last, q.actions, q.dtype = m, d, e, nblocks, first.n_last, first.actions, A.HK_F32
+        self.workspace, self._retired = None, []
+
+    def workspace_for(self, batch: int) -> torch.Tensor:
+        """the workspace for a call on `batch` rows, allocated (for twice the rows) and zeroed where the one at hand is
+        too small -- not inside a graph capture: call this, or the forward, once before"""
+        need = int(lib().hk_customnet_workspace_bytes(batch, self.m))
+        if self.workspace is None or self.workspace.numel() * 8 < need:
+            # room for twice the rows: a batch that grows a little does not allocate again.  A workspace that is replaced
+            # stays alive with the plan: a captured graph may still point at it
+            if self.workspace is not None:
+                self._retired.append(self.workspace)
+            words = (int(lib().hk_customnet_workspace_bytes(2 * batch, self.m)) + 15) // 16
+            # (zeroed once: the library's counters at its head, which every call leaves zero)
+            self.workspace = torch.zeros((words, 2), dtype=torch.int64, device=self.device)
+        return self.workspace
+
+
+def customnet_forward(x: torch.Tensor, plan: CustomnetPlan, tile: Optional[int] = None, raw_value: bool = False,
+                      gate: Optional[Tuple[torch.Tensor, int]] = None,
+                      out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """The forward of CustomNet in two launches (hk_customnet_forward; the rule, to the bit, is in
+    include/hironaka_hip_customnet.h): the rows are grouped by their point count and every row runs the ONE tower its count
+    names, then the heads.  x: [B, ...] float32 rows of m * d + e features (flattened behind the batch dimension; the rows
+    may lie any number of elements apart -- a column slice of a wider buffer).  Returns (policy [B, A], value [B]).  out:
+    (policy, value) to write into, as pvnet_forward's; tile, raw_value and gate as pvnet_forward's.  The plan's workspace
+    is used by the call: calls on one plan belong on one stream.  Inside a graph capture a call must find the plan built and
+    its workspace large enough: building a plan copies the table to the device and a batch that outgrows the workspace
+    allocates and zeroes a new one, neither of which belongs in a capture -- make a call of the largest batch (or
+    `plan.workspace_for(batch)`) before capturing, as the search loops' warm-up does.  That no TOWER parameter shares a
+    byte with policy or value is not checked (the library checks x, the heads, the table and the workspace against them).
+    Everything is float32 on one HIP device (a TypeError otherwise).  Nothing here synchronises."""
+    if not isinstance(plan, CustomnetPlan):
+        raise TypeError(f"plan must be a CustomnetPlan. Got {type(plan).__name__}.")
+    policy, value = out if out is not None else (None, None)
+    word, want = None, 0
+    if gate is not None:
+        word, want = gate
+        _require_device(word, "gate[0]")
+        if word.dtype != torch.int32 or word.numel() != 1 or word.device != plan.device:
+            raise TypeError(f"gate[0] must be an int32 tensor of one element on {plan.device}. "
+                            f"Got {word.dtype} {tuple(word.shape)} on {word.device}.")
+    tile_flag = _mlp_tile_flag(tile)
+    dev = plan.device
+    x = _mlp_rows(x, "x", dev)
+    batch, k = x.shape
+    if k != plan.k_in:
+        raise ValueError(f"the rows have {plan.k_in} features ({plan.m} points of {plan.d} and {plan.e} more). Got {k}.")
+    _mlp_batch_limit(batch)
+    a = plan.actions
+    for name, given, shape in (("policy", policy, (batch, a)), ("value", value, (batch,))):
+        if given is not None:
+            _mlp_given_out(given, name, dev, shape)
+    if policy is None:
+        policy = torch.empty((batch, a), dtype=torch.float32, device=dev)
+    if value is None:
+        value = torch.empty((batch,), dtype=torch.float32, device=dev)
+    if batch == 0:
+        return policy, value
+    workspace = plan.workspace_for(batch)
+    q = plan.desc
+    q.x, q.x_stride, q.batch = x.data_ptr(), x.stride(0) if batch > 1 else k, batch
+    q.policy, q.policy_stride = policy.data_ptr(), policy.stride(0) if batch > 1 else a
+    q.value, q.value_stride = value.data_ptr(), value.stride(0) if batch > 1 else 1
+    q.workspace, q.workspace_bytes = workspace.data_ptr(), workspace.numel() * 8
+    q.gate, q.want = (word.data_ptr(), int(want)) if word is not None else (None, 0)
+    q.flags = tile_flag | (A.HK_CUSTOMNET_RAW_VALUE if raw_value else 0)
+    with torch.cuda.device(dev):
+        check(lib().hk_customnet_forward(C.byref(q), _stream(policy)), "hk_customnet_forward")
     return policy, value
 
 

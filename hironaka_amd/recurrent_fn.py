@@ -235,8 +235,8 @@ class UnifiedExpander:
         -> agent network where the kind is 1, host network where it is 0 -> hk_unified_prior (masked, padded selection)
 
     A model is GATEABLE when it is one of HipTrainer's wrappers of a network it built itself (``model.module`` is a
-    ``net.DenseResNet``) whose ``fused_reason`` is None: its launch is hk_unified_pvnet_forward, which returns at once
-    where the kind is the other one, so an expansion costs one network, not two.  Any other callable
+    ``net.DenseResNet`` or a ``net.CustomNet``) whose ``fused_reason`` is None: its launch is hk_unified_pvnet_forward (the
+    two launches of hk_customnet_forward with its gate for a CustomNet), which returns at once where the kind is the other one, so an expansion costs one network, not two.  Any other callable
     (``trainer_api.standin_mlp`` among them) is opaque: BOTH networks run on every expansion and hk_unified_prior takes
     the one the kind names.  Results are identical to the generic path (tests/test_gpu_unified_search.py)."""
 
@@ -257,9 +257,9 @@ class UnifiedExpander:
     @staticmethod
     def _plan(model):
         """the block table of a gateable model, None for any other callable"""
-        from .net import DenseResNet
+        from .net import CustomNet, DenseResNet
         module = getattr(model, "module", None)
-        if not isinstance(module, DenseResNet):
+        if not isinstance(module, (DenseResNet, CustomNet)):
             return None
         with torch.no_grad():  # as the wrapper calls it
             if module.fused_reason is not None or module.Dense_0.weight.device.type != "cuda":
@@ -297,7 +297,8 @@ class UnifiedExpander:
             logits, value = state[name + "_logits"], state[name + "_value"]
             plan = self._plan(model)
             if plan is not None:
-                ops.pvnet_forward(x, plan, gate=(kind, want), out=(logits, value))
+                forward = ops.customnet_forward if isinstance(plan, ops.CustomnetPlan) else ops.pvnet_forward
+                forward(x, plan, gate=(kind, want), out=(logits, value))
             else:  # an opaque callable: it runs whatever the kind is
                 logits, value = model(x.contiguous(), model_params)
                 logits = logits.to(torch.float32).contiguous()

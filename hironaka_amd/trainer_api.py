@@ -20,7 +20,9 @@ through the network are then ``hk_pvgrad_forward`` / ``hk_pvgrad_backward`` inst
 rank is refused (the mean of the gradients over the ranks is not built).  The networks' FORWARD is here: where the config
 has a ``host`` / ``agent`` section with ``net_arch`` and ``net_type`` is ``dense`` or ``dense_resnet``, the trainer builds
 ``hironaka_amd.net``'s modules as JAXTrainer builds flax's (jax_trainer.py:216-218; ``built_nets[role]``) and calls them
-under ``torch.no_grad()``.  Otherwise the two networks arrive as callables
+under ``torch.no_grad()``.  With ``HipTrainer(..., custom_net=True)`` the net types ``custom`` / ``custom_dense`` build
+``hironaka_amd.net.CustomNet`` the same way (off by default: without the flag both raise as before; ``train`` runs it
+through torch autograd, ``fused_training`` has no effect on it).  Otherwise the two networks arrive as callables
 ``net(features, params) -> (policy_logits [B, A], value [B])`` together with their parameter objects
 (``host_params`` / ``agent_params``: opaque, handed back to the callables) -- the role ``model.apply`` plays in
 ``get_apply_fn`` (hironaka/jax/net.py:110-133); the feature transform in front of them (rescale + row sort,
@@ -171,7 +173,8 @@ class HipTrainer:
                  host_net: Optional[Callable] = None, agent_net: Optional[Callable] = None,
                  host_params: Any = None, agent_params: Any = None,
                  host_feature_fn=None, agent_feature_fn=None, device=None, use_graph: bool = False,
-                 fused_expand: bool = True, loss_fn: Optional[Callable] = None, fused_training: bool = False):
+                 fused_expand: bool = True, loss_fn: Optional[Callable] = None, fused_training: bool = False,
+                 custom_net: bool = False):
         if isinstance(config, str):
             import yaml
             with open(config, "r") as stream:
@@ -200,7 +203,7 @@ class HipTrainer:
             if given[role] is None and isinstance(section, dict) and "net_arch" in section:
                 from .net import build_net
                 module = build_net(self.net_type, role, 2 ** d - d - 1 if role == "host" else d, section["net_arch"],
-                                   (m, d), seed=_split(key, 2)[i]).to(self.device)
+                                   (m, d), seed=_split(key, 2)[i], custom_net=custom_net).to(self.device)
                 # fused_training: the gradient step's forward and backward through the network are the library's
                 # (hironaka_amd.net.DenseResNet.fused_training; off by default)
                 module.fused_training = bool(fused_training)

@@ -640,6 +640,8 @@ int hk_search_morin_play(const hk_morin_play_desc* desc, void* stream);
 #include "hironaka_hip_mlp_train.h"
 /* within ABI 6: hk_pvnet_forward, likewise */
 #include "hironaka_hip_pvnet.h"
+/* within ABI 6: hk_customnet_forward / hk_customnet_workspace_bytes, likewise */
+#include "hironaka_hip_customnet.h"
 /* within ABI 6: hk_pv_loss, likewise */
 #include "hironaka_hip_pvloss.h"
 /* within ABI 6: hk_pvgrad_forward / hk_pvgrad_backward, likewise */
