@@ -1,8 +1,8 @@
-"""Randomised parity of the three network kernels -- hk_mlp_forward ("mlp"), hk_train_mlp_forward / hk_train_mlp_backward
-("train") and hk_pvnet_forward ("pvnet") -- against their numpy rules, bit for bit, on cases whose axes are drawn JOINTLY:
-batch, forced tile, widths, depth, options, input segments, the layout of inputs and outputs, the layout of the parameters
-(fresh allocations, or every tensor of the net back to back in one sentinel-padded flat buffer at any 4-byte boundary) and
-a stray NaN or Inf.
+"""Randomised parity of the five network kernels -- hk_mlp_forward ("mlp"), hk_train_mlp_forward / hk_train_mlp_backward
+("train"), hk_pvnet_forward ("pvnet"), hk_pvgrad_forward / hk_pvgrad_backward ("pvgrad") and hk_customnet_forward
+("customnet") -- against their numpy rules, bit for bit, on cases whose axes are drawn JOINTLY: batch, forced tile, widths,
+depth, options, input segments, the layout of inputs and outputs, the layout of the parameters (fresh allocations, or every
+tensor of the net back to back in one sentinel-padded flat buffer at any 4-byte boundary) and a stray NaN or Inf.
 
     python tests/fuzz_nets.py --minutes 3 [--seed 0] [--family mlp]      # by hand, on the GPU
 
@@ -12,7 +12,12 @@ Four separable parts, so that everything but the launch runs without a GPU (test
     device(case) -> got           the same names from the operators of hironaka_amd.ops
     compare(case, got, want)      same_bits on every name; raises Mismatch and dumps the arrays under DUMP
 tests/test_gpu_fuzz_nets.py runs a fixed, seeded slice (`run_cases`) as a `-m gpu` test.  Case i of a seed has a generator
-of its own (`case_rng`), so a failing case is rebuilt from (family, seed, index) alone (`case_at`)."""
+of its own (`case_rng`), so a failing case is rebuilt from (family, seed, index) alone (`case_at`).
+
+"pvgrad" draws FINITE inputs only (case["nonfinite"] is None): every weight gradient is a chain over all rows of the batch,
+so one NaN row reaches every element of every gradient and the case compares NaN masks instead of bits (test_gpu_pvgrad.py
+says the same).  Both new families run with raw_value: the tanh path is not pinned to the bit.  "customnet" keeps the
+broadcast layout of x: the operator takes a row stride of zero (every row is then the first: one group)."""
 import argparse
 import collections
 import os
@@ -26,12 +31,16 @@ for _p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import customnet_rules as C  # noqa: E402
 import mlp_rules as M  # noqa: E402
 import mlp_train_rules as T  # noqa: E402
+import pvgrad_rules as G  # noqa: E402
 import pvnet_rules as P  # noqa: E402
+from hironaka_amd import _abi as A  # noqa: E402  (constants alone: neither torch nor the library)
 from mlp_rules import F32, same_bits  # noqa: E402
 
-FAMILIES = ("mlp", "train", "pvnet")
+# (case_rng seeds by a family's index here: new families go behind the others, whose cases then stay what they were)
+FAMILIES = ("mlp", "train", "pvnet", "pvgrad", "customnet")
 SENTINEL = -77.25  # test_gpu_mlp.SENTINEL: what Guarded fills its storage with
 WIDTHS = (1, 3, 15, 16, 17, 18, 33, 60, 63, 64, 100, 255, 256)
 HIDDEN = tuple(w for w in WIDTHS if w >= 8)  # behind a ReLU: a narrower layer leaves rows that are all zero
@@ -43,9 +52,26 @@ TRAIN_CAP = 1024
 DEEP = 32
 # the rule costs about one fma32 over [batch, n] per k: a case whose batch * sum(k * n) lies above this is drawn again
 # (mlp, pvnet: a 256-wide pair of layers at 193 rows; train, whose backward costs twice the forward: a 64-wide net at 1 024)
-WORK_CAP = {"mlp": 30e6, "pvnet": 30e6, "train": 12e6}
+# (pvgrad: train's, three times the forward -- two narrow dense blocks at 4 096 rows, a 32-wide residue block at 1 024, a
+# 256-wide one at 17; customnet: a row runs one tower, the rule besides costs a pass per tower)
+WORK_CAP = {"mlp": 30e6, "pvnet": 30e6, "train": 12e6, "pvgrad": 12e6, "customnet": 20e6}
 INPUT_KINDS = ("dense", "offset", "stride", "broadcast")
 OUTPUT_KINDS = ("dense", "offset", "stride")
+# pvgrad: ROWSUM's residues, both sides of the 16-row tile, several tiles, the operator's cap (the nets with the table's
+# boundary counts of Denses and the deep ones take the small batches alone: the work cap)
+PVGRAD_BATCHES = (1, 2, 3, 15, 16, 17, 33, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4095, 4096)
+PVGRAD_CAP = A.HK_PVGRAD_MAX_BATCH
+PVGRAD_TABLE = A.HK_PVGRAD_TABLE  # Denses per launch of the parameter gradients, the two heads among them
+# customnet: points, coordinates, features behind the points; the large m cost the rule a pass per tower: drawn less often
+POINTS = (1, 2, 5, 20, 63, 64)
+DIMS = (2, 3, 4)
+EXTRAS = (0, 1, 3, 16)
+ODD_WIDTHS = (15, 17, 24, 33)
+LARGE_ROWS = (1023, 1024, 1025, 2049)  # the group launch takes 1 024 rows per workgroup
+STRUCTURES = ("uniform", "one group", "no tower", "no point", "tile", "extremes")
+# what a case may plant at coordinate 0 of a point slot, and whether the rule's `>= 0` counts it a point
+EDGES = {"-0": (-0.0, True), "+subnormal": (2.0 ** -149, True), "-subnormal": (-2.0 ** -149, False),
+         "nan": (np.nan, False), "+inf": (np.inf, True), "-inf": (-np.inf, False)}
 
 Layout = collections.namedtuple("Layout", "kind offset stride")
 Layout.__doc__ = """where a [batch, width] tensor lies in its storage: `offset` elements in, rows `stride` elements apart.
@@ -181,8 +207,16 @@ def leaves(case, written=False):
 
 
 def grad_shapes(case):
-    """the shapes of train's gradients in parameter order"""
+    """the shapes of train's (pvgrad's) gradients in parameter order"""
+    if case["family"] == "pvgrad":  # every parameter, in the walk's order: ops.PvnetPlan.params'
+        return [a.shape for a in leaves(case)]
     return [a.shape for l in case["net"] for a in (l.weight, l.bias, l.bn_weight, l.bn_bias) if a is not None]
+
+
+def grads_flat(case):
+    """whether the gradients are views of the second flat buffer: train's with flat parameters, pvgrad's by a draw of
+    its own"""
+    return case["params"] == "flat" if case["family"] == "train" else case.get("grads") == "flat"
 
 
 def positions(sizes, start, gaps):
@@ -209,7 +243,7 @@ def _draw_params(rng, case):
     tensor lands on an arbitrary 4-byte boundary"""
     case["params"] = "flat" if _coin(rng) else "fresh"
     read, stats = leaves(case), leaves(case, True)
-    extra = len(grad_shapes(case)) if case["family"] == "train" else 0
+    extra = len(grad_shapes(case)) if case["family"] in ("train", "pvgrad") else 0
     case["start"], case["gaps"] = int(rng.integers(0, 4)), [int(g) for g in rng.integers(0, 2, len(read))]
     case["start2"], case["gaps2"] = int(rng.integers(0, 4)), [int(g) for g in rng.integers(0, 2, len(stats) + extra)]
     at = positions([a.size for a in read], case["start"], case["gaps"])[0] if case["params"] == "flat" else [0] * len(read)
@@ -359,7 +393,239 @@ def _draw_pvnet(rng):
     return case
 
 
-_DRAW = {"mlp": _draw_mlp, "train": _draw_train, "pvnet": _draw_pvnet}
+def _strip_norms(rng, blocks, eps, drops):
+    """the blocks with `eps` and with the scale and the shift of each group norm stripped separately (`drops` collects
+    what was kept, per normed Dense)"""
+    def strip(d):
+        if d is None or d.gn_scale is None:
+            return d
+        # (a group of one column -- width 32 -- normalises to zero: without its shift the block's output is zero)
+        keep = (_coin(rng, 0.7), _coin(rng, 0.7) or d.weight.shape[0] == 32)
+        drops.append(keep)
+        return d._replace(gn_scale=d.gn_scale if keep[0] else None, gn_bias=d.gn_bias if keep[1] else None)
+    return [b._replace(dense1=strip(b.dense1), dense2=strip(b.dense2), proj=strip(b.proj), eps=eps) for b in blocks]
+
+
+def _norm_options(bias, drops):
+    return dict(bias=bias, scale_on=any(s for s, _ in drops), scale_off=any(not s for s, _ in drops),
+                shift_on=any(s for _, s in drops), shift_off=any(not s for _, s in drops),
+                scale_alone=any(s and not t for s, t in drops), shift_alone=any(t and not s for s, t in drops))
+
+
+def _seldom_broadcast(rng, case, name, p=0.6):
+    """a broadcast x makes every row the first: most of the time another layout is drawn in its place"""
+    if case["layout"][name].kind == "broadcast" and _coin(rng, p):
+        case["layout"][name] = _draw_layout(rng, case["io_widths"][name], OUTPUT_KINDS)
+
+
+def _pvgrad_menus(batch):
+    """(k0, normed widths besides 32, dense widths, the most blocks) that the work cap leaves a batch of this size"""
+    if batch <= 65:
+        return WIDTHS, (64, 128, 256), HIDDEN + (32,), 6
+    if batch <= 257:
+        return tuple(w for w in WIDTHS if w <= 100), (64, 128), tuple(w for w in HIDDEN if w <= 64) + (32,), 4
+    if batch <= 1025:  # (no normed width but 32 fits: behind a 32-wide dense block)
+        return tuple(w for w in WIDTHS if w <= 64), (), (15, 16, 17, 18, 32, 32, 33), 3
+    return tuple(w for w in WIDTHS if w <= 33), (), (15, 16, 17, 18, 33), 2  # dense blocks alone
+
+
+def _pvgrad_trunk(rng, k0, nb, target, normed, dense, narrow, seldom):
+    """(block widths, kinds) of nb blocks behind k0 inputs, or None where the draw got stuck.  target: the number of Denses
+    the trunk must have exactly (a dense block has one, a residue block two, three with a projection), or None.
+    A 32-wide residue block has dz == 0 exactly (a group of one column), so that nothing in front of one WITH a
+    projection gets a gradient: width 32 is drawn behind a 32-wide block, where the block needs no projection and the
+    gradient passes, and with a projection with the probability `seldom` alone"""
+    arch, kinds, k, left = [], [], k0, target
+    for i in range(nb):
+        if target is None:
+            residue = _coin(rng, 0.6)
+            same = residue and k in NORMED and _coin(rng, 0.5 if k == 32 else 1 / 3)
+        else:
+            rest = nb - i - 1
+            counts = [c for c in (1, 2, 3) if rest <= left - c <= 3 * rest and (c != 2 or k in NORMED)]
+            if not counts:
+                return None
+            c = int(_pick(rng, counts))
+            left -= c
+            residue, same = c > 1, c == 2
+        if residue and same:
+            n = k
+        elif residue:
+            menu = [w for w in normed if w != k or target is None]
+            if k != 32 and seldom and _coin(rng, seldom):
+                n = 32
+            elif menu:
+                n = int(_pick(rng, menu))
+            elif target is None and k == 32:
+                n = k  # (no other normed width fits the batch: no projection)
+            elif target is None:
+                residue = False
+            else:
+                return None
+        if not residue:
+            # a dense block narrower than 8 leaves rows that are all zero: seldom, and rarely as the last block
+            thin = narrow and _coin(rng, 0.15) and (i + 1 < nb or _coin(rng, 0.1))
+            n = int(_pick(rng, (1, 3) if thin else dense))
+        arch.append(n)
+        kinds.append("residue" if residue else "dense")
+        k = n
+    return arch, kinds
+
+
+def dense_count(case):
+    """the Denses of a pvgrad case as hk_pvgrad_backward's table counts them: those of every block, and the two heads"""
+    return sum(1 + (b.dense2 is not None) + (b.proj is not None) for b in case["net"].blocks) + 2
+
+
+def _draw_pvgrad(rng):
+    case = dict(family="pvgrad")
+    # what the net is drawn for: the table's boundary (exactly HK_PVGRAD_TABLE Denses, one more), the depth, or freely
+    # ("launches": the depth again, with so many residue blocks that the parameter table takes more than two launches,
+    # which the work cap leaves the batches up to 3)
+    mode = _pick(rng, ("table",) * 2 + ("table + 1",) * 2 + ("deep",) + ("launches",) * 2 + ("free",) * 17)
+    # (the rule's weight gradients are chains over the rows, one step of numpy per row and Dense whatever the widths: the
+    # batches above 1 000 rows are drawn half as often as the others)
+    small = tuple(b for b in PVGRAD_BATCHES if b <= 65)
+    often = tuple(b for b in PVGRAD_BATCHES if b <= 257)
+    batch = int(_pick(rng, {"free": PVGRAD_BATCHES + often, "deep": small[:6], "launches": small[:3]}.get(mode, small)))
+    k0s, normed, dense, most = _pvgrad_menus(batch)
+    # (decided once, not per attempt: the nets the work cap turns away are the wide ones, and a 32-wide block is cheap)
+    seldom = 0.3 if _coin(rng, 0.03) else 0.0
+    while True:
+        bias = _coin(rng)
+        k0 = int(_pick(rng, k0s))
+        # (inputs() draws zeros: without a bias a row of zeros stays one to the end, and a narrow x has such rows)
+        if not bias and ((k0 == 1 and batch >= 15) or (k0 == 3 and batch > 257)):
+            continue
+        if mode == "free":
+            trunk = _pvgrad_trunk(rng, k0, int(rng.integers(1, most + 1)), None, normed, dense, bias and batch <= 65, seldom)
+        elif mode in ("deep", "launches"):
+            # (the deep nets of the larger batches get 64-wide blocks, most without a projection)
+            many = mode == "launches"
+            trunk = _pvgrad_trunk(rng, k0, DEEP, int(rng.integers(2 * PVGRAD_TABLE, 3 * DEEP - 3)) if many else None,
+                                  (64, 128) if many else (64,), (15, 16, 33, 64), False, seldom)
+        else:
+            target = PVGRAD_TABLE - 2 + (mode == "table + 1")
+            trunk = _pvgrad_trunk(rng, k0, int(rng.integers((target + 2) // 3, A.HK_PVNET_MAX_BLOCKS + 1)), target,
+                                  (64, 128), (15, 16, 17, 18, 32, 33), False, seldom)
+        if trunk is None:
+            continue
+        arch, kinds = trunk
+        actions = int(_pick(rng, ACTIONS if batch <= 257 else tuple(a for a in ACTIONS if a <= 17)))
+        widths = [k0] + arch
+        work = _work(batch, widths) + batch * sum(n * n + (k != n) * k * n
+                                                  for k, n, kd in zip(widths[:-1], arch, kinds) if kd == "residue")
+        if 3 * (work + batch * arch[-1] * (actions + 1)) <= WORK_CAP["pvgrad"]:
+            break
+    net = P.random_net(rng, k0, arch, actions, kinds, bias, True)
+    eps = float(_pick(rng, (P.EPS, 1e-5)))
+    drops = []
+    net = net._replace(blocks=_strip_norms(rng, net.blocks, eps, drops))
+    case.update(batch=batch, tile=None, widths=widths, kinds=kinds, actions=actions, k0=k0, k1=0, mode=mode,
+                options=_norm_options(bias, drops), net=net, eps=eps)
+    case["denses"] = dense_count(case)
+    # everything with a layout is read: x and the two gradients at the outputs may be columns of one record
+    _draw_io(rng, case, {"x0": k0, "grad_policy": actions, "grad_value": 1}, {})
+    for name in ("grad_policy", "grad_value"):  # (the operator copies a gradient whose rows overlap: not a layout of its own)
+        if case["layout"][name].kind == "broadcast":
+            case["layout"][name] = Layout("dense", 0, case["io_widths"][name])
+    _seldom_broadcast(rng, case, "x0")
+    case["x"] = _flatten_broadcast(case, inputs(rng, batch, k0), [("x0", k0)])
+    case["grad_kind"] = "sparse" if _coin(rng, 0.3) else "mean"
+    if case["grad_kind"] == "sparse":  # one non-zero row
+        row = int(rng.integers(batch))
+        gp, gv = np.zeros((batch, actions), F32), np.zeros(batch, F32)
+        gp[row], gv[row] = rng.standard_normal(actions).astype(F32), F32(rng.standard_normal())
+    else:  # test_gpu_pvgrad.grads_in: of the size a mean over the batch gives, with a few zeros
+        gp = (rng.standard_normal((batch, actions)) / batch).astype(F32)
+        gp[rng.random((batch, actions)) < 0.05] = 0
+        gv = (rng.standard_normal(batch) / batch).astype(F32)
+    case["grad_policy"], case["grad_value"] = gp, gv
+    case["nonfinite"] = None  # finite only: a NaN row reaches every weight gradient
+    _draw_params(rng, case)
+    case["grads"] = "flat" if _coin(rng) else "own"
+    return case
+
+
+def _customnet_counts(rng, structure, batch, m, tile):
+    """(the point count of every row, the batch) of a structure; "tile" may ask for more rows"""
+    t = tile or 16
+    if structure == "uniform":
+        return rng.integers(0, m + 1, batch), batch
+    if structure == "one group":
+        return np.full(batch, int(rng.integers(0, m))), batch
+    if structure == "no tower":
+        return np.full(batch, m), batch
+    if structure == "no point":
+        return np.zeros(batch, np.int64), batch
+    if structure == "extremes":
+        return np.where(rng.random(batch) < 0.5, 0, m), batch
+    # one group of exactly the tile's rows, one more or one fewer, among rows of the other counts
+    size = t + int(_pick(rng, (-1, 0, 1)))
+    if batch < size + 2:
+        batch = int(_pick(rng, (3 * t - 1, 3 * t, 3 * t + 1)))
+    c = int(rng.integers(0, m + 1))
+    others = np.array([v for v in range(m + 1) if v != c])
+    cs = np.concatenate([np.full(size, c), others[rng.integers(0, len(others), batch - size)]])
+    return cs[rng.permutation(batch)], batch
+
+
+def _draw_customnet(rng):
+    case = dict(family="customnet")
+    while True:
+        tile = _pick(rng, TILES)
+        large = _coin(rng, 0.08)  # more than one workgroup of the group launch, with a small net
+        m = int(_pick(rng, (1, 2, 5) if large else POINTS[:4] * 3 + POINTS[4:]))
+        d, e = int(_pick(rng, DIMS)), int(_pick(rng, EXTRAS))
+        batch = int(_pick(rng, LARGE_ROWS)) if large else _draw_batch(rng, tile)
+        nb = 1 if large else int(rng.integers(1, 4))
+        kinds = ["residue" if _coin(rng) else "dense" for _ in range(nb)]
+        normed = (32, 64) if large or m >= 20 else (32, 64, 128)
+        arch = [int(_pick(rng, normed if kd == "residue" else ODD_WIDTHS + (16, 64))) for kd in kinds]
+        actions = int(_pick(rng, ACTIONS))
+        if m * d + e > A.HK_PVNET_MAX_WIDTH or arch[-1] + e > A.HK_PVNET_MAX_WIDTH:
+            continue
+        widest = [m * d + e] + arch  # the last tower's widths
+        work = _work(batch, widest) + batch * sum(2 * n * n for n, kd in zip(arch, kinds) if kd == "residue")
+        # (a pass of the rule over one tower costs what some 400 elements per term of its chains cost)
+        if work + 400 * m * (sum(widest) + 2 * sum(n for n, kd in zip(arch, kinds) if kd == "residue")) <= WORK_CAP["customnet"]:
+            break
+    bias = _coin(rng)
+    eps = float(_pick(rng, (P.EPS, 1e-5)))
+    net = C.random_net(rng, m, d, e, arch, actions, kinds, bias, True, float(_pick(rng, (1.0, 4.0))))
+    drops = []
+    net = net._replace(towers=[_strip_norms(rng, tower, eps, drops) for tower in net.towers])
+    structure = "no tower" if _coin(rng, 0.03) else _pick(rng, ("uniform", "uniform", "one group", "no point", "tile", "tile",
+                                                                  "extremes"))
+    cs, batch = _customnet_counts(rng, structure, batch, m, tile)
+    holes = _coin(rng, 0.3)
+    k = m * d + e
+    case.update(batch=batch, tile=tile, m=m, d=d, e=e, widths=[k] + arch, kinds=kinds, actions=actions, k0=k, k1=0,
+                options=_norm_options(bias, drops), net=net, eps=eps, structure=structure, holes=holes)
+    _draw_io(rng, case, {"x0": k}, {"policy": actions, "value": 1}, together=("policy", "value"))
+    _seldom_broadcast(rng, case, "x0")
+    x = C.rows_with_counts(rng, cs, m, d, e, holes)
+    # an edge value at coordinate 0 of one point slot, which decides the tower of its row; one time in five a NaN or an Inf
+    # in another column as well.  (the finite ones are drawn twice as often: the non-finite cases have a cap)
+    case["nonfinite"] = None
+    if _coin(rng, 0.18):
+        lone = case["layout"]["x0"].kind == "broadcast"  # (every row is the first)
+        row, slot = 0 if lone else int(rng.integers(batch)), int(rng.integers(m))
+        kind = _pick(rng, ("-0", "+subnormal", "-subnormal") * 2 + ("nan", "+inf", "-inf"))
+        x[row, slot * d] = F32(EDGES[kind][0])
+        planted = [(row, slot * d, kind)]
+        if _coin(rng, 0.2):
+            row2, col = 0 if lone else int(rng.integers(batch)), int(_pick(rng, [c for c in range(k) if c != slot * d]))
+            other = _pick(rng, ("nan", "nan", "+inf"))
+            x[row2, col] = F32(EDGES[other][0])
+            planted.append((row2, col, other))
+        case["nonfinite"] = tuple(planted)
+    case["x"] = _flatten_broadcast(case, x, [("x0", k)])
+    _draw_params(rng, case)
+    return case
+
+
+_DRAW = {"mlp": _draw_mlp, "train": _draw_train, "pvnet": _draw_pvnet, "pvgrad": _draw_pvgrad, "customnet": _draw_customnet}
 
 
 def draw(rng, family):
@@ -383,7 +649,8 @@ def case_at(family, seed, index):
 def scalars(case):
     """the case without its arrays"""
     keep = ("family", "index", "seed", "batch", "tile", "widths", "kinds", "actions", "k0", "k1", "options", "eps", "layout",
-            "record", "params", "start", "gaps", "start2", "gaps2", "nonfinite")
+            "record", "params", "start", "gaps", "start2", "gaps2", "nonfinite", "mode", "denses", "grad_kind", "grads",
+            "m", "d", "e", "structure", "holes")
     return {k: case[k] for k in keep if k in case}
 
 
@@ -410,13 +677,12 @@ def _record(case, values):
 
 def _param_images(case, stats_after=None, grads=None):
     """"params": the read-only parameters as the launch must leave them -- the flat buffer, or the arrays one behind the
-    other; "written" (train, flat): the second buffer with the updated statistics and the gradients"""
+    other; "written" (where grads_flat): the second buffer with train's updated statistics and the gradients"""
     read = leaves(case)
-    if case["params"] == "fresh":
-        return {"params": np.concatenate([a.ravel() for a in read])}
-    out = {"params": pack(read, case["start"], case["gaps"])[0]}
-    if case["family"] == "train":
-        out["written"] = pack(list(stats_after) + list(grads), case["start2"], case["gaps2"])[0]
+    out = {"params": np.concatenate([a.ravel() for a in read]) if case["params"] == "fresh"
+           else pack(read, case["start"], case["gaps"])[0]}
+    if grads_flat(case):
+        out["written"] = pack(list(stats_after or ()) + list(grads), case["start2"], case["gaps2"])[0]
     return out
 
 
@@ -441,6 +707,20 @@ def rule(case):
         want["policy"], want["value"] = policy, value
         values.update(policy=policy, value=value)
         want.update(_param_images(case))
+    elif family == "pvgrad":
+        policy, value, saved = G.forward_saved(x, case["net"])
+        grads = G.param_grads(G.backward(saved, case["net"], case["grad_policy"], case["grad_value"]))
+        want["policy"], want["value"] = policy, value
+        for j, (_, g) in enumerate(grads):
+            want[f"grad{j}"] = np.ascontiguousarray(g, F32)
+        values.update(grad_policy=case["grad_policy"], grad_value=case["grad_value"])
+        want.update(_param_images(case, None, [g for _, g in grads]))
+    elif family == "customnet":
+        policy, value = C.forward(x, case["net"], case["m"], case["d"], case["e"])
+        want["policy"], want["value"] = policy, value
+        values.update(policy=policy, value=value)
+        want.update(_param_images(case))
+        want["workspace"] = np.zeros(1 + A.HK_CUSTOMNET_MAX_POINTS + 1, np.int32)  # the ticket and the histogram: zero again
     else:
         layers = case["net"]
         out, saved, stats = T.forward(x, layers, case["options"]["input_relu"])
@@ -463,8 +743,14 @@ def rule(case):
 def last_hidden(case):
     """the activations the last Linear (pvnet: the heads) reads, by the rule; None for a net of one layer"""
     family, x = case["family"], case["x"]
-    if family == "pvnet":
+    if family in ("pvnet", "pvgrad"):
         return P.trunk(x, case["net"].blocks)
+    if family == "customnet":  # the chosen tower's result, of the rows that have a tower
+        m, d = case["m"], case["d"]
+        c = C.counts(x, m, d)
+        rows = [P.trunk(np.concatenate([x[c == t, : (t + 1) * d], x[c == t, m * d:]], axis=1), case["net"].towers[t])
+                for t in range(m) if (c == t).any()]
+        return np.concatenate(rows) if rows else None
     if len(case["widths"]) < 3:
         return None
     if family == "mlp":
@@ -473,10 +759,16 @@ def last_hidden(case):
     return T.forward(x, case["net"][:-1], case["options"]["input_relu"])[0]
 
 
-def degenerate(case):
-    """some row's last hidden activations are all zero: nothing behind that point is tested on it"""
+def degenerate(case, want=None):
+    """some row's last hidden activations are all zero: nothing behind that point is tested on it (customnet: of the rows
+    with a tower; those without are zero by design).  pvgrad as well: the gradient of the first block's weight is all
+    zero by the rule (`want`: rule(case), where the caller has it)."""
     h = last_hidden(case)
-    return h is not None and bool((h == 0).all(axis=1).any())
+    if h is not None and bool((h == 0).all(axis=1).any()):
+        return True
+    if case["family"] == "pvgrad":
+        return not (rule(case) if want is None else want)["grad0"].any()
+    return False
 
 
 # ---- device -------------------------------------------------------------------------------------------------------------
@@ -545,10 +837,37 @@ def device(case):
     values = _segments_of(case)
     if family == "train":
         values["grad_out"] = case["grad"]
+    if family == "pvgrad":
+        values.update(grad_policy=case["grad_policy"], grad_value=case["grad_value"])
     views, stores = _device_io(case, values)
     net, read, written, grads = _device_net(case)
     got = {}
-    if family == "mlp":
+    blocks = lambda bs: [ops.PvnetBlock(b.kind, *(None if d is None else ops.PvnetDense(*d)  # noqa: E731
+                                                  for d in (b.dense1, b.dense2, b.proj)), b.eps) for b in bs]
+    if family == "pvgrad":
+        if case["grads"] == "flat":  # the gradients as views of a second sentinel-padded flat buffer
+            shapes = grad_shapes(case)
+            flat2, where = pack([np.full(s, SENTINEL, F32) for s in shapes], case["start2"], case["gaps2"])
+            written = torch.from_numpy(flat2).cuda()
+            grads = [written[p:p + int(np.prod(s))].view(*s) for p, s in zip(where, shapes)]
+        plan = ops.PvnetPlan(blocks(net.blocks), net.policy, net.value)
+        p, v, saved = ops.pvnet_train_forward(views["x0"], plan, raw_value=True)
+        gs = ops.pvnet_backward(saved, views["grad_policy"], views["grad_value"][:, 0], grads=grads)
+        assert grads is None or all(g is t for g, t in zip(gs, grads))
+        got["policy"], got["value"] = _np(p), _np(v)
+        for j, g in enumerate(gs):
+            got[f"grad{j}"] = _np(g)
+        if written is not None:
+            got["written"] = _np(written)
+    elif family == "customnet":
+        plan = ops.CustomnetPlan([blocks(tower) for tower in net.towers], net.policy, net.value, (case["m"], case["d"]), case["e"])
+        p, v = ops.customnet_forward(views["x0"], plan, tile=case["tile"], raw_value=True,
+                                     out=(views["policy"], views["value"][:, 0]))
+        got["policy"], got["value"] = _np(p), _np(v)
+        # the ticket and the histogram at the head of the plan's workspace (words 1 and 4 .. 68)
+        head = _np(plan.workspace.view(torch.int32).reshape(-1)[:72])
+        got["workspace"] = head[[1] + list(range(4, 5 + A.HK_CUSTOMNET_MAX_POINTS))]
+    elif family == "mlp":
         input_bn, layers = net
         out = ops.mlp_forward(views["x0"], [ops.MlpLayer(*l) for l in layers], x1=views.get("x1"),
                               input_relu=case["options"]["input_relu"], out=views["out"], tile=case["tile"],
