@@ -659,6 +659,36 @@ class hk_pvgrad_desc(C.Structure):
     ]
 
 
+# include/hironaka_hip_customgrad.h: offsets in floats into one gradient buffer; NONE: not there
+HK_CUSTOMGRAD_NONE = -1
+HK_CUSTOMGRAD_HEADER, HK_CUSTOMGRAD_FIRST, HK_CUSTOMGRAD_SIZE = 144, 4, 72
+
+
+class hk_customgrad_dense(C.Structure):
+    _fields_ = [(name, C.c_int64) for name in ("d_weight", "d_bias", "d_gn_scale", "d_gn_bias")]
+
+
+class hk_customgrad_block(C.Structure):
+    _fields_ = [("dense1", hk_customgrad_dense), ("dense2", hk_customgrad_dense), ("proj", hk_customgrad_dense)]
+
+
+class hk_customgrad_desc(C.Structure):
+    _fields_ = [
+        ("net", hk_customnet_desc),
+        ("grad_table", C.c_void_p),
+        ("grads", C.c_void_p),
+        ("grad_policy", C.c_void_p),
+        ("grad_value", C.c_void_p),
+        ("grad_policy_stride", C.c_int64),
+        ("grad_value_stride", C.c_int64),
+        ("grad_floats", C.c_uint64),
+        ("policy", hk_customgrad_dense),
+        ("value", hk_customgrad_dense),
+        ("n", C.c_int32 * HK_PVNET_MAX_BLOCKS),
+        ("kind", C.c_int32 * HK_PVNET_MAX_BLOCKS),
+    ]
+
+
 # include/hironaka_hip_unified.h
 HK_UNIFIED_REPOSITION, HK_UNIFIED_SCALE_OBSERVATION = 1, 2
 HK_UNIFIED_MAX_DIM = 5  # the search takes at most 32 actions
@@ -824,6 +854,13 @@ PVGRAD_PROTOTYPES = {
     "hk_pvgrad_backward": (C.c_int, [C.POINTER(hk_pvgrad_desc), _vp]),
 }
 
+# the entry points of include/hironaka_hip_customgrad.h: the device library's only, as above
+CUSTOMGRAD_PROTOTYPES = {
+    "hk_customgrad_workspace_bytes": (C.c_uint64, [C.POINTER(hk_customgrad_desc)]),
+    "hk_customgrad_forward": (C.c_int, [C.POINTER(hk_customgrad_desc), _vp]),
+    "hk_customgrad_backward": (C.c_int, [C.POINTER(hk_customgrad_desc), _vp]),
+}
+
 # the entry points of include/hironaka_hip_unified.h: the device library's only, as above
 UNIFIED_PROTOTYPES = {
     "hk_unified_expand": (C.c_int, [C.POINTER(hk_unified_expand_desc), _vp]),
@@ -846,13 +883,13 @@ DQN_MOVE_PROTOTYPES = {
 def bind(lib: C.CDLL, prototypes=None) -> None:
     """Attach restype/argtypes (default: PROTOTYPES, DEVICE_PROTOTYPES, PLAY_PROTOTYPES, TREE_PROTOTYPES, ENV_PROTOTYPES,
     REPLAY_PROTOTYPES, DQN_PROTOTYPES, OPTIM_PROTOTYPES, MLP_PROTOTYPES, MLP_TRAIN_PROTOTYPES, PVNET_PROTOTYPES,
-    CUSTOMNET_PROTOTYPES, PVLOSS_PROTOTYPES, PVGRAD_PROTOTYPES, UNIFIED_PROTOTYPES, SPIVAKOVSKY_PROTOTYPES and DQN_MOVE_PROTOTYPES); raises
+    CUSTOMNET_PROTOTYPES, PVLOSS_PROTOTYPES, PVGRAD_PROTOTYPES, CUSTOMGRAD_PROTOTYPES, UNIFIED_PROTOTYPES, SPIVAKOVSKY_PROTOTYPES and DQN_MOVE_PROTOTYPES); raises
     AttributeError for a symbol the library lacks."""
     if prototypes is None:
         prototypes = {**PROTOTYPES, **DEVICE_PROTOTYPES, **PLAY_PROTOTYPES, **TREE_PROTOTYPES, **ENV_PROTOTYPES,
                       **REPLAY_PROTOTYPES, **DQN_PROTOTYPES, **OPTIM_PROTOTYPES, **MLP_PROTOTYPES,
                       **MLP_TRAIN_PROTOTYPES, **PVNET_PROTOTYPES, **CUSTOMNET_PROTOTYPES, **PVLOSS_PROTOTYPES,
-                      **PVGRAD_PROTOTYPES, **UNIFIED_PROTOTYPES, **SPIVAKOVSKY_PROTOTYPES,
+                      **PVGRAD_PROTOTYPES, **CUSTOMGRAD_PROTOTYPES, **UNIFIED_PROTOTYPES, **SPIVAKOVSKY_PROTOTYPES,
                       **DQN_MOVE_PROTOTYPES}
     for name, (res, args) in prototypes.items():
         fn = getattr(lib, name)

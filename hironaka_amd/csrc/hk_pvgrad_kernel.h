@@ -99,6 +99,49 @@ __device__ __forceinline__ void pvgrad_save_panel(const float* panel, float* out
   }
 }
 
+// one block of the training forward on a row tile: the rows row0 .. below `batch` (where the tile ends), the block's saved
+// [., N] arrays `sz` floats apart from `base`.  The block's input is in `cur` and so is its result (a dense block swaps the
+// panels).  The one copy of the body: pvgrad_forward_kernel's and hk::customgrad_forward_kernel's (hk_customgrad_kernel.h)
+__device__ __forceinline__ void pvgrad_forward_block(const hk_pvnet_block& B, float* base, int64_t sz, float*& cur, float*& nxt,
+                                                     float* const wst, PvgradAcc& acc, int64_t row0, int batch, int tid) {
+  constexpr int TR = kPvgradTile;
+  typedef PvgradTile T;
+  auto f = [](const void* p) { return static_cast<const float*>(p); };
+  const int K = B.k, N = B.n;
+  if (B.kind == HK_PVNET_DENSE) {
+    mlp_dense<TR, false>(acc, cur, wst, f(B.dense1.weight), f(B.dense1.bias), nullptr, nullptr, K, N, tid);
+    pvnet_store<TR, false>(acc, nxt, N, tid, acc, false);
+    pvgrad_save_panel(nxt, base + kPgDenseH * sz, N, row0, batch, tid);
+    float* const swap = cur;
+    cur = nxt;
+    nxt = swap;
+    return;
+  }
+  const bool proj = K != N;
+  PvgradAcc o;
+  if (proj) {
+    mlp_dense<TR, false>(o, cur, wst, f(B.proj.weight), f(B.proj.bias), nullptr, nullptr, K, N, tid);
+    pvgrad_save(o, base + kPgZp * sz, N, row0, batch, tid);
+    pvnet_group_norm<TR>(o, B.proj, B.eps, N, tid);
+  } else {
+#pragma unroll
+    for (int i = 0; i < T::TPW; ++i) o[0][i] = mlp_f4{0.0f, 0.0f, 0.0f, 0.0f};
+  }
+  mlp_dense<TR, false>(acc, cur, wst, f(B.dense1.weight), f(B.dense1.bias), nullptr, nullptr, K, N, tid);
+  pvgrad_save(acc, base + kPgZ1 * sz, N, row0, batch, tid);
+  pvnet_group_norm<TR>(acc, B.dense1, B.eps, N, tid);
+  pvnet_store<TR, false>(acc, nxt, N, tid, acc, false);
+  pvgrad_save_panel(nxt, base + kPgA * sz, N, row0, batch, tid);
+  mlp_dense<TR, false>(acc, nxt, wst, f(B.dense2.weight), f(B.dense2.bias), nullptr, nullptr, N, N, tid);
+  pvgrad_save(acc, base + kPgZ2 * sz, N, row0, batch, tid);
+  pvnet_group_norm<TR>(acc, B.dense2, B.eps, N, tid);
+  pvnet_store<TR, true>(acc, cur, N, tid, o, proj);
+  pvgrad_save_panel(cur, base + kPgH * sz, N, row0, batch, tid);
+}
+
+// (HK_PVGRAD_BODIES_ONLY: a second translation unit that builds its own kernels from the bodies -- hk_customgrad.hip -- leaves
+// the three kernels to hk_pvgrad.hip)
+#ifndef HK_PVGRAD_BODIES_ONLY
 __global__ __launch_bounds__(kWave * mlp_waves(kPvgradTile)) void pvgrad_forward_kernel(const PvgradForwardArgs args) {
   constexpr int TR = kPvgradTile;
   typedef PvgradTile T;
@@ -119,38 +162,8 @@ __global__ __launch_bounds__(kWave * mlp_waves(kPvgradTile)) void pvgrad_forward
   float* base = args.ws;
   for (int l = 0; l < q.nblocks; ++l) {
     const hk_pvnet_block& B = q.block[l];
-    const int K = B.k, N = B.n;
-    const int64_t sz = (int64_t)batch * N;
-    if (B.kind == HK_PVNET_DENSE) {
-      mlp_dense<TR, false>(acc, cur, wst, f(B.dense1.weight), f(B.dense1.bias), nullptr, nullptr, K, N, tid);
-      pvnet_store<TR, false>(acc, nxt, N, tid, acc, false);
-      pvgrad_save_panel(nxt, base + kPgDenseH * sz, N, row0, batch, tid);
-      float* const swap = cur;
-      cur = nxt;
-      nxt = swap;
-      base += pvgrad_slots(B) * sz;
-      continue;
-    }
-    const bool proj = K != N;
-    PvgradAcc o;
-    if (proj) {
-      mlp_dense<TR, false>(o, cur, wst, f(B.proj.weight), f(B.proj.bias), nullptr, nullptr, K, N, tid);
-      pvgrad_save(o, base + kPgZp * sz, N, row0, batch, tid);
-      pvnet_group_norm<TR>(o, B.proj, B.eps, N, tid);
-    } else {
-#pragma unroll
-      for (int i = 0; i < T::TPW; ++i) o[0][i] = mlp_f4{0.0f, 0.0f, 0.0f, 0.0f};
-    }
-    mlp_dense<TR, false>(acc, cur, wst, f(B.dense1.weight), f(B.dense1.bias), nullptr, nullptr, K, N, tid);
-    pvgrad_save(acc, base + kPgZ1 * sz, N, row0, batch, tid);
-    pvnet_group_norm<TR>(acc, B.dense1, B.eps, N, tid);
-    pvnet_store<TR, false>(acc, nxt, N, tid, acc, false);
-    pvgrad_save_panel(nxt, base + kPgA * sz, N, row0, batch, tid);
-    mlp_dense<TR, false>(acc, nxt, wst, f(B.dense2.weight), f(B.dense2.bias), nullptr, nullptr, N, N, tid);
-    pvgrad_save(acc, base + kPgZ2 * sz, N, row0, batch, tid);
-    pvnet_group_norm<TR>(acc, B.dense2, B.eps, N, tid);
-    pvnet_store<TR, true>(acc, cur, N, tid, o, proj);
-    pvgrad_save_panel(cur, base + kPgH * sz, N, row0, batch, tid);
+    const int64_t sz = (int64_t)batch * B.n;
+    pvgrad_forward_block(B, base, sz, cur, nxt, wst, acc, row0, batch, tid);
     base += pvgrad_slots(B) * sz;
   }
 
@@ -177,6 +190,8 @@ __global__ __launch_bounds__(kWave * mlp_waves(kPvgradTile)) void pvgrad_forward
     }
   }
 }
+
+#endif
 
 // ---- the row chain ----------------------------------------------------------------------------------------------------
 
@@ -296,6 +311,56 @@ __device__ __forceinline__ void pvgrad_gnb(PvgradAcc& dz, const PvgradAcc& e, co
   }
 }
 
+// one block of the row chain, backward: D is the gradient at the block's output when it is called and at its input when it
+// returns -- but for the net's `first` block, whose input gets none.  The rows, `base` and `sz` as pvgrad_forward_block's;
+// pa and pb are the two panels.  The one copy of the body: pvgrad_rows_kernel's and hk::customgrad_rows_kernel's
+__device__ __forceinline__ void pvgrad_backward_block(const hk_pvnet_block& B, bool first, float* base, int64_t sz, PvgradAcc& D,
+                                                      float* const pa, float* const pb, float* const wst, int64_t row0, int batch,
+                                                      int tid) {
+  typedef PvgradTile T;
+  auto f = [](const void* p) { return static_cast<const float*>(p); };
+  const int K = B.k, N = B.n;
+  const float* W1 = f(B.dense1.weight);
+  if (B.kind == HK_PVNET_DENSE) {
+    pvgrad_mask(D, base + kPgDenseH * sz, base + kPgDenseDz1 * sz, N, row0, batch, tid);
+    if (first) return;
+    __syncthreads();
+    pvgrad_to_panel(D, pa, N, tid);
+    pvgrad_dense_t(D, pa, wst, [&](int c) { return W1 + (int64_t)c * K; }, N, K, tid);
+    return;
+  }
+  const bool proj = K != N;
+  const float* W2 = f(B.dense2.weight);
+  PvgradAcc t;
+  pvgrad_mask(D, base + kPgH * sz, base + kPgE * sz, N, row0, batch, tid);  // D is e from here
+  pvgrad_gnb(t, D, base + kPgZ2 * sz, B.dense2, B.eps, base + kPgGx2 * sz, base + kPgDz2 * sz, N, row0, batch, tid);
+  __syncthreads();
+  pvgrad_to_panel(t, pa, N, tid);
+  pvgrad_dense_t(t, pa, wst, [&](int c) { return W2 + (int64_t)c * N; }, N, N, tid);
+  pvgrad_mask(t, base + kPgA * sz, base + kPgDa * sz, N, row0, batch, tid);
+  pvgrad_gnb(t, t, base + kPgZ1 * sz, B.dense1, B.eps, base + kPgGx1 * sz, base + kPgDz1 * sz, N, row0, batch, tid);
+  if (first) {
+    if (proj) pvgrad_gnb(t, D, base + kPgZp * sz, B.proj, B.eps, base + kPgGxp * sz, base + kPgDzp * sz, N, row0, batch, tid);
+    return;
+  }
+  PvgradAcc d1;
+  __syncthreads();
+  pvgrad_to_panel(t, pb, N, tid);
+  pvgrad_dense_t(d1, pb, wst, [&](int c) { return W1 + (int64_t)c * K; }, N, K, tid);
+  if (proj) {
+    const float* Wq = f(B.proj.weight);
+    pvgrad_gnb(t, D, base + kPgZp * sz, B.proj, B.eps, base + kPgGxp * sz, base + kPgDzp * sz, N, row0, batch, tid);
+    __syncthreads();
+    pvgrad_to_panel(t, pa, N, tid);
+    pvgrad_dense_t(D, pa, wst, [&](int c) { return Wq + (int64_t)c * K; }, N, K, tid);
+  }
+#pragma unroll
+  for (int i = 0; i < T::TPW; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) D[0][i][r] = d1[0][i][r] + D[0][i][r];  // d1 + e, or d1 + the projection's product
+}
+
+#ifndef HK_PVGRAD_BODIES_ONLY
 __global__ __launch_bounds__(kWave * mlp_waves(kPvgradTile)) void pvgrad_rows_kernel(const PvgradRowsArgs args) {
   constexpr int TR = kPvgradTile;
   typedef PvgradTile T;
@@ -353,61 +418,23 @@ __global__ __launch_bounds__(kWave * mlp_waves(kPvgradTile)) void pvgrad_rows_ke
 
   for (int l = q.nblocks - 1; l >= 0; --l) {
     const hk_pvnet_block& B = q.block[l];
-    const int K = B.k, N = B.n;
-    const int64_t sz = (int64_t)batch * N;
+    const int64_t sz = (int64_t)batch * B.n;
     base -= pvgrad_slots(B) * sz;
-    const float* W1 = f(B.dense1.weight);
-    if (B.kind == HK_PVNET_DENSE) {
-      pvgrad_mask(D, base + kPgDenseH * sz, base + kPgDenseDz1 * sz, N, row0, batch, tid);
-      if (l == 0) break;
-      __syncthreads();
-      pvgrad_to_panel(D, pa, N, tid);
-      pvgrad_dense_t(D, pa, wst, [&](int c) { return W1 + (int64_t)c * K; }, N, K, tid);
-      continue;
-    }
-    const bool proj = K != N;
-    const float* W2 = f(B.dense2.weight);
-    PvgradAcc t;
-    pvgrad_mask(D, base + kPgH * sz, base + kPgE * sz, N, row0, batch, tid);  // D is e from here
-    pvgrad_gnb(t, D, base + kPgZ2 * sz, B.dense2, B.eps, base + kPgGx2 * sz, base + kPgDz2 * sz, N, row0, batch, tid);
-    __syncthreads();
-    pvgrad_to_panel(t, pa, N, tid);
-    pvgrad_dense_t(t, pa, wst, [&](int c) { return W2 + (int64_t)c * N; }, N, N, tid);
-    pvgrad_mask(t, base + kPgA * sz, base + kPgDa * sz, N, row0, batch, tid);
-    pvgrad_gnb(t, t, base + kPgZ1 * sz, B.dense1, B.eps, base + kPgGx1 * sz, base + kPgDz1 * sz, N, row0, batch, tid);
-    if (l == 0) {
-      if (proj) pvgrad_gnb(t, D, base + kPgZp * sz, B.proj, B.eps, base + kPgGxp * sz, base + kPgDzp * sz, N, row0, batch, tid);
-      break;
-    }
-    PvgradAcc d1;
-    __syncthreads();
-    pvgrad_to_panel(t, pb, N, tid);
-    pvgrad_dense_t(d1, pb, wst, [&](int c) { return W1 + (int64_t)c * K; }, N, K, tid);
-    if (proj) {
-      const float* Wq = f(B.proj.weight);
-      pvgrad_gnb(t, D, base + kPgZp * sz, B.proj, B.eps, base + kPgGxp * sz, base + kPgDzp * sz, N, row0, batch, tid);
-      __syncthreads();
-      pvgrad_to_panel(t, pa, N, tid);
-      pvgrad_dense_t(D, pa, wst, [&](int c) { return Wq + (int64_t)c * K; }, N, K, tid);
-    }
-#pragma unroll
-    for (int i = 0; i < T::TPW; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) D[0][i][r] = d1[0][i][r] + D[0][i][r];  // d1 + e, or d1 + the projection's product
+    pvgrad_backward_block(B, l == 0, base, sz, D, pa, pb, wst, row0, batch, tid);
   }
 }
+
+#endif
 
 // ---- the parameter gradients ----------------------------------------------------------------------------------------------
 constexpr int kPvgradParamThreads = kWave;
 
-__global__ __launch_bounds__(kPvgradParamThreads) void pvgrad_params_kernel(const PvgradParamsArgs args) {
-  const int lane = threadIdx.x, lm = lane & 15, lg = lane >> 4;
-  int at = 0;
-  for (int i = 1; i < args.count; ++i)
-    if (args.t[i].tile0 <= (int)blockIdx.x) at = i;
-  const PvgradParam& P = args.t[at];
-  const int B = args.batch, n = P.n, k = P.k, KT = (k + 15) >> 4;
-  const int local = (int)blockIdx.x - P.tile0, jt = local / KT, kt = local - jt * KT;
+// one wave's 16 x 16 tile (jt, kt) of a Dense's parameter gradients over the B rows its pointers begin at, in ascending
+// order; B == 0 writes +0.  The one copy of the chain: pvgrad_params_kernel's and hk::customgrad_params_kernel's, which
+// hands it a group's run of slots
+__device__ __forceinline__ void pvgrad_param_tile(const PvgradParam& P, int B, int jt, int kt, int lane) {
+  const int lm = lane & 15, lg = lane >> 4;
+  const int n = P.n, k = P.k;
   const int j = jt * 16 + lm, kcol = kt * 16 + lm;
   const bool jin = j < n, kin = kcol < k, sums = kt == 0, normed = P.ge != nullptr;
   const float* dzp = P.dz + (jin ? j : n - 1);
@@ -463,5 +490,18 @@ __global__ __launch_bounds__(kPvgradParamThreads) void pvgrad_params_kernel(cons
     }
   }
 }
+
+#ifndef HK_PVGRAD_BODIES_ONLY
+__global__ __launch_bounds__(kPvgradParamThreads) void pvgrad_params_kernel(const PvgradParamsArgs args) {
+  int at = 0;
+  for (int i = 1; i < args.count; ++i)
+    if (args.t[i].tile0 <= (int)blockIdx.x) at = i;
+  const PvgradParam& P = args.t[at];
+  const int KT = (P.k + 15) >> 4;
+  const int local = (int)blockIdx.x - P.tile0, jt = local / KT;
+  pvgrad_param_tile(P, args.batch, jt, local - jt * KT, threadIdx.x);
+}
+
+#endif
 
 }  // namespace hk

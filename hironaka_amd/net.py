@@ -19,7 +19,9 @@ every tower on every row and multiplies all but one result by a one-hot of the r
 (hk_customnet_forward, include/hironaka_hip_customnet.h: two launches) groups the rows by their count and runs ONE tower per
 row.  A row whose points are ALL there (count == max_num_points) gets no tower at all -- the reference's one_hot(m, m) is
 all zero -- and its heads see zeros and the extra features: followed here, in both paths.  build_net and HipTrainer build
-it only with `custom_net=True`; without the flag both net types raise as before."""
+it only with `custom_net=True`; without the flag both net types raise as before.  Its gradient step is torch autograd
+through the reference's formula unless `CustomNet.fused_tower_training` is set (off by default): then the forward and backward
+are hk_customgrad_forward / hk_customgrad_backward (include/hironaka_hip_customgrad.h), one tower per row both ways."""
 import copy
 import math
 from functools import partial
@@ -103,6 +105,7 @@ class _PolicyValueNet(nn.Module):
 
     fused_enabled = True
     fused_training = False
+    fused_tower_training = False
     fused_last_reason = None
 
     @property
@@ -372,7 +375,15 @@ class CustomNet(_PolicyValueNet):
     towers, the mask, the sum -- differentiable, and the path HipTrainer.train takes through autograd.  `fused_enabled`,
     `fused_reason` and `fused_last_reason` are DenseResNet's; `fused_training` exists because HipTrainer sets it and has
     no effect: with gradients on `fused_last_reason` says "gradients are on".  The two paths differ in the last bits, and
-    where a row holds a NaN: the mask multiplies the other towers' NaN by zero, which is NaN.  Nothing here synchronises."""
+    where a row holds a NaN: the mask multiplies the other towers' NaN by zero, which is NaN.  Nothing here synchronises.
+
+    With `fused_tower_training = True` (a class attribute, off by default; HipTrainer(..., fused_tower_training=True) sets
+    it) a call with gradients on is served too: the forward and backward are a once-differentiable autograd.Function over
+    ops.customnet_train_forward / ops.customnet_backward (include/hironaka_hip_customgrad.h states the rule: every row runs
+    ONE tower both ways, a tower's gradients sum over its own rows, a tower without rows gets zeros) where the module is
+    servable apart from "gradients are on", the input is float32 on the device, requires no gradient and has at most
+    HK_PVGRAD_MAX_BATCH rows, and no parameter is used twice; parameters that require no gradient get None.  Anything else
+    is `plain_forward`, with `fused_last_reason` saying why.  deepcopy and pickle carry the flag and not the plan."""
 
     def __init__(self, output_size: int, net_arch: List[int], spec: Tuple[int, int], block_cls=DenseResidueBlock,
                  role: Optional[str] = None, extra_dim: Optional[int] = None, seed: int = 0):
@@ -459,7 +470,7 @@ class CustomNet(_PolicyValueNet):
         if not self.fused_enabled:
             return "fused_enabled is False"
         reason = self._checked()[1]
-        if reason is None and self._records_graph():
+        if reason is None and not self.fused_tower_training and self._records_graph():
             return "gradients are on"
         return reason
 
@@ -483,15 +494,27 @@ class CustomNet(_PolicyValueNet):
             reason = "fused_enabled is False"
         else:
             key, reason = self._checked()
-            if reason is None and self._records_graph():
+            if reason is None and not self.fused_tower_training and self._records_graph():
                 reason = "gradients are on"
         if reason is None:
             reason = self._input_reason(x, self.Dense_0.weight.device)
+        grads = reason is None and self._records_graph()  # (only with fused_tower_training)
+        if grads:
+            params = [t for b in self.blocks for child in b.children() for t in child.parameters(recurse=False)]
+            params += list(self.Dense_0.parameters()) + list(self.Dense_1.parameters())
+            if x.shape[0] > A.HK_PVGRAD_MAX_BATCH:
+                reason = f"more than {A.HK_PVGRAD_MAX_BATCH} rows with gradients on"
+            elif len({id(p) for p in params}) < len(params):
+                reason = "a parameter is used twice and gradients are on"
         self.__dict__["fused_last_reason"] = reason
         if reason is not None:
             return self.plain_forward(x)
         from . import ops
-        p, v = ops.customnet_forward(x, self._cached_plan(key))
+        plan = self._cached_plan(key)
+        if grads:
+            p, v = _CustomnetTrainFunction.apply(plan, x, *plan.params)
+        else:
+            p, v = ops.customnet_forward(x, plan)
         return p, v.unsqueeze(1)
 
 
@@ -514,6 +537,26 @@ class _PvnetTrainFunction(torch.autograd.Function):
         ctx.saved_tensors  # the version check, before anything is launched
         from . import ops
         grads = ops.pvnet_backward(ctx.hk_saved, grad_policy, grad_value)
+        return (None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))
+
+
+class _CustomnetTrainFunction(torch.autograd.Function):
+    """forward: ops.customnet_train_forward; backward: ops.customnet_backward; otherwise _PvnetTrainFunction's"""
+
+    @staticmethod
+    def forward(ctx, plan, x, *params):
+        from . import ops
+        policy, value, saved = ops.customnet_train_forward(x, plan)
+        ctx.hk_saved = saved
+        ctx.save_for_backward(*params)
+        return policy, value
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_policy, grad_value):
+        ctx.saved_tensors  # the version check, before anything is launched
+        from . import ops
+        grads = ops.customnet_backward(ctx.hk_saved, grad_policy, grad_value)
         return (None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))
 
 

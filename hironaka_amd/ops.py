@@ -2326,6 +2326,41 @@ class CustomnetPlan:
             setattr(q, name, getattr(first.desc, name))
         q.m, q.d, q.e, q.nblocks, q.n_last, q.actions, q.dtype = m, d, e, nblocks, first.n_last, first.actions, A.HK_F32
         self.workspace, self._retired = None, []
+        # the gradients of customnet_backward (include/hironaka_hip_customgrad.h): `params` in module order -- tower after
+        # tower, block after block (PvnetPlan.params' order inside a tower), then the policy head's and the value head's --
+        # and where each one's gradient begins in ONE flat buffer of `grad_floats` floats.  The gradient table, parallel to
+        # the tower table, holds those offsets; it is written here, once, and nobody can read it back: every offset is this
+        # loop's, inside the buffer, and no two gradients share a float
+        self.params, self.grad_starts, floats = [], [], 0
+        gtable = (A.hk_customgrad_block * (m * nblocks))()
+        for rec in gtable:
+            for which in ("dense1", "dense2", "proj"):
+                for field in ("d_weight", "d_bias", "d_gn_scale", "d_gn_bias"):
+                    setattr(getattr(rec, which), field, A.HK_CUSTOMGRAD_NONE)
+        self.grad_desc = g = A.hk_customgrad_desc()
+        for head in (g.policy, g.value):
+            for field in ("d_weight", "d_bias", "d_gn_scale", "d_gn_bias"):
+                setattr(head, field, A.HK_CUSTOMGRAD_NONE)
+
+        def place(param, record, field):
+            nonlocal floats
+            setattr(record, field, floats)
+            self.params.append(param)
+            self.grad_starts.append(floats)
+            floats += (param.numel() + 3) & ~3
+
+        for t, p in enumerate(plans):
+            for param, (block, which, field) in zip(p.params, p.grad_fields):
+                if which is not None:
+                    place(param, getattr(gtable[t * nblocks + block], which), field)
+        for param, (block, which, field) in zip(first.params, first.grad_fields):
+            if which is None:
+                place(param, getattr(g, block), field)
+        self.grad_floats = floats
+        self.grad_table = torch.frombuffer(bytearray(bytes(gtable)), dtype=torch.uint8).to(dev)
+        g.grad_table, g.grad_floats = self.grad_table.data_ptr(), floats
+        for l in range(nblocks):
+            g.n[l], g.kind[l] = first.desc.block[l].n, first.desc.block[l].kind
 
     def workspace_for(self, batch: int) -> torch.Tensor:
         """the workspace for a call on `batch` rows, allocated (for twice the rows) and zeroed where the one at hand is
@@ -2752,4 +2787,106 @@ def pvnet_backward(saved: PvnetSaved, grad_policy: torch.Tensor, grad_value: tor
         setattr(getattr(g, block) if which is None else getattr(g.block[block], which), field, ptr)
     with torch.cuda.device(dev):
         check(lib().hk_pvgrad_backward(C.byref(g), _stream(saved.policy)), "hk_pvgrad_backward")
+    return grads
+
+
+# ---- the training-mode forward of CustomNet and its backward: one tower per row both ways (hironaka_hip_customgrad.h) -------
+
+class CustomnetSaved:
+    """what customnet_backward needs of one customnet_train_forward: the plan, the input rows, the results (value as the
+    kernel stored it) and the workspace that holds the grouping and every saved array"""
+
+    def __init__(self, plan, x, policy, value, workspace, raw_value):
+        self.plan, self.x, self.policy, self.value, self.workspace, self.raw_value = plan, x, policy, value, workspace, raw_value
+
+
+def _customgrad_desc(plan: CustomnetPlan, x, policy, value, workspace, raw_value: bool):
+    """the plan's hk_customgrad_desc with the fields of one call filled in"""
+    g = plan.grad_desc
+    batch, k, a = x.shape[0], x.shape[1], plan.actions
+    g.net = plan.desc
+    q = g.net
+    q.x, q.x_stride, q.batch = x.data_ptr(), x.stride(0) if batch > 1 else k, batch
+    q.policy, q.policy_stride = policy.data_ptr(), policy.stride(0) if batch > 1 else a
+    q.value, q.value_stride = value.data_ptr(), value.stride(0) if batch > 1 else 1
+    q.gate, q.want = None, 0
+    q.flags = A.HK_CUSTOMNET_RAW_VALUE if raw_value else 0
+    q.workspace, q.workspace_bytes = (workspace.data_ptr(), 4 * workspace.numel()) if workspace is not None else (None, 0)
+    g.grads = g.grad_policy = g.grad_value = None
+    return g
+
+
+def customnet_train_forward(x: torch.Tensor, plan: CustomnetPlan, raw_value: bool = False):
+    """customnet_forward with what the backward needs saved, in two launches (hk_customgrad_forward; the rule is in
+    include/hironaka_hip_customgrad.h): a stable grouping of the rows by their point count, then every row through the ONE
+    tower its count names.  Returns (policy [B, A], value [B], saved): policy and value have customnet_forward's bits,
+    `saved` (a CustomnetSaved) is what customnet_backward takes.  The buffers are new per call (the plan's workspace is
+    not used).  At most HK_PVGRAD_MAX_BATCH rows.  Nothing here synchronises."""
+    if not isinstance(plan, CustomnetPlan):
+        raise TypeError(f"plan must be a CustomnetPlan. Got {type(plan).__name__}.")
+    dev = plan.device
+    x = _mlp_rows(x, "x", dev)
+    batch, k = x.shape
+    if k != plan.k_in:
+        raise ValueError(f"the rows have {plan.k_in} features ({plan.m} points of {plan.d} and {plan.e} more). Got {k}.")
+    if batch > A.HK_PVGRAD_MAX_BATCH:
+        raise ValueError(f"at most {A.HK_PVGRAD_MAX_BATCH} rows. Got {batch}.")
+    policy = torch.empty((batch, plan.actions), dtype=torch.float32, device=dev)
+    value = torch.empty((batch,), dtype=torch.float32, device=dev)
+    g = _customgrad_desc(plan, x, policy, value, None, raw_value)
+    floats = lib().hk_customgrad_workspace_bytes(C.byref(g)) // 4 if batch else 0
+    workspace = torch.empty(max(floats, 4), dtype=torch.float32, device=dev)
+    # (aliases without autograd's marks: see mlp_train_forward)
+    saved = CustomnetSaved(plan, x, policy.detach(), value.detach(), workspace, bool(raw_value))
+    if batch == 0:
+        return policy, value, saved
+    g.net.workspace, g.net.workspace_bytes = workspace.data_ptr(), 4 * workspace.numel()
+    with torch.cuda.device(dev):
+        check(lib().hk_customgrad_forward(C.byref(g), _stream(policy)), "hk_customgrad_forward")
+    return policy, value, saved
+
+
+def customnet_backward(saved: CustomnetSaved, grad_policy: torch.Tensor, grad_value: torch.Tensor,
+                       out: Optional[torch.Tensor] = None):
+    """The backward of one customnet_train_forward in two launches (hk_customgrad_backward: the row chain, then the
+    parameter gradients of every tower over its own rows and of the heads over all): grad_policy [B, A] and grad_value [B]
+    or [B, 1] are the gradients with respect to the forward's policy and value (the tanh's result, or the raw value where
+    the forward ran with raw_value); their rows may lie any number of elements apart.  Returns the gradients of the plan's
+    `params`, in that order: views of ONE flat float32 buffer of `plan.grad_floats` floats -- `out`, where it is given (a
+    contiguous float32 tensor of that many elements on the device), a new one otherwise.  A tower that saw no row gets
+    zeros.  The input gets no gradient.  The parameters must be what they were in the forward.  Nothing here
+    synchronises."""
+    if not isinstance(saved, CustomnetSaved):
+        raise TypeError(f"saved must be a CustomnetSaved. Got {type(saved).__name__}.")
+    plan = saved.plan
+    dev = plan.device
+    batch, a = saved.policy.shape
+    for name, t, shapes in (("grad_policy", grad_policy, ((batch, a),)), ("grad_value", grad_value, ((batch,), (batch, 1)))):
+        _require_device(t, name)
+        if t.dtype != torch.float32 or t.device != dev or tuple(t.shape) not in shapes:
+            raise TypeError(f"{name} must be a float32 tensor of shape {' or '.join(map(str, shapes))} on {dev}. "
+                            f"Got {t.dtype} {tuple(t.shape)} on {t.device}.")
+    if (a > 1 and grad_policy.stride(1) != 1) or (batch > 1 and grad_policy.stride(0) < a):
+        grad_policy = grad_policy.contiguous()
+    if batch > 1 and grad_value.stride(0) < 1:
+        grad_value = grad_value.contiguous()
+    if out is not None:
+        _require_device(out, "out")
+        if out.dtype != torch.float32 or out.device != dev:
+            raise TypeError(f"out must be a float32 tensor on {dev}. Got {out.dtype} on {out.device}.")
+        if out.dim() != 1 or out.numel() != plan.grad_floats or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous tensor of {plan.grad_floats} floats. Got {tuple(out.shape)}.")
+        buf = out
+    else:
+        buf = torch.empty(plan.grad_floats, dtype=torch.float32, device=dev)
+    grads = [buf[s:s + p.numel()].view(p.shape) for s, p in zip(plan.grad_starts, plan.params)]
+    if batch == 0:
+        buf.zero_()
+        return grads
+    g = _customgrad_desc(plan, saved.x, saved.policy, saved.value, saved.workspace, saved.raw_value)
+    g.grads = buf.data_ptr()
+    g.grad_policy, g.grad_policy_stride = grad_policy.data_ptr(), grad_policy.stride(0) if batch > 1 else a
+    g.grad_value, g.grad_value_stride = grad_value.data_ptr(), grad_value.stride(0) if batch > 1 else 1
+    with torch.cuda.device(dev):
+        check(lib().hk_customgrad_backward(C.byref(g), _stream(saved.policy)), "hk_customgrad_backward")
     return grads

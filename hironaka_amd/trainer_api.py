@@ -22,7 +22,9 @@ has a ``host`` / ``agent`` section with ``net_arch`` and ``net_type`` is ``dense
 ``hironaka_amd.net``'s modules as JAXTrainer builds flax's (jax_trainer.py:216-218; ``built_nets[role]``) and calls them
 under ``torch.no_grad()``.  With ``HipTrainer(..., custom_net=True)`` the net types ``custom`` / ``custom_dense`` build
 ``hironaka_amd.net.CustomNet`` the same way (off by default: without the flag both raise as before; ``train`` runs it
-through torch autograd, ``fused_training`` has no effect on it).  Otherwise the two networks arrive as callables
+through torch autograd and ``fused_training`` has no effect on it; with ``fused_tower_training=True`` as well the built
+``CustomNet`` carries ``CustomNet.fused_tower_training``: its forward and backward in a gradient step are then
+``hk_customgrad_forward`` / ``hk_customgrad_backward``, one tower per row, off by default).  Otherwise the two networks arrive as callables
 ``net(features, params) -> (policy_logits [B, A], value [B])`` together with their parameter objects
 (``host_params`` / ``agent_params``: opaque, handed back to the callables) -- the role ``model.apply`` plays in
 ``get_apply_fn`` (hironaka/jax/net.py:110-133); the feature transform in front of them (rescale + row sort,
@@ -174,7 +176,7 @@ class HipTrainer:
                  host_params: Any = None, agent_params: Any = None,
                  host_feature_fn=None, agent_feature_fn=None, device=None, use_graph: bool = False,
                  fused_expand: bool = True, loss_fn: Optional[Callable] = None, fused_training: bool = False,
-                 custom_net: bool = False):
+                 custom_net: bool = False, fused_tower_training: bool = False):
         if isinstance(config, str):
             import yaml
             with open(config, "r") as stream:
@@ -207,6 +209,10 @@ class HipTrainer:
                 # fused_training: the gradient step's forward and backward through the network are the library's
                 # (hironaka_amd.net.DenseResNet.fused_training; off by default)
                 module.fused_training = bool(fused_training)
+                # fused_tower_training: the same for a CustomNet, one tower per row both ways
+                # (hironaka_amd.net.CustomNet.fused_tower_training; off by default)
+                if fused_tower_training and hasattr(module, "fused_tower_training"):
+                    module.fused_tower_training = True
                 self.built_nets[role] = module
                 given[role] = _without_grad(module)
         host_net, agent_net = given["host"], given["agent"]

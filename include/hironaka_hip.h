@@ -646,6 +646,8 @@ int hk_search_morin_play(const hk_morin_play_desc* desc, void* stream);
 #include "hironaka_hip_pvloss.h"
 /* within ABI 6: hk_pvgrad_forward / hk_pvgrad_backward, likewise */
 #include "hironaka_hip_pvgrad.h"
+/* within ABI 6: hk_customgrad_forward / hk_customgrad_backward / hk_customgrad_workspace_bytes, likewise */
+#include "hironaka_hip_customgrad.h"
 /* within ABI 6: hk_unified_expand / hk_unified_prior / hk_unified_pvnet_forward, likewise */
 #include "hironaka_hip_unified.h"
 /* within ABI 6: hk_spivakovsky_select, likewise */
